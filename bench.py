@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — DP cell-updates/s of the alignGraphs hot path on the BASELINE workload (256 seqs x 1000 aa, WAG).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 `python bench.py --gpus N` without a launcher (WORLD_SIZE unset, N > 1) starts that launcher itself, before anything
@@ -54,7 +54,41 @@ def parse_args():
     ap.add_argument("--only-config", default=None, choices=["c4", "c5"], help="profiling runs: three passes over the jobs of BASELINE config 4 / 5 and nothing else")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU, no compute: only the launch / rendezvous / work-queue / aggregation plumbing (gloo), for CPU rehearsals")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the results of the last one as DIR/<name>.npy (rank 0), to compare two builds output for output")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.dry_run or args.only_config):
+        ap.error("--dump-outputs needs the timed loop over the headline batch (not with --dry-run or --only-config)")
+    return args
+
+
+DUMP_CAP_BYTES = 60 << 20   # array bytes of --dump-outputs: with the .npy headers under 64 MB in all
+
+
+def dump_outputs(out_dir, results):
+    """What a caller of the timed path receives from its last step (pgm_align_batch_fetch: per job the score, status, n_tr_indels
+    and the two node mappings) as float32 / float64 .npy files.  The mappings of the jobs are concatenated in job order (map_len:
+    each job's share); their uint32 values, PGM_GAP included, are exact in float64.  Above DUMP_CAP_BYTES in all, a fixed seeded
+    sample of the jobs is written (job: their indices in the batch)."""
+    import numpy as np
+    lens = np.array([len(r["map1"]) for r in results], np.int64)
+    job = np.arange(len(results))
+    if 16 * lens.sum() + 40 * len(results) > DUMP_CAP_BYTES:
+        order = np.random.default_rng(0).permutation(len(results))
+        job = np.sort(order[np.cumsum(16 * lens[order] + 40) <= DUMP_CAP_BYTES])
+    sel = [results[i] for i in job]
+    arrays = {"job": job.astype(np.float64),
+              "score": np.array([r["score"] for r in sel], np.float32),
+              "status": np.array([r["status"] for r in sel], np.float64),
+              "n_tr_indels": np.array([r["n_tr_indels"] for r in sel], np.float64),
+              "map_len": lens[job].astype(np.float64),
+              "map1": np.concatenate([r["map1"] for r in sel]).astype(np.float64),
+              "map2": np.concatenate([r["map2"] for r in sel]).astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def launch_ranks(args):
@@ -244,6 +278,8 @@ def main():
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0)
     total_cells = sum_over_ranks(float(cells) * args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, batch.cj.results())   # the caller buffers still hold the last timed step's results
 
     # ---- roofline of the dominant kernel (pgm_fill_kernel beside pgm_lean_kernel: DP fill + tracebacks): HIP events on the
     # library's stream, recorded by every launch of the timed loop above and averaged over exactly those launches ----
