@@ -11,8 +11,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# (PGM_TOOLS_LIB=1: the tools build of the same library, `make -C prographmsa_amd/csrc tools` — experiment switches compiled in)
-LIB_PATH = os.path.join(_HERE, "lib", "libpgm_hip_tools.so" if os.environ.get("PGM_TOOLS_LIB") else "libpgm_hip.so")
+LIB_PATH = os.path.join(_HERE, "lib", "libpgm_hip.so")
 PGMSA_PATH = os.path.join(_HERE, "bin", "pgmsa")
 
 PGM_OK, PGM_ERR_INVALID, PGM_ERR_DEVICE, PGM_ERR_BACKTRACK, PGM_ERR_NOMEM = 0, 1, 2, 3, 4
@@ -92,7 +91,7 @@ def _load():
         "pgm_align_batch_destroy": (None, [vp, vp]),
         "pgm_align_batch_cells": (C.c_uint64, [vp]),
         "pgm_align_batch_test_stall": (C.c_int, [vp, u32, u32, u32]),
-        "pgm_test_cu_shares": (C.c_int, [u32, C.c_double, u32, C.c_double, u32, C.c_double, u32, u32, C.c_double, C.c_double, u32, C.POINTER(C.c_uint32)]),
+        "pgm_test_cu_shares": (C.c_int, [u32, C.c_double, u32, C.c_double, u32, C.c_double, u32, u32, C.c_double, C.POINTER(C.c_uint32)]),
         "pgm_align_batch_stage_times": (C.c_int, [vp, C.c_int] + [C.POINTER(C.c_float)] * 3 + [C.POINTER(u32)]),
         "pgm_align_batch_job_times": (C.c_int, [vp, vp, C.POINTER(C.c_uint64)]),
         "pgm_align_batch_time": (C.c_int, [vp, vp, C.c_int] + [C.POINTER(C.c_float)] * 4),

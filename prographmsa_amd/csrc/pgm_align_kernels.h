@@ -506,9 +506,6 @@ __device__ __forceinline__ float pgm_emission_at(const PgmJob &J, uint32_t y, ui
     return J.S[(((size_t)b * J.nblk + (t / PGM_BLOCK)) * 64u + l) * PGM_BLOCK + (t % PGM_BLOCK)];
 }
 
-#ifndef PGM_POLL_PREFETCH
-#define PGM_POLL_PREFETCH 1
-#endif
 #define PGM_TB_T 32        // tile edge (rows and columns)
 #define PGM_TB_BAND 6      // successor links are built for the diagonals within this distance of the walker's (half of it for chain-only jobs)
 #define PGM_TB_LK 4        // an M-state link is precomputed for cells whose two nodes have at most this many predecessors each
@@ -576,7 +573,9 @@ __device__ static void pgm_traceback_publish(const PgmJob &J, const uint32_t len
 }
 
 // lq: the batch's queue of pre-link tasks (pgm_fill_kernel's idle phase): lq[0] tasks announced, lq[1] tracebacks finished, lq_ids[k] = job + 1
-__device__ static void pgm_traceback_job(const PgmJob &J, PgmTbLds &T, const int tid, const int nthreads, unsigned long long *stat,
+// (out of line, as pgm_prelink_tile: inlined into pgm_tb_kernel, the two walkers' private arrays were promoted to LDS — 16 KB more per
+// worker — and the kernel's register allocation changed)
+__device__ __attribute__((noinline)) static void pgm_traceback_job(const PgmJob &J, PgmTbLds &T, const int tid, const int nthreads,
                                          int *lq, int *lq_ids, const uint32_t jid) {
     constexpr uint32_t TT = PGM_TB_T;
     const uint32_t n1 = J.n1, n2 = J.n2;
@@ -986,7 +985,6 @@ __device__ static void pgm_traceback_job(const PgmJob &J, PgmTbLds &T, const int
         // graphs are 1 node back; in merged graphs most skip edges span a few nodes (farther ones are read from memory)
         const uint32_t margin = J.has_extras ? 4u : 1u;
         uint32_t guard = 0;
-        unsigned long long st_reload = 0, st_nreload = 0, st_slow = 0, st_stage = 0, st_grid = 0;
         bool score_stale = false;
         uint32_t nl_y = 0xFFFFFFFFu, nl_x = 0xFFFFFFFFu;   // last cell at which the pre-linked tables had nothing to follow
         uint32_t glo = 1u, ghi = 0u;                       // grid rows whose tables are in LDS (none: lo > hi)
@@ -1054,7 +1052,6 @@ __device__ static void pgm_traceback_job(const PgmJob &J, PgmTbLds &T, const int
                 if (moved) {
                     current_state = st == 0u ? State_m : (st == 1u ? State_x : State_y);
                     score_stale = true;
-                    ++st_grid;
                     continue;
                 }
                 nl_y = y; nl_x = x;   // nothing to follow from here: decide this cell the usual way, then look again
@@ -1065,20 +1062,17 @@ __device__ static void pgm_traceback_job(const PgmJob &J, PgmTbLds &T, const int
             if (reload && !(nolink && y == nl_y && x == nl_x)) {
                 ty0 = y >= TT - 1 ? y - (TT - 1) : 0u;
                 tx0 = x >= TT - 1 ? x - (TT - 1) : 0u;
-                const unsigned long long r0 = stat ? __builtin_amdgcn_s_memrealtime() : 0ull;
                 ay = y; ax = x; adiag = (int)(y - ty0) - (int)(x - tx0);
                 if (lane == 0) { T.ty0 = ty0; T.tx0 = tx0; T.ay = y; T.ax = x; T.req = 1; }
                 __syncthreads();        // request posted
                 stage();
                 __syncthreads();        // cells, scores, predecessor lists staged
-                if (stat) st_stage += __builtin_amdgcn_s_memrealtime() - r0;
                 if (use_links) {
                     links();
                     __syncthreads();    // successor table complete but for the cells of links_big
                     links_big();
                     __syncthreads();
                 }
-                if (stat) { st_reload += __builtin_amdgcn_s_memrealtime() - r0; ++st_nreload; }
             }
             // fast path: follow the precomputed links.  A link's low 12 bits are the table index of the next (state, cell),
             // so the chase is one LDS read per step; it ends at the first (cell, state) without a link (off the band, near
@@ -1160,7 +1154,6 @@ __device__ static void pgm_traceback_job(const PgmJob &J, PgmTbLds &T, const int
                     }
                 }
             }
-            ++st_slow;
             if (score_stale) {   // the score of (cell, state) is the cell's value for that state
                 const float4 c = cell_at(y, x);
                 current_score = current_state == State_m ? c.x : (current_state == State_x ? c.y : c.w);
@@ -1261,7 +1254,6 @@ __device__ static void pgm_traceback_job(const PgmJob &J, PgmTbLds &T, const int
             J.result->status = status;
             T.len = mo.len;
             T.req = 2;
-            if (stat) { stat[0] = (st_stage << 32) | st_reload; stat[1] = (st_nreload << 32) | ((st_grid & 0xffffull) << 16) | (st_slow & 0xffffull); }
         }
         __syncthreads();                // "request" that ends the loaders' loop
     }
@@ -1281,7 +1273,7 @@ __device__ static void pgm_traceback_job(const PgmJob &J, PgmTbLds &T, const int
 // plus a halo of PGM_LK_H rows / columns.  No link where the walker's general code has to look: a predecessor beyond the
 // halo, more than PGM_TB_PK predecessors, a repeat edge, an inconsistent source.  The job is complete (its traceback has
 // started), so every cell read here is final.
-__device__ static void pgm_prelink_tile(const PgmJob &J, PgmLkLds &G, const uint32_t k, const int tid) {
+__device__ __attribute__((noinline)) static void pgm_prelink_tile(const PgmJob &J, PgmLkLds &G, const uint32_t k, const int tid) {
     constexpr uint32_t TT = PGM_LK_T, HW = PGM_LK_HW, NT = 64u * PGM_WAVES, PK = PGM_TB_PK;
     const uint32_t n1 = J.n1, n2 = J.n2;
     const uint32_t w = min(J.lcols, PGM_LK_W), r = k / PGM_LK_W, jj = k % PGM_LK_W;
@@ -1456,14 +1448,6 @@ __device__ static void pgm_prelink_tile(const PgmJob &J, PgmLkLds &G, const uint
 #define PGM_SPIN_LIMIT (1u << 24)
 #define PGM_IDLE_LIMIT_TICKS 400000000ull   /* 4 s of the 100 MHz real-time counter: a worker that has seen nothing happen for that long raises the abort flag */
 
-// A job's last band is complete (and every store of it waited for): append the job to the ready queue of the traceback kernel that
-// runs beside the sweeps (tbq_off == 0: the tracebacks follow on the stream instead).
-__device__ __forceinline__ void pgm_tbq_push(int *sync, const uint32_t tbq_off, const uint32_t job) {
-    if (tbq_off == 0u) return;
-    const int k = __hip_atomic_fetch_add(sync + PGM_SY_TBQ_TAIL, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(sync + tbq_off + k, (int)job + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // ---------------------------------------------------------------------------------------------
 // Fill kernel (GraphAlign.h:212-260 incl. the border initialisation as row/column 0).
 //
@@ -1502,13 +1486,10 @@ __device__ __forceinline__ void pgm_tbq_push(int *sync, const uint32_t tbq_off, 
 //         terms it holds in its register windows (chain terms, X from columns x-2 / x-3, Y from row y-2, two M pairs), merges
 //         the maxima seven helper wavefronts have folded ahead of it (pgm_terms_helper), stores the cell and records W, Y, X
 //         in the history
-// DBG = false (production): no timeline accumulators, no experiment switches (their branches and scalar registers are gone)
-template <int MODE, bool DBG>
+template <int MODE>
 __device__ __forceinline__ void pgm_sweep_band(const PgmJob &J, const uint32_t b, uint8_t *slot, const int lane, int *abort_flag, bool &aborted,
-                                               const uint32_t spin_limit, const bool stall, unsigned long long *wait_acc_, int *sw_generic, const uint32_t dbg_flags_) {
+                                               const uint32_t spin_limit, const bool stall, int *sw_generic) {
     constexpr bool NEAR = MODE == 1, HELPED = MODE == 2, EXTRAS = MODE != 0;
-    unsigned long long *const wait_acc = DBG ? wait_acc_ : nullptr;
-    const uint32_t dbg_flags = DBG ? dbg_flags_ : 0u;
     constexpr int BL = PGM_BLOCK, VL = PGM_VL, HS = 64 + PGM_VL, NR = PGM_NRING, KF = PGM_KF;
     constexpr int RS = HELPED ? 5 : 3;   // float4 per column of the ring: {q0, fd0-3, fc0-3}, or the whole node summary for the far helper
     typedef __attribute__((address_space(3))) int pgm_lds_int;
@@ -1555,8 +1536,8 @@ __device__ __forceinline__ void pgm_sweep_band(const PgmJob &J, const uint32_t b
     const uint32_t lb = (uint32_t)(VL + lane);
     float *res = (float *)(slot + J.aux_off + PGM_AUX_RES);
     // HELPED: the helper wavefronts whose terms this sweep waits for (bit h = wavefront h of the worker): 1, 2 the near terms,
-    // 3, 4 the far edges of the columns, 5-7 the far edges of the rows (experiment switches: 32 without the former, 16 the latter)
-    const uint32_t hmask = HELPED ? ((((dbg_flags & 32u) ? 0u : 0x06u) | ((has_far && !(dbg_flags & 16u)) ? 0xf8u : 0u)) & ~(dbg_flags >> 16)) : 0u;   // (bits 17-23 of the switches: do not wait for that wavefront)
+    // 3, 4 the far edges of the columns, 5-7 the far edges of the rows
+    const uint32_t hmask = HELPED ? (0x06u | (has_far ? 0xf8u : 0u)) : 0u;
     int seen_min = hmask ? 0 : 0x7fffffff;   // steps whose terms every helper has published
 
     for (uint32_t i = (uint32_t)lane; i < D * HS; i += 64u) { hW[i] = PGM_NEG_INF; hY[i] = PGM_NEG_INF; }
@@ -1622,7 +1603,6 @@ __device__ __forceinline__ void pgm_sweep_band(const PgmJob &J, const uint32_t b
         if (seen != 0x7fffffff && !aborted) {
             const int need = (int)min(steps_needed, tsteps);
             uint32_t spins = 0;
-            const unsigned long long w0 = (wait_acc && seen < need) ? __builtin_amdgcn_s_memrealtime() : 0ull;
             while (seen < need) {
                 seen = __builtin_amdgcn_readfirstlane(__hip_atomic_load((const PGM_GLOBAL int *)(uintptr_t)&J.prog[b - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
                 if (seen >= need) break;
@@ -1633,7 +1613,6 @@ __device__ __forceinline__ void pgm_sweep_band(const PgmJob &J, const uint32_t b
                     break;
                 }
             }
-            if (w0) wait_acc[0] += __builtin_amdgcn_s_memrealtime() - w0;
         }
     };
     // split-phase poll: the progress word is read one block ahead (no round trip on the band's own critical path);
@@ -1692,22 +1671,19 @@ __device__ __forceinline__ void pgm_sweep_band(const PgmJob &J, const uint32_t b
             const uint32_t rslot = x & (uint32_t)(NR - 1);   // column summaries: part-major, part k of column c at ring3[k * NR + (c & (NR - 1))]
             const float4 cn = cn_n;
             const float iW1 = inW1, iY1 = inY1, iW2 = inW2, iY2 = inY2, iW3 = inW3, iY3 = inY3;
-            if (HELPED && !(dbg_flags & 2u)) {
+            if (HELPED) {
                 // The helper wavefronts run ahead.  Their seven counters (words of wavefronts that do not take part were set to
                 // "far ahead" in the prologue) are read with the look-ahead operands of the PREVIOUS step — two 128-bit reads of the
                 // same words by every lane, minimum on the vector unit — so normally this step only compares; it reads them
                 // again (and waits) only if the helpers really are behind.
                 const int want = (int)t + 1;
-#if PGM_POLL_PREFETCH
                 {
                     int m = min(min(hw_a.y, hw_a.z), min(hw_a.w, hw_b.x));
                     m = min(m, min(min(hw_b.y, hw_b.z), hw_b.w));
                     seen_min = max(seen_min, __builtin_amdgcn_readfirstlane(m));
                 }
-#endif
                 if (__builtin_expect(seen_min < want, 0)) {
                     uint32_t spins = 0;
-                    const unsigned long long h0 = wait_acc ? __builtin_amdgcn_s_memrealtime() : 0ull;
                     for (;;) {
                         const pgm_v4i wa = *(const __attribute__((address_space(3))) pgm_v4i *)sw, wb = *(const __attribute__((address_space(3))) pgm_v4i *)(sw + 4);
                         int m = min(min(wa.y, wa.z), min(wa.w, wb.x));
@@ -1717,14 +1693,11 @@ __device__ __forceinline__ void pgm_sweep_band(const PgmJob &J, const uint32_t b
                         __builtin_amdgcn_s_sleep(1);
                         if (++spins > (1u << 22)) { __hip_atomic_store((PGM_GLOBAL int *)(uintptr_t)abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); aborted = true; break; }
                     }
-                    if (wait_acc) wait_acc[1] += __builtin_amdgcn_s_memrealtime() - h0;
                 }
                 asm volatile("" ::: "memory");
-#if PGM_POLL_PREFETCH
                 hw_a = *(const __attribute__((address_space(3))) pgm_v4i *)sw; hw_b = *(const __attribute__((address_space(3))) pgm_v4i *)(sw + 4);   // for step t + 1
-#endif
             }
-            if (!(dbg_flags & 64u)) {   // operands of step t + 1 (their virtual-lane entries and column summaries were staged at least a block ago)
+            {   // operands of step t + 1 (their virtual-lane entries and column summaries were staged at least a block ago)
                 cn_n = ring3[(x + 1u) & (uint32_t)(NR - 1)];
                 const uint32_t tm0 = (t & Dm) * HS, tm1 = ((t - 1u) & Dm) * HS, tm2 = ((t - 2u) & Dm) * HS;
                 inW1 = hW[tm0 + VL - 1]; inY1 = hY[tm0 + VL - 1];
@@ -1734,7 +1707,7 @@ __device__ __forceinline__ void pgm_sweep_band(const PgmJob &J, const uint32_t b
             // maxima over the helpers' terms of this step: read with the other LDS operands, merged after the chain terms; the
             // words are reset for step t + 4 (no helper writes that step before this one is recorded: far_slack <= 4)
             float rM = PGM_NEG_INF, rX = PGM_NEG_INF, rY = PGM_NEG_INF;
-            if (HELPED && !(dbg_flags & 2u)) {
+            if (HELPED) {
                 const uint32_t ro = (t & 3u) * 192u + (uint32_t)lane;
                 rM = res[ro]; rX = res[ro + 64]; rY = res[ro + 128];
                 res[ro] = PGM_NEG_INF; res[ro + 64] = PGM_NEG_INF; res[ro + 128] = PGM_NEG_INF;
@@ -1754,10 +1727,8 @@ __device__ __forceinline__ void pgm_sweep_band(const PgmJob &J, const uint32_t b
                 const float n2W = pgm_dpp_wave_shr1(u1W[sm1], iW2), n2Y = pgm_dpp_wave_shr1(u1Y, iY2);
                 u2W[s0] = n2W; u2Y = n2Y;
             }
-            if (!(dbg_flags & 128u)) {
-                u1W[s0] = pgm_dpp_wave_shr1(W_o, iW1);
-                u1Y = pgm_dpp_wave_shr1(Y_o, iY1);
-            } else { u1W[s0] = W_o; u1Y = Y_o; }
+            u1W[s0] = pgm_dpp_wave_shr1(W_o, iW1);
+            u1Y = pgm_dpp_wave_shr1(Y_o, iY1);
             auto mterm = [&](float w, float cy, float cx) { return __fsub_rn(__fsub_rn(__fadd_rn(w, S), cy), cx); };
             auto xterm = [&](float xp, float wp, float cx) { return __fsub_rn(fmaxf(__fadd_rn(xp, ge), __fadd_rn(wp, gopen_x)), cx); };
             auto yterm = [&](float yp, float wp, float cy) { return __fsub_rn(fmaxf(__fadd_rn(yp, ge), __fadd_rn(wp, gopen_y)), cy); };
@@ -1860,8 +1831,8 @@ __device__ __forceinline__ void pgm_sweep_band(const PgmJob &J, const uint32_t b
             float Wv = fmaxf(Mv, fmaxf(Xv, Yv));
             if (xs == x_init) Wv = s_init;
             if (!active) { Mv = PGM_NEG_INF; Xv = PGM_NEG_INF; Yv = PGM_NEG_INF; Wv = PGM_NEG_INF; }
-            pgm_store_cell_masked(cells_rsrc, t, lane, active && !(dbg_flags & 1u), Mv, Xv, Wv, Yv);
-            if (record && !(dbg_flags & 8u)) {
+            pgm_store_cell_masked(cells_rsrc, t, lane, active, Mv, Xv, Wv, Yv);
+            if (record) {
                 const uint32_t ho = (t & Dm) * HS + lb;
                 hW[ho] = Wv;
                 hY[ho] = Yv;
@@ -2190,7 +2161,7 @@ __device__ __forceinline__ void pgm_sweep_chain(const PgmJob &J, const int wave,
 // them are requested at the same time and arrive while it walks (only a change of band is not foreseen).  Mapping entries
 // are collected in LDS and go out in blocks.
 template <int R>
-__device__ static void pgm_traceback_chain(const PgmJob &J, uint8_t *pool, uint32_t *len_lds, const int tid, const int nthreads, unsigned long long *stat) {
+__device__ static void pgm_traceback_chain(const PgmJob &J, uint8_t *pool, uint32_t *len_lds, const int tid, const int nthreads) {
     constexpr int WB = 16, NW = WB * R;          // window: WB blocks of 8 steps x R rows x 64 lanes, one word each
     constexpr uint32_t MB = 2048u;
     const uint32_t n1 = J.n1, n2 = J.n2, nblk = J.nblk;
@@ -2264,15 +2235,12 @@ __device__ static void pgm_traceback_chain(const PgmJob &J, uint8_t *pool, uint3
             for (int k = 0; k < NW; ++k) win[(cur * NW + k) * 64 + lane] = pf[k];
             wb = pf_b; wq0 = pf_q0;
         };
-        unsigned long long st_win = 0, st_nwin = 0, st_miss = 0, st_iter = 0;   // timeline build only
         auto need_window = [&](uint32_t yy, uint32_t xx) {   // (wave-uniform arguments) the window that holds cell (yy, xx)
             const int b = (int)(yy / (64u * R)), qw = (int)((xx + (yy % (64u * R)) / R) >> 3);
             if (b != wb || qw > wq0 || qw < wq0 - (WB - 1)) {
-                const unsigned long long r0 = stat ? __builtin_amdgcn_s_memrealtime() : 0ull;
-                if (pf_b != b || qw > pf_q0 || qw < pf_q0 - (WB - 1)) { issue(b, qw); ++st_miss; }
+                if (pf_b != b || qw > pf_q0 || qw < pf_q0 - (WB - 1)) issue(b, qw);
                 land();
                 if (wq0 >= WB) issue(wb, wq0 - WB);   // what the walk needs next unless it changes band
-                if (stat) { st_win += __builtin_amdgcn_s_memrealtime() - r0; ++st_nwin; }
             }
         };
         auto code_of = [&](uint32_t yy, uint32_t xx, bool &inwin) -> uint32_t {   // per-lane cell; inwin: its word is in the current window
@@ -2292,7 +2260,6 @@ __device__ static void pgm_traceback_chain(const PgmJob &J, uint8_t *pool, uint3
         uint32_t guard = 0;
         while ((x | y) != 0u && status == PGM_OK) {
             if (++guard > n1 + n2 + 4) { status = PGM_ERR_BACKTRACK; break; }
-            ++st_iter;
             if (state == State_m) {
                 // ---- a diagonal run: lane k looks at cell (y - 1 - k, x - 1 - k) ----
                 if (y == 0u || x == 0u) { status = PGM_ERR_BACKTRACK; break; }
@@ -2356,11 +2323,6 @@ __device__ static void pgm_traceback_chain(const PgmJob &J, uint8_t *pool, uint3
             J.result->len = len;
             J.result->status = status;
             *len_lds = len;
-            if (stat) {   // {ticks since the band end of wavefront 0 until the walk began << 40 | window ticks << 20 | walk ticks, windows << 32 | misses << 16 | iterations}
-                const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-                stat[0] = (((stat[1] - stat[-2]) & 0xfffffull) << 40) | ((st_win & 0xfffffull) << 20) | ((now - stat[1]) & 0xfffffull);
-                stat[1] = (st_nwin << 32) | (st_miss << 16) | st_iter;
-            }
         }
     }
     __threadfence_block();
@@ -2401,7 +2363,7 @@ __device__ static void pgm_traceback_chain(const PgmJob &J, uint8_t *pool, uint3
 // Columns with more on-chip entries than the summary holds keep the rest in an overflow table (LDS copy, any helper).
 template <int GROUP, bool LONG, bool MASK = false>   // MASK: the column summaries of this job may hold long entries in their last slots
 __device__ __forceinline__ void pgm_terms_helper(const PgmJob &J, const uint32_t b, uint8_t *slot, const int lane, int *sw_generic,
-                                                 const int hidx, const uint32_t part, const uint32_t nparts, const bool idle = false, const bool nofold = false, unsigned long long *hst = nullptr,
+                                                 const int hidx, const uint32_t part, const uint32_t nparts,
                                                  const uint32_t tpar = 0u, const uint32_t tstr = 1u, const int flag_idx = 8, float *sblk_own = nullptr, const bool builder = true) {
     // (tpar, tstr: the steps this wavefront evaluates, t % tstr == tpar — pgm_crit_kernel deals the steps of a band to two wavefronts
     // per part; flag_idx: the word "row entry list built"; sblk_own: this wavefront's score block; builder: part 0 builds the list)
@@ -2440,7 +2402,7 @@ __device__ __forceinline__ void pgm_terms_helper(const PgmJob &J, const uint32_t
     const uint32_t ncol_row = rowvalid ? ncol : 0u;
     const float4 *S_band = (const float4 *)(J.S + (size_t)b * nblk * 64u * BL);
     const uint32_t lb = (uint32_t)(VL + lane);
-    auto fold = [&](float *p, float v) { if (nofold) return; __builtin_amdgcn_ds_fmaxf((pgm_lds_float *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP, false); };
+    auto fold = [&](float *p, float v) { __builtin_amdgcn_ds_fmaxf((pgm_lds_float *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP, false); };
     // cell (r, c) of the job = byte offset row_off(r) + c * 1024 into the job's cell storage (32-bit: the host only
     // marks entries long / remote when the job's storage is smaller than 4 GiB)
     const __amdgpu_buffer_rsrc_t job_rsrc = pgm_band_rsrc(J.cells, LONG ? J.nb * tsteps * 1024u : 16u);
@@ -2563,8 +2525,6 @@ __device__ __forceinline__ void pgm_terms_helper(const PgmJob &J, const uint32_t
     };
     load_s_block(0);
     int seen = 0;
-    unsigned long long hwait = 0;
-    const unsigned long long ht0 = hst ? __builtin_amdgcn_s_memrealtime() : 0ull;
     if (LONG && GROUP != 0) {   // the FIFOs are primed once the sweep's prologue is done (column ring staged)
         while (seen < 1) {
             seen = __builtin_amdgcn_readfirstlane(__hip_atomic_load(sw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
@@ -2593,10 +2553,8 @@ __device__ __forceinline__ void pgm_terms_helper(const PgmJob &J, const uint32_t
             const int need = max(1, (int)t - slack + 2);
             while (seen < need) {   // (a sleeping poll: a tight one would keep the CU's LDS pipeline and this SIMD's issue slots busy;
                                     //  the far helpers have three steps of lead, the wavefront of the step t - 3 term has none to give away)
-                const unsigned long long w0 = hst ? __builtin_amdgcn_s_memrealtime() : 0ull;
                 seen = __builtin_amdgcn_readfirstlane(__hip_atomic_load(sw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
                 if (seen < need) { if (GROUP == 0 || tstr == 2u) __builtin_amdgcn_s_sleep(1); else __builtin_amdgcn_s_sleep(4); }   // (pgm_crit_kernel's steps are short: a finer poll)
-                if (hst) hwait += __builtin_amdgcn_s_memrealtime() - w0;
             }
             asm volatile("" ::: "memory");
             const int xs = (int)t - lane;
@@ -2604,8 +2562,7 @@ __device__ __forceinline__ void pgm_terms_helper(const PgmJob &J, const uint32_t
             const float4 cn = ring3[rslot];
             float *rs = res + (t & 3u) * 192u;
             const int s0 = i & 3, sm1 = (i + 3) & 3, sm2 = (i + 2) & 3, sm3 = (i + 1) & 3;
-            if (idle) {   // (experiments: hand-shake only)
-            } else if (GROUP == 0) {
+            if (GROUP == 0) {
                 const float S = Sc[i];
                 auto w_at = [&](int dy, int dx) { return hW[((t - (uint32_t)(dy + dx)) & Dm) * HS + lb - (uint32_t)dy]; };
                 auto mt = [&](float w, float cy, float cx) { return __fsub_rn(__fsub_rn(__fadd_rn(w, S), cy), cx); };
@@ -2783,17 +2740,10 @@ __device__ __forceinline__ void pgm_terms_helper(const PgmJob &J, const uint32_t
             __hip_atomic_store(sw + hidx, (int)t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     }
-    if (hst && lane == 0) { hst[hidx] = hwait; hst[8 + hidx] = __builtin_amdgcn_s_memrealtime() - ht0; }   // timeline: ticks in the poll loop, ticks in all
 }
 
-// NOTRACEBACK = true: timing build for tools (the fill alone, no traceback); DBG = true: timeline (PGM_FILL_TRACE) and the
-// experiment switches of PGM_TEST_NOSTORE
-template <bool NOTRACEBACK, bool DBG>
 __global__ void __launch_bounds__(64 * PGM_WAVES, 1) pgm_fill_kernel(const PgmJob *__restrict__ jobs, const PgmItem *__restrict__ items, uint32_t nitems,
-                                                      int *__restrict__ sync, unsigned long long *__restrict__ trace,
-                                                      uint32_t spin_limit, uint32_t stall_job, uint32_t stall_band, uint32_t dbg_flags_, uint32_t ticket_off, uint32_t tbq_off) {
-    const uint32_t dbg_flags = DBG ? dbg_flags_ : 0u;
-    if (!DBG) trace = nullptr;
+                                                      int *__restrict__ sync, uint32_t spin_limit, uint32_t stall_job, uint32_t stall_band, uint32_t ticket_off) {
     int *abort_flag = sync;        // [0] abort flag, [1] ticket counter of the band list, [2] lean list; the traceback kernel's words from [32] on (PGM_SY_*)
     // LDS of the band sweeps (one slot per sweeping wavefront)
     __shared__ __attribute__((aligned(16))) struct { uint8_t pool[PGM_POOL]; } L;
@@ -2819,41 +2769,34 @@ __global__ void __launch_bounds__(64 * PGM_WAVES, 1) pgm_fill_kernel(const PgmJo
             const uint32_t pr = __builtin_amdgcn_readfirstlane(item.prio);
             if (pr >= 3u) __builtin_amdgcn_s_setprio(3); else if (pr == 2u) __builtin_amdgcn_s_setprio(2); else if (pr == 1u) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
         }
-        // optional timeline (tools/probe_trace.py): per item {worker, start, end of band, end of traceback} in 100 MHz ticks
-        if (trace && threadIdx.x == 0) { trace[6 * it] = blockIdx.x; trace[6 * it + 1] = __builtin_amdgcn_s_memrealtime(); trace[6 * it + 2] = 0; trace[6 * it + 3] = 0; trace[6 * it + 4] = 0; trace[6 * it + 5] = 0; }
         const PgmJob &J = jobs[item.job];
         const uint32_t b = item.band + (uint32_t)role;
         const bool last_band = (item.band + item.count == J.nb);
-        const unsigned long long clk0 = (DBG && trace) ? __builtin_readcyclecounter() : 0ull;
         if ((uint32_t)role < item.count) {
-            unsigned long long wait_ticks[2] = {0, 0};   // timeline only: waiting for band b-1, waiting for the helpers
             const bool stall = item.job == stall_job && b == stall_band;
             uint8_t *slot = L.pool + (size_t)role * J.slot_bytes;
-            if (J.mode2) pgm_sweep_band<2, DBG>(J, b, slot, lane, abort_flag, aborted, spin_limit, stall, trace ? wait_ticks : nullptr, fsync, dbg_flags);
-            else if (J.has_extras) pgm_sweep_band<1, DBG>(J, b, slot, lane, abort_flag, aborted, spin_limit, stall, trace ? wait_ticks : nullptr, nullptr, dbg_flags);
-            else pgm_sweep_band<0, DBG>(J, b, slot, lane, abort_flag, aborted, spin_limit, stall, trace ? wait_ticks : nullptr, nullptr, dbg_flags);
-            if (trace && threadIdx.x == 0) { trace[6 * it] |= wait_ticks[0] << 16; if (!last_band) { trace[6 * it + 4] = wait_ticks[1]; trace[6 * it + 5] = __builtin_readcyclecounter() - clk0; } }   // (wavefront 0 of the worker; worker id in the low 16 bits)
-        } else if (J.mode2 && !(dbg_flags & 4u)) {
+            if (J.mode2) pgm_sweep_band<2>(J, b, slot, lane, abort_flag, aborted, spin_limit, stall, fsync);
+            else if (J.has_extras) pgm_sweep_band<1>(J, b, slot, lane, abort_flag, aborted, spin_limit, stall, nullptr);
+            else pgm_sweep_band<0>(J, b, slot, lane, abort_flag, aborted, spin_limit, stall, nullptr);
+        } else if (J.mode2) {
             // helpers of the sweeping wavefront 0 (a MODE 2 item is one band); they yield issue slots to sweeping wavefronts
             __builtin_amdgcn_s_setprio(0);
-            unsigned long long *hst = trace ? trace + 6 * (size_t)nitems + 16 * (size_t)it : nullptr;
-            if (role <= 2) { if (!(dbg_flags & 32u)) pgm_terms_helper<0, false>(J, item.band, L.pool, lane, fsync, role, (uint32_t)(role - 1), 2u, false, false, hst); }
-            else if (J.has_far && !(dbg_flags & 16u)) {
+            if (role <= 2) pgm_terms_helper<0, false>(J, item.band, L.pool, lane, fsync, role, (uint32_t)(role - 1), 2u);
+            else if (J.has_far) {
                 // wavefront 4 shares its SIMD with the sweeping wavefront 0: it gets the part that usually has the least to do
                 // (the last third of the row entry passes); column helpers: wavefronts 3 and 7, row helpers: 5, 6, 4
                 if (role == 3 || role == 7) {
                     const uint32_t part = role == 3 ? 0u : 1u;
-                    if (!J.long2) pgm_terms_helper<1, false>(J, item.band, L.pool, lane, fsync, role, part, 2u, (dbg_flags & 256u) != 0, (dbg_flags & 2048u) != 0, hst);
-                    else if (part == 0u) pgm_terms_helper<1, false, true>(J, item.band, L.pool, lane, fsync, role, 0u, 1u, (dbg_flags & 256u) != 0, false, hst);
-                    else pgm_terms_helper<1, true>(J, item.band, L.pool, lane, fsync, role, 0u, 0u, (dbg_flags & 256u) != 0, false, hst);   // (nparts = 0: the long entries only)
+                    if (!J.long2) pgm_terms_helper<1, false>(J, item.band, L.pool, lane, fsync, role, part, 2u);
+                    else if (part == 0u) pgm_terms_helper<1, false, true>(J, item.band, L.pool, lane, fsync, role, 0u, 1u);
+                    else pgm_terms_helper<1, true>(J, item.band, L.pool, lane, fsync, role, 0u, 0u);   // (nparts = 0: the long entries only)
                 } else {
                     const uint32_t part = role == 4 ? 2u : (uint32_t)(role - 5);
-                    if (J.long1 | J.long2) pgm_terms_helper<2, true>(J, item.band, L.pool, lane, fsync, role, part, (uint32_t)PGM_CPARTS, (dbg_flags & 512u) != 0, false, hst);
-                    else pgm_terms_helper<2, false>(J, item.band, L.pool, lane, fsync, role, part, (uint32_t)PGM_CPARTS, (dbg_flags & 512u) != 0, (dbg_flags & 2048u) != 0, hst);
+                    if (J.long1 | J.long2) pgm_terms_helper<2, true>(J, item.band, L.pool, lane, fsync, role, part, (uint32_t)PGM_CPARTS);
+                    else pgm_terms_helper<2, false>(J, item.band, L.pool, lane, fsync, role, part, (uint32_t)PGM_CPARTS);
                 }
             }
         }
-        if (trace && threadIdx.x == 0) trace[6 * it + 2] = __builtin_amdgcn_s_memrealtime();
         if (last_band) {
             // The last band of a job is the last one to finish.  Its traceback is not this kernel's business (the walker's code in
             // here cost the sweeps 40 VGPRs, and a worker that walks for 0.6 ms sweeps nothing): pgm_tb_kernel follows on the stream.
@@ -2862,7 +2805,7 @@ __global__ void __launch_bounds__(64 * PGM_WAVES, 1) pgm_fill_kernel(const PgmJo
             if (threadIdx.x == 0) J.times[0] = __builtin_amdgcn_s_memrealtime();
             if (threadIdx.x == 0 && __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
                 J.result->score = 0.f; J.result->n_tr_indels = 0; J.result->len = 0; J.result->status = PGM_ERR_DEVICE; J.hresult->score = 0.f; J.hresult->n_tr_indels = 0; J.hresult->len = 0; __threadfence_system(); __hip_atomic_store(&J.hresult->status, (int32_t)PGM_ERR_DEVICE, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            } else if (threadIdx.x == 0) pgm_tbq_push(sync, tbq_off, item.job);
+            }
         }
     }
 }
@@ -2880,7 +2823,7 @@ __global__ void __launch_bounds__(64 * PGM_WAVES, 1) pgm_fill_kernel(const PgmJo
 // sweeping wavefronts each — and [nnarrow, nbands) WIDE bands that need up to a quarter (a 32-step history: the middle levels of a
 // guide tree) — the remaining workers, PGM_WIDE_WAVES sweeping wavefronts each (the others leave).
 __global__ void __launch_bounds__(64 * PGM_WAVES, 1) pgm_band_kernel(const PgmJob *__restrict__ jobs, const PgmItem *__restrict__ bands, uint32_t nnarrow, uint32_t nbands,
-                                                                  uint32_t nworkers_narrow, int *__restrict__ sync, uint32_t spin_limit, uint32_t stall_job, uint32_t stall_band, uint32_t tbq_off) {
+                                                                  uint32_t nworkers_narrow, int *__restrict__ sync, uint32_t spin_limit, uint32_t stall_job, uint32_t stall_band) {
     __shared__ __attribute__((aligned(16))) uint8_t pool[PGM_POOL];
     int *abort_flag = sync;
     const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -2903,29 +2846,23 @@ __global__ void __launch_bounds__(64 * PGM_WAVES, 1) pgm_band_kernel(const PgmJo
         const PgmJob &J = jobs[item.job];
         const uint32_t b = item.band;
         const bool stall = item.job == stall_job && b == stall_band;
-        if (J.has_extras) pgm_sweep_band<1, false>(J, b, slot, lane, abort_flag, aborted, spin_limit, stall, nullptr, nullptr, 0u);
-        else pgm_sweep_band<0, false>(J, b, slot, lane, abort_flag, aborted, spin_limit, stall, nullptr, nullptr, 0u);
+        if (J.has_extras) pgm_sweep_band<1>(J, b, slot, lane, abort_flag, aborted, spin_limit, stall, nullptr);
+        else pgm_sweep_band<0>(J, b, slot, lane, abort_flag, aborted, spin_limit, stall, nullptr);
         if (b + 1u == J.nb && lane == 0) J.times[0] = __builtin_amdgcn_s_memrealtime();
         if (b + 1u == J.nb && lane == 0 && __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {   // an aborted batch leaves its records here
             J.result->score = 0.f; J.result->n_tr_indels = 0; J.result->len = 0; J.result->status = PGM_ERR_DEVICE; J.hresult->score = 0.f; J.hresult->n_tr_indels = 0; J.hresult->len = 0; __threadfence_system(); __hip_atomic_store(&J.hresult->status, (int32_t)PGM_ERR_DEVICE, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        } else if (b + 1u == J.nb && lane == 0) pgm_tbq_push(sync, tbq_off, item.job);
+        }
     }
 }
 
 // ---------------------------------------------------------------------------------------------
 // Tracebacks of the jobs the sweep kernels (pgm_fill_kernel, pgm_crit_kernel, pgm_band_kernel) have swept, and the pre-linking that
-// makes the long ones short.  One worker of 512 threads per CU.  A worker takes jobs until there is none left; from then on (and
-// while the job it has claimed is still being swept) it pre-links grid tiles of the corridors of the tracebacks under way
+// makes the long ones short.  One worker of 512 threads per CU.  A worker takes jobs until there is none left; from then on it
+// pre-links grid tiles of the corridors of the tracebacks under way
 // (pgm_prelink_tile), in the order their walkers will reach them, and leaves when the last traceback has finished.
 //
-// Two ways of getting jobs:
-//   tbq_off == 0  the kernel FOLLOWS a sweep kernel on its stream (every cell final and visible): entry k of `list`, largest job first
-//   tbq_off != 0  the kernel runs BESIDE the sweep kernels from the start of the stage, on CUs of its own (round 4: with the sweeps
-//                 fast, a traceback that only starts when its whole launch is through was the longest tail of the stage): the worker
-//                 that completes a job's last band appends the job to the ready queue sync_[tbq_off ..] (pgm_tbq_push); a worker
-//                 here claims queue position k, waits for its entry (agent-scope acquire: the job's cells were written through by
-//                 wavefronts that waited for their stores before they published their progress) and walks that job.
-//   walk == 0     pre-link only: instances that follow a sweep kernel on its CUs and lend them to the tracebacks still under way.
+// The kernel FOLLOWS a sweep kernel on its stream (every cell final and visible) and takes entry k of `list`, largest job first.
+// walk == 0: pre-link only (an instance that follows a sweep kernel on its CUs and lends them to the tracebacks still under way).
 // All grids of a stage are resident together (their workers add up to the CUs of the device).  Round 3 ran this kernel beside the
 // sweeps with its grid WAITING for CUs and saw the sweeps stop for a minute in one launch of a few hundred: every sweep worker was
 // resident (counters), ticket 250 of 787 taken, bands with a finished predecessor not started, the traceback grid with zero CUs.
@@ -2934,18 +2871,14 @@ __global__ void __launch_bounds__(64 * PGM_WAVES, 1) pgm_band_kernel(const PgmJo
 // (they keep their place in the list but make no progress) to let the other in, which cannot make progress either while the first
 // still owns work it needs; every switch costs milliseconds, and a poll budget counted in polls, not in time, stretched the
 // round trips to a minute.  Hence the rule, enforced by the host (cu_shares): no grid of a stage ever waits for a CU.
-template <bool DBG>
 __global__ void __launch_bounds__(64 * PGM_WAVES, 1) pgm_tb_kernel(const PgmJob *__restrict__ jobs, const int2 *__restrict__ list, uint32_t ntb, int *__restrict__ sync_,
-                                                                unsigned long long *__restrict__ trace, uint32_t spin_limit, uint32_t lq_off, uint32_t sybase,
-                                                                uint32_t tbq_off, uint32_t walk) {
-    if (!DBG) trace = nullptr;
+                                                                uint32_t spin_limit, uint32_t lq_off, uint32_t sybase, uint32_t walk) {
     __shared__ __attribute__((aligned(16))) union { PgmTbLds t; PgmLkLds g; } L;
     __shared__ int cmd_lds, arg_lds;
     // (a batch has up to two instances of this kernel — behind pgm_band_kernel and behind pgm_fill_kernel — each with its own
     // list, counters (sybase) and announcements)
     int *abort_flag = sync_, *sync = sync_ + sybase, *lq = sync + PGM_SY_LQ_N, *lq_ids = sync_ + lq_off;
     bool walking = walk != 0u;   // there may be a job left to take
-    int claimed = -1;            // (thread 0, tbq_off != 0) position of the ready queue this worker has claimed and is waiting for
     uint32_t lk_backoff = 0u, lk_first = 0u;   // (thread 0: first announcement that may still have tiles)
     // the worker gives up — and says so: abort flag — after spin_limit idle polls (the hand-off test's knob) or, by default, when
     // nothing has happened for PGM_IDLE_LIMIT_TICKS of the real-time counter (not after a number of polls: a poll's length varies)
@@ -2959,18 +2892,9 @@ __global__ void __launch_bounds__(64 * PGM_WAVES, 1) pgm_tb_kernel(const PgmJob 
             else if ((spin_limit && polls > spin_limit) || (!spin_limit && (polls & 255u) == 255u && __builtin_amdgcn_s_memrealtime() - idle_since > PGM_IDLE_LIMIT_TICKS)) {
                 __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 cmd = -1;
-            } else if (walking && tbq_off == 0u) {
+            } else if (walking) {
                 const uint32_t k = (uint32_t)__hip_atomic_fetch_add(sync + PGM_SY_TBQ_N, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (k < ntb) { cmd = -3; arg_lds = list[k].x; } else cmd = -5;
-            } else if (walking) {
-                if (claimed < 0) {
-                    const uint32_t k = (uint32_t)__hip_atomic_fetch_add(sync + PGM_SY_TBQ_N, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (k < ntb) claimed = (int)k; else cmd = -5;
-                }
-                if (claimed >= 0) {
-                    const int id = __hip_atomic_load(sync_ + tbq_off + claimed, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-                    if (id != 0) { cmd = -3; arg_lds = id - 1; claimed = -1; }
-                }
             }
             if (cmd == -2 && (polls & ((1u << lk_backoff) - 1u)) == 0u) {
                 // pre-link: the first announcements first (the jobs are taken largest first, so these are the longest walks), at most
@@ -3005,18 +2929,9 @@ __global__ void __launch_bounds__(64 * PGM_WAVES, 1) pgm_tb_kernel(const PgmJob 
         if (threadIdx.x == 0) idle_since = __builtin_amdgcn_s_memrealtime();
         if (cmd == -3) {
             const int jid = arg_lds;
-            int it = 0;   // (the job's last item of the work list: the timeline's slot; tools build, following a kernel)
-            if (trace) for (uint32_t k = 0; k < ntb; ++k) if (list[k].x == jid) it = list[k].y;
-            if (tbq_off != 0u) {   // the job's cells come from other CUs of this very stage: nothing stale in this CU's cache
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-            }
-            pgm_traceback_job(jobs[jid], L.t, (int)threadIdx.x, 64 * PGM_WAVES, trace ? trace + 6 * it + 4 : nullptr, lq, lq_ids, (uint32_t)jid);
+            pgm_traceback_job(jobs[jid], L.t, (int)threadIdx.x, 64 * PGM_WAVES, lq, lq_ids, (uint32_t)jid);
             if (threadIdx.x == 0) jobs[jid].times[1] = __builtin_amdgcn_s_memrealtime();
-            if (trace && threadIdx.x == 0) trace[6 * it + 3] = __builtin_amdgcn_s_memrealtime();
         } else {
-            if (tbq_off != 0u) { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); }
             pgm_prelink_tile(jobs[arg_lds], L.g, (uint32_t)cmd, (int)threadIdx.x);
         }
     }
@@ -3032,7 +2947,7 @@ __global__ void __launch_bounds__(64 * PGM_WAVES, 1) pgm_tb_kernel(const PgmJob 
 #define PGM_LEAN_LDS (8 * PGM_LEAN_RING * 8 > 49152 ? 8 * PGM_LEAN_RING * 8 : 49152)
 template <int R>
 __global__ void __launch_bounds__(64 * PGM_WAVES, 2) pgm_lean_kernel(const PgmJob *__restrict__ jobs, const uint32_t *__restrict__ list, uint32_t nlist,
-                                                                  int *__restrict__ sync, unsigned long long *__restrict__ trace, uint32_t spin_limit) {
+                                                                  int *__restrict__ sync, uint32_t spin_limit) {
     __shared__ __attribute__((aligned(16))) uint8_t pool[PGM_LEAN_LDS];   // rings of the sweep; windows and mapping block of the walk
     __shared__ __attribute__((aligned(16))) int fsync[16];                // [0..7] columns produced, [8..15] columns consumed by wavefront w
     __shared__ int item_lds, tb_go;
@@ -3053,7 +2968,6 @@ __global__ void __launch_bounds__(64 * PGM_WAVES, 2) pgm_lean_kernel(const PgmJo
         const int it = item_lds;
         if (it < 0) break;
         const PgmJob &J = jobs[list[it]];
-        if (trace && threadIdx.x == 0) { trace[6 * it] = blockIdx.x; trace[6 * it + 1] = __builtin_amdgcn_s_memrealtime(); trace[6 * it + 2] = 0; trace[6 * it + 3] = 0; trace[6 * it + 4] = 0; trace[6 * it + 5] = 0; }
         const bool tabmode = J.tabhdr != nullptr && pgm_gld(J.tabhdr) == 0;   // (wave-uniform: every node of both graphs has a class)
         if (tabmode) {
             // the job's score table: entry (class of the row, class of the column) from one node of either class, with the operations of
@@ -3077,7 +2991,6 @@ __global__ void __launch_bounds__(64 * PGM_WAVES, 2) pgm_lean_kernel(const PgmJo
         }
         else if (J.keep_cells) pgm_sweep_chain<R, true>(J, role, lane, pool, fsync, abort_flag, aborted, spin_limit);
         else pgm_sweep_chain<R, false>(J, role, lane, pool, fsync, abort_flag, aborted, spin_limit);
-        if (trace && threadIdx.x == 0) trace[6 * it + 2] = __builtin_amdgcn_s_memrealtime();
         __syncthreads();
         if (threadIdx.x == 0) {
             J.times[0] = __builtin_amdgcn_s_memrealtime();
@@ -3088,11 +3001,9 @@ __global__ void __launch_bounds__(64 * PGM_WAVES, 2) pgm_lean_kernel(const PgmJo
         __syncthreads();
         if (tb_go != 0) {
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            if (trace && threadIdx.x == 0) trace[6 * it + 5] = __builtin_amdgcn_s_memrealtime();   // (the walker's statistics are relative to this)
-            pgm_traceback_chain<R>(J, pool, &tb_len, (int)threadIdx.x, 64 * PGM_WAVES, trace ? trace + 6 * it + 4 : nullptr);
+            pgm_traceback_chain<R>(J, pool, &tb_len, (int)threadIdx.x, 64 * PGM_WAVES);
             if (threadIdx.x == 0) J.times[1] = __builtin_amdgcn_s_memrealtime();
         }
-        if (trace && threadIdx.x == 0) trace[6 * it + 3] = __builtin_amdgcn_s_memrealtime();
     }
 }
 

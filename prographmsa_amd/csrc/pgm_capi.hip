@@ -30,13 +30,6 @@
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &m) { g_err = m; return code; }
-// Experiment switches of tools/ (timeline, strip-down variants, work-list parameters) exist only in the tools build of the
-// library (make tools: -DPGM_TOOLS, lib/libpgm_hip_tools.so); the release library reads none of them.
-#ifdef PGM_TOOLS
-static const char *tools_env(const char *k) { return getenv(k); }
-#else
-static const char *tools_env(const char *) { return nullptr; }
-#endif
 #define HIPCHK(x)                                                                                   \
     do {                                                                                            \
         hipError_t e_ = (x);                                                                        \
@@ -58,7 +51,6 @@ struct pgm_ctx {
     hipStream_t stream2 = nullptr;   // the lean kernel runs beside the fill kernel (pgm_lean_kernel)
     hipStream_t stream3 = nullptr;   // ... and so does the band kernel (pgm_band_kernel)
     hipStream_t stream4 = nullptr;   // ... and the fill kernel's launch for the longest chains
-    hipStream_t stream5 = nullptr;   // ... and the traceback kernel that runs beside them
     // The big buffers of a destroyed batch are kept for the next one (a progressive alignment issues one batch per tree
     // level: hipMalloc / hipFree of several GB per call would dominate the call).  Slot k holds at most one buffer.
     enum { C_IN, C_WORK, C_CELLS, C_OUT, C_S, C_HOST, C_HIN, C_SMALL, C_SLOTS };   // C_HOST, C_HIN: pinned host memory; C_SMALL: the batch's counters, job descriptors, work list
@@ -144,7 +136,6 @@ struct DevLayout {  // sizes of device-only regions
     }
 };
 
-#define PGM_LEAN_RSHIFT_DEFAULT 1   /* rows per lane of the lean sweep: R = 1 << rshift (the release library: 2) */
 struct pgm_align_batch {
     uint32_t njobs = 0;
     uint64_t cells = 0;
@@ -171,8 +162,6 @@ struct pgm_align_batch {
     PgmItem *d_bands = nullptr;
     unsigned long long *d_times = nullptr;   // per job {last band complete, traceback published}, then the launch's start (ticks of 10 ns)
     hipEvent_t ev_join_b = nullptr;
-    uint32_t ntb_beside_workers = 0, tbq_off = 0;   // pgm_tb_kernel beside the sweeps: its workers (0: the tracebacks follow their launches), its ready queue inside d_sync
-    hipEvent_t ev_join_t = nullptr;
     bool crit_c3 = false, rest_c3 = false;   // every item of the launch for the longest chains / of the main launch belongs to a crit3 job: pgm_crit_kernel sweeps that list
     uint32_t ncrit = 0, ncrit_workers = 0, ntb_c = 0;   // the first ncrit items of the work list: the jobs with the longest chains, swept by a launch of their own on their own CUs; their tracebacks
     hipEvent_t ev_join_c = nullptr;
@@ -180,13 +169,11 @@ struct pgm_align_batch {
     uint32_t lq_off = 0, ntb = 0, ntb_workers = 0;   // pre-link announcements inside d_sync; jobs of the general path (one traceback each); workers of pgm_tb_kernel
     int2 *d_tblist = nullptr;         // those jobs, largest first: (job, its last item of the work list)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // stream -> stream2 after the emission kernel, stream2 -> stream after the lean kernel
-    unsigned long long *d_trace = nullptr;   // PGM_FILL_TRACE=file: per-item timeline, written by fetch (tools only)
-    unsigned long long *d_c3dbg = nullptr;   // PGM_C3_DBG (tools build): wait statistics of pgm_crit_kernel, 64 words per item, printed by fetch
     uint32_t test_spin_limit = 0, test_stall_job = 0xFFFFFFFFu, test_stall_band = 0;   // pgm_align_batch_test_stall
     double acc_ms[3] = {0, 0, 0};     // device time of prep / emission / fill (+ lean kernel + tracebacks) summed over the launches fetched since the last reset
     uint32_t acc_n = 0;
     bool ev_pending = false;          // the last launch recorded its stage events and they have not been read yet
-    uint32_t nitems = 0, lean_rshift = PGM_LEAN_RSHIFT_DEFAULT;
+    uint32_t nitems = 0;
     uint32_t nworkers = 0, maxnblk = 0;
     PgmJob *d_jobs = nullptr;
     uint32_t *d_order = nullptr;
@@ -223,7 +210,6 @@ int pgm_ctx_create(int device, pgm_ctx **out) {
     HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     HIPCHK(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
     HIPCHK(hipStreamCreateWithFlags(&c->stream3, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&c->stream5, hipStreamNonBlocking));
     {   // (the launch of the longest chains on the highest stream priority the device offers)
         int lo = 0, hi = 0;
         if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) { (void)hipGetLastError(); lo = hi = 0; }
@@ -291,7 +277,6 @@ void pgm_ctx_destroy(pgm_ctx *ctx) {
     for (int k = 0; k < 2; ++k) if (ctx->sc_ev[k]) (void)hipEventDestroy(ctx->sc_ev[k]);
     for (int k = 0; k < pgm_ctx::C_SLOTS; ++k)
         if (ctx->cache_ptr[k]) slot_free(k, ctx->cache_ptr[k]);
-    if (ctx->stream5) (void)hipStreamDestroy(ctx->stream5);
     if (ctx->stream4) (void)hipStreamDestroy(ctx->stream4);
     if (ctx->stream3) (void)hipStreamDestroy(ctx->stream3);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
@@ -527,9 +512,6 @@ static void layout_job(BatchLayout &L, uint32_t n1, uint32_t n2, uint32_t dim, u
     // pre-linked traceback tiles (PgmJob::ltab): the long jobs of the general path (from PGM_LK_MIN_ROWS rows: the ones whose
     // tracebacks end a batch; pre-linking every job of the headline batch — 26 000 tiles — cost the sweeps still running 30 %)
     o.lrows = (!lean && n1 - 1 >= PGM_LK_MIN_ROWS && n2 - 1 >= 4 * PGM_LK_T) ? (n1 - 1 + PGM_LK_T - 1) / PGM_LK_T : 0u;
-#ifdef PGM_NO_PRELINK   /* A/B builds only: same kernels, no pre-linking */
-    o.lrows = 0u;
-#endif
     o.lcols = (n2 - 1 + PGM_LK_T - 1) / PGM_LK_T;
     o.ltab = L.W.take(std::max<size_t>((size_t)o.lrows * PGM_LK_W * PGM_LK_TAB * 2, 16), 256);
     o.lready = L.sync_ints;                              // tiles complete per grid row, then the claim counter and the walker's row (zeroed with the progress counters)
@@ -623,20 +605,16 @@ static hipError_t scratch_events(pgm_ctx *ctx) {
 //   (chain >= 1.5 x the parallel time) wants the other launches' traffic out of the chain's way early: the lean queue gets the
 //   fewest CUs with which it ends within 0.6 t_goal, the band queue within 0.75 t_goal (measured on the headline batch, round 3);
 //   a batch bound by throughput wants every queue to end together: the factors go to 1 as the chain's lead shrinks to nothing.
-//   tb     the traceback kernel that runs beside the sweeps (ntb = 0: the tracebacks follow their launches instead): a third of its
-//          work over t_goal — the jobs of a level end together, late in the stage, when the CUs of the sweep kernels join in (an
-//          instance of the kernel follows each of them); the workers here take the early finishers — at most a third of the CUs
 //   rest   the main launch: what is left, never less than its own work needs to end within t_goal — if the shares do not fit,
 //          they are cut back in proportion.
-struct CuShares { uint32_t lean, band, crit, rest, tb, rest_need; double t_goal, fl, fb; };
-static CuShares cu_shares(uint32_t cus, double lean_cost, uint32_t nlean, double band_cost, uint32_t nbands, double rest_cost, uint32_t nrest, uint32_t ncrit, double rsweep,
-                          double tb_cost = 0.0, uint32_t ntb = 0, double tb_frac = 0.35) {
-    CuShares r = {0u, 0u, 0u, 0u, 0u, 0u, 0.0, 1.0, 1.0};
+struct CuShares { uint32_t lean, band, crit, rest, rest_need; double t_goal, fl, fb; };
+static CuShares cu_shares(uint32_t cus, double lean_cost, uint32_t nlean, double band_cost, uint32_t nbands, double rest_cost, uint32_t nrest, uint32_t ncrit, double rsweep) {
+    CuShares r = {0u, 0u, 0u, 0u, 0u, 0.0, 1.0, 1.0};
     cus = std::max(1u, cus);
-    const uint32_t queues = (nlean != 0) + (nbands != 0) + (nrest != 0) + (ntb != 0);
+    const uint32_t queues = (nlean != 0) + (nbands != 0) + (nrest != 0);
     if (ncrit != 0 && cus > queues) r.crit = std::min(std::min(ncrit, cus / 2u), cus - queues);
     const uint32_t cap = std::max(1u, cus - r.crit);
-    const double sum = (nlean ? lean_cost : 0.0) + (nbands ? band_cost : 0.0) + (nrest ? rest_cost : 0.0) + (ntb ? tb_cost : 0.0);
+    const double sum = (nlean ? lean_cost : 0.0) + (nbands ? band_cost : 0.0) + (nrest ? rest_cost : 0.0);
     const double t_par = std::max(1e-3, sum / cap);
     r.t_goal = std::max(std::max(rsweep, t_par), 1e-3);
     const double w = std::min(1.0, std::max(0.0, (rsweep / t_par - 1.0) / 0.5));
@@ -645,23 +623,22 @@ static CuShares cu_shares(uint32_t cus, double lean_cost, uint32_t nlean, double
     const uint32_t band_most = (nbands + PGM_WAVES - 1) / PGM_WAVES;
     uint32_t lean = nlean ? need(lean_cost, r.fl * r.t_goal, nlean) : 0u, band = nbands ? need(band_cost, r.fb * r.t_goal, band_most) : 0u;
     uint32_t rest = nrest ? need(rest_cost, r.t_goal, nrest) : 0u;
-    uint32_t tb = ntb ? need(tb_frac * tb_cost, r.t_goal, std::max(1u, std::min(ntb, cap / 3u))) : 0u;
-    if (lean + band + rest + tb > cap) {   // cut back in proportion to the work, at least one CU each (cap >= queues unless the device has fewer CUs than queues)
-        const double scale = (double)cap / (double)(lean + band + rest + tb);
+    if (lean + band + rest > cap) {   // cut back in proportion to the work, at least one CU each (cap >= queues unless the device has fewer CUs than queues)
+        const double scale = (double)cap / (double)(lean + band + rest);
         auto cut = [&](uint32_t v) { return v ? std::max(1u, (uint32_t)std::floor(v * scale)) : 0u; };
-        lean = cut(lean); band = cut(band); rest = cut(rest); tb = cut(tb);
-        while (lean + band + rest + tb > cap) {   // (rounding up to one CU each)
-            uint32_t *big = &rest; if (band > *big) big = &band; if (lean > *big) big = &lean; if (tb > *big) big = &tb;
+        lean = cut(lean); band = cut(band); rest = cut(rest);
+        while (lean + band + rest > cap) {   // (rounding up to one CU each)
+            uint32_t *big = &rest; if (band > *big) big = &band; if (lean > *big) big = &lean;
             if (*big <= 1u) break;
             --*big;
         }
     }
     r.rest_need = rest;
-    const uint32_t left = cap > lean + band + rest + tb ? cap - lean - band - rest - tb : 0u;
+    const uint32_t left = cap > lean + band + rest ? cap - lean - band - rest : 0u;
     if (nrest) rest = std::min(nrest, rest + left);          // the main launch takes what is left ...
     else if (nbands) band = std::min(band_most, band + left);   // ... or the band queue, or the lean queue
     else if (nlean) lean = std::min(nlean, lean + left);
-    r.lean = lean; r.band = band; r.rest = rest; r.tb = tb;
+    r.lean = lean; r.band = band; r.rest = rest;
     return r;
 }
 
@@ -695,29 +672,15 @@ static hipError_t launch_all(pgm_ctx *ctx, pgm_align_batch *b, bool timed) {
     else hipLaunchKernelGGL((pgm_emission_skew_kernel<64, 1>), eg, dim3(4 * PGM_ROWS), 0, s, b->d_jobs);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (timed && (e = hipEventRecord(b->ev[2], s)) != hipSuccess) return e;
-    // One kernel does the DP fill of every band and, right after a job's last band, that job's traceback.
-    const char *dbg = tools_env("PGM_FILL_DBG");   // 8: the fill alone, no traceback (tools build)
-    const int dbgv = dbg ? atoi(dbg) : 0;
+    // The sweep kernels, then the traceback kernel behind each of them on its stream.
     // test knobs for the hand-off time-out path (tests/test_gpu_align.py): a shorter spin limit, and one band of one job
     // that never publishes its progress ("job:band"), so that the band below it times out and the batch aborts
     const uint32_t spin_limit = b->test_spin_limit ? b->test_spin_limit : PGM_SPIN_LIMIT, stall_job = b->test_stall_job, stall_band = b->test_stall_band;   // (pgm_align_batch_test_stall)
-    // timing experiments only (results are garbage): 1 = the cell stores are dropped, 2 = the sweeping wavefront of a MODE 2 band
-    // does not merge the helpers' terms, 4 = no helpers, 8 = no history records
-    const uint32_t dbg_flags = tools_env("PGM_TEST_NOSTORE") ? (uint32_t)atoi(tools_env("PGM_TEST_NOSTORE")) : 0u;   // (tools build)
     const bool fork = b->nlean != 0;
     const bool bandk = b->nbands != 0;
-    const bool tbk = (b->nitems != 0 || bandk) && (b->ntb + b->ntb_c + b->ntb_b) != 0 && dbgv != 8 && !tools_env("PGM_NO_TBK");   // the traceback kernel behind the fill kernel (PGM_NO_TBK, tools build: the sweeps alone, every result stays pending)
+    const bool tbk = (b->nitems != 0 || bandk) && (b->ntb + b->ntb_c + b->ntb_b) != 0;   // the traceback kernel behind the sweep kernels
     const bool critk = b->ncrit != 0;
-    const uint32_t ntb_all = b->ntb + b->ntb_c + b->ntb_b;
-    const bool beside = tbk && b->ntb_beside_workers != 0 && !b->d_trace;   // the tracebacks run beside the sweeps (else: behind their launches)
-    const uint32_t tbq = beside ? b->tbq_off : 0u;
-    if ((fork || bandk || critk || beside) && (e = hipEventRecord(b->ev_fork, s)) != hipSuccess) return e;
-    if (beside) {   // first of all, so that its workers are resident when the sweep grids fill the rest of the device
-        if ((e = hipStreamWaitEvent(ctx->stream5, b->ev_fork, 0)) != hipSuccess) return e;
-        hipLaunchKernelGGL((pgm_tb_kernel<false>), dim3(b->ntb_beside_workers), dim3(64 * PGM_WAVES), 0, ctx->stream5, b->d_jobs, b->d_tblist, ntb_all, b->d_sync, b->d_trace, b->test_spin_limit, b->lq_off, 0u, tbq, 1u);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        if ((e = hipEventRecord(b->ev_join_t, ctx->stream5)) != hipSuccess) return e;
-    }
+    if ((fork || bandk || critk) && (e = hipEventRecord(b->ev_fork, s)) != hipSuccess) return e;
     if (critk && (e = hipStreamWaitEvent(ctx->stream4, b->ev_fork, 0)) != hipSuccess) return e;
     if (fork && (e = hipStreamWaitEvent(ctx->stream2, b->ev_fork, 0)) != hipSuccess) return e;
     if (bandk && (e = hipStreamWaitEvent(ctx->stream3, b->ev_fork, 0)) != hipSuccess) return e;
@@ -725,64 +688,44 @@ static hipError_t launch_all(pgm_ctx *ctx, pgm_align_batch *b, bool timed) {
     // The launch of the longest chains goes out on the PRIMARY stream, right behind the emission kernel; the main launch on stream4, behind
     // the fork event like the lean and band kernels (a kernel behind an event of another stream starts 50-60 us later: measured on the
     // root of the headline batch, whose traceback is the last thing the stage waits for, when it was the other way round).
-    const bool swap_streams = critk && !tools_env("PGM_C3_DBG");
-    hipStream_t sc = swap_streams ? s : ctx->stream4, sr = swap_streams ? ctx->stream4 : s;
-#ifdef PGM_TOOLS
-    if (tools_env("PGM_C3_DBG") && !b->d_c3dbg && b->nitems && hipMalloc((void **)&b->d_c3dbg, 512 * (size_t)b->nitems) != hipSuccess) b->d_c3dbg = nullptr;
-    if (b->d_c3dbg) (void)hipMemsetAsync(b->d_c3dbg, 0, 512 * (size_t)b->nitems, s);
-    if (critk && b->crit_c3 && b->d_c3dbg) hipLaunchKernelGGL((pgm_crit_kernel<true>), dim3(b->ncrit_workers), dim3(64 * PGM_C3_WAVES), 0, sc, b->d_jobs, b->d_items, b->ncrit, b->d_sync, spin_limit, stall_job, stall_band, (uint32_t)PGM_SY_CRIT_TICKET, b->d_c3dbg, tbq);
-    else
-#endif
-    if (critk && b->crit_c3) hipLaunchKernelGGL((pgm_crit_kernel<false>), dim3(b->ncrit_workers), dim3(64 * PGM_C3_WAVES), 0, sc, b->d_jobs, b->d_items, b->ncrit, b->d_sync, spin_limit, stall_job, stall_band, (uint32_t)PGM_SY_CRIT_TICKET, (unsigned long long *)nullptr, tbq);
-    else if (critk) hipLaunchKernelGGL((pgm_fill_kernel<false, false>), dim3(b->ncrit_workers), dim3(64 * PGM_WAVES), 0, sc, b->d_jobs, b->d_items, b->ncrit, b->d_sync, b->d_trace, spin_limit, stall_job, stall_band, dbg_flags, (uint32_t)PGM_SY_CRIT_TICKET, tbq);
-    if (nrest == 0) {}   // (no job for this launch)
-#ifdef PGM_TOOLS
-    else if (b->rest_c3 && b->d_c3dbg) hipLaunchKernelGGL((pgm_crit_kernel<true>), dim3(b->nworkers), dim3(64 * PGM_C3_WAVES), 0, sr, b->d_jobs, b->d_items + b->ncrit, nrest, b->d_sync, spin_limit, stall_job, stall_band, 1u, b->d_c3dbg + 64 * (size_t)b->ncrit, tbq);
-#endif
-    else if (b->rest_c3) hipLaunchKernelGGL((pgm_crit_kernel<false>), dim3(b->nworkers), dim3(64 * PGM_C3_WAVES), 0, sr, b->d_jobs, b->d_items + b->ncrit, nrest, b->d_sync, spin_limit, stall_job, stall_band, 1u, (unsigned long long *)nullptr, tbq);
-    else if (dbgv == 8) hipLaunchKernelGGL((pgm_fill_kernel<true, true>), dim3(b->nworkers), dim3(64 * PGM_WAVES), 0, sr, b->d_jobs, b->d_items + b->ncrit, nrest, b->d_sync, b->d_trace, spin_limit, stall_job, stall_band, dbg_flags, 1u, tbq);
-    else if (b->d_trace || dbg_flags) hipLaunchKernelGGL((pgm_fill_kernel<false, true>), dim3(b->nworkers), dim3(64 * PGM_WAVES), 0, sr, b->d_jobs, b->d_items + b->ncrit, nrest, b->d_sync, b->d_trace, spin_limit, stall_job, stall_band, dbg_flags, 1u, tbq);
-    else hipLaunchKernelGGL((pgm_fill_kernel<false, false>), dim3(b->nworkers), dim3(64 * PGM_WAVES), 0, sr, b->d_jobs, b->d_items + b->ncrit, nrest, b->d_sync, b->d_trace, spin_limit, stall_job, stall_band, dbg_flags, 1u, tbq);
+    hipStream_t sc = critk ? s : ctx->stream4, sr = critk ? ctx->stream4 : s;
+    // a part of the work list, swept by pgm_crit_kernel (every item of it belongs to a crit3 job) or by pgm_fill_kernel
+    auto sweep = [&](hipStream_t st, uint32_t workers, const PgmItem *list, uint32_t n, bool c3, uint32_t ticket_off) {
+        if (c3) hipLaunchKernelGGL(pgm_crit_kernel, dim3(workers), dim3(64 * PGM_C3_WAVES), 0, st, b->d_jobs, list, n, b->d_sync, spin_limit, stall_job, stall_band, ticket_off);
+        else hipLaunchKernelGGL(pgm_fill_kernel, dim3(workers), dim3(64 * PGM_WAVES), 0, st, b->d_jobs, list, n, b->d_sync, spin_limit, stall_job, stall_band, ticket_off);
+    };
+    // the tracebacks of the jobs tblist[first, first + n), behind their sweep kernel on its stream and its CUs
+    auto tracebacks = [&](hipStream_t st, uint32_t workers, uint32_t first, uint32_t n, uint32_t lq_off, uint32_t sybase) {
+        hipLaunchKernelGGL(pgm_tb_kernel, dim3(workers), dim3(64 * PGM_WAVES), 0, st, b->d_jobs, b->d_tblist + first, n, b->d_sync, b->test_spin_limit, lq_off, sybase, 1u);
+    };
+    if (critk) sweep(sc, b->ncrit_workers, b->d_items, b->ncrit, b->crit_c3, (uint32_t)PGM_SY_CRIT_TICKET);
+    if (nrest != 0) sweep(sr, b->nworkers, b->d_items + b->ncrit, nrest, b->rest_c3, 1u);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (fork) {
         // the lean jobs' kernel, launched after the fill kernel (whose grid leaves nlean_workers CUs free)
-        unsigned long long *tr2 = b->d_trace ? b->d_trace + 22 * (size_t)b->nitems : nullptr;
-#ifdef PGM_TOOLS
-        if (b->lean_rshift == 2u) hipLaunchKernelGGL((pgm_lean_kernel<4>), dim3(b->nlean_workers), dim3(64 * PGM_WAVES), 0, ctx->stream2, b->d_jobs, b->d_lean, b->nlean, b->d_sync, tr2, spin_limit);
-        else if (b->lean_rshift == 0u) hipLaunchKernelGGL((pgm_lean_kernel<1>), dim3(b->nlean_workers), dim3(64 * PGM_WAVES), 0, ctx->stream2, b->d_jobs, b->d_lean, b->nlean, b->d_sync, tr2, spin_limit);
-        else
-#endif
-        hipLaunchKernelGGL((pgm_lean_kernel<2>), dim3(b->nlean_workers), dim3(64 * PGM_WAVES), 0, ctx->stream2, b->d_jobs, b->d_lean, b->nlean, b->d_sync, tr2, spin_limit);
+        hipLaunchKernelGGL((pgm_lean_kernel<2>), dim3(b->nlean_workers), dim3(64 * PGM_WAVES), 0, ctx->stream2, b->d_jobs, b->d_lean, b->nlean, b->d_sync, spin_limit);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     const uint32_t njp = (b->njobs + 3u) / 4u * 4u;
     if (bandk) {
         // the bands of the MODE 0 / 1 jobs, one per wavefront, on their share of the CUs; their tracebacks follow on the same
         // stream and the same CUs (the band queue is done well before the chains of the fill kernel are)
-        hipLaunchKernelGGL(pgm_band_kernel, dim3(b->nband_workers), dim3(64 * PGM_WAVES), 0, ctx->stream3, b->d_jobs, b->d_bands, b->nbands_narrow, b->nbands, b->nband_workers - b->nwide_workers, b->d_sync, spin_limit, stall_job, stall_band, tbq);
+        hipLaunchKernelGGL(pgm_band_kernel, dim3(b->nband_workers), dim3(64 * PGM_WAVES), 0, ctx->stream3, b->d_jobs, b->d_bands, b->nbands_narrow, b->nbands, b->nband_workers - b->nwide_workers, b->d_sync, spin_limit, stall_job, stall_band);
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        // (tracebacks beside the sweeps: what follows a sweep kernel on its CUs joins in — the jobs that are ready and not yet claimed, then pre-linking)
-        if (beside) hipLaunchKernelGGL((pgm_tb_kernel<false>), dim3(b->nband_workers), dim3(64 * PGM_WAVES), 0, ctx->stream3, b->d_jobs, b->d_tblist, ntb_all, b->d_sync, b->d_trace, b->test_spin_limit, b->lq_off, 0u, tbq, 1u);
-        else if (tbk && b->ntb_b) hipLaunchKernelGGL((pgm_tb_kernel<false>), dim3(b->ntb_b_workers), dim3(64 * PGM_WAVES), 0, ctx->stream3, b->d_jobs, b->d_tblist + b->ntb + b->ntb_c, b->ntb_b, b->d_sync, b->d_trace, b->test_spin_limit, b->lq_off + njp, 8u, 0u, 1u);
+        if (tbk && b->ntb_b) tracebacks(ctx->stream3, b->ntb_b_workers, b->ntb + b->ntb_c, b->ntb_b, b->lq_off + njp, 8u);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         if ((e = hipEventRecord(b->ev_join_b, ctx->stream3)) != hipSuccess) return e;
     }
     if (critk) {
-        if (beside) hipLaunchKernelGGL((pgm_tb_kernel<false>), dim3(b->ncrit_workers), dim3(64 * PGM_WAVES), 0, sc, b->d_jobs, b->d_tblist, ntb_all, b->d_sync, b->d_trace, b->test_spin_limit, b->lq_off, 0u, tbq, 1u);
-        else if (tbk && b->ntb_c) hipLaunchKernelGGL((pgm_tb_kernel<false>), dim3(b->ncrit_workers), dim3(64 * PGM_WAVES), 0, sc, b->d_jobs, b->d_tblist + b->ntb, b->ntb_c, b->d_sync, b->d_trace, b->test_spin_limit, b->lq_off + 2 * njp, 16u, 0u, 1u);
+        if (tbk && b->ntb_c) tracebacks(sc, b->ncrit_workers, b->ntb, b->ntb_c, b->lq_off + 2 * njp, 16u);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    if (beside && nrest != 0) {
-        hipLaunchKernelGGL((pgm_tb_kernel<false>), dim3(b->nworkers), dim3(64 * PGM_WAVES), 0, sr, b->d_jobs, b->d_tblist, ntb_all, b->d_sync, b->d_trace, b->test_spin_limit, b->lq_off, 0u, tbq, 1u);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    } else if (!beside && tbk && b->ntb) {
+    if (tbk && b->ntb) {
         // the tracebacks of the fill kernel's jobs, behind it on its stream
-        if (b->d_trace) hipLaunchKernelGGL((pgm_tb_kernel<true>), dim3(b->ntb_workers), dim3(64 * PGM_WAVES), 0, sr, b->d_jobs, b->d_tblist, b->ntb, b->d_sync, b->d_trace, b->test_spin_limit, b->lq_off, 0u, 0u, 1u);
-        else hipLaunchKernelGGL((pgm_tb_kernel<false>), dim3(b->ntb_workers), dim3(64 * PGM_WAVES), 0, sr, b->d_jobs, b->d_tblist, b->ntb, b->d_sync, b->d_trace, b->test_spin_limit, b->lq_off, 0u, 0u, 1u);
+        tracebacks(sr, b->ntb_workers, 0u, b->ntb, b->lq_off, 0u);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (critk && (e = hipEventRecord(b->ev_join_c, ctx->stream4)) != hipSuccess) return e;   // (behind whatever went to stream4)
-    if (beside && (e = hipStreamWaitEvent(s, b->ev_join_t, 0)) != hipSuccess) return e;
     if (bandk && (e = hipStreamWaitEvent(s, b->ev_join_b, 0)) != hipSuccess) return e;
     if (critk && (e = hipStreamWaitEvent(s, b->ev_join_c, 0)) != hipSuccess) return e;
     if (fork && ((e = hipEventRecord(b->ev_join, ctx->stream2)) != hipSuccess || (e = hipStreamWaitEvent(s, b->ev_join, 0)) != hipSuccess)) return e;
@@ -795,10 +738,10 @@ static hipError_t launch_all(pgm_ctx *ctx, pgm_align_batch *b, bool timed) {
 extern "C" {
 
 int pgm_test_cu_shares(uint32_t cus, double lean_cost, uint32_t nlean, double band_cost, uint32_t nbands, double rest_cost, uint32_t nrest,
-                       uint32_t ncrit, double longest_chain, double tb_cost, uint32_t ntb, uint32_t *out5) {
-    if (!out5) return fail(PGM_ERR_INVALID, "null argument");
-    const CuShares r = cu_shares(cus, lean_cost, nlean, band_cost, nbands, rest_cost, nrest, ncrit, longest_chain, tb_cost, ntb);
-    out5[0] = r.lean; out5[1] = r.band; out5[2] = r.crit; out5[3] = r.rest; out5[4] = r.tb;
+                       uint32_t ncrit, double longest_chain, uint32_t *out4) {
+    if (!out4) return fail(PGM_ERR_INVALID, "null argument");
+    const CuShares r = cu_shares(cus, lean_cost, nlean, band_cost, nbands, rest_cost, nrest, ncrit, longest_chain);
+    out4[0] = r.lean; out4[1] = r.band; out4[2] = r.crit; out4[3] = r.rest;
     return PGM_OK;
 }
 
@@ -855,11 +798,9 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
         J.dp = a->dim <= 20 ? 20 : 64;
         J.ncol = c->n - 1;
         J.tsteps = J.ncol + 63;
-        // chain-only jobs: the lean sweep, R rows per lane (the band's buffer descriptor must stay below 1 GiB: see pgm_sweep_chain)
-        uint32_t lean_rshift = PGM_LEAN_RSHIFT_DEFAULT;
-        if (const char *v = tools_env("PGM_LEAN_RSHIFT")) lean_rshift = (uint32_t)std::min(2, std::max(0, atoi(v)));   // (tools build: R = 1, 2, 4)
-        b->lean_rshift = lean_rshift;
-        J.lean = (!tools_env("PGM_NO_LEAN") && two_chains[i] && ((uint64_t)J.tsteps * 1024u << lean_rshift) < (1ull << 30)) ? 1u : 0u;
+        // chain-only jobs: the lean sweep, R = 2 rows per lane (pgm_lean_kernel<2>; the band's buffer descriptor must stay below 1 GiB: see pgm_sweep_chain)
+        constexpr uint32_t lean_rshift = 1u;
+        J.lean = (two_chains[i] && ((uint64_t)J.tsteps * 1024u << lean_rshift) < (1ull << 30)) ? 1u : 0u;
         J.rshift = J.lean ? lean_rshift : 0u;
         J.nb = (a->n - 1 + (PGM_ROWS << J.rshift) - 1) / (PGM_ROWS << J.rshift);
         J.nblk = (J.tsteps + PGM_BLOCK - 1) / PGM_BLOCK;
@@ -885,8 +826,6 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
     b->s_bytes = std::max<size_t>(L.SL.bytes, 16);
     b->lq_off = (uint32_t)L.sync_ints;                   // ids of the jobs whose tracebacks have started (pre-link announcements)
     L.sync_ints += 3 * (((size_t)njobs + 3) / 4 * 4);  // (one array per instance of pgm_tb_kernel)
-    b->tbq_off = (uint32_t)L.sync_ints;                  // ready queue of the traceback kernel that runs beside the sweeps
-    L.sync_ints += ((size_t)njobs + 3) / 4 * 4 + 4;
     const size_t sync_ints = L.sync_ints;
     b->sync_ints = sync_ints;
     hipError_t alloc_err = hipSuccess, alloc_host_err = hipSuccess;
@@ -905,7 +844,6 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
                  small_bands = SM.take(sizeof(PgmItem) * std::max<size_t>(1, total_bands)), small_times = SM.take(16 * (size_t)std::max(1u, njobs) + 16);
     bool any_lean = false;
     for (uint32_t i = 0; i < njobs; ++i) any_lean = any_lean || (b->jobs[i].lean && !b->jobs[i].keep_cells);
-    if (tools_env("PGM_NO_LEAN_TABLE") || getenv("PGM_X_NO_LEAN_TABLE")) any_lean = false;   // (the second: a release-build switch for tools/ab scripts)
     const size_t small_tabhdr = SM.take(any_lean ? 4 * (size_t)PGM_TAB_HDR * njobs : 16);
     const size_t small_bytes = SM.bytes;
     std::atomic<int> alloc_state(0);   // 1: the device buffers exist (the flattening threads then upload their jobs' slices), -1: failed
@@ -955,10 +893,8 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
     const double tc1 = now_ms();
     {
         std::atomic<int> bad(-1);
-        const bool job_stats = tools_env("PGM_JOB_STATS") != nullptr;                               // tools build only
-        const bool no_helper = tools_env("PGM_NO_HELPER") != nullptr;
-        const int mode2_min_bands = tools_env("PGM_MODE2_BANDS") ? atoi(tools_env("PGM_MODE2_BANDS")) : 20;   // tools build only
-        const uint32_t mode2_min_hd = tools_env("PGM_MODE2_HD") ? (uint32_t)atoi(tools_env("PGM_MODE2_HD")) : 32u;
+        // (a job with helper wavefronts: one of at least mode2_min_bands bands, or one whose history of at least mode2_min_hd steps does not fit WIDE)
+        constexpr uint32_t mode2_min_bands = 20u, mode2_min_hd = 32u;
         // (the chain of sweeps the batch's largest job would have in pgm_crit_kernel, from the sizes alone: what the other jobs' chains are held against)
         double longest_crit_chain = 0.0;
         for (uint32_t i = 0; i < njobs; ++i)
@@ -969,7 +905,7 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
         // of the headline family alone: 2.05 -> 1.56 and 2.29 -> 1.40 ms per call; level 2, 64 jobs, would fill the device 1.6 times over
         // and stays: 2.2 against 2.4 ms).
         uint32_t promote_bands = 0xffffffffu;
-        if (!tools_env("PGM_MODE2_BANDS") && !tools_env("PGM_NO_PROMOTE")) {
+        {
             double crit_load = 0.0;
             for (uint32_t i = 0; i < njobs; ++i)
                 if (!b->jobs[i].lean) crit_load += (double)((g1[i]->n - 1 + PGM_ROWS - 1) / PGM_ROWS) * (double)(g2[i]->n - 1 + 63) * 0.42;
@@ -1000,7 +936,7 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
                 // shortens its step by a factor of 2-3, and serve the long edges from the cell storage with a prefetch.
                 const uint32_t nb_job = (g1[i]->n - 1 + PGM_ROWS - 1) / PGM_ROWS;
                 // (the helpers address the job's cell storage with 32-bit byte offsets)
-                const bool allow_long = !tools_env("PGM_NO_LONG") && (uint64_t)J.nb * J.tsteps * 1024u < (1ull << 32);
+                const bool allow_long = (uint64_t)J.nb * J.tsteps * 1024u < (1ull << 32);
                 const bool has_long = (o.s1.has_long | o.s2.has_long) != 0 && allow_long;
                 // (a job whose self-contained sweep fits a quarter of the LDS and that is not on the critical path — fewer than 20 bands —
                 // goes to pgm_band_kernel's WIDE workers, four bands per CU, instead of one band per CU with helper wavefronts)
@@ -1009,8 +945,8 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
                 const uint32_t slot1 = 2u * hD * (64u + PGM_VL) * 4u + hDX * 64u * 4u + PGM_NRING * 48u;
                 const double far_density = 0.5 * ((double)o.s1.cp[g1[i]->n] / g1[i]->n + (double)o.s2.cp[g2[i]->n] / g2[i]->n);
                 const double chain_wide = ((double)(nb_job - 1) * 78.0 + (double)(g2[i]->n - 1 + 63)) * (0.7 + 10.0 * far_density);
-                const bool fits_wide = slot1 <= (uint32_t)(PGM_POOL / PGM_WIDE_WAVES / 16 * 16) && chain_wide <= 0.9 * longest_crit_chain && !tools_env("PGM_NO_WIDE");
-                J.mode2 = (J.has_extras && ((hD >= mode2_min_hd && !fits_wide) || nb_job >= (uint32_t)mode2_min_bands || nb_job >= promote_bands || has_long) && !no_helper) ? 1u : 0u;
+                const bool fits_wide = slot1 <= (uint32_t)(PGM_POOL / PGM_WIDE_WAVES / 16 * 16) && chain_wide <= 0.9 * longest_crit_chain;
+                J.mode2 = (J.has_extras && ((hD >= mode2_min_hd && !fits_wide) || nb_job >= mode2_min_bands || nb_job >= promote_bands || has_long)) ? 1u : 0u;
                 if (J.mode2) {   // (a MODE 2 sweep keeps every on-chip distance of the graphs, whatever the number of entries of a node)
                     while (hD < o.s1.maxd_cap + o.s2.maxd_cap + (uint32_t)PGM_BLOCK) hD *= 2;
                     while (hDX < o.s2.maxd_cap + 1) hDX *= 2;
@@ -1036,8 +972,7 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
                 J.c3_off = J.slot_bytes;
                 // (and no interior node without predecessors: the chain wavefront carries no code for them)
                 J.crit3 = (J.mode2 && !J.long1 && !J.long2 && J.nov2 == 0 && o.s1.ngeneric + o.s2.ngeneric == 0 && o.s1.nkill + o.s2.nkill == 0 &&
-                           J.slot_bytes + (uint32_t)PGM_C3_BYTES <= (uint32_t)PGM_POOL && !tools_env("PGM_NO_CRIT3") && !tools_env("PGM_FILL_TRACE") &&
-                           !tools_env("PGM_TEST_NOSTORE") && !tools_env("PGM_FILL_DBG")) ? 1u : 0u;   // (the timeline and strip-down switches of the tools build belong to pgm_fill_kernel)
+                           J.slot_bytes + (uint32_t)PGM_C3_BYTES <= (uint32_t)PGM_POOL) ? 1u : 0u;
                 if (J.crit3 && J.hDX < 8u) {   // (the chain wavefront addresses a block of eight steps from one base: no ring wraps inside a block)
                     J.slot_bytes += (8u - J.hDX) * 256u; J.aux_off += (8u - J.hDX) * 256u; J.ov_off += (8u - J.hDX) * 256u; J.rh_off += (8u - J.hDX) * 256u; J.c3_off += (8u - J.hDX) * 256u;
                     J.hDX = 8u;
@@ -1047,27 +982,6 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
                 J.far_slack = std::max(1u, std::min(4u, std::min(o.s1.far_dmin, o.s2.far_dmin)));
                 J.nslots = J.mode2 ? 1u : std::max(1u, std::min((uint32_t)PGM_WAVES, (uint32_t)PGM_POOL / J.slot_bytes));
                 if (J.lean) J.nslots = PGM_WAVES;
-                if (job_stats) {   // tools: how the nodes of this job are served
-                    uint32_t gen[2] = {0, 0}, lng = 0;
-                    for (int side = 0; side < 2; ++side) {
-                        const PgmNode2 *ni = (const PgmNode2 *)(b->h_in + (side ? o.s2.ni : o.s1.ni));
-                        const uint32_t nn = side ? g2[i]->n : g1[i]->n;
-                        for (uint32_t v = 0; v < nn; ++v) { gen[side] += (ni[v].flags & PGM_NF_GENERIC) != 0; if (side) lng += PGM_NF_NLONG(ni[v].flags); }
-                    }
-                    fprintf(stderr, "pgm job %u: %u x %u mode2 %u crit3 %u slot %u B hD %u hDX %u far_slack %u generic rows %u cols %u remote row entries %u long col entries %u far nodes %u + %u overflow cols %u\n",
-                            i, g1[i]->n, g2[i]->n, J.mode2, J.crit3, J.slot_bytes, J.hD, J.hDX, J.far_slack, gen[0], gen[1], o.s1.remote, lng, o.s1.far_nodes, o.s2.far_nodes, J.nov2);
-                    for (int side = 0; side < 2; ++side) {
-                        const SideOff &so = side ? o.s2 : o.s1;
-                        const PgmNode2 *ni = (const PgmNode2 *)(b->h_in + so.ni);
-                        const uint32_t nn = side ? g2[i]->n : g1[i]->n;
-                        for (uint32_t v = 0; v < nn; ++v)
-                            if (ni[v].flags & PGM_NF_GENERIC) {
-                                uint32_t nl = 0;
-                                for (uint32_t k = so.cp[v]; k < so.cp[v + 1]; ++k) nl += so.cd[k] > (uint32_t)PGM_DCAP;
-                                fprintf(stderr, "   generic %s %u: %u far candidates, %u of them long\n", side ? "col" : "row", v, so.cp[v + 1] - so.cp[v], nl);
-                            }
-                    }
-                }
                 o.M = A.put(model[i]->M, sizeof(double) * J.dim * J.dim);
                 o.pi = A.put(model[i]->pi, sizeof(double) * J.dim);
                 if (A.overflow) { bad.store((int)i); return; }
@@ -1157,23 +1071,18 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
     std::vector<PgmItem> items;
     std::vector<uint32_t> lean_list;
     double lean_cost = 0.0, other_cost = 0.0;   // worker-microseconds of the two kernels' queues
-    uint32_t capacity = (uint32_t)ctx->prop.multiProcessorCount;
     // persistent workers: one workgroup of 8 wavefronts per CU (it owns the CU's LDS for its sweeps' histories)
-    if (const char *env_c = tools_env("PGM_FILL_WORKERS"))   // tools build only
-        capacity = std::min<uint32_t>((uint32_t)ctx->prop.multiProcessorCount, (uint32_t)std::max(1, atoi(env_c)));
+    uint32_t capacity = (uint32_t)ctx->prop.multiProcessorCount;
     std::vector<PgmItem> bands;   // pgm_band_kernel's list: one band per entry
     if (njobs) {
         struct Item { double rem, dur, gap; uint32_t job, band, count; };
         std::vector<std::vector<Item>> per_job(njobs), per_job_b(njobs), per_job_c(njobs), per_job_w(njobs);   // main launch, narrow bands, longest chains, wide bands
         std::vector<double> chain_of(njobs, 0.0);   // chain of sweeps of the jobs of the fill kernel
         const double lag = PGM_ROWS + 3.0 * PGM_BLOCK;
-        auto envd = [](const char *k, double d) { const char *v = tools_env(k); return v ? atof(v) : d; };   // tools build only
-        const double tau_x = envd("PGM_SIM_TAU_X", 0.65), tau_c = envd("PGM_SIM_TAU_C", 0.45), tau_2 = envd("PGM_SIM_TAU_2", 0.6), eager = envd("PGM_SIM_EAGER", 0.7);
-        const double tau_3 = envd("PGM_SIM_TAU_3", 0.42);   // a band of a crit3 job (pgm_crit_kernel)
-        const double tau_l = envd("PGM_SIM_TAU_L", 0.34);   // lean sweep: us per step of R rows per lane
-        // The jobs without helper wavefronts go to pgm_band_kernel, band by band (not with the timeline of the tools build, whose
-        // slots are the fill kernel's items, and not a job whose sweep would not fit an eighth of the LDS)
-        const bool use_bands = !tools_env("PGM_FILL_TRACE") && !tools_env("PGM_NO_BANDK");
+        constexpr double tau_x = 0.65, tau_c = 0.45, tau_2 = 0.6, eager = 0.7;
+        constexpr double tau_3 = 0.42;   // a band of a crit3 job (pgm_crit_kernel)
+        constexpr double tau_l = 0.34;   // lean sweep: us per step of R rows per lane
+        // The jobs without helper wavefronts go to pgm_band_kernel, band by band (not a job whose sweep would not fit a quarter of the LDS)
         size_t total = 0, total_b = 0, total_w = 0;
         double rmax = 1.0, rsweep = 1.0;   // longest remaining path with / without the traceback behind it
         for (uint32_t q = 0; q < njobs; ++q) {
@@ -1187,8 +1096,8 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
                 lean_list.push_back(i);
                 continue;
             }
-            const bool narrow = use_bands && !J.mode2 && J.slot_bytes <= (uint32_t)(PGM_POOL / PGM_WAVES / 16 * 16);
-            const bool wide = use_bands && !J.mode2 && !narrow && J.slot_bytes <= (uint32_t)(PGM_POOL / PGM_WIDE_WAVES / 16 * 16);
+            const bool narrow = !J.mode2 && J.slot_bytes <= (uint32_t)(PGM_POOL / PGM_WAVES / 16 * 16);
+            const bool wide = !J.mode2 && !narrow && J.slot_bytes <= (uint32_t)(PGM_POOL / PGM_WIDE_WAVES / 16 * 16);
             const bool per_band = narrow || wide;
             if (!per_band) chain_of[i] = tau * ((double)(J.nb - 1) * lag + J.tsteps);
             const uint32_t group = per_band ? 1u : J.nslots;       // bands per item, one per wavefront of the worker
@@ -1221,29 +1130,18 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
         }
         band_cost += wide_cost;   // one queue for the shares: pgm_band_kernel's workers, split below
         size_t total_c = 0;
-        if (use_bands && total != 0) {
+        if (total != 0) {
             uint32_t ncj = 0, nrestj = 0;
             for (uint32_t i = 0; i < njobs; ++i) if (!per_job[i].empty()) { if (chain_of[i] >= 0.85 * rsweep) ++ncj; else ++nrestj; }
             if (ncj != 0 && nrestj != 0)
                 for (uint32_t i = 0; i < njobs; ++i)
                     if (!per_job[i].empty() && chain_of[i] >= 0.85 * rsweep) { total_c += per_job[i].size(); for (const Item &it : per_job[i]) crit_cost += it.dur; }
         }
-        // the tracebacks of the jobs of the fill, crit and band kernels run beside the sweeps on CUs of their own (not with the timeline
-        // of the tools build, whose slots belong to the kernels that follow each other)
-        double tb_cost = 0.0;
-        uint32_t ntb_all = 0;
-        // (measured on the headline batch, round 4: the jobs of a guide-tree level end together, late in the stage — beside the sweeps the
-        // workers of this kernel idle until then, and the root's walk loses the pre-linkers that the launch of the longest chains hands it
-        // when its tracebacks follow it: 3.3 ms against 2.9.  Kept for batches whose jobs end at different times: PGM_TB_BESIDE=1.)
-        const bool tb_beside = getenv("PGM_TB_BESIDE") != nullptr && !tools_env("PGM_FILL_TRACE") && !tools_env("PGM_NO_TBK") && !tools_env("PGM_FILL_DBG");
-        for (uint32_t i = 0; i < njobs; ++i) if (!b->jobs[i].lean) { ++ntb_all; tb_cost += (b->jobs[i].has_extras ? 0.3 : 0.2) * (double)(b->jobs[i].n1 + b->jobs[i].n2); }
-        if (!tb_beside) { ntb_all = 0; tb_cost = 0.0; }
-        CuShares sh = cu_shares(capacity, lean_cost, (uint32_t)lean_list.size(), band_cost, (uint32_t)(total_b + 2 * total_w), other_cost - crit_cost, (uint32_t)(total - total_c), (uint32_t)total_c, rsweep, tb_cost, ntb_all);
+        CuShares sh = cu_shares(capacity, lean_cost, (uint32_t)lean_list.size(), band_cost, (uint32_t)(total_b + 2 * total_w), other_cost - crit_cost, (uint32_t)(total - total_c), (uint32_t)total_c, rsweep);
         if (total_c != 0 && sh.crit == 0) {   // no CU to spare for a launch of their own: the longest chains stay in the main launch
             total_c = 0; crit_cost = 0.0;
-            sh = cu_shares(capacity, lean_cost, (uint32_t)lean_list.size(), band_cost, (uint32_t)(total_b + 2 * total_w), other_cost, (uint32_t)total, 0u, rsweep, tb_cost, ntb_all);
+            sh = cu_shares(capacity, lean_cost, (uint32_t)lean_list.size(), band_cost, (uint32_t)(total_b + 2 * total_w), other_cost, (uint32_t)total, 0u, rsweep);
         }
-        b->ntb_beside_workers = sh.tb;
         if (total_c != 0)
             for (uint32_t i = 0; i < njobs; ++i)
                 if (!per_job[i].empty() && chain_of[i] >= 0.85 * rsweep) per_job_c[i].swap(per_job[i]);
@@ -1252,7 +1150,6 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
         uint32_t lean_cus = sh.lean, band_cus = sh.band, crit_cus = sh.crit;
         // (a lean job is one worker's: the queue ends after ceil(jobs / workers) rounds — the fewest workers with that many rounds do)
         if (lean_cus) { const uint32_t rounds = ((uint32_t)lean_list.size() + lean_cus - 1u) / lean_cus; lean_cus = ((uint32_t)lean_list.size() + rounds - 1u) / rounds; }
-        if (const char *v = tools_env("PGM_LEAN_CUS")) if (lean_cus) lean_cus = std::max(1u, std::min(std::min(capacity - 1u, (uint32_t)lean_list.size()), (uint32_t)atoi(v)));
         b->nlean = (uint32_t)lean_list.size();
         b->nlean_workers = lean_cus;
         // event simulation: free workers (min-heap of times), ready items (max-heap of remaining paths), pending successors
@@ -1310,8 +1207,7 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
                 if (total_w) e = std::max(e, simulate(per_job_w, total_w, wide_cus * PGM_WIDE_WAVES, bands_w));
                 return e;
             };
-            if (const char *v = tools_env("PGM_BAND_CUS")) band_cus = std::max(1u, std::min(most, (uint32_t)atoi(v)));
-            else if (total != 0) {
+            if (total != 0) {
                 for (int it = 0; it < 3 && band_cus < most; ++it) {
                     band_end = run(band_cus);
                     if (band_end <= sh.fb * t_goal) break;
@@ -1325,7 +1221,7 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
             b->nbands_narrow = (uint32_t)(total_b ? bands.size() : 0);
             bands.insert(bands.end(), bands_w.begin(), bands_w.end());
         }
-        if (total_b + total_w != 0 && !tools_env("PGM_BAND_CUS")) {
+        if (total_b + total_w != 0) {
             // the tracebacks of the band kernel's jobs follow it on its CUs, one worker per job: with fewer workers than jobs the last ones
             // wait a whole walk longer — a round less if the main launch can spare the CUs for it
             uint32_t nbj = 0;
@@ -1349,7 +1245,7 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
                 if (!per_job_c[i].empty()) need += std::min<uint32_t>(b->jobs[i].nb, b->jobs[i].tsteps / (uint32_t)std::max(1.0, lag) + 2u);
             crit_cus = std::max(1u, std::min(crit_cus, need));
         }
-        capacity = std::max(1u, capacity > lean_cus + band_cus + crit_cus + sh.tb ? capacity - lean_cus - band_cus - crit_cus - sh.tb : 1u);   // the main launch's CUs
+        capacity = std::max(1u, capacity > lean_cus + band_cus + crit_cus ? capacity - lean_cus - band_cus - crit_cus : 1u);   // the main launch's CUs
         b->ncrit_workers = crit_cus;
         std::vector<PgmItem> items_rest;
         const double crit_end = total_c ? simulate(per_job_c, total_c, crit_cus, items) : 0.0;
@@ -1370,12 +1266,6 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
     for (size_t k = 0; k < items.size(); ++k)
         if (!b->jobs[items[k].job].crit3) { if (k < b->ncrit) b->crit_c3 = false; else b->rest_c3 = false; }
     if (lean_list.empty()) lean_list.push_back(0u);
-    if (tools_env("PGM_FILL_TRACE") && njobs &&   // (tools build) 6 words per item + 16 per item for the helper wavefronts, then 6 words per lean job
-        hipMalloc((void **)&b->d_trace, 176 * items.size() + 48 * (size_t)njobs) != hipSuccess) {
-        b->d_trace = nullptr;
-        pgm_align_batch_destroy(ctx, b);
-        return fail(PGM_ERR_NOMEM, "no device memory for the timeline of PGM_FILL_TRACE");
-    }
     if (items.size() > std::max<size_t>(1, total_bands)) {   // (cannot happen: an item holds at least one band)
         pgm_align_batch_destroy(ctx, b);
         return fail(PGM_ERR_DEVICE, "work list longer than the number of bands");
@@ -1416,7 +1306,6 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
     (void)hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming);
     (void)hipEventCreateWithFlags(&b->ev_join_b, hipEventDisableTiming);
     (void)hipEventCreateWithFlags(&b->ev_join_c, hipEventDisableTiming);
-    (void)hipEventCreateWithFlags(&b->ev_join_t, hipEventDisableTiming);
     if (cprof)
         fprintf(stderr, "    create: sizes %.2f ms, pinned input block %.2f, flatten %.2f, wait for the allocations %.2f (device %.2f, pinned results %.2f), work list %.2f, upload of %.1f MB %.2f\n",
                 tc0 - tcs, tc1 - tc0, tc2 - tc1, tc3 - tc2, tc_alloc, tc_hostalloc, tc4 - tc3, b->in_bytes / 1e6, now_ms() - tc4);
@@ -1473,8 +1362,6 @@ int pgm_align_batch_fetch(pgm_ctx *ctx, pgm_align_batch *b, pgm_align_out *out) 
     // results + mappings were written into the pinned block by the kernel itself (PgmJob::hmap1/hmap2/hresult): wait for
     // the stream, then scatter
     int rc = PGM_OK;
-    if (tools_env("PGM_FILL_DBG"))   // instrumented kernel variants leave their counters in the device block
-        HIPCHK(hipMemcpyAsync(b->h_out, b->d_out, b->out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipMemcpyAsync(b->h_flag, b->d_sync, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     // Finished jobs are copied out while the kernel is still running: a job's traceback worker writes the reversed mappings
     // and then the result record (status word last) into the pinned block; all but the largest jobs are done long before the
@@ -1497,15 +1384,13 @@ int pgm_align_batch_fetch(pgm_ctx *ctx, pgm_align_batch *b, pgm_align_out *out) 
         }
         return (int)n;
     };
-    if (!tools_env("PGM_FILL_DBG") && !b->d_trace) {
-        for (;;) {
-            const int n = collect();
-            if (n < 0) { (void)hipStreamSynchronize(ctx->stream); return fail(n == -1 ? PGM_ERR_INVALID : PGM_ERR_DEVICE, n == -1 ? "null mapping buffer" : "corrupt result length"); }
-            if ((uint32_t)n == b->njobs) break;
-            const hipError_t q = hipStreamQuery(ctx->stream);
-            if (q == hipSuccess) break;                       // (an aborted launch leaves records pending)
-            if (q != hipErrorNotReady) return fail(PGM_ERR_DEVICE, std::string("fill kernel: ") + hipGetErrorString(q));
-        }
+    for (;;) {
+        const int n = collect();
+        if (n < 0) { (void)hipStreamSynchronize(ctx->stream); return fail(n == -1 ? PGM_ERR_INVALID : PGM_ERR_DEVICE, n == -1 ? "null mapping buffer" : "corrupt result length"); }
+        if ((uint32_t)n == b->njobs) break;
+        const hipError_t q = hipStreamQuery(ctx->stream);
+        if (q == hipSuccess) break;                       // (an aborted launch leaves records pending)
+        if (q != hipErrorNotReady) return fail(PGM_ERR_DEVICE, std::string("fill kernel: ") + hipGetErrorString(q));
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     if (b->ev_pending) {   // stage times of the launch just completed (pgm_align_batch_stage_times)
@@ -1517,70 +1402,11 @@ int pgm_align_batch_fetch(pgm_ctx *ctx, pgm_align_batch *b, pgm_align_out *out) 
         else (void)hipGetLastError();
     }
     const int aborted = *b->h_flag;
-#ifdef PGM_TOOLS
-    if (aborted || tools_env("PGM_DUMP_SYNC")) {   // the counters of the launch, for a post-mortem
-        std::vector<int> sy(b->sync_ints);
-        (void)hipMemcpy(sy.data(), b->d_sync, 4 * b->sync_ints, hipMemcpyDeviceToHost);
-        fprintf(stderr, "sync: abort %d ticket %d lean %d | lq_n %d tb_done %d tb ticket %d | nitems %u nworkers %u nlean %u lean_workers %u ntb %u\n", sy[0], sy[1], sy[2],
-                sy[PGM_SY_LQ_N], sy[PGM_SY_TB_DONE], sy[PGM_SY_TBQ_N], b->nitems, b->nworkers, b->nlean, b->nlean_workers, b->ntb);
-        for (uint32_t i = 0; i < b->njobs; ++i) {
-            const PgmJob &J = b->jobs[i];
-            if (J.lean) continue;
-            const int *pr = sy.data() + (J.prog - b->d_sync);
-            bool done = true;
-            for (uint32_t q = 0; q < J.nb; ++q) done = done && pr[q] >= (int)J.tsteps;
-            if (!done) { fprintf(stderr, "  job %u (%u x %u, mode2 %u, %u bands): prog", i, J.n1, J.n2, J.mode2, J.nb); for (uint32_t q = 0; q < J.nb; ++q) fprintf(stderr, " %d", pr[q]); fprintf(stderr, " (of %u)\n", J.tsteps); }
-        }
-    }
-#endif
-#ifdef PGM_TOOLS
-    if (b->d_c3dbg && tools_env("PGM_C3_DBG")) {   // who waits for whom in pgm_crit_kernel: per job, means over its bands (ticks of 10 ns -> us)
-        std::vector<unsigned long long> dg(64 * (size_t)b->nitems);
-        std::vector<PgmItem> its(b->nitems);
-        (void)hipMemcpy(dg.data(), b->d_c3dbg, 512 * (size_t)b->nitems, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(its.data(), b->d_items, sizeof(PgmItem) * b->nitems, hipMemcpyDeviceToHost);
-        const uint32_t want = (uint32_t)atoi(tools_env("PGM_C3_DBG"));   // job index + 1 (0: every job)
-        for (uint32_t j = 0; j < b->njobs; ++j) {
-            if (!b->jobs[j].crit3 || (want && want != j + 1)) continue;
-            double acc[64] = {0}; uint32_t n = 0;
-            for (uint32_t k = 0; k < b->nitems; ++k) if (its[k].job == j) { for (int w = 0; w < 64; ++w) acc[w] += (double)dg[64 * (size_t)k + w]; ++n; }
-            if (!n) continue;
-            for (double &v : acc) v /= n * 100.0;
-            fprintf(stderr, "c3dbg job %u (%u x %u, %u bands, %u steps): chain %.0f us, of it waiting for fold %.0f, for the band above %.0f (%.0f waits per band) | fold 0: %.0f us, waiting for the record %.0f, for helpers %.0f (%.0f late) | fold 1: %.0f / %.0f / %.0f (%.0f) | near: %.0f us waiting %.0f; %.0f / %.0f\n",
-                    j, b->jobs[j].n1, b->jobs[j].n2, b->jobs[j].nb, b->jobs[j].tsteps, acc[0], acc[1], acc[2], acc[3] * 100.0, acc[4], acc[5], acc[6], acc[7] * 100.0, acc[8], acc[9], acc[10], acc[11] * 100.0, acc[12], acc[13], acc[16], acc[17]);
-            if (want) for (uint32_t k = 0; k < b->nitems; ++k) if (its[k].job == j && (its[k].band % 4u == 0u || its[k].band + 1u == b->jobs[j].nb)) {   // every fourth band of the job asked for
-                const unsigned long long *g = dg.data() + 64 * (size_t)k;
-                fprintf(stderr, "   band %2u: chain %.0f us (waiting for fold %.0f, for the band above %.0f), %.2f GHz | fold 0 waits: record %.0f, helpers %.0f | near waits %.0f | helpers poll/all: cols", its[k].band, g[0] / 100.0, g[1] / 100.0, g[2] / 100.0,
-                        (double)g[60] / std::max<double>(1.0, (double)g[0]) / 10.0, g[5] / 100.0, g[6] / 100.0, g[13] / 100.0);
-                for (int q = 0; q < 10; ++q) { const int w = q < 8 ? 20 + q : 28 + q; fprintf(stderr, "%s %.0f/%.0f", q == 4 ? " rows" : "", g[w] / 100.0, g[w + 8] / 100.0); }
-                fprintf(stderr, "\n");
-            }
-            fprintf(stderr, "   helpers (poll us / all us): columns");
-            for (int k = 0; k < 10; ++k) { const int w = k < 8 ? 20 + k : 28 + k; fprintf(stderr, "%s %.0f/%.0f", k == 4 ? " | rows" : "", acc[w], acc[w + 8]); }
-            fprintf(stderr, "\n");
-        }
-    }
-#endif
     if (aborted) return fail(PGM_ERR_DEVICE, "fill kernel: a band hand-off timed out");
-    if (b->d_trace) {
-        // timeline dump for tools/probe_trace.py: nitems x {worker, start, band end, traceback end} + the item list
-        std::vector<unsigned long long> tr(22 * (size_t)b->nitems + 6 * (size_t)b->nlean + 1);
-        std::vector<PgmItem> its(std::max(1u, b->nitems));
-        std::vector<uint32_t> lj(std::max(1u, b->nlean));
-        HIPCHK(hipMemcpy(tr.data(), b->d_trace, 176 * (size_t)b->nitems + 48 * (size_t)b->nlean, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(its.data(), b->d_items, sizeof(PgmItem) * b->nitems, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(lj.data(), b->d_lean, 4 * (size_t)b->nlean, hipMemcpyDeviceToHost));
-        if (FILE *f = fopen(tools_env("PGM_FILL_TRACE") ? tools_env("PGM_FILL_TRACE") : "/dev/null", "wb")) {
-            // nitems, items, 22 words per item; then nlean, the lean jobs in queue order, 6 words per lean job
-            fwrite(&b->nitems, 4, 1, f); fwrite(its.data(), sizeof(PgmItem), b->nitems, f); fwrite(tr.data(), 8, 22 * (size_t)b->nitems, f);
-            fwrite(&b->nlean, 4, 1, f); fwrite(lj.data(), 4, b->nlean, f); fwrite(tr.data() + 22 * (size_t)b->nitems, 8, 6 * (size_t)b->nlean, f);
-            fclose(f);
-        }
-    }
     for (uint32_t i = 0; i < b->njobs; ++i) {
         PgmJob::Result res;
         memcpy(&res, b->h_out + b->res_off[i], sizeof res);
-        if (res.status == PGM_STATUS_PENDING && !tools_env("PGM_FILL_DBG")) return fail(PGM_ERR_DEVICE, "fill kernel: a job's result record was never written");
+        if (res.status == PGM_STATUS_PENDING) return fail(PGM_ERR_DEVICE, "fill kernel: a job's result record was never written");
         if (res.status != PGM_OK) rc = res.status;
         if (copied[i]) continue;
         out[i].score = res.score;
@@ -1603,14 +1429,12 @@ void pgm_align_batch_destroy(pgm_ctx *ctx, pgm_align_batch *b) {
     if (ctx && ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
     if (ctx && ctx->stream3) (void)hipStreamSynchronize(ctx->stream3);
     if (ctx && ctx->stream4) (void)hipStreamSynchronize(ctx->stream4);
-    if (ctx && ctx->stream5) (void)hipStreamSynchronize(ctx->stream5);
     for (int k = 0; k < 5; ++k)
         if (b->ev[k]) (void)hipEventDestroy(b->ev[k]);
     if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
     if (b->ev_join) (void)hipEventDestroy(b->ev_join);
     if (b->ev_join_b) (void)hipEventDestroy(b->ev_join_b);
     if (b->ev_join_c) (void)hipEventDestroy(b->ev_join_c);
-    if (b->ev_join_t) (void)hipEventDestroy(b->ev_join_t);
     cache_give(ctx, pgm_ctx::C_IN, b->d_in, b->cap[pgm_ctx::C_IN]);
     cache_give(ctx, pgm_ctx::C_WORK, b->d_work, b->cap[pgm_ctx::C_WORK]);
     cache_give(ctx, pgm_ctx::C_CELLS, b->d_cells, b->cap[pgm_ctx::C_CELLS]);
@@ -1619,8 +1443,6 @@ void pgm_align_batch_destroy(pgm_ctx *ctx, pgm_align_batch *b) {
     cache_give(ctx, pgm_ctx::C_SMALL, b->d_small, b->cap[pgm_ctx::C_SMALL]);
     cache_give(ctx, pgm_ctx::C_HOST, b->h_out, b->cap[pgm_ctx::C_HOST]);
     cache_give(ctx, pgm_ctx::C_HIN, b->h_in, b->cap[pgm_ctx::C_HIN]);
-    if (b->d_trace) (void)hipFree(b->d_trace);
-    if (b->d_c3dbg) (void)hipFree(b->d_c3dbg);
     delete b;
 }
 

@@ -44,12 +44,8 @@ __device__ __forceinline__ float pgm_max3(float a, float b, float c) { float r; 
 
 // ---------------------------------------------------------------------------------------------
 // CHAIN wavefront.
-// (DBG, tools build: dbg[0..3] = ticks of 10 ns in all / waiting for the fold wavefronts / waiting for the band above, waits entered)
-template <bool DBG>
 __device__ __forceinline__ void pgm_crit_sweep(const PgmJob &J, const uint32_t b, uint8_t *slot, const int lane, int *abort_flag, bool &aborted,
-                                               const uint32_t spin_limit, const bool stall, int *sw_generic, unsigned long long *dbg) {
-    unsigned long long d_fold = 0, d_prev = 0, d_n = 0;
-    const unsigned long long d_t0 = DBG ? __builtin_amdgcn_s_memrealtime() : 0ull, d_c0 = DBG ? __builtin_readcyclecounter() : 0ull;
+                                               const uint32_t spin_limit, const bool stall, int *sw_generic) {
     constexpr int BL = PGM_BLOCK, VL = PGM_VL, HS = 64 + PGM_VL, NR = PGM_NRING, RS = 5;
     typedef __attribute__((address_space(3))) int pgm_lds_int;
     typedef float pgm_v2f __attribute__((ext_vector_type(2)));
@@ -71,11 +67,7 @@ __device__ __forceinline__ void pgm_crit_sweep(const PgmJob &J, const uint32_t b
     const float gopen_x = (rowvalid && y == 0) ? sg : gi;
     const uint32_t ncol_row = rowvalid ? ncol : 0u;
     const int x_init = (rowvalid && y == 0) ? 0 : -0x40000000;
-#ifdef PGM_X_NOHAND   /* timing experiment (results are wrong): every band sweeps as if it were the first, nothing handed over */
-    const bool has_next = false, has_prev = false;
-#else
     const bool has_next = (b + 1 < nb), has_prev = (b > 0);
-#endif
     float4 *cells_band = J.cells + (size_t)b * tsteps * 64u;
     const __amdgpu_buffer_rsrc_t cells_rsrc = pgm_band_rsrc(cells_band, tsteps * 1024u);
     const float4 *cells_prev = J.cells + (size_t)(b - 1) * tsteps * 64u;
@@ -123,7 +115,6 @@ __device__ __forceinline__ void pgm_crit_sweep(const PgmJob &J, const uint32_t b
         if (seen != 0x7fffffff && !aborted) {
             const int need = (int)min(steps_needed, tsteps);
             uint32_t spins = 0;
-            const unsigned long long w0 = (DBG && seen < need) ? __builtin_amdgcn_s_memrealtime() : 0ull;
             while (seen < need) {
                 seen = __builtin_amdgcn_readfirstlane(__hip_atomic_load((const PGM_GLOBAL int *)(uintptr_t)&J.prog[b - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
                 if (seen >= need) break;
@@ -134,7 +125,6 @@ __device__ __forceinline__ void pgm_crit_sweep(const PgmJob &J, const uint32_t b
                     break;
                 }
             }
-            if (DBG && w0) d_prev += __builtin_amdgcn_s_memrealtime() - w0;
         }
     };
     auto poll_issue = [&]() { if (seen != 0x7fffffff) pend = __hip_atomic_load((const PGM_GLOBAL int *)(uintptr_t)&J.prog[b - 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
@@ -158,11 +148,7 @@ __device__ __forceinline__ void pgm_crit_sweep(const PgmJob &J, const uint32_t b
         if (lane >= PGM_C3_H0 && lane < PGM_C3_H0 + 16) {
             // helper wavefronts that take no part in this band publish nothing: {NEAR, COLUMNS 0, 1, ROWS 0, 1, 2, -, -} per parity
             const int k = (lane - PGM_C3_H0) & 7;
-#ifdef PGM_X_NOFAR   /* timing experiment (results are wrong): no far helpers */
-            const bool runs = k == 0;
-#else
             const bool runs = k == 0 || (has_far && k <= 5);
-#endif
             if (!runs) sw[lane] = 0x7fffffff;
         }
         asm volatile("" ::: "memory");
@@ -201,7 +187,6 @@ __device__ __forceinline__ void pgm_crit_sweep(const PgmJob &J, const uint32_t b
             asm volatile("" : "+v"(Xv), "+v"(Yv), "+v"(cB));   // (the chain terms are issued before the wavefront waits for the counter)
             if (__builtin_expect(__builtin_amdgcn_readfirstlane(cB) < want, 0)) {
                 uint32_t spins = 0;
-                const unsigned long long w0 = DBG ? __builtin_amdgcn_s_memrealtime() : 0ull;
                 for (;;) {
                     cB = __hip_atomic_load(sw + 1 + (i & 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     asm volatile("" ::: "memory");
@@ -211,7 +196,6 @@ __device__ __forceinline__ void pgm_crit_sweep(const PgmJob &J, const uint32_t b
                     if (__builtin_amdgcn_readfirstlane(cB) >= want) break;
                     if (++spins > (1u << 22)) { __hip_atomic_store((PGM_GLOBAL int *)(uintptr_t)abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); aborted = true; break; }
                 }
-                if (DBG) { d_fold += __builtin_amdgcn_s_memrealtime() - w0; ++d_n; }
             }
             float Mv = pM;
             Xv = pgm_max2(Xv, pX);
@@ -219,9 +203,7 @@ __device__ __forceinline__ void pgm_crit_sweep(const PgmJob &J, const uint32_t b
             float Wv = pgm_max3(Mv, Xv, Yv);
             if (xs == x_init) Wv = s_init;
             Mv = active ? Mv : PGM_NEG_INF; Xv = active ? Xv : PGM_NEG_INF; Yv = active ? Yv : PGM_NEG_INF; Wv = active ? Wv : PGM_NEG_INF;
-#ifndef PGM_X_NOSTORE   /* timing experiment: no cell stores */
             pgm_store_cell_masked(cells_rsrc, t, lane, active, Mv, Xv, Wv, Yv);
-#endif
             {
                 const uint32_t ho = hb + lb + (uint32_t)(i * HS);
                 hW[ho] = Wv;
@@ -258,7 +240,6 @@ __device__ __forceinline__ void pgm_crit_sweep(const PgmJob &J, const uint32_t b
         poll_issue();
     }
     __hip_atomic_store(sw, 0x7fffffff, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // releases the other wavefronts (also after an abort)
-    if (DBG && dbg && lane == 0) { dbg[0] = __builtin_amdgcn_s_memrealtime() - d_t0; dbg[1] = d_fold; dbg[2] = d_prev; dbg[3] = d_n; dbg[60] = __builtin_readcyclecounter() - d_c0; }   // ([60]: shader cycles of the band)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (lane == 0 && !stall) __hip_atomic_store(&J.prog[b], aborted ? (int)0 : (int)0x7fffffff, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -282,11 +263,8 @@ __device__ __forceinline__ PgmCritRow pgm_crit_row(const PgmJob &J, const uint32
 // FOLD wavefront of the steps t % 2 == Q: the three terms that read step t - 2 — M from (y-1, x-1), X from column x-2, Y from row
 // y-2 — merged with everything the NEAR and far helper wavefronts have folded for the step (res[t & 3], read and reset here) into
 // the step's pre-folded maxima.  This is the only work between "step t - 2 recorded" and "step t may be merged": kept short.
-// (DBG: dbg[0..3] = ticks in all / waiting for the record of step t - 2 / waiting for the helpers, steps whose maxima were taken late)
-template <int Q, bool DBG>
-__device__ __forceinline__ void pgm_crit_fold(const PgmJob &J, const uint32_t b, uint8_t *slot, const int lane, int *sw_generic, int *abort_flag, unsigned long long *dbg) {
-    unsigned long long d_rec = 0, d_help = 0, d_late = 0;
-    const unsigned long long d_t0 = DBG ? __builtin_amdgcn_s_memrealtime() : 0ull;
+template <int Q>
+__device__ __forceinline__ void pgm_crit_fold(const PgmJob &J, const uint32_t b, uint8_t *slot, const int lane, int *sw_generic, int *abort_flag) {
     constexpr int BL = PGM_BLOCK, VL = PGM_VL, HS = 64 + PGM_VL, NR = PGM_NRING;
     typedef __attribute__((address_space(3))) int pgm_lds_int;
     typedef int pgm_v4i __attribute__((ext_vector_type(4)));
@@ -350,13 +328,11 @@ __device__ __forceinline__ void pgm_crit_fold(const PgmJob &J, const uint32_t b,
             {
                 const int need = max(1, (int)t);
                 uint32_t spins = 0;
-                const unsigned long long w0 = (DBG && seen < need) ? __builtin_amdgcn_s_memrealtime() : 0ull;
                 while (seen < need) {
                     seen = __builtin_amdgcn_readfirstlane(__hip_atomic_load(sw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
                     if (seen < need && ++spins > (1u << 24)) { __hip_atomic_store((PGM_GLOBAL int *)(uintptr_t)abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); gone = true; break; }
                 }
                 asm volatile("" ::: "memory");
-                if (DBG && w0) d_rec += __builtin_amdgcn_s_memrealtime() - w0;
                 if (seen == 0x7fffffff) gone = true;
             }
             const float w11 = hW[((t - 2u) & Dm) * HS + lb - 1u];
@@ -367,12 +343,10 @@ __device__ __forceinline__ void pgm_crit_fold(const PgmJob &J, const uint32_t b,
             float Yv = __fsub_rn(fmaxf(__fadd_rn(y2, ge), __fadd_rn(wy2, gopen_y)), c2y);
             if (!merged) {   // ... or as soon as they are
                 uint32_t spins = 0;
-                const unsigned long long w0 = DBG ? __builtin_amdgcn_s_memrealtime() : 0ull;
                 while (!gone && !helpers_done()) {
                     if (++spins > (1u << 22)) { __hip_atomic_store((PGM_GLOBAL int *)(uintptr_t)abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); gone = true; }
                     else if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(sw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) == 0x7fffffff) gone = true;
                 }
-                if (DBG) { d_help += __builtin_amdgcn_s_memrealtime() - w0; ++d_late; }
                 take();
             }
             Mv = fmaxf(Mv, rM); Xv = fmaxf(Xv, rX); Yv = fmaxf(Yv, rY);
@@ -382,17 +356,14 @@ __device__ __forceinline__ void pgm_crit_fold(const PgmJob &J, const uint32_t b,
         }
     }
     __hip_atomic_store(sw + 1 + Q, 0x7fffffff, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (DBG && dbg && lane == 0) { dbg[0] = __builtin_amdgcn_s_memrealtime() - d_t0; dbg[1] = d_rec; dbg[2] = d_help; dbg[3] = d_late; }
 }
 
 // ---------------------------------------------------------------------------------------------
 // NEAR wavefront of the steps t % 2 == Q: the ten near terms that read step t - 3 and older — the M pairs (y-1, x-2), (y-2, x-1)
 // [t - 3], (y-1, x-3), (y-2, x-2), (y-3, x-1) [t - 4], (y-2, x-3), (y-3, x-2) [t - 5], (y-3, x-3) [t - 6], X from column x-3 and
 // Y from row y-3 [t - 3] — folded into res[t & 3] like the far helpers' terms (three steps of lead).
-template <int Q, bool DBG>
-__device__ __forceinline__ void pgm_crit_near(const PgmJob &J, const uint32_t b, uint8_t *slot, const int lane, int *sw_generic, const int hidx, unsigned long long *dbg) {
-    unsigned long long d_wait = 0;
-    const unsigned long long d_t0 = DBG ? __builtin_amdgcn_s_memrealtime() : 0ull;
+template <int Q>
+__device__ __forceinline__ void pgm_crit_near(const PgmJob &J, const uint32_t b, uint8_t *slot, const int lane, int *sw_generic, const int hidx) {
     constexpr int BL = PGM_BLOCK, VL = PGM_VL, HS = 64 + PGM_VL, NR = PGM_NRING;
     typedef __attribute__((address_space(3))) int pgm_lds_int;
     typedef __attribute__((address_space(3))) float pgm_lds_float;
@@ -424,10 +395,8 @@ __device__ __forceinline__ void pgm_crit_near(const PgmJob &J, const uint32_t b,
         for (int i = Q; i < BL; i += 2) {
             const uint32_t t = t0 + (uint32_t)i;
             const int need = max(1, (int)t - 1);      // step t - 3 recorded
-            const unsigned long long w0 = (DBG && seen < need) ? __builtin_amdgcn_s_memrealtime() : 0ull;
             while (seen < need) seen = __builtin_amdgcn_readfirstlane(__hip_atomic_load(sw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
             asm volatile("" ::: "memory");
-            if (DBG && w0) d_wait += __builtin_amdgcn_s_memrealtime() - w0;
             const int xs = (int)t - lane;
             const float4 cn = ring3[((uint32_t)xs) & (uint32_t)(NR - 1)];
             const float S = Sc[i];
@@ -450,7 +419,6 @@ __device__ __forceinline__ void pgm_crit_near(const PgmJob &J, const uint32_t b,
             __hip_atomic_store(sw + hidx, (int)t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     }
-    if (DBG && dbg && lane == 0) { dbg[0] = __builtin_amdgcn_s_memrealtime() - d_t0; dbg[1] = d_wait; }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -470,9 +438,9 @@ struct PgmCritHist {
 };
 
 // COLUMNS: the far edges of the columns, one row per lane; this wavefront: the entries j = part, part + 2, ... of the steps t % 2 == Q.
-template <int Q, bool DBG>
+template <int Q>
 __device__ __forceinline__ void pgm_crit_cols(const PgmJob &J, const uint32_t b, uint8_t *slot, const int lane, int *sw_generic, const int hidx,
-                                              const uint32_t part, unsigned long long *hst) {
+                                              const uint32_t part) {
     constexpr int BL = PGM_BLOCK, VL = PGM_VL, HS = 64 + PGM_VL, NR = PGM_NRING, KF = PGM_KF8;
     typedef __attribute__((address_space(3))) int pgm_lds_int;
     typedef __attribute__((address_space(3))) float pgm_lds_float;
@@ -498,16 +466,12 @@ __device__ __forceinline__ void pgm_crit_cols(const PgmJob &J, const uint32_t b,
     };
     load_s_block(0);
     int seen = 0;
-    unsigned long long hwait = 0;
-    const unsigned long long ht0 = (DBG && hst) ? __builtin_amdgcn_s_memrealtime() : 0ull;
     auto wait_rec = [&](int need) {
-        const unsigned long long w0 = (DBG && hst && seen < need) ? __builtin_amdgcn_s_memrealtime() : 0ull;
         while (seen < need) {
             seen = __builtin_amdgcn_readfirstlane(__hip_atomic_load(sw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
             if (seen < need) __builtin_amdgcn_s_sleep(1);
         }
         asm volatile("" ::: "memory");
-        if (DBG && w0) hwait += __builtin_amdgcn_s_memrealtime() - w0;
     };
     wait_rec(1);   // (the column ring is staged by the chain wavefront's prologue)
     // entry lists of the wavefront's next step (graph data: fetched a step of its own ahead)
@@ -568,7 +532,6 @@ __device__ __forceinline__ void pgm_crit_cols(const PgmJob &J, const uint32_t b,
             __hip_atomic_store(sw + hidx, (int)t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     }
-    if (DBG && hst && lane == 0) { hst[hidx] = hwait; hst[8 + hidx] = __builtin_amdgcn_s_memrealtime() - ht0; }
 }
 
 // ROWS: the far edges of the rows, one (row, far edge) entry per lane (pgm_terms_helper<2>: the band's entry list, passes of 64
@@ -576,9 +539,9 @@ __device__ __forceinline__ void pgm_crit_cols(const PgmJob &J, const uint32_t b,
 // near columns, parts 1 and 2 the pairs with every other far edge of the entry's column; otherwise part k takes the passes k, k + 3,
 // k + 6).  This wavefront: the steps t % 2 == Q.  The column summary and the far-edge lists of the FIRST pass are fetched a step of
 // its own ahead (see above); `builder`: this wavefront builds the band's entry list.
-template <int Q, bool DBG>
+template <int Q>
 __device__ __forceinline__ void pgm_crit_rows(const PgmJob &J, const uint32_t b, uint8_t *slot, const int lane, int *sw_generic, const int hidx,
-                                              const uint32_t part, float *sblk_generic, const bool builder, unsigned long long *hst) {
+                                              const uint32_t part, float *sblk_generic, const bool builder) {
     constexpr int BL = PGM_BLOCK, VL = PGM_VL, HS = 64 + PGM_VL, NR = PGM_NRING, KF = PGM_KF8, KQ = 3;
     typedef __attribute__((address_space(3))) int pgm_lds_int;
     typedef __attribute__((address_space(3))) float pgm_lds_float;
@@ -644,16 +607,12 @@ __device__ __forceinline__ void pgm_crit_rows(const PgmJob &J, const uint32_t b,
     };
     load_s_block(0);
     int seen = 0;
-    unsigned long long hwait = 0;
-    const unsigned long long ht0 = (DBG && hst) ? __builtin_amdgcn_s_memrealtime() : 0ull;
     auto wait_rec = [&](int need) {
-        const unsigned long long w0 = (DBG && hst && seen < need) ? __builtin_amdgcn_s_memrealtime() : 0ull;
         while (seen < need) {
             seen = __builtin_amdgcn_readfirstlane(__hip_atomic_load(sw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
             if (seen < need) __builtin_amdgcn_s_sleep(1);
         }
         asm volatile("" ::: "memory");
-        if (DBG && w0) hwait += __builtin_amdgcn_s_memrealtime() - w0;
     };
     wait_rec(1);
     // one pass of one step: the entry's column summary `cno` and, for the pairs, the lists g* of that column's far edges (nw: the
@@ -739,18 +698,13 @@ __device__ __forceinline__ void pgm_crit_rows(const PgmJob &J, const uint32_t b,
             __hip_atomic_store(sw + hidx, (int)t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     }
-    if (DBG && hst && lane == 0) { hst[hidx] = hwait; hst[8 + hidx] = __builtin_amdgcn_s_memrealtime() - ht0; }
 }
 
 // ---------------------------------------------------------------------------------------------
 // One workgroup of sixteen wavefronts per CU; items: single bands of crit3 jobs, in list order through an atomic ticket
 // (as pgm_fill_kernel: a job's bands ascending, so the band a sweep waits for is already running).
-// DBG (tools build, PGM_C3_DBG): per item 64 words of wait statistics — [4 w ..] wavefront w: see the role functions; [32 + w], [48 + w]:
-// ticks in the poll loop / in all of helper wavefront w (pgm_terms_helper's timeline words).
-template <bool DBG>
 __global__ void __launch_bounds__(64 * PGM_C3_WAVES, 1) pgm_crit_kernel(const PgmJob *__restrict__ jobs, const PgmItem *__restrict__ items, uint32_t nitems,
-                                                                     int *__restrict__ sync, uint32_t spin_limit, uint32_t stall_job, uint32_t stall_band, uint32_t ticket_off,
-                                                                     unsigned long long *__restrict__ dbg_, uint32_t tbq_off) {
+                                                                     int *__restrict__ sync, uint32_t spin_limit, uint32_t stall_job, uint32_t stall_band, uint32_t ticket_off) {
     int *abort_flag = sync;
     __shared__ __attribute__((aligned(16))) struct { uint8_t pool[PGM_POOL]; } L;
     __shared__ int item_lds;
@@ -774,33 +728,25 @@ __global__ void __launch_bounds__(64 * PGM_C3_WAVES, 1) pgm_crit_kernel(const Pg
         const uint32_t b = item.band;
         const bool last_band = (item.band + item.count == J.nb);
         uint8_t *slot = L.pool;
-        unsigned long long *dbg = (DBG && dbg_) ? dbg_ + 64 * (size_t)it : nullptr;
         if (role == 0) {
             __builtin_amdgcn_s_setprio(3);
             const bool stall = item.job == stall_job && b == stall_band;
-            pgm_crit_sweep<DBG>(J, b, slot, lane, abort_flag, aborted, spin_limit, stall, fsync, dbg);
+            pgm_crit_sweep(J, b, slot, lane, abort_flag, aborted, spin_limit, stall, fsync);
         } else if (role <= 2) {
             __builtin_amdgcn_s_setprio(2);
-            if (role == 1) pgm_crit_fold<0, DBG>(J, b, slot, lane, fsync, abort_flag, dbg ? dbg + 4 : nullptr); else pgm_crit_fold<1, DBG>(J, b, slot, lane, fsync, abort_flag, dbg ? dbg + 8 : nullptr);
+            if (role == 1) pgm_crit_fold<0>(J, b, slot, lane, fsync, abort_flag); else pgm_crit_fold<1>(J, b, slot, lane, fsync, abort_flag);
         } else if (role <= 14) {
             __builtin_amdgcn_s_setprio(0);
             // helpers: {NEAR, COLUMNS 0, 1, ROWS 0, 1, 2} x {even, odd steps}
             const uint32_t par = (role - 3) & 1u, kind = (uint32_t)(role - 3) >> 1;   // kind 0: near; 1, 2: columns; 3, 4, 5: rows
             const int hidx = PGM_C3_H0 + 8 * (int)par + (int)kind;
-            if (kind == 0u) { if (par == 0u) pgm_crit_near<0, DBG>(J, b, slot, lane, fsync, hidx, dbg ? dbg + 12 : nullptr); else pgm_crit_near<1, DBG>(J, b, slot, lane, fsync, hidx, dbg ? dbg + 16 : nullptr); }
-#ifdef PGM_X_NOFAR
-            else if (false) {
-#else
+            if (kind == 0u) { if (par == 0u) pgm_crit_near<0>(J, b, slot, lane, fsync, hidx); else pgm_crit_near<1>(J, b, slot, lane, fsync, hidx); }
             else if (J.has_far) {
-#endif
-                // (the helper writes hst[hidx] = ticks in its poll loop and hst[8 + hidx] = ticks in all: words w and w + 8, w = 20 + k for the
-                // wavefronts k = role - 5 < 8, 28 + k for the last two)
-                unsigned long long *hst = dbg ? dbg + ((role - 5 < 8) ? 20 + (role - 5) : 28 + (role - 5)) - hidx : nullptr;
-                if (kind <= 2u) { if (par == 0u) pgm_crit_cols<0, DBG>(J, b, slot, lane, fsync, hidx, kind - 1u, hst); else pgm_crit_cols<1, DBG>(J, b, slot, lane, fsync, hidx, kind - 1u, hst); }
+                if (kind <= 2u) { if (par == 0u) pgm_crit_cols<0>(J, b, slot, lane, fsync, hidx, kind - 1u); else pgm_crit_cols<1>(J, b, slot, lane, fsync, hidx, kind - 1u); }
                 else {
                     float *sb = (float *)(slot + J.c3_off + PGM_C3_SBLK) + ((kind - 3u) * 2u + par) * 512u;
-                    if (par == 0u) pgm_crit_rows<0, DBG>(J, b, slot, lane, fsync, hidx, kind - 3u, sb, kind == 3u, hst);
-                    else pgm_crit_rows<1, DBG>(J, b, slot, lane, fsync, hidx, kind - 3u, sb, false, hst);
+                    if (par == 0u) pgm_crit_rows<0>(J, b, slot, lane, fsync, hidx, kind - 3u, sb, kind == 3u);
+                    else pgm_crit_rows<1>(J, b, slot, lane, fsync, hidx, kind - 3u, sb, false);
                 }
             }
         }
@@ -809,7 +755,7 @@ __global__ void __launch_bounds__(64 * PGM_C3_WAVES, 1) pgm_crit_kernel(const Pg
             if (threadIdx.x == 0) J.times[0] = __builtin_amdgcn_s_memrealtime();
             if (threadIdx.x == 0 && __hip_atomic_load(abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {   // an aborted batch leaves its records here
                 J.result->score = 0.f; J.result->n_tr_indels = 0; J.result->len = 0; J.result->status = PGM_ERR_DEVICE; J.hresult->score = 0.f; J.hresult->n_tr_indels = 0; J.hresult->len = 0; __threadfence_system(); __hip_atomic_store(&J.hresult->status, (int32_t)PGM_ERR_DEVICE, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            } else if (threadIdx.x == 0) pgm_tbq_push(sync, tbq_off, item.job);
+            }
         }
     }
 }

@@ -192,7 +192,6 @@ struct PgmJob {
 #define PGM_SY_LQ_N 32      // tracebacks that have started (pre-link announcements, ids in lq_ids)
 #define PGM_SY_TB_DONE 33   // tracebacks finished
 #define PGM_SY_TBQ_N 34     // ticket counter of the traceback kernel's job list
-#define PGM_SY_TBQ_TAIL 35  // jobs in the ready queue of the traceback kernel that runs beside the sweeps
 #define PGM_LK_W 4u        // grid tiles per grid row in the corridor around the diagonal (paths of the headline batch stay within 40 columns of it)
 #define PGM_LK_T 32u       // tile edge
 #define PGM_LK_NR 4u       // grid rows of tables a walker keeps in LDS (fetched together when known to be complete)
