@@ -161,7 +161,7 @@ __global__ void __launch_bounds__(NODES) pgm_prep_kernel(const PgmJob *__restric
 // Classes of the nodes of the lean jobs' graphs (PgmJob::cls1 / cls2 / tabhdr), once per batch (the inputs of a batch do not change
 // between its launches): grid = (njobs, 2, slices), one thread per node.  The class is decided on the float value of the column, as
 // pgm_prep_kernel casts it.
-#define PGM_TAB_HDR 128   /* ints per job: [0] some node without a class, [1 ..] a node + 1 per class of graph 1, then of graph 2 */
+#define PGM_TAB_HDR 136   /* ints per job: [0] some node without a class, [1 ..] a node + 1 per class of graph 1, then of graph 2 (D + 2 each) */
 __global__ void __launch_bounds__(256) pgm_classify_kernel(const PgmJob *__restrict__ jobs) {
     const PgmJob &J = jobs[blockIdx.x];
     if (!J.tabhdr) return;
@@ -2944,7 +2944,11 @@ __global__ void __launch_bounds__(64 * PGM_WAVES, 1) pgm_tb_kernel(const PgmJob 
 // Persistent workers take whole jobs (largest first) through an atomic ticket; a job's eight wavefronts sweep its bands
 // (pgm_sweep_chain), then wavefront 0 walks the decision bits (pgm_traceback_chain).  The host launches it on a second
 // stream beside pgm_fill_kernel, whose grid leaves the CUs for it free.
-#define PGM_LEAN_LDS (8 * PGM_LEAN_RING * 8 > 49152 ? 8 * PGM_LEAN_RING * 8 : 49152)
+#define PGM_LEAN_TAB_BYTES (4 * (PGM_MAX_DIM + 2) * (PGM_MAX_DIM + 2))
+#define PGM_LEAN_LDS (PGM_LEAN_TAB_OFF + PGM_LEAN_TAB_BYTES > 49152 ? PGM_LEAN_TAB_OFF + PGM_LEAN_TAB_BYTES : 49152)
+// (every alphabet the host accepts: class ids D + 1 of both graphs in the header, a (D + 2)^2 score table behind the rings)
+static_assert(1 + 2 * (PGM_MAX_DIM + 2) <= PGM_TAB_HDR, "PGM_TAB_HDR must hold the classes of both graphs at PGM_MAX_DIM");
+static_assert(PGM_LEAN_TAB_OFF + 4 * (PGM_MAX_DIM + 2) * (PGM_MAX_DIM + 2) <= PGM_LEAN_LDS && PGM_LEAN_LDS % 16 == 0, "the lean kernel's LDS must hold the score table at PGM_MAX_DIM");
 template <int R>
 __global__ void __launch_bounds__(64 * PGM_WAVES, 2) pgm_lean_kernel(const PgmJob *__restrict__ jobs, const uint32_t *__restrict__ list, uint32_t nlist,
                                                                   int *__restrict__ sync, uint32_t spin_limit) {

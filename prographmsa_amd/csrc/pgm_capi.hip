@@ -487,9 +487,10 @@ static void finalize_side(uint8_t *base, uint32_t n, SideOff &o, int side, bool 
 // progress counters (pass 1 of pgm_align_batch_create).
 struct JobOff { SideOff s1, s2; size_t M, pi, g1f, a1, t2, aux2, map1, map2, ms, mp, res, cells, tb1, tb2, S, prog, codes, endcell, ltab, lready, cls; uint32_t lrows, lcols; };
 struct BatchLayout { DevLayout W, C, O, SL; size_t sync_ints = 64; };   // sync: [0] abort flag, [1] ticket counter of the band list, [2] of the lean list; on a cache line of their own, [32] pre-link tasks announced, [33] tracebacks finished (polled by every idle worker)
-static void layout_job(BatchLayout &L, uint32_t n1, uint32_t n2, uint32_t dim, uint32_t rshift, bool lean, bool keep, JobOff &o) {
+// dp: the padded stride of the converted profiles (PgmJob::dp), the same for every job of a batch
+static void layout_job(BatchLayout &L, uint32_t n1, uint32_t n2, uint32_t dp, uint32_t rshift, bool lean, bool keep, JobOff &o) {
     const uint32_t R = 1u << rshift, rows = PGM_ROWS * R;
-    const uint32_t dp = dim <= 20 ? 20 : 64, nb = (n1 - 1 + rows - 1) / rows, tsteps = (n2 - 1) + 63;
+    const uint32_t nb = (n1 - 1 + rows - 1) / rows, tsteps = (n2 - 1) + 63;
     const uint32_t nblk = (tsteps + PGM_BLOCK - 1) / PGM_BLOCK, maxn = std::max(n1, n2);
     o.g1f = L.W.take(sizeof(float) * (size_t)dp * n1);
     o.a1 = L.W.take(sizeof(float) * n1);
@@ -785,9 +786,14 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
         const pgm_graph *a = g1[i], *c = g2[i];
         two_chains[i] = (a && c && a->n >= 2 && c->n >= 2 && a->e_rowptr && c->e_rowptr && a->e_col && c->e_col && a->e_val && c->e_val && graph_is_chain(a) && graph_is_chain(c)) ? 1 : 0;
     });
+    // The prep and emission kernels are instantiated once per batch for its largest alphabet and read every job's converted
+    // profiles with that padded stride: all jobs of a batch get it, whatever their own alphabet.
+    uint32_t batch_dim = 0;
+    for (uint32_t i = 0; i < njobs; ++i) if (g1[i]) batch_dim = std::max(batch_dim, g1[i]->dim);
+    const uint32_t batch_dp = batch_dim <= 20 ? 20u : 64u;
     for (uint32_t i = 0; i < njobs; ++i) {
         const pgm_graph *a = g1[i], *c = g2[i];
-        if (!a || !c || !model[i] || a->dim != c->dim || a->dim == 0 || a->dim > 64 || a->n < 2 || c->n < 2 || !model[i]->M || !model[i]->pi ||
+        if (!a || !c || !model[i] || a->dim != c->dim || a->dim == 0 || a->dim > PGM_MAX_DIM || a->n < 2 || c->n < 2 || !model[i]->M || !model[i]->pi ||
             (!a->sites && !ref_of(res1, i)) || !a->e_rowptr || (!c->sites && !ref_of(res2, i)) || !c->e_rowptr) {
             delete b;
             return fail(PGM_ERR_INVALID, "invalid job " + std::to_string(i));
@@ -795,7 +801,7 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
         PgmJob &J = b->jobs[i];
         memset(&J, 0, sizeof J);
         J.n1 = a->n; J.n2 = c->n; J.dim = a->dim;
-        J.dp = a->dim <= 20 ? 20 : 64;
+        J.dp = batch_dp;
         J.ncol = c->n - 1;
         J.tsteps = J.ncol + 63;
         // chain-only jobs: the lean sweep, R = 2 rows per lane (pgm_lean_kernel<2>; the band's buffer descriptor must stay below 1 GiB: see pgm_sweep_chain)
@@ -814,7 +820,7 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
         Off &o = off[i];
         in_base[i + 1] = in_base[i] + side_bound(a, ref_of(res1, i)) + side_bound(c, ref_of(res2, i)) + model_bound_bytes(a->dim);
         J.keep_cells = (!J.lean || (flags & PGM_BATCH_KEEP_MATRICES)) ? 1u : 0u;
-        layout_job(L, J.n1, J.n2, J.dim, J.rshift, J.lean != 0, J.keep_cells != 0, o);
+        layout_job(L, J.n1, J.n2, J.dp, J.rshift, J.lean != 0, J.keep_cells != 0, o);
         b->res_off[i] = o.res; b->map1_off[i] = o.map1; b->map2_off[i] = o.map2;
     }
     // The device buffers and the pinned result block are allocated (or taken from the context's cache) on a thread of their own

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include "../../include/pgm_hip.h"
 
+#define PGM_MAX_DIM 64     /* largest alphabet of an alignGraphs job the C ABI accepts (pgm_align_batch_create_res) */
 #define PGM_HALO 0         /* every lane of a band owns a row (the rows above the band are "virtual lanes" in the LDS history) */
 #define PGM_ROWS 64        /* rows per band = lanes of the sweeping wavefront */
 #define PGM_VL 16          /* virtual lanes: the last 16 rows of the previous band, kept in the LDS history of the band below */
@@ -86,7 +87,7 @@ struct PgmTbNode {
 
 struct PgmJob {
     uint32_t n1, n2;       // node counts incl. START/END
-    uint32_t dim, dp;      // alphabet size and padded size (multiple of 4)
+    uint32_t dim, dp;      // alphabet size and padded size (multiple of 4): the same for every job of a batch, 20 or 64 after its largest alphabet
     uint32_t nb;           // number of row bands = ceil((n1-1)/(64 R))
     uint32_t ncol;         // stored columns = n2-1
     uint32_t tsteps;       // steps per band = ncol + 63

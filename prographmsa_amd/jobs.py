@@ -228,6 +228,21 @@ def random_graph(rng, n, dim, skip_frac=0.15, repeat_frac=0.0, onehot_frac=0.5, 
     return Graph(n, dim, sites.reshape(-1), rp, col, val, rrp, rcol, ru)
 
 
+def sequence_job(seed, L1, L2, dim=20, unknown_frac=0.05):
+    """A chain-only job of two SEQUENCE graphs of L1 and L2 residues: every profile column one-hot, uniform 1 / dim (a residue
+    without a value) or empty (START / END), as the reference's SequenceGraph lays them out."""
+    rng = np.random.default_rng(seed)
+    job = random_job(seed, L1 + 2, L2 + 2, dim=dim, skip_frac=0.0, drop_chain_frac=0.0)
+    for g, L in ((job.g1, L1), (job.g2, L2)):
+        m = np.zeros((L + 2, dim))
+        s = rng.integers(0, dim, L)
+        for i, v in enumerate(s):
+            if rng.random() < unknown_frac: m[i + 1, :] = 1.0 / dim
+            else: m[i + 1, v] = 1.0
+        g.sites = m.reshape(-1)
+    return job
+
+
 def random_job(seed, n1, n2, dim=20, **kw):
     rng = np.random.default_rng(seed)
     g1 = random_graph(rng, n1, dim, **kw)

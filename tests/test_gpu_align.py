@@ -270,17 +270,7 @@ def test_sequence_graph_jobs_score_table_after_other_batches(ctx):
     the second pass of a run), 20 and 61 states, residues without a value: scores and mappings against the oracle."""
     from prographmsa_amd import jobs as J
     import oracle_lib
-    def seqjob(seed, L1, L2, D):
-        rng = np.random.default_rng(seed)
-        job = J.random_job(seed, L1 + 2, L2 + 2, dim=D, skip_frac=0.0, drop_chain_frac=0.0)
-        for g, L in ((job.g1, L1), (job.g2, L2)):
-            m = np.zeros((L + 2, D))
-            s = rng.integers(0, D, L)
-            for i, v in enumerate(s):
-                if rng.random() < 0.05: m[i + 1, :] = 1.0 / D      # a residue without a value
-                else: m[i + 1, v] = 1.0
-            g.sites = m.reshape(-1)
-        return job
+    seqjob = J.sequence_job   # (5 % residues without a value)
     for D in (20, 61):
         for rnd in range(3):
             mixed = [J.random_job(9100 + 10 * rnd + k, 300 + 37 * k, 280 + 41 * k, dim=D, skip_frac=0.2) for k in range(3)] + \

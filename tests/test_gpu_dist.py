@@ -25,7 +25,8 @@ def _scan(r1, r2, D):
     return c, int(g[0])
 
 
-@pytest.mark.parametrize("D,nrows,L", [(20, 7, 1), (20, 9, 63), (20, 12, 64), (20, 10, 65), (20, 8, 1000), (61, 6, 333), (20, 40, 3274)])
+@pytest.mark.parametrize("D,nrows,L", [(20, 7, 1), (20, 9, 63), (20, 12, 64), (20, 10, 65), (20, 8, 1000), (61, 6, 333), (20, 40, 3274),
+                                       (21, 9, 65), (64, 8, 333)])   # (symbols from 20 on are not counted)
 def test_prealigned_pair_counts_bit_exact(ctx, D, nrows, L):
     import prographmsa_amd as pg
     rng = np.random.default_rng(100 + L)

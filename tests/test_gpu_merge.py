@@ -11,7 +11,7 @@ pytestmark = pytest.mark.gpu
 GAP = 0xFFFFFFFF
 
 
-@pytest.mark.parametrize("D", [20, 61])
+@pytest.mark.parametrize("D", [1, 4, 20, 31, 32, 33, 61, 63, 64])   # (the kernel pads to 32 or 64 states; 64: 71 712 bytes of LDS)
 def test_merge_profiles_bit_exact(ctx, D):
     import oracle_lib
     import prographmsa_amd as pg
@@ -173,7 +173,7 @@ def test_resident_onehot_leaves_against_the_oracle(ctx):
     from prographmsa_amd import jobs as J
     import oracle_lib
     P = lambda a, t: a.ctypes.data_as(C.POINTER(t))
-    for D in (20, 61):
+    for D in (4, 20, 33, 61, 64):
         rng = np.random.default_rng(900 + D)
         lens = [73, 131]
         syms = [rng.integers(0, D, L).astype(np.int8) for L in lens]

@@ -28,7 +28,7 @@ def _score(dim, rng):
     return s.reshape(-1)
 
 
-@pytest.mark.parametrize("dim", [20, 61])
+@pytest.mark.parametrize("dim", [1, 4, 20, 21, 33, 61])
 def test_nw_pairs_bit_exact(ctx, dim):
     import oracle_lib
     rng = np.random.default_rng(5 + dim)
