@@ -306,6 +306,36 @@ int pgm_resident_onehot(pgm_ctx *ctx, uint32_t dim, uint32_t nseq, const int8_t 
 int pgm_resident_import(pgm_ctx *ctx, pgm_ctx *src_ctx, const double *src, uint64_t count, const double **dst);
 float pgm_merge_last_kernel_ms(pgm_ctx *ctx);
 
+/* ---- root search: gap masks and gap parsimony (reference src/FindRoot.h, src/GapParsimony.h) ----------------------- */
+/* A gap mask holds one bit per column per row, set where the row has a gap: row r is words [r * W, (r + 1) * W) with
+ * W = ceil(ncols / 64), column c is bit c % 64 of word c / 64; bits past ncols are ignored on input and zero on output. */
+
+/* extend_alignment (reference src/ProgressiveAlignment.h:245-264) in bit form: the nrows rows of src (ncols_in columns) as rows
+ * of a merged alignment of ncols_out columns.  mapping[j] (j < ncols_out) is the node of the child's graph behind merged column
+ * j, PGM_GAP for none: a mapped column takes the child's next column in rank order, an unmapped one is a gap.  The non-gap
+ * entries of mapping must number exactly ncols_in (PGM_ERR_INVALID otherwise).  All jobs of a call run in one launch. */
+typedef struct pgm_gapmask_job {
+    const uint64_t *src;       /* nrows x ceil(ncols_in / 64) words */
+    const uint32_t *mapping;   /* ncols_out entries */
+    uint64_t *dst;             /* out: nrows x ceil(ncols_out / 64) words */
+    uint32_t nrows, ncols_in, ncols_out;
+} pgm_gapmask_job;
+int pgm_gapmask_extend_batch(pgm_ctx *ctx, uint32_t njobs, const pgm_gapmask_job *jobs);
+
+/* GapParsimony::scoreAlignment (reference src/GapParsimony.h:100-125) of many candidate alignments in one launch: Fitch
+ * parsimony of the residue / gap pattern, columns in blocks of 32 as the reference packs them — including its padding loop,
+ * which leaves the last 32 columns uncounted when ncols is a multiple of 32.  Per candidate: the masks of its nleaves rows and
+ * a rooted binary topology of nleaves - 1 internal nodes, children[2k], children[2k + 1] the two children of internal node k
+ * (ids below nleaves are rows, nleaves + m is internal node m < k: post-order, the last one is the root); each id is a child
+ * once.  scores[i] = the exact count.  PGM_ERR_INVALID: nleaves < 2, ncols == 0, a child out of range or not in post-order. */
+typedef struct pgm_parsimony_job {
+    const uint64_t *masks;      /* nleaves x ceil(ncols / 64) words */
+    const uint32_t *children;   /* 2 * (nleaves - 1) */
+    uint32_t nleaves, ncols;
+} pgm_parsimony_job;
+int pgm_gap_parsimony_batch(pgm_ctx *ctx, uint32_t njobs, const pgm_parsimony_job *jobs, uint32_t *scores);
+float pgm_parsimony_last_kernel_ms(pgm_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,15 @@ class pgm_site_ref(C.Structure):
     _fields_ = [("dev_sites", C.POINTER(C.c_double)), ("node_map", C.POINTER(C.c_uint32)), ("ncols", C.c_uint32)]
 
 
+class pgm_gapmask_job(C.Structure):
+    _fields_ = [("src", C.POINTER(C.c_uint64)), ("mapping", C.POINTER(C.c_uint32)), ("dst", C.POINTER(C.c_uint64)),
+                ("nrows", C.c_uint32), ("ncols_in", C.c_uint32), ("ncols_out", C.c_uint32)]
+
+
+class pgm_parsimony_job(C.Structure):
+    _fields_ = [("masks", C.POINTER(C.c_uint64)), ("children", C.POINTER(C.c_uint32)), ("nleaves", C.c_uint32), ("ncols", C.c_uint32)]
+
+
 class pgm_align_out(C.Structure):
     _fields_ = [("score", C.c_float), ("n_tr_indels", C.c_uint32), ("len", C.c_uint32), ("status", C.c_int32),
                 ("map1", C.POINTER(C.c_uint32)), ("map2", C.POINTER(C.c_uint32))]
@@ -65,6 +74,7 @@ EXPORTS = [
     "pgm_nw_pairs_batch", "pgm_nw_pairs_submit", "pgm_nw_pairs_wait", "pgm_nw_last_kernel_ms", "pgm_host_alloc", "pgm_host_free", "pgm_csprofile_load", "pgm_csprofile_create_batch", "pgm_csprofile_create_batch_res",
     "pgm_csprofile_last_kernel_ms", "pgm_mldist_batch", "pgm_prealigned_counts_batch", "pgm_kmer_cosine", "pgm_dist_last_kernel_ms",
     "pgm_merge_profiles_batch", "pgm_merge_profiles_batch_ex", "pgm_resident_reset", "pgm_resident_onehot", "pgm_resident_import", "pgm_merge_last_kernel_ms",
+    "pgm_gapmask_extend_batch", "pgm_gap_parsimony_batch", "pgm_parsimony_last_kernel_ms",
 ]
 
 
@@ -120,6 +130,9 @@ def _load():
         "pgm_resident_onehot": (C.c_int, [vp, u32, u32, C.POINTER(C.c_int8), C.POINTER(u32), C.POINTER(C.POINTER(C.c_double))]),
         "pgm_resident_import": (C.c_int, [vp, vp, C.POINTER(C.c_double), C.c_uint64, C.POINTER(C.POINTER(C.c_double))]),
         "pgm_merge_last_kernel_ms": (C.c_float, [vp]),
+        "pgm_gapmask_extend_batch": (C.c_int, [vp, u32, C.POINTER(pgm_gapmask_job)]),
+        "pgm_gap_parsimony_batch": (C.c_int, [vp, u32, C.POINTER(pgm_parsimony_job), C.POINTER(u32)]),
+        "pgm_parsimony_last_kernel_ms": (C.c_float, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = the library does not export a declared symbol

@@ -26,6 +26,7 @@
 #include "pgm_csprofile_kernels.h"
 #include "pgm_dist_kernels.h"
 #include "pgm_merge_kernels.h"
+#include "pgm_parsimony_kernels.h"
 #include "pgm_pool.h"
 
 static thread_local std::string g_err;
@@ -57,7 +58,7 @@ struct pgm_ctx {
     void *cache_ptr[C_SLOTS] = {};
     size_t cache_bytes[C_SLOTS] = {};
     hipDeviceProp_t prop;
-    float nw_ms = 0, cs_ms = 0, ml_ms = 0, merge_ms = 0;
+    float nw_ms = 0, cs_ms = 0, ml_ms = 0, merge_ms = 0, pars_ms = 0;
     // grow-only scratch buffers of the all-pairs / context-profile calls (slot = position in the call's buffer list): a
     // guide-tree stage issues many calls (one per pair tile), hipMalloc / hipFree of up to 2 GB per call would dominate them
     enum { SC_DEV = 24, SC_HOST = 4 };
@@ -1557,3 +1558,4 @@ int pgm_align_batch_read_matrices(pgm_ctx *ctx, pgm_align_batch *b, uint32_t job
 #include "pgm_csprofile_capi.inc"
 #include "pgm_dist_capi.inc"
 #include "pgm_merge_capi.inc"
+#include "pgm_parsimony_capi.inc"

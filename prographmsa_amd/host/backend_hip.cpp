@@ -108,6 +108,16 @@ struct HipBackend : Backend {
         int rc = pgm_kmer_cosine(ctx_of(worker), nseq, ncols, counts, cosine);
         if (rc != PGM_OK) error("pgm_kmer_cosine failed (%d): %s", rc, pgm_last_error());
     }
+    bool gapmask_extend_batch(uint32_t njobs, const pgm_gapmask_job *jobs, int worker) override {
+        int rc = pgm_gapmask_extend_batch(ctx_of(worker), njobs, jobs);
+        if (rc != PGM_OK) error("pgm_gapmask_extend_batch failed (%d): %s", rc, pgm_last_error());
+        return true;
+    }
+    bool gap_parsimony_batch(uint32_t njobs, const pgm_parsimony_job *jobs, uint32_t *scores, int worker) override {
+        int rc = pgm_gap_parsimony_batch(ctx_of(worker), njobs, jobs, scores);
+        if (rc != PGM_OK) error("pgm_gap_parsimony_batch failed (%d): %s", rc, pgm_last_error());
+        return true;
+    }
     bool merge_profiles_batch(uint32_t njobs, const pgm_merge_job *jobs, int worker) override {
         int rc = pgm_merge_profiles_batch(ctx_of(worker), njobs, jobs);
         if (rc != PGM_OK) error("pgm_merge_profiles_batch failed (%d): %s", rc, pgm_last_error());

@@ -21,7 +21,9 @@ static void usage() {
     std::cerr << "USAGE: pgmsa [-f|--fasta] [-t|--tree <newick>] [-o <file>] [-T] [-I] [-a] [-m] [-M]\n"
                  "             [--codon] [-c|--cs_profile <lib>] [-i <iters>] [-g rate] [-e prob] [-E prob]\n"
                  "             [-s prob] [-A] [--early_refinement] [--ancestral_seqs] [--profile_out <file>] [-R] [--read_repeats <file>]\n"
-                 "             [--dump_jobs <file>] [--dump_dist <file>] [--stats] <fasta file>\n";
+                 "             [-r|--reroot [-r]] [--dump_jobs <file>] [--dump_dist <file>] [--stats] <fasta file>\n"
+                 "  -r, --reroot  realign with the guide tree rooted on every branch and keep the alignment of the lowest gap\n"
+                 "                parsimony score; given twice (-rr), a hill climb over neighbouring branches instead\n";
 }
 
 // The backend (device contexts: the HIP runtime's start-up takes 80-400 ms) is created on a thread of its own while the
@@ -122,7 +124,10 @@ static int doAlign(const Alphabet &a, const std::map<std::string, std::string> &
         if (host_switches().profile) fprintf(stderr, "guide tree from the alignment: %.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tt0).count());
         old_result = result;
     }
-    if (!cmdlineopts.onlytree_flag) result = progressive_alignment(a, seqs2, *tree, csprofile.get(), *model_factory, &reps);
+    // the final alignment (main.cpp:433-440): with -r the guide tree rerooted on the branch of the lowest gap parsimony
+    if (!cmdlineopts.onlytree_flag)
+        result = cmdlineopts.reroot_flag ? progressive_alignment_find_root(a, seqs2, *tree, *model_factory, &reps)
+                                         : progressive_alignment(a, seqs2, *tree, csprofile.get(), *model_factory, &reps);
     if (host_switches().profile) fprintf(stderr, "[%.1f ms] back in main\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     double t_prog = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     out_tree = tree;
@@ -153,9 +158,16 @@ static int doAlign(const Alphabet &a, const std::map<std::string, std::string> &
         Backend &be = default_backend();
         fprintf(stderr,
                 "{\"backend\": \"%s\", \"init_s\": %.6f, \"tree_s\": %.6f, \"progressive_s\": %.6f, \"align_cells\": %llu, \"align_s\": %.6f, "
-                "\"nw_cells\": %llu, \"nw_s\": %.6f, \"mldist_s\": %.6f, \"merge_profiles_s\": %.6f, \"farm_workers\": %d, \"farm_tiles\": %d, \"farm_level_workers\": %d, \"farm_leaf_workers\": %d, \"resident\": %s, \"resident_imports\": %d, \"switches\": \"%s\"}\n",
+                "\"nw_cells\": %llu, \"nw_s\": %.6f, \"mldist_s\": %.6f, \"merge_profiles_s\": %.6f, \"farm_workers\": %d, \"farm_tiles\": %d, \"farm_level_workers\": %d, \"farm_leaf_workers\": %d, \"resident\": %s, \"resident_imports\": %d, \"switches\": \"%s\"",
                 be.name(), t_init, t_tree, t_prog, (unsigned long long)be.cells_aligned, be.seconds_align,
                 (unsigned long long)be.cells_nw, be.seconds_nw, be.seconds_mldist, be.seconds_merge_profiles, be.farm_workers, be.farm_tiles, be.farm_level_workers, be.farm_leaf_workers, be.resident_pass ? "true" : "false", be.resident_imports, host_switches().describe().c_str());
+        if (cmdlineopts.reroot_flag) {   // (keys of the root search only when it ran)
+            const RootSearchStats &r = root_search_stats;
+            fprintf(stderr, ", \"reroot\": %d, \"reroot_merges\": %d, \"reroot_candidates\": %d, \"reroot_heights\": %d, \"reroot_batches\": %d, "
+                            "\"reroot_align_s\": %.6f, \"reroot_host_merge_s\": %.6f, \"reroot_gapmask_s\": %.6f, \"reroot_parsimony_s\": %.6f, \"reroot_rows_s\": %.6f",
+                    cmdlineopts.reroot_flag, r.merges, r.candidates, r.heights, r.batches, r.align_s, r.host_merge_s, r.gapmask_s, r.parsimony_s, r.select_s);
+        }
+        fprintf(stderr, "}\n");
     }
     return 0;
 }
@@ -206,11 +218,17 @@ int main(int argc, char **argv) {
             else if (s == "--dump_jobs") dump = val();
             else if (s == "--dump_dist") dist_dump = val();
             else if (s == "--stats") stats = true;
+            else if (s == "--reroot") ++cmdlineopts.reroot_flag;
+            else if (s.size() >= 2 && s[0] == '-' && s.find_first_not_of('r', 1) == std::string::npos) cmdlineopts.reroot_flag += (int)s.size() - 1;   // -r, -rr (TCLAP's MultiSwitchArg)
             else if (s == "-h" || s == "--help") { usage(); return 0; }
             else if (!s.empty() && s[0] == '-') { std::cerr << "Command line error: unknown flag " << s << std::endl; return 1; }
             else cmdlineopts.sequence_file = s;
         }
         if (cmdlineopts.sequence_file.empty()) { usage(); return 1; }
+        if (cmdlineopts.reroot_flag && (cmdlineopts.ancestral_flag || !cmdlineopts.profile_file.empty())) {
+            std::cerr << "ERROR:--ancestral_seqs and --profile_out cannot be combined with -r (the root search keeps no ancestral profiles)" << std::endl;
+            return 2;
+        }
         if (cmdlineopts.codon_flag) {  // main.cpp:225-241
             if (!indel_set) cmdlineopts.indel_rate /= 2.6;
             if (!edgehl_set) cmdlineopts.edge_halflife *= 2.6;

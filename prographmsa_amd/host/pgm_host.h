@@ -39,6 +39,7 @@ struct cmdlineopts_t {
     bool mldist_flag = false, mldist_gap_flag = false, codon_flag = false, inputorder_flag = false;
     bool ancestral_flag = false;
     bool earlyref_flag = false;       // --early_refinement (ProgressiveAlignment.h:102-110)
+    int reroot_flag = 0;              // -r / --reroot, counted (main.cpp:117): 1 = every branch, 2 or more = hill climbing (FindRoot.h:276-320)
     std::string profile_file;   // --profile_out (main.cpp:132)
     std::string readreps_file;  // --read_repeats (main.cpp:108)
     bool repeats_flag = false;  // -R: here only the "TR indels" lines on stderr (T-REKS itself is not run: --read_repeats supplies the repeats)
@@ -287,6 +288,10 @@ struct Backend {
     // node profiles of a batch of merged graphs on the device (numeric part); false = host arithmetic
     virtual bool merge_profiles_batch(uint32_t, const pgm_merge_job *, int = 0) { return false; }
     double seconds_merge_profiles = 0;
+    // the root search (FindRoot.h, GapParsimony.h): gap masks carried through a height's merges, and the gap parsimony scores of
+    // the candidate alignments (include/pgm_hip.h); false = this backend has no such kernel (the host's own code runs)
+    virtual bool gapmask_extend_batch(uint32_t, const pgm_gapmask_job *, int = 0) { return false; }
+    virtual bool gap_parsimony_batch(uint32_t, const pgm_parsimony_job *, uint32_t *, int = 0) { return false; }
     virtual void csprofile_create_batch(const class CSProfile &lib, uint32_t nseq, const int8_t *syms, const uint32_t *offs,
                                         const double *tau, const double *pi, const double *p_uniform, double *out,
                                         const uint64_t *out_offs, int worker = 0) = 0;
@@ -421,6 +426,19 @@ ProgressiveAlignmentResult progressive_alignment(const Alphabet &a, const std::m
                                                  const PhyTree &tree, const CSProfile *csprofile,
                                                  const ModelFactory &model_factory,
                                                  const std::map<std::string, std::vector<repeat_t>> *repeats = nullptr);
+// progressive_alignment_find_root (FindRoot.h:236-336): the alignment of the guide tree rerooted on the branch of the lowest gap
+// parsimony score, every branch (cmdlineopts.reroot_flag == 1) or a hill climb over neighbouring branches; prints the score.
+// The directed subtree merges of all candidates run as one DAG, height by height, through the level machinery of the plain pass.
+struct RootSearchStats {
+    bool ran = false;
+    int merges = 0, candidates = 0, heights = 0, batches = 0;
+    double align_s = 0, host_merge_s = 0, gapmask_s = 0, parsimony_s = 0, select_s = 0;
+    uint64_t cells = 0;
+};
+extern RootSearchStats root_search_stats;
+ProgressiveAlignmentResult progressive_alignment_find_root(const Alphabet &a, const std::map<std::string, sequence_t> &sequences,
+                                                           const PhyTree &tree, const ModelFactory &model_factory,
+                                                           const std::map<std::string, std::vector<repeat_t>> *repeats = nullptr);
 
 // ---------------------------------------------------------------------------------------
 // Distances / guide tree

@@ -9,6 +9,7 @@
 #include "../csrc/pgm_pool.h"
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
@@ -21,15 +22,14 @@
 
 namespace pgm {
 
-// extend_alignment (ProgressiveAlignment.h:245-264)
+// extend_alignment (ProgressiveAlignment.h:245-264): the rows of a child as rows of the merged graph of n nodes
 void parallel_for(size_t n, const std::function<void(size_t)> &fn);
 // `spread`: the rows are filled on the host threads (the few nodes near the root carry hundreds of rows each)
-static void extend_alignment(const Alphabet &a, ProgressiveAlignmentResult &result, const std::vector<index_t> &mapping,
-                             const std::map<std::string, sequence_t> &aligned_sequences, bool spread) {
+static void extend_rows(const Alphabet &a, std::map<std::string, sequence_t> &out, index_t n, const std::vector<index_t> &mapping,
+                        const std::map<std::string, sequence_t> &aligned_sequences, bool spread) {
     std::vector<std::pair<const sequence_t *, sequence_t *>> rows;
     rows.reserve(aligned_sequences.size());
-    for (const auto &kv : aligned_sequences) rows.emplace_back(&kv.second, &result.aligned_sequences[kv.first]);
-    const index_t n = result.graph.size();
+    for (const auto &kv : aligned_sequences) rows.emplace_back(&kv.second, &out[kv.first]);
     auto fill = [&](size_t r) {
         sequence_t extended(n - 2, a.unknown());
         const sequence_t &original = *rows[r].first;
@@ -42,6 +42,10 @@ static void extend_alignment(const Alphabet &a, ProgressiveAlignmentResult &resu
     };
     if (spread && rows.size() >= 64) parallel_for(rows.size(), fill);
     else for (size_t r = 0; r < rows.size(); ++r) fill(r);
+}
+static void extend_alignment(const Alphabet &a, ProgressiveAlignmentResult &result, const std::vector<index_t> &mapping,
+                             const std::map<std::string, sequence_t> &aligned_sequences, bool spread) {
+    extend_rows(a, result.aligned_sequences, result.graph.size(), mapping, aligned_sequences, spread);
 }
 
 // ancestral sequences and profiles (--ancestral_seqs; ProgressiveAlignment.h:289-411)
@@ -105,10 +109,13 @@ void parallel_for(size_t n, const std::function<void(size_t)> &fn) {
 namespace {
 struct Node {
     std::string tr_note;   // -R: "TR indels at (...): n" of this internal node
-    const PhyTree *tree;
+    const PhyTree *tree;   // the guide-tree node (a merge of the root search's DAG has none; its leaves have theirs)
     int child[2] = {-1, -1};
+    double len[2] = {0, 0}, sup[2] = {1, 1};   // length and support of the branches to the two children
     int height = 0;
+    int refs = 0;          // merges that still read this result (the root search's DAG: up to three)
     ProgressiveAlignmentResult res;
+    std::vector<index_t> map[2];   // the root search: anc.mapping1 / mapping2 of the merge (rows are not carried through the DAG)
 };
 struct Pending {  // state of one align_progressive_results call between its two halves
     Model model, model1, model2;
@@ -127,6 +134,8 @@ static int collect(const PhyTree &t, std::vector<Node> &nodes) {
     n.tree = &t;
     n.child[0] = c0;
     n.child[1] = c1;
+    if (!t.isLeaf())
+        for (int i = 0; i < 2; ++i) { n.len[i] = t[i].getBranchLength(); n.sup[i] = t[i].getBranchSupport(); }
     n.height = t.isLeaf() ? 0 : 1 + std::max(nodes[c0].height, nodes[c1].height);
     nodes.push_back(std::move(n));
     return (int)nodes.size() - 1;
@@ -196,6 +205,24 @@ std::map<std::string, std::vector<repeat_t>> read_repeats(const Alphabet &a, con
     }
     std::cerr << "found " << n_repeats << " repeats in " << n_sequences << " sequences" << std::endl;
     return map;
+}
+
+// tandem-repeat annotation of the leaves (ProgressiveAlignment.cpp:30-38)
+static void attach_repeats(std::vector<Node> &nodes, const std::vector<int> &leaves, const std::map<std::string, std::vector<repeat_t>> *repeats) {
+    if (!repeats || repeats->empty()) return;
+    for (int li : leaves) {
+        Node &nd = nodes[li];
+        auto it2 = repeats->find(nd.tree->getName());
+        if (it2 == repeats->end()) continue;
+        for (const repeat_t &rep : it2->second) {
+            std::vector<int> tr_hom(nd.res.graph.size(), -1);
+            if ((size_t)rep.start + 1 + rep.tr_hom.size() > tr_hom.size()) error("repeat beyond the end of sequence %s", nd.tree->getName().c_str());
+            std::copy(rep.tr_hom.begin(), rep.tr_hom.end(), tr_hom.begin() + rep.start + 1);
+            nd.res.tr_homologies.push_back(tr_hom);
+            nd.res.tr_source.push_back(nd.tree->getName());
+        }
+        nd.res.graph.addRepeats(nd.res.tr_homologies);
+    }
 }
 
 // A resident pass on several device contexts: the guide tree is cut into subtrees — the most expensive subtree of the cut is replaced
@@ -337,6 +364,231 @@ static void early_refinement(const Alphabet &a, std::vector<Node> &nodes, const 
         if (with_repeats) result.graph.addRepeats(result.tr_homologies);
         nd.res = std::move(result);
     });
+}
+
+namespace {
+// what a level of merges needs besides the nodes: the plain pass and the root search's DAG run the same code
+struct LevelEnv {
+    const Alphabet &a;
+    const ModelFactory &model_factory;
+    const std::map<std::string, std::vector<repeat_t>> *repeats;
+    bool resident_pass;
+    bool earlyref;   // early refinement of every merged node (the plain pass with --early_refinement)
+    bool dag;        // the root search: merges keep their mappings instead of extending rows; children released by reference count
+    std::chrono::steady_clock::time_point tl0;
+};
+}  // namespace
+
+// align_progressive_results (ProgressiveAlignment.h:413-476) of every node of `level` (their children are done) in one batch
+static void run_level(const LevelEnv &env, std::vector<Node> &nodes, std::vector<int> &owner, const std::vector<int> &level, int h) {
+    const Alphabet &a = env.a;
+    const ModelFactory &model_factory = env.model_factory;
+    const std::map<std::string, std::vector<repeat_t>> *repeats = env.repeats;
+    const bool resident_pass = env.resident_pass;
+    const auto tl0 = env.tl0;
+    const size_t L = level.size();
+    std::vector<Pending> pend(L);
+    const auto tp0 = std::chrono::steady_clock::now();
+    if (resident_pass)   // children of a node above the cut of the subtrees: the profiles of the one on another worker are copied over
+        for (size_t k = 0; k < L; ++k) {
+            const Node &nd = nodes[level[k]];
+            for (int c = 0; c < 2; ++c) {
+                const int ch = nd.child[c];
+                Graph &g = nodes[ch].res.graph;
+                if (owner[(size_t)ch] == owner[(size_t)level[k]] || !g.devSites()) continue;
+                const double *there = default_backend().resident_import(owner[(size_t)level[k]], owner[(size_t)ch], g.devSites(), (size_t)a.DIM * g.size());
+                if (!there) error("the backend could not copy resident profiles between its workers");
+                g.setDevSites(there);
+                owner[(size_t)ch] = owner[(size_t)level[k]];
+                ++default_backend().resident_imports;
+            }
+        }
+    parallel_for(L, [&](size_t k) {
+        Node &nd = nodes[level[k]];
+        const ProgressiveAlignmentResult &r1 = nodes[nd.child[0]].res, &r2 = nodes[nd.child[1]].res;
+        double distance1 = nd.len[0], distance2 = nd.len[1];
+        double gap_distance1 = distance1, gap_distance2 = distance2;
+        if (r1.is_csprofile) distance1 = 0;
+        if (r2.is_csprofile) distance2 = 0;
+        Pending &p = pend[k];
+        p.model = model_factory.getModel(distance1 + distance2, gap_distance1 + gap_distance2);
+        p.model1 = model_factory.getModel(distance1, gap_distance1);
+        p.model2 = model_factory.getModel(distance2, gap_distance2);
+        p.cg1.reset(new CleanedGraph(r1.graph));
+        p.cg2.reset(new CleanedGraph(r2.graph));
+    });
+    const auto tp1 = std::chrono::steady_clock::now();
+    std::vector<const Graph *> g1(L), g2(L);
+    std::vector<const Model *> mm(L);
+    for (size_t k = 0; k < L; ++k) { g1[k] = pend[k].cg1.get(); g2[k] = pend[k].cg2.get(); mm[k] = &pend[k].model; }
+    // graphs merged on the device one level below: their profiles never left it (gathered there through the cleaned graphs' node maps)
+    std::vector<pgm_site_ref> rs1, rs2;
+    {
+        bool any = false;
+        for (size_t k = 0; k < L; ++k) any = any || pend[k].cg1->devSites() || pend[k].cg2->devSites();
+        if (any) {
+            rs1.assign(L, pgm_site_ref{nullptr, nullptr, 0u}); rs2.assign(L, pgm_site_ref{nullptr, nullptr, 0u});
+            for (size_t k = 0; k < L; ++k) {
+                if (pend[k].cg1->devSites()) rs1[k] = pgm_site_ref{pend[k].cg1->devSites(), pend[k].cg1->nodeMap(), (uint32_t)pend[k].cg1->originalSize()};
+                if (pend[k].cg2->devSites()) rs2[k] = pgm_site_ref{pend[k].cg2->devSites(), pend[k].cg2->nodeMap(), (uint32_t)pend[k].cg2->originalSize()};
+            }
+        }
+    }
+    std::vector<int> worker_of(L, 0);
+    for (size_t k = 0; k < L; ++k) worker_of[k] = owner[(size_t)level[k]];
+    std::vector<AlignmentResult> ar = alignGraphsBatch(g1, g2, mm, rs1, rs2, resident_pass && default_backend().workers() > 1 ? &worker_of : nullptr);
+    const auto tp2 = std::chrono::steady_clock::now();
+    // mergeGraphs of the whole level: plans on host threads, the node profiles (P g products, L2 normalisation: the
+    // arithmetic of the merge) in ONE device batch, then edges / Graph / extend_alignment on host threads again
+    std::vector<MergePlan> plans(L);
+    std::vector<std::vector<double>> profiles(L);
+    // The merged profiles stay on the device when nothing on the host reads them: one device context, no --profile_out /
+    // --ancestral_seqs, no job dump (Backend::resident; PGM_NO_RESIDENT=1 keeps the round trip)
+    const bool resident = resident_pass;
+    std::vector<const double *> dev_profiles(L, nullptr);
+    parallel_for(L, [&](size_t k) {
+        Node &nd = nodes[level[k]];
+        Pending &p = pend[k];
+        p.cg1->uncleanMapping(ar[k].mapping1);
+        p.cg2->uncleanMapping(ar[k].mapping2);
+        plans[k] = planMerge(nodes[nd.child[0]].res.graph, nodes[nd.child[1]].res.graph, ar[k].mapping1, ar[k].mapping2);
+        if (!resident) profiles[k].assign((size_t)a.DIM * plans[k].mapping1.size(), 0.0);
+    });
+    const auto tq0 = std::chrono::steady_clock::now();
+    bool on_device = false;
+    // (a resident pass: the graphs below need the plans only, not the profiles — the device batch of the node profiles runs on a
+    // thread of its own beside them)
+    std::thread merge_thread;
+    std::exception_ptr merge_error;
+    std::vector<pgm_merge_job> mj(L);   // (filled before the thread starts: the graphs section below releases the children)
+    bool all_on_device = true;
+    if (!host_switches().host_merge)
+        for (size_t k = 0; k < L; ++k) {
+            Node &nd = nodes[level[k]];
+            const Graph &ga = nodes[nd.child[0]].res.graph, &gb = nodes[nd.child[1]].res.graph;
+            pgm_merge_job &j = mj[k];
+            j.dim = (uint32_t)a.DIM; j.n1 = ga.size(); j.n2 = gb.size(); j.nnodes = (uint32_t)plans[k].mapping1.size();
+            j.sites1 = ga.devSites() ? ga.devSites() : ga.col(0); j.sites2 = gb.devSites() ? gb.devSites() : gb.col(0);
+            j.P1 = pend[k].model1.P.data(); j.P2 = pend[k].model2.P.data();
+            j.k1 = plans[k].mapping1.data(); j.k2 = plans[k].mapping2.data(); j.g2_with_P1 = plans[k].g2_with_P1.data();
+            j.profiles = resident ? nullptr : profiles[k].data();
+            all_on_device = all_on_device && ga.devSites() && gb.devSites();
+        }
+    auto merge_on_device = [&]() {
+    if (!host_switches().host_merge) {
+        const auto tm0 = std::chrono::steady_clock::now();
+        {
+            // the merges of a level are independent: dealt to the device contexts by the size of the merged graph
+            Backend &be = default_backend();
+            std::vector<uint64_t> cost(L);
+            for (size_t k = 0; k < L; ++k) cost[k] = mj[k].nnodes;
+            const std::vector<std::vector<uint32_t>> shards = farm_shards(cost, be.workers());
+            if (resident && be.workers() > 1) {   // every merge where its children are: one batch per worker, concurrently
+                std::vector<std::vector<uint32_t>> mine((size_t)be.workers());
+                for (size_t k = 0; k < L; ++k) mine[(size_t)worker_of[k]].push_back((uint32_t)k);
+                std::vector<char> ok(mine.size(), 1);
+                farm_run(mine, [&](int w) {
+                    const std::vector<uint32_t> &sh = mine[(size_t)w];
+                    std::vector<pgm_merge_job> q(sh.size());
+                    std::vector<const double *> dv(sh.size(), nullptr);
+                    for (size_t k = 0; k < sh.size(); ++k) q[k] = mj[sh[k]];
+                    ok[(size_t)w] = be.merge_profiles_batch_res((uint32_t)q.size(), q.data(), dv.data(), w) ? 1 : 0;
+                    for (size_t k = 0; k < sh.size(); ++k) dev_profiles[sh[k]] = dv[k];
+                });
+                on_device = true;
+                for (char c : ok) on_device = on_device && c;
+                if (!on_device) error("the backend could not keep the merged profiles on the device");
+            } else if (resident) {
+                on_device = be.merge_profiles_batch_res((uint32_t)L, mj.data(), dev_profiles.data(), 0);
+                if (!on_device) error("the backend could not keep the merged profiles on the device");
+            } else if (shards.size() <= 1) {
+                on_device = be.merge_profiles_batch((uint32_t)L, mj.data(), 0);
+            } else {
+                std::vector<char> ok(shards.size(), 0);
+                farm_run(shards, [&](int w) {
+                    const std::vector<uint32_t> &sh = shards[(size_t)w];
+                    std::vector<pgm_merge_job> q(sh.size());
+                    for (size_t k = 0; k < sh.size(); ++k) q[k] = mj[sh[k]];
+                    ok[(size_t)w] = be.merge_profiles_batch((uint32_t)q.size(), q.data(), w) ? 1 : 0;
+                });
+                on_device = true;
+                for (size_t w = 0; w < shards.size(); ++w) on_device = on_device && (ok[w] || shards[w].empty());
+            }
+        }
+        default_backend().seconds_merge_profiles += std::chrono::duration<double>(std::chrono::steady_clock::now() - tm0).count();
+    }
+    };
+    if (resident && all_on_device && !host_switches().host_merge) merge_thread = std::thread([&]() { try { merge_on_device(); } catch (...) { merge_error = std::current_exception(); } });
+    else merge_on_device();
+    struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } merge_joiner{merge_thread};   // (also when the section below throws)
+    const auto tq1 = std::chrono::steady_clock::now();
+    std::atomic<long long> ns_merge(0), ns_extend(0);
+    parallel_for(L, [&](size_t k) {
+        const auto tk0 = std::chrono::steady_clock::now();
+        Node &nd = nodes[level[k]];
+        ProgressiveAlignmentResult &r1 = nodes[nd.child[0]].res, &r2 = nodes[nd.child[1]].res;
+        Pending &p = pend[k];
+        ProgressiveAlignmentResult &result = nd.res;
+        result.score = ar[k].score;
+        result.is_csprofile = false;
+        result.n_tr_indels = ar[k].n_tr_indels + r1.n_tr_indels + r2.n_tr_indels;
+        if (!resident && !on_device) mergeProfilesHost(r1.graph, r2.graph, p.model1, p.model2, plans[k], profiles[k]);
+        AncestralResult anc = finishMerge(r1.graph, r2.graph, plans[k], resident ? nullptr : profiles[k].data(), nd.sup[0], nd.sup[1]);
+        result.graph = anc.graph;
+        const auto tk1 = std::chrono::steady_clock::now();
+        if (!env.dag) {
+            extend_alignment(a, result, anc.mapping1, r1.aligned_sequences, L == 1);
+            extend_alignment(a, result, anc.mapping2, r2.aligned_sequences, L == 1);
+        } else {
+            nd.map[0] = anc.mapping1;
+            nd.map[1] = anc.mapping2;
+        }
+        ns_merge += std::chrono::duration_cast<std::chrono::nanoseconds>(tk1 - tk0).count();
+        ns_extend += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tk1).count();
+        if (!r1.tr_homologies.empty() || !r2.tr_homologies.empty()) {   // ProgressiveAlignment.h:455-456, 468
+            extend_tr_homologies(result, anc.mapping1, r1.tr_homologies, r1.tr_source);
+            extend_tr_homologies(result, anc.mapping2, r2.tr_homologies, r2.tr_source);
+        }
+        if (!cmdlineopts.profile_file.empty() || cmdlineopts.ancestral_flag) {
+            result.profiles.insert(r1.profiles.begin(), r1.profiles.end());
+            result.profiles.insert(r2.profiles.begin(), r2.profiles.end());
+        }
+        if (cmdlineopts.ancestral_flag) {   // ProgressiveAlignment.h:458-466
+            if (r1.aligned_sequences.size() > 1) ancestral_seq(a, result, create_ancestral_seq_name(r1.aligned_sequences), r1.graph, &anc.mapping1, anc.is_matched, p.model1);
+            if (r2.aligned_sequences.size() > 1) ancestral_seq(a, result, create_ancestral_seq_name(r2.aligned_sequences), r2.graph, &anc.mapping2, anc.is_matched, p.model2);
+            ancestral_seq(a, result, create_ancestral_seq_name(result.aligned_sequences), result.graph, nullptr, anc.is_matched, p.model);
+        }
+        if (cmdlineopts.repeats_flag && !env.dag) nd.tr_note = "TR indels at " + create_ancestral_seq_name(result.aligned_sequences) + ": " + std::to_string(ar[k].n_tr_indels);   // (:470-473)
+        if (repeats && !repeats->empty()) result.graph.addRepeats(result.tr_homologies);   // (:468; with no annotation at all the merged graph has no repeat edges either way)
+        // children are no longer needed (the reference copies them by value and drops them)
+        if (!env.earlyref && !env.dag) {   // (the reference's alignment_cache, ProgressiveAlignment.h:107-109: the parent's refinement reads them again)
+            r1 = ProgressiveAlignmentResult();
+            r2 = ProgressiveAlignmentResult();
+        }
+        p.cg1.reset();
+        p.cg2.reset();
+        profiles[k] = std::vector<double>();
+    });
+    if (merge_thread.joinable()) {
+        merge_thread.join();
+        if (merge_error) std::rethrow_exception(merge_error);
+    }
+    if (resident) for (size_t k = 0; k < L; ++k) nodes[level[k]].res.graph.setDevSites(dev_profiles[k]);
+    if (env.dag)   // a directed result of the root search is read by up to three merges, of any heights
+        for (size_t k = 0; k < L; ++k)
+            for (int c = 0; c < 2; ++c) {
+                Node &ch = nodes[(size_t)nodes[level[k]].child[c]];
+                if (--ch.refs == 0) ch.res = ProgressiveAlignmentResult();
+            }
+    if (env.earlyref) early_refinement(a, nodes, level, model_factory, repeats && !repeats->empty());
+    const auto tp3 = std::chrono::steady_clock::now();
+    if (host_switches().profile)
+        fprintf(stderr, "[%.1f ms] level %d: %zu nodes, host pre %.1f ms, alignGraphsBatch %.1f ms, host post (merge, extend) %.1f ms\n",
+                std::chrono::duration<double, std::milli>(tp3 - tl0).count(), h, L,
+                std::chrono::duration<double, std::milli>(tp1 - tp0).count(), std::chrono::duration<double, std::milli>(tp2 - tp1).count(),
+                std::chrono::duration<double, std::milli>(tp3 - tp2).count()),
+        fprintf(stderr, "    post: plans %.1f ms, node profiles %.1f, edges / graphs / extend %.1f (summed over the nodes: graphs %.2f ms, extend_alignment %.2f)\n", std::chrono::duration<double, std::milli>(tq0 - tp2).count(),
+                std::chrono::duration<double, std::milli>(tq1 - tq0).count(), std::chrono::duration<double, std::milli>(tp3 - tq1).count(), ns_merge.load() / 1e6, ns_extend.load() / 1e6);
 }
 
 ProgressiveAlignmentResult progressive_alignment(const Alphabet &a, const std::map<std::string, sequence_t> &sequences,
@@ -510,221 +762,17 @@ ProgressiveAlignmentResult progressive_alignment(const Alphabet &a, const std::m
         }
     }
 
-    if (repeats && !repeats->empty()) {   // tandem-repeat annotation of the leaves (ProgressiveAlignment.cpp:30-38)
-        for (int li : leaves) {
-            Node &nd = nodes[li];
-            auto it2 = repeats->find(nd.tree->getName());
-            if (it2 == repeats->end()) continue;
-            for (const repeat_t &rep : it2->second) {
-                std::vector<int> tr_hom(nd.res.graph.size(), -1);
-                if ((size_t)rep.start + 1 + rep.tr_hom.size() > tr_hom.size()) error("repeat beyond the end of sequence %s", nd.tree->getName().c_str());
-                std::copy(rep.tr_hom.begin(), rep.tr_hom.end(), tr_hom.begin() + rep.start + 1);
-                nd.res.tr_homologies.push_back(tr_hom);
-                nd.res.tr_source.push_back(nd.tree->getName());
-            }
-            nd.res.graph.addRepeats(nd.res.tr_homologies);
-        }
-    }
+    attach_repeats(nodes, leaves, repeats);
     if (host_switches().profile)
         fprintf(stderr, "leaves: %zu, %.1f ms (names / owners %.2f, graphs %.2f, profiles %.2f)\n", leaves.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count(),
                 std::chrono::duration<double, std::milli>(tl1 - tl0).count(), std::chrono::duration<double, std::milli>(tl2 - tl1).count(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl2).count());
     // ---- internal nodes, one guide-tree level per batch (ProgressiveAlignment.h:413-476) ----
+    const LevelEnv env{a, model_factory, repeats, resident_pass, cmdlineopts.earlyref_flag, false, tl0};
     for (int h = 1; h <= maxh; ++h) {
         std::vector<int> level;
         for (size_t i = 0; i < nodes.size(); ++i)
             if (nodes[i].height == h) level.push_back((int)i);
-        const size_t L = level.size();
-        std::vector<Pending> pend(L);
-        const auto tp0 = std::chrono::steady_clock::now();
-        if (resident_pass)   // children of a node above the cut of the subtrees: the profiles of the one on another worker are copied over
-            for (size_t k = 0; k < L; ++k) {
-                const Node &nd = nodes[level[k]];
-                for (int c = 0; c < 2; ++c) {
-                    const int ch = nd.child[c];
-                    Graph &g = nodes[ch].res.graph;
-                    if (owner[(size_t)ch] == owner[(size_t)level[k]] || !g.devSites()) continue;
-                    const double *there = default_backend().resident_import(owner[(size_t)level[k]], owner[(size_t)ch], g.devSites(), (size_t)a.DIM * g.size());
-                    if (!there) error("the backend could not copy resident profiles between its workers");
-                    g.setDevSites(there);
-                    owner[(size_t)ch] = owner[(size_t)level[k]];
-                    ++default_backend().resident_imports;
-                }
-            }
-        parallel_for(L, [&](size_t k) {
-            Node &nd = nodes[level[k]];
-            const ProgressiveAlignmentResult &r1 = nodes[nd.child[0]].res, &r2 = nodes[nd.child[1]].res;
-            double distance1 = (*nd.tree)[0].getBranchLength(), distance2 = (*nd.tree)[1].getBranchLength();
-            double gap_distance1 = distance1, gap_distance2 = distance2;
-            if (r1.is_csprofile) distance1 = 0;
-            if (r2.is_csprofile) distance2 = 0;
-            Pending &p = pend[k];
-            p.model = model_factory.getModel(distance1 + distance2, gap_distance1 + gap_distance2);
-            p.model1 = model_factory.getModel(distance1, gap_distance1);
-            p.model2 = model_factory.getModel(distance2, gap_distance2);
-            p.cg1.reset(new CleanedGraph(r1.graph));
-            p.cg2.reset(new CleanedGraph(r2.graph));
-        });
-        const auto tp1 = std::chrono::steady_clock::now();
-        std::vector<const Graph *> g1(L), g2(L);
-        std::vector<const Model *> mm(L);
-        for (size_t k = 0; k < L; ++k) { g1[k] = pend[k].cg1.get(); g2[k] = pend[k].cg2.get(); mm[k] = &pend[k].model; }
-        // graphs merged on the device one level below: their profiles never left it (gathered there through the cleaned graphs' node maps)
-        std::vector<pgm_site_ref> rs1, rs2;
-        {
-            bool any = false;
-            for (size_t k = 0; k < L; ++k) any = any || pend[k].cg1->devSites() || pend[k].cg2->devSites();
-            if (any) {
-                rs1.assign(L, pgm_site_ref{nullptr, nullptr, 0u}); rs2.assign(L, pgm_site_ref{nullptr, nullptr, 0u});
-                for (size_t k = 0; k < L; ++k) {
-                    if (pend[k].cg1->devSites()) rs1[k] = pgm_site_ref{pend[k].cg1->devSites(), pend[k].cg1->nodeMap(), (uint32_t)pend[k].cg1->originalSize()};
-                    if (pend[k].cg2->devSites()) rs2[k] = pgm_site_ref{pend[k].cg2->devSites(), pend[k].cg2->nodeMap(), (uint32_t)pend[k].cg2->originalSize()};
-                }
-            }
-        }
-        std::vector<int> worker_of(L, 0);
-        for (size_t k = 0; k < L; ++k) worker_of[k] = owner[(size_t)level[k]];
-        std::vector<AlignmentResult> ar = alignGraphsBatch(g1, g2, mm, rs1, rs2, resident_pass && default_backend().workers() > 1 ? &worker_of : nullptr);
-        const auto tp2 = std::chrono::steady_clock::now();
-        // mergeGraphs of the whole level: plans on host threads, the node profiles (P g products, L2 normalisation: the
-        // arithmetic of the merge) in ONE device batch, then edges / Graph / extend_alignment on host threads again
-        std::vector<MergePlan> plans(L);
-        std::vector<std::vector<double>> profiles(L);
-        // The merged profiles stay on the device when nothing on the host reads them: one device context, no --profile_out /
-        // --ancestral_seqs, no job dump (Backend::resident; PGM_NO_RESIDENT=1 keeps the round trip)
-        const bool resident = resident_pass;
-        std::vector<const double *> dev_profiles(L, nullptr);
-        parallel_for(L, [&](size_t k) {
-            Node &nd = nodes[level[k]];
-            Pending &p = pend[k];
-            p.cg1->uncleanMapping(ar[k].mapping1);
-            p.cg2->uncleanMapping(ar[k].mapping2);
-            plans[k] = planMerge(nodes[nd.child[0]].res.graph, nodes[nd.child[1]].res.graph, ar[k].mapping1, ar[k].mapping2);
-            if (!resident) profiles[k].assign((size_t)a.DIM * plans[k].mapping1.size(), 0.0);
-        });
-        const auto tq0 = std::chrono::steady_clock::now();
-        bool on_device = false;
-        // (a resident pass: the graphs below need the plans only, not the profiles — the device batch of the node profiles runs on a
-        // thread of its own beside them)
-        std::thread merge_thread;
-        std::exception_ptr merge_error;
-        std::vector<pgm_merge_job> mj(L);   // (filled before the thread starts: the graphs section below releases the children)
-        bool all_on_device = true;
-        if (!host_switches().host_merge)
-            for (size_t k = 0; k < L; ++k) {
-                Node &nd = nodes[level[k]];
-                const Graph &ga = nodes[nd.child[0]].res.graph, &gb = nodes[nd.child[1]].res.graph;
-                pgm_merge_job &j = mj[k];
-                j.dim = (uint32_t)a.DIM; j.n1 = ga.size(); j.n2 = gb.size(); j.nnodes = (uint32_t)plans[k].mapping1.size();
-                j.sites1 = ga.devSites() ? ga.devSites() : ga.col(0); j.sites2 = gb.devSites() ? gb.devSites() : gb.col(0);
-                j.P1 = pend[k].model1.P.data(); j.P2 = pend[k].model2.P.data();
-                j.k1 = plans[k].mapping1.data(); j.k2 = plans[k].mapping2.data(); j.g2_with_P1 = plans[k].g2_with_P1.data();
-                j.profiles = resident ? nullptr : profiles[k].data();
-                all_on_device = all_on_device && ga.devSites() && gb.devSites();
-            }
-        auto merge_on_device = [&]() {
-        if (!host_switches().host_merge) {
-            const auto tm0 = std::chrono::steady_clock::now();
-            {
-                // the merges of a level are independent: dealt to the device contexts by the size of the merged graph
-                Backend &be = default_backend();
-                std::vector<uint64_t> cost(L);
-                for (size_t k = 0; k < L; ++k) cost[k] = mj[k].nnodes;
-                const std::vector<std::vector<uint32_t>> shards = farm_shards(cost, be.workers());
-                if (resident && be.workers() > 1) {   // every merge where its children are: one batch per worker, concurrently
-                    std::vector<std::vector<uint32_t>> mine((size_t)be.workers());
-                    for (size_t k = 0; k < L; ++k) mine[(size_t)worker_of[k]].push_back((uint32_t)k);
-                    std::vector<char> ok(mine.size(), 1);
-                    farm_run(mine, [&](int w) {
-                        const std::vector<uint32_t> &sh = mine[(size_t)w];
-                        std::vector<pgm_merge_job> q(sh.size());
-                        std::vector<const double *> dv(sh.size(), nullptr);
-                        for (size_t k = 0; k < sh.size(); ++k) q[k] = mj[sh[k]];
-                        ok[(size_t)w] = be.merge_profiles_batch_res((uint32_t)q.size(), q.data(), dv.data(), w) ? 1 : 0;
-                        for (size_t k = 0; k < sh.size(); ++k) dev_profiles[sh[k]] = dv[k];
-                    });
-                    on_device = true;
-                    for (char c : ok) on_device = on_device && c;
-                    if (!on_device) error("the backend could not keep the merged profiles on the device");
-                } else if (resident) {
-                    on_device = be.merge_profiles_batch_res((uint32_t)L, mj.data(), dev_profiles.data(), 0);
-                    if (!on_device) error("the backend could not keep the merged profiles on the device");
-                } else if (shards.size() <= 1) {
-                    on_device = be.merge_profiles_batch((uint32_t)L, mj.data(), 0);
-                } else {
-                    std::vector<char> ok(shards.size(), 0);
-                    farm_run(shards, [&](int w) {
-                        const std::vector<uint32_t> &sh = shards[(size_t)w];
-                        std::vector<pgm_merge_job> q(sh.size());
-                        for (size_t k = 0; k < sh.size(); ++k) q[k] = mj[sh[k]];
-                        ok[(size_t)w] = be.merge_profiles_batch((uint32_t)q.size(), q.data(), w) ? 1 : 0;
-                    });
-                    on_device = true;
-                    for (size_t w = 0; w < shards.size(); ++w) on_device = on_device && (ok[w] || shards[w].empty());
-                }
-            }
-            default_backend().seconds_merge_profiles += std::chrono::duration<double>(std::chrono::steady_clock::now() - tm0).count();
-        }
-        };
-        if (resident && all_on_device && !host_switches().host_merge) merge_thread = std::thread([&]() { try { merge_on_device(); } catch (...) { merge_error = std::current_exception(); } });
-        else merge_on_device();
-        struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } merge_joiner{merge_thread};   // (also when the section below throws)
-        const auto tq1 = std::chrono::steady_clock::now();
-        std::atomic<long long> ns_merge(0), ns_extend(0);
-        parallel_for(L, [&](size_t k) {
-            const auto tk0 = std::chrono::steady_clock::now();
-            Node &nd = nodes[level[k]];
-            ProgressiveAlignmentResult &r1 = nodes[nd.child[0]].res, &r2 = nodes[nd.child[1]].res;
-            Pending &p = pend[k];
-            ProgressiveAlignmentResult &result = nd.res;
-            result.score = ar[k].score;
-            result.is_csprofile = false;
-            result.n_tr_indels = ar[k].n_tr_indels + r1.n_tr_indels + r2.n_tr_indels;
-            if (!resident && !on_device) mergeProfilesHost(r1.graph, r2.graph, p.model1, p.model2, plans[k], profiles[k]);
-            AncestralResult anc = finishMerge(r1.graph, r2.graph, plans[k], resident ? nullptr : profiles[k].data(), (*nd.tree)[0].getBranchSupport(), (*nd.tree)[1].getBranchSupport());
-            result.graph = anc.graph;
-            const auto tk1 = std::chrono::steady_clock::now();
-            extend_alignment(a, result, anc.mapping1, r1.aligned_sequences, L == 1);
-            extend_alignment(a, result, anc.mapping2, r2.aligned_sequences, L == 1);
-            ns_merge += std::chrono::duration_cast<std::chrono::nanoseconds>(tk1 - tk0).count();
-            ns_extend += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tk1).count();
-            if (!r1.tr_homologies.empty() || !r2.tr_homologies.empty()) {   // ProgressiveAlignment.h:455-456, 468
-                extend_tr_homologies(result, anc.mapping1, r1.tr_homologies, r1.tr_source);
-                extend_tr_homologies(result, anc.mapping2, r2.tr_homologies, r2.tr_source);
-            }
-            if (!cmdlineopts.profile_file.empty() || cmdlineopts.ancestral_flag) {
-                result.profiles.insert(r1.profiles.begin(), r1.profiles.end());
-                result.profiles.insert(r2.profiles.begin(), r2.profiles.end());
-            }
-            if (cmdlineopts.ancestral_flag) {   // ProgressiveAlignment.h:458-466
-                if (r1.aligned_sequences.size() > 1) ancestral_seq(a, result, create_ancestral_seq_name(r1.aligned_sequences), r1.graph, &anc.mapping1, anc.is_matched, p.model1);
-                if (r2.aligned_sequences.size() > 1) ancestral_seq(a, result, create_ancestral_seq_name(r2.aligned_sequences), r2.graph, &anc.mapping2, anc.is_matched, p.model2);
-                ancestral_seq(a, result, create_ancestral_seq_name(result.aligned_sequences), result.graph, nullptr, anc.is_matched, p.model);
-            }
-            if (cmdlineopts.repeats_flag) nd.tr_note = "TR indels at " + create_ancestral_seq_name(result.aligned_sequences) + ": " + std::to_string(ar[k].n_tr_indels);   // (:470-473)
-            if (repeats && !repeats->empty()) result.graph.addRepeats(result.tr_homologies);   // (:468; with no annotation at all the merged graph has no repeat edges either way)
-            // children are no longer needed (the reference copies them by value and drops them)
-            if (!cmdlineopts.earlyref_flag) {   // (the reference's alignment_cache, ProgressiveAlignment.h:107-109: the parent's refinement reads them again)
-                r1 = ProgressiveAlignmentResult();
-                r2 = ProgressiveAlignmentResult();
-            }
-            p.cg1.reset();
-            p.cg2.reset();
-            profiles[k] = std::vector<double>();
-        });
-        if (merge_thread.joinable()) {
-            merge_thread.join();
-            if (merge_error) std::rethrow_exception(merge_error);
-        }
-        if (resident) for (size_t k = 0; k < L; ++k) nodes[level[k]].res.graph.setDevSites(dev_profiles[k]);
-        if (cmdlineopts.earlyref_flag) early_refinement(a, nodes, level, model_factory, repeats && !repeats->empty());
-        const auto tp3 = std::chrono::steady_clock::now();
-        if (host_switches().profile)
-            fprintf(stderr, "[%.1f ms] level %d: %zu nodes, host pre %.1f ms, alignGraphsBatch %.1f ms, host post (merge, extend) %.1f ms\n",
-                    std::chrono::duration<double, std::milli>(tp3 - tl0).count(), h, L,
-                    std::chrono::duration<double, std::milli>(tp1 - tp0).count(), std::chrono::duration<double, std::milli>(tp2 - tp1).count(),
-                    std::chrono::duration<double, std::milli>(tp3 - tp2).count()),
-            fprintf(stderr, "    post: plans %.1f ms, node profiles %.1f, edges / graphs / extend %.1f (summed over the nodes: graphs %.2f ms, extend_alignment %.2f)\n", std::chrono::duration<double, std::milli>(tq0 - tp2).count(),
-                    std::chrono::duration<double, std::milli>(tq1 - tq0).count(), std::chrono::duration<double, std::milli>(tp3 - tq1).count(), ns_merge.load() / 1e6, ns_extend.load() / 1e6);
+        run_level(env, nodes, owner, level, h);
     }
     if (cmdlineopts.repeats_flag)   // the reference prints them as its recursion returns: post-order, which is the order of `nodes`
         for (const Node &nd : nodes) if (!nd.tr_note.empty()) std::cerr << nd.tr_note << std::endl;
@@ -736,5 +784,465 @@ ProgressiveAlignmentResult progressive_alignment(const Alphabet &a, const std::m
         fprintf(stderr, "[%.1f ms] nodes released\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count());
     return out;
 }
+
+// ==== root search (FindRoot.h, GapParsimony.h) =====================================================================
+// The reference memoises one alignment per directed subtree of the unrooted guide tree (node::getAlignment) and one per branch
+// (edge::getAlignment), computing them on demand in its recursion.  Here they are the nodes of a DAG of merges, run height by
+// height through run_level like the levels of a plain pass.  Rows are not carried through the DAG: every merge keeps its two
+// mappings and a gap mask of its rows (one bit per column), which is all the gap parsimony reads; the winner's rows are
+// composed from the mappings at the end.
+RootSearchStats root_search_stats;
+
+namespace {
+struct UNode { int edges[3] = {-1, -1, -1}; const PhyTree *tree = nullptr; };   // edges[0]: toward the original root
+struct UEdge { int nodes[2] = {-1, -1}; double length = -1, support = -1; };      // nodes[0]: the parent side
+struct UGraph {
+    std::vector<UNode> nodes;
+    std::vector<UEdge> edges;
+    bool isLeaf(int n) const { return nodes[(size_t)n].edges[1] < 0; }
+    int other(int e, int n) const { return edges[(size_t)e].nodes[0] == n ? edges[(size_t)e].nodes[1] : edges[(size_t)e].nodes[0]; }
+    int slot(int n, int e) const { for (int j = 0; j < 3; ++j) if (nodes[(size_t)n].edges[j] == e) return j; error("invalid edge"); }
+};
+struct GapMask {
+    std::vector<uint64_t> bits;   // rows.size() x ceil(ncols / 64) words (include/pgm_hip.h)
+    uint32_t ncols = 0;
+    std::vector<int> rows;        // the graph leaves of the rows, in order
+    int refs = 0;                 // merges that still extend it
+};
+}  // namespace
+
+// tree2graph (FindRoot.h:176-234): edges in creation order, the edge to child 0 and its whole subtree before the edge to child 1
+static void tree2graph(UGraph &g, int current, const PhyTree &tree) {
+    g.nodes[(size_t)current].tree = &tree;
+    if (tree.isLeaf()) return;
+    if (tree.n_children() != 2) error("multifurcations not allowed");
+    for (int i = 0; i < 2; ++i) {
+        const int e = (int)g.edges.size(), n = (int)g.nodes.size();
+        g.edges.push_back(UEdge());
+        g.nodes.push_back(UNode());
+        g.edges[(size_t)e].length = tree[i].getBranchLength();
+        g.edges[(size_t)e].support = tree[i].getBranchSupport();
+        g.edges[(size_t)e].nodes[0] = current; g.edges[(size_t)e].nodes[1] = n;
+        g.nodes[(size_t)current].edges[1 + i] = e;
+        g.nodes[(size_t)n].edges[0] = e;
+        tree2graph(g, n, tree[i]);
+    }
+}
+
+// FindRoot.h:242-275: a bifurcating root becomes one edge (lengths summed, the larger support), a trifurcating one a node of three
+static UGraph unrooted_graph(const PhyTree &tree) {
+    UGraph g;
+    if (tree.n_children() == 2) {
+        UEdge e0;
+        e0.length = tree[0].getBranchLength() + tree[1].getBranchLength();
+        e0.support = std::max(tree[0].getBranchSupport(), tree[1].getBranchSupport());
+        e0.nodes[0] = 0; e0.nodes[1] = 1;
+        g.edges.push_back(e0);
+        g.nodes.resize(2);
+        g.nodes[0].edges[0] = 0; g.nodes[1].edges[0] = 0;
+        tree2graph(g, 0, tree[0]);
+        tree2graph(g, 1, tree[1]);
+    } else if (tree.n_children() == 3) {
+        g.nodes.resize(1);
+        for (int i = 0; i < 3; ++i) {
+            const int e = (int)g.edges.size(), n = (int)g.nodes.size();
+            g.edges.push_back(UEdge());
+            g.nodes.push_back(UNode());
+            g.edges[(size_t)e].length = tree[i].getBranchLength();
+            g.edges[(size_t)e].support = tree[i].getBranchSupport();
+            g.edges[(size_t)e].nodes[0] = 0; g.edges[(size_t)e].nodes[1] = n;
+            g.nodes[(size_t)n].edges[0] = e;
+            g.nodes[0].edges[i] = e;
+            tree2graph(g, n, tree[i]);
+        }
+    } else {
+        error("multifurcations not allowed");
+    }
+    return g;
+}
+
+// the host's own code behind Backend::gapmask_extend_batch / gap_parsimony_batch (same bits)
+static void gapmask_extend_host(const pgm_gapmask_job &j) {
+    const uint32_t wi = (j.ncols_in + 63) / 64, wo = (j.ncols_out + 63) / 64;
+    uint32_t mapped = 0;
+    for (uint32_t c = 0; c < j.ncols_out; ++c) mapped += j.mapping[c] != PGM_GAP;
+    if (mapped != j.ncols_in) error("gap mask: the mapping does not cover the child's columns");
+    for (uint32_t r = 0; r < j.nrows; ++r) {
+        const uint64_t *src = j.src + (size_t)r * wi;
+        uint64_t *dst = j.dst + (size_t)r * wo;
+        std::fill(dst, dst + wo, 0ull);
+        uint32_t k = 0;
+        for (uint32_t c = 0; c < j.ncols_out; ++c) {
+            uint64_t bit = 1;
+            if (j.mapping[c] != PGM_GAP) { bit = (src[k >> 6] >> (k & 63)) & 1ull; ++k; }
+            dst[c >> 6] |= bit << (c & 63);
+        }
+    }
+}
+static uint64_t spread32(uint32_t v) {   // bit c to bit 2c
+    uint64_t x = v;
+    x = (x | (x << 16)) & 0x0000FFFF0000FFFFull;
+    x = (x | (x << 8)) & 0x00FF00FF00FF00FFull;
+    x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full;
+    x = (x | (x << 2)) & 0x3333333333333333ull;
+    x = (x | (x << 1)) & 0x5555555555555555ull;
+    return x;
+}
+// GapParsimony.h:22-125 on a post-order topology: blocks of 32 columns, bit 2c residue, bit 2c + 1 gap; the padding loop's ones
+// (the whole last block when the length is a multiple of 32)
+static uint32_t gap_parsimony_host(const pgm_parsimony_job &j) {
+    const uint32_t nb = (j.ncols + 31) / 32, words = (j.ncols + 63) / 64, ninner = j.nleaves - 1;
+    std::vector<uint64_t> cons((size_t)ninner * nb);
+    auto leaf = [&](uint32_t row, uint32_t b) {
+        const uint32_t g = (uint32_t)(j.masks[(size_t)row * words + (b >> 1)] >> (32u * (b & 1u)));
+        const uint32_t nv = b + 1 < nb ? 32u : j.ncols % 32u;
+        const uint32_t vm = nv == 32u ? 0xFFFFFFFFu : (1u << nv) - 1u;
+        return spread32(~g & vm) | (spread32(g & vm) << 1) | (spread32(~vm) * 3ull);
+    };
+    uint32_t score = 0;
+    for (uint32_t k = 0; k < ninner; ++k)
+        for (uint32_t b = 0; b < nb; ++b) {
+            uint64_t w[2];
+            for (int s = 0; s < 2; ++s) {
+                const uint32_t c = j.children[2 * (size_t)k + s];
+                w[s] = c < j.nleaves ? leaf(c, b) : cons[(size_t)(c - j.nleaves) * nb + b];
+            }
+            const uint64_t x = w[0] & w[1];
+            uint64_t t = ~x;
+            t = t & (t << 1) & 0xAAAAAAAAAAAAAAAAull;
+            score += (uint32_t)__builtin_popcountll(t);
+            cons[(size_t)k * nb + b] = x | t | (t >> 1);
+        }
+    return score;
+}
+
+namespace {
+struct RootSearch {
+    const Alphabet &a;
+    const std::map<std::string, sequence_t> &sequences;
+    const LevelEnv &env;
+    UGraph g;
+    std::vector<Node> nodes;                  // the DAG: leaves, directed results, candidates
+    std::vector<GapMask> mask;
+    std::vector<std::array<int, 3>> dres;     // graph node, edge slot -> DAG node of the node's result seen from that edge
+    std::vector<int> cand;                    // edge -> DAG node of its candidate
+    std::vector<double> score;                // edge -> gap parsimony score (-1: not yet)
+    std::vector<char> done;
+    std::vector<int> owner;
+    // the batch bound: the cells of the largest alignGraphs batch the kernels have been tested with (the headline family's top levels)
+    static constexpr double MAX_BATCH_CELLS = 2.7e8;
+
+    RootSearch(const Alphabet &a_, const std::map<std::string, sequence_t> &seqs, const LevelEnv &e, const PhyTree &tree)
+        : a(a_), sequences(seqs), env(e), g(unrooted_graph(tree)) {
+        dres.assign(g.nodes.size(), std::array<int, 3>{{-1, -1, -1}});
+        cand.assign(g.edges.size(), -1);
+        score.assign(g.edges.size(), -1.0);
+    }
+    int add_node(Node &&n) {
+        nodes.push_back(std::move(n));
+        mask.push_back(GapMask());
+        done.push_back(0);
+        return (int)nodes.size() - 1;
+    }
+    // the consumers a directed result has in the full DAG: the results of the node across its edge seen from that node's other
+    // edges, and the candidate of the edge itself
+    int consumers(int n, int s) const {
+        const int m = g.other(g.nodes[(size_t)n].edges[s], n);
+        int deg = 0;
+        for (int j = 0; j < 3; ++j) deg += g.nodes[(size_t)m].edges[j] >= 0;
+        return deg;
+    }
+    // node::getAlignment (FindRoot.h:85-122): the results of the two other neighbours, ascending edge slots
+    int directed(int n, int s) {
+        if (dres[(size_t)n][(size_t)s] >= 0) return dres[(size_t)n][(size_t)s];
+        Node nd;
+        nd.tree = nullptr;
+        if (g.isLeaf(n)) {
+            nd.tree = g.nodes[(size_t)n].tree;
+        } else {
+            const int i1 = s == 0 ? 1 : 0, i2 = s == 2 ? 1 : 2;
+            const int sl[2] = {i1, i2};
+            for (int c = 0; c < 2; ++c) {
+                const int e = g.nodes[(size_t)n].edges[sl[c]], m = g.other(e, n);
+                nd.child[c] = directed(m, g.slot(m, e));
+                nd.len[c] = g.edges[(size_t)e].length;
+                nd.sup[c] = g.edges[(size_t)e].support;
+            }
+            nd.height = 1 + std::max(nodes[(size_t)nd.child[0]].height, nodes[(size_t)nd.child[1]].height);
+        }
+        nd.refs = consumers(n, s);
+        const int id = add_node(std::move(nd));
+        mask[(size_t)id].refs = nodes[(size_t)id].refs;
+        if (g.isLeaf(n)) mask[(size_t)id].rows.assign(1, n);
+        dres[(size_t)n][(size_t)s] = id;
+        return id;
+    }
+    // edge::getAlignment (FindRoot.h:124-134): the two sides at half the edge's length each, its support on both
+    int candidate(int e) {
+        if (cand[(size_t)e] >= 0) return cand[(size_t)e];
+        const UEdge &ue = g.edges[(size_t)e];
+        Node nd;
+        nd.tree = nullptr;
+        for (int c = 0; c < 2; ++c) {
+            const int m = ue.nodes[c];
+            nd.child[c] = directed(m, g.slot(m, e));
+            nd.len[c] = ue.length / 2;
+            nd.sup[c] = ue.support;
+        }
+        nd.height = 1 + std::max(nodes[(size_t)nd.child[0]].height, nodes[(size_t)nd.child[1]].height);
+        const int id = add_node(std::move(nd));
+        cand[(size_t)e] = id;
+        return id;
+    }
+
+    void build_leaves(const std::vector<int> &leaves) {
+        const bool resident_leaves = env.resident_pass;
+        parallel_for(leaves.size(), [&](size_t k) {
+            Node &nd = nodes[(size_t)leaves[k]];
+            const sequence_t &seq = sequences.at(nd.tree->getName());
+            nd.res.score = 0;
+            nd.res.n_tr_indels = 0;
+            nd.res.is_csprofile = false;   // (the header's tree2graph: plain sequence graphs even with -c, FindRoot.h:183)
+            nd.res.graph = resident_leaves ? Graph(a.DIM, (index_t)seq.size() + 2, Graph::NoSites()) : SequenceGraph(a, seq);
+            GapMask &m = mask[(size_t)leaves[k]];
+            m.ncols = (uint32_t)seq.size();
+            m.bits.assign((seq.size() + 63) / 64, 0ull);
+            for (size_t c = 0; c < seq.size(); ++c) if (a.isGap(seq[c])) m.bits[c >> 6] |= 1ull << (c & 63);
+            done[(size_t)leaves[k]] = 1;
+        });
+        if (resident_leaves && !leaves.empty()) {
+            std::vector<uint32_t> offs(leaves.size() + 1, 0);
+            for (size_t s = 0; s < leaves.size(); ++s) offs[s + 1] = offs[s] + (uint32_t)sequences.at(nodes[(size_t)leaves[s]].tree->getName()).size();
+            std::vector<int8_t> syms(offs[leaves.size()]);
+            parallel_for(leaves.size(), [&](size_t s) {
+                int8_t *out = syms.data() + offs[s];
+                for (int8_t c : sequences.at(nodes[(size_t)leaves[s]].tree->getName())) *out++ = a.isValid(c) ? (int8_t)a.value(c) : (int8_t)-1;
+            });
+            std::vector<const double *> dev(leaves.size(), nullptr);
+            if (!default_backend().resident_onehot((uint32_t)a.DIM, (uint32_t)leaves.size(), syms.data(), offs.data(), dev.data(), 0)) error("the backend could not build the leaf graphs on the device");
+            for (size_t s = 0; s < leaves.size(); ++s) nodes[(size_t)leaves[s]].res.graph.setDevSites(dev[s]);
+        }
+        attach_repeats(nodes, leaves, env.repeats);
+    }
+
+    // the gap masks of a height's merges: each child's rows through the merge's mapping, in one backend call
+    void extend_masks(const std::vector<int> &level) {
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<pgm_gapmask_job> jobs;
+        for (int v : level) {
+            Node &nd = nodes[(size_t)v];
+            GapMask &m = mask[(size_t)v];
+            const size_t n = nd.map[0].size();
+            if (n < 2 || nd.map[1].size() != n) error("root search: inconsistent merge mappings");
+            m.ncols = (uint32_t)(n - 2);
+            const size_t words = (m.ncols + 63) / 64;
+            const GapMask &m0 = mask[(size_t)nd.child[0]], &m1 = mask[(size_t)nd.child[1]];
+            m.rows = m0.rows;
+            m.rows.insert(m.rows.end(), m1.rows.begin(), m1.rows.end());
+            m.bits.assign(m.rows.size() * words, 0ull);
+            size_t row = 0;
+            for (int c = 0; c < 2; ++c) {
+                const GapMask &cm = mask[(size_t)nd.child[c]];
+                pgm_gapmask_job j;
+                j.src = cm.bits.data(); j.mapping = nd.map[c].data() + 1; j.dst = m.bits.data() + row * words;
+                j.nrows = (uint32_t)cm.rows.size(); j.ncols_in = cm.ncols; j.ncols_out = m.ncols;
+                jobs.push_back(j);
+                row += cm.rows.size();
+            }
+        }
+        if (!jobs.empty() && !default_backend().gapmask_extend_batch((uint32_t)jobs.size(), jobs.data(), 0))
+            parallel_for(jobs.size(), [&](size_t q) { gapmask_extend_host(jobs[q]); });
+        for (int v : level)
+            for (int c = 0; c < 2; ++c) {
+                GapMask &cm = mask[(size_t)nodes[(size_t)v].child[c]];
+                if (--cm.refs == 0) cm = GapMask();
+            }
+        root_search_stats.gapmask_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+
+    // the rooted topology of the candidate of edge e over the rows of its mask: post-order, the root last
+    uint32_t topo(int n, int from, const std::vector<int> &row_of, std::vector<uint32_t> &children, uint32_t nleaves) const {
+        if (g.isLeaf(n)) return (uint32_t)row_of[(size_t)n];
+        uint32_t c[2];
+        int k = 0;
+        for (int j = 0; j < 3; ++j) {
+            const int e = g.nodes[(size_t)n].edges[j];
+            if (e == from || e < 0) continue;
+            c[k++] = topo(g.other(e, n), e, row_of, children, nleaves);
+        }
+        children.push_back(c[0]); children.push_back(c[1]);
+        return nleaves + (uint32_t)(children.size() / 2 - 1);
+    }
+    void score_candidates(const std::vector<int> &edges) {
+        if (edges.empty()) return;
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<std::vector<uint32_t>> children(edges.size());
+        std::vector<pgm_parsimony_job> jobs(edges.size());
+        std::vector<int> row_of(g.nodes.size(), -1);
+        for (size_t q = 0; q < edges.size(); ++q) {
+            const int e = edges[q];
+            const GapMask &m = mask[(size_t)cand[(size_t)e]];
+            for (size_t r = 0; r < m.rows.size(); ++r) row_of[(size_t)m.rows[r]] = (int)r;
+            const uint32_t nl = (uint32_t)m.rows.size();
+            const uint32_t c0 = topo(g.edges[(size_t)e].nodes[0], e, row_of, children[q], nl);
+            const uint32_t c1 = topo(g.edges[(size_t)e].nodes[1], e, row_of, children[q], nl);
+            children[q].push_back(c0); children[q].push_back(c1);
+            jobs[q].masks = m.bits.data(); jobs[q].children = children[q].data(); jobs[q].nleaves = nl; jobs[q].ncols = m.ncols;
+            if (nl < 2 || m.ncols == 0) error("root search: a candidate alignment without rows or columns");
+        }
+        std::vector<uint32_t> sc(edges.size(), 0);
+        if (!default_backend().gap_parsimony_batch((uint32_t)jobs.size(), jobs.data(), sc.data(), 0))
+            parallel_for(jobs.size(), [&](size_t q) { sc[q] = gap_parsimony_host(jobs[q]); });
+        for (size_t q = 0; q < edges.size(); ++q) {
+            score[(size_t)edges[q]] = (score_t)sc[q];   // (unsigned -> score_t, FindRoot.h:279)
+            const int c = cand[(size_t)edges[q]];
+            mask[(size_t)c] = GapMask();
+            nodes[(size_t)c].res.graph = Graph();   // (score and TR indels stay; the rows are composed from the mappings)
+            nodes[(size_t)c].res.tr_homologies.clear();
+            nodes[(size_t)c].res.tr_source.clear();
+        }
+        root_search_stats.parsimony_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+
+    // every merge the candidates of `edges` still need, height by height; then their scores
+    void evaluate(const std::vector<int> &edges) {
+        std::vector<int> todo;
+        for (int e : edges) if (score[(size_t)e] < 0) todo.push_back(e);
+        if (todo.empty()) return;
+        for (int e : todo) candidate(e);
+        std::vector<std::vector<int>> by_height;
+        std::vector<char> seen(nodes.size(), 0);
+        std::vector<int> stack;
+        for (int e : todo) stack.push_back(cand[(size_t)e]);
+        while (!stack.empty()) {
+            const int v = stack.back(); stack.pop_back();
+            if (seen[(size_t)v] || done[(size_t)v]) continue;
+            seen[(size_t)v] = 1;
+            const Node &nd = nodes[(size_t)v];
+            if ((size_t)nd.height >= by_height.size()) by_height.resize((size_t)nd.height + 1);
+            by_height[(size_t)nd.height].push_back(v);
+            if (nd.child[0] >= 0) { stack.push_back(nd.child[0]); stack.push_back(nd.child[1]); }
+        }
+        owner.assign(nodes.size(), 0);
+        if (!by_height.empty() && !by_height[0].empty()) build_leaves(by_height[0]);
+        for (size_t h = 1; h < by_height.size(); ++h) {
+            std::vector<int> &level = by_height[h];
+            if (level.empty()) continue;
+            std::sort(level.begin(), level.end());
+            // a height above the batch bound goes in several batches
+            std::vector<int> chunk;
+            double cells = 0;
+            const auto t0 = std::chrono::steady_clock::now();
+            const double align0 = default_backend().seconds_align;
+            auto flush = [&]() {
+                if (chunk.empty()) return;
+                run_level(env, nodes, owner, chunk, (int)h);
+                ++root_search_stats.batches;
+                chunk.clear();
+                cells = 0;
+            };
+            for (int v : level) {
+                const Node &nd = nodes[(size_t)v];
+                const double c = (double)(nodes[(size_t)nd.child[0]].res.graph.size() - 2) * (double)(nodes[(size_t)nd.child[1]].res.graph.size() - 2);
+                if (!chunk.empty() && cells + c > MAX_BATCH_CELLS) flush();
+                chunk.push_back(v);
+                cells += c;
+            }
+            flush();
+            const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), align = default_backend().seconds_align - align0;
+            root_search_stats.align_s += align;
+            root_search_stats.host_merge_s += wall - align;
+            root_search_stats.merges += (int)level.size();
+            ++root_search_stats.heights;
+            for (int v : level) done[(size_t)v] = 1;
+            extend_masks(level);
+            std::vector<int> scored;
+            for (int e : todo) if (cand[(size_t)e] >= 0 && nodes[(size_t)cand[(size_t)e]].height == (int)h) scored.push_back(e);
+            score_candidates(scored);
+            root_search_stats.candidates += (int)scored.size();
+        }
+    }
+
+    // the winner's rows: extend_alignment down its sub-DAG, composed from the kept mappings
+    std::map<std::string, sequence_t> rows(int v) const {
+        const Node &nd = nodes[(size_t)v];
+        std::map<std::string, sequence_t> out;
+        if (nd.child[0] < 0) {
+            out[nd.tree->getName()] = sequences.at(nd.tree->getName());
+            return out;
+        }
+        for (int c = 0; c < 2; ++c) {
+            const std::map<std::string, sequence_t> r = rows(nd.child[c]);
+            extend_rows(a, out, (index_t)nd.map[c].size(), nd.map[c], r, r.size() >= 64);
+        }
+        return out;
+    }
+};
+}  // namespace
+
+ProgressiveAlignmentResult progressive_alignment_find_root(const Alphabet &a, const std::map<std::string, sequence_t> &sequences,
+                                                           const PhyTree &tree, const ModelFactory &model_factory,
+                                                           const std::map<std::string, std::vector<repeat_t>> *repeats) {
+    if (!cmdlineopts.profile_file.empty() || cmdlineopts.ancestral_flag) error("--profile_out and --ancestral_seqs cannot be combined with -r");
+    const auto t0 = std::chrono::steady_clock::now();
+    Backend &be = default_backend();
+    be.resident_reset();
+    // one device context (worker 0); the root search keeps no early refinement (FindRoot.h calls align_progressive_results only)
+    const bool resident_pass = be.resident() && !host_switches().host_merge && !job_dump_active();
+    be.resident_pass = resident_pass;
+    be.resident_imports = 0;
+    root_search_stats = RootSearchStats();
+    root_search_stats.ran = true;
+    const LevelEnv env{a, model_factory, repeats, resident_pass, false, true, t0};
+    RootSearch rs(a, sequences, env, tree);
+    for (size_t n = 0; n < rs.g.nodes.size(); ++n)
+        if (rs.g.isLeaf((int)n) && !sequences.count(rs.g.nodes[n].tree->getName())) error("unknown sequence name: %s", rs.g.nodes[n].tree->getName().c_str());
+    const int E = (int)rs.g.edges.size();
+    int best_edge = 0;
+    if (cmdlineopts.reroot_flag == 1) {   // every branch, the first minimum in edge order (FindRoot.h:281-289)
+        std::vector<int> all(E);
+        for (int e = 0; e < E; ++e) all[(size_t)e] = e;
+        rs.evaluate(all);
+        for (int e = 1; e < E; ++e) if (rs.score[(size_t)e] < rs.score[(size_t)best_edge]) best_edge = e;
+    } else {   // hill climbing over the neighbouring branches (FindRoot.h:290-320), one iteration's candidates per batch
+        rs.evaluate({0});
+        int best_node = -1;
+        score_t best_score = rs.score[0];
+        for (;;) {
+            const int old_edge = best_edge, old_node = best_node;
+            std::vector<std::pair<int, int>> tries;
+            for (int i = 0; i < 2; ++i) {
+                const int n = rs.g.edges[(size_t)old_edge].nodes[i];
+                if (n == old_node) continue;
+                for (int j = 0; j < 3; ++j) {
+                    const int e = rs.g.nodes[(size_t)n].edges[j];
+                    if (e == old_edge || e < 0) continue;
+                    tries.emplace_back(n, e);
+                }
+            }
+            std::vector<int> es;
+            for (const auto &t : tries) es.push_back(t.second);
+            rs.evaluate(es);
+            for (const auto &t : tries)
+                if (rs.score[(size_t)t.second] < best_score) { best_edge = t.second; best_score = rs.score[(size_t)t.second]; best_node = t.first; }
+            if (best_edge == old_edge) break;
+        }
+    }
+    const score_t best_score = rs.score[(size_t)best_edge];
+    std::cerr << "best gap parsimony score: " << best_score << std::endl;
+    const auto ts = std::chrono::steady_clock::now();
+    const int w = rs.cand[(size_t)best_edge];
+    ProgressiveAlignmentResult result;
+    result.score = rs.nodes[(size_t)w].res.score;
+    result.n_tr_indels = rs.nodes[(size_t)w].res.n_tr_indels;
+    result.aligned_sequences = rs.rows(w);
+    root_search_stats.select_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count();
+    if (host_switches().profile)
+        fprintf(stderr, "root search: %d merges in %d heights (%d batches), %d candidates; align %.1f ms, host merges %.1f, gap masks %.1f, parsimony %.1f, rows %.1f\n",
+                root_search_stats.merges, root_search_stats.heights, root_search_stats.batches, root_search_stats.candidates, root_search_stats.align_s * 1e3,
+                root_search_stats.host_merge_s * 1e3, root_search_stats.gapmask_s * 1e3, root_search_stats.parsimony_s * 1e3, root_search_stats.select_s * 1e3);
+    return result;
+}
+
 
 }  // namespace pgm
