@@ -336,6 +336,31 @@ typedef struct pgm_parsimony_job {
 int pgm_gap_parsimony_batch(pgm_ctx *ctx, uint32_t njobs, const pgm_parsimony_job *jobs, uint32_t *scores);
 float pgm_parsimony_last_kernel_ms(pgm_ctx *ctx);
 
+/* ---- weighted least-squares guide-tree refinement (reference src/LeastSquares.cpp) --------------------------------- */
+/* pgm_wls_load keeps an n x n distance matrix D and weight matrix W (row-major, entry (k, l) at k * n + l) on the device,
+ * in fp64, until the next load or pgm_ctx_destroy.  2 <= n <= PGM_WLS_MAX_N. */
+#define PGM_WLS_MAX_N 32768
+int pgm_wls_load(pgm_ctx *ctx, uint32_t n, const double *D, const double *W);
+
+/* The subtree pair sums of LeastSquares.cpp:309-325 for many edges in one call.  A job splits the leaves into nsub subtrees
+ * (4 around an edge, 5 around a quintet): label[l] is the subtree of leaf l (0..nsub-1) or -1, offset[l] the path length from
+ * leaf l to its subtree's root.  For every pair of subtrees p < q, pair index s in lexicographic order ((0,1), (0,2), ...):
+ *   out[PGM_WLS_OUT * j + s]      = sum over k in p, l in q of W(k,l) * ((D(k,l) - offset[k]) - offset[l])
+ *   out[PGM_WLS_OUT * j + 10 + s] = sum over k in p, l in q of W(k,l)
+ * and 0 in the slots past nsub (nsub - 1) / 2.  Each term takes the reference's operations, rounded to nearest, without
+ * contraction; the terms are added in the fixed order of DESIGN.md ("WLS refinement"), the same in every call, so the host
+ * statement of that order (Backend::wls_pair_sums_batch) gives the same bits.  PGM_ERR_INVALID: nothing loaded, nsub not 4
+ * or 5, a label outside [-1, nsub), a NULL pointer. */
+#define PGM_WLS_OUT 20
+typedef struct pgm_wls_job {
+    const int8_t *label;     /* n entries */
+    const double *offset;    /* n entries (read where label >= 0) */
+    uint32_t nsub;
+} pgm_wls_job;
+int pgm_wls_pair_sums_batch(pgm_ctx *ctx, uint32_t njobs, const pgm_wls_job *jobs, double *out);
+float pgm_wls_last_kernel_ms(pgm_ctx *ctx);       /* device time of the last pair-sums call */
+uint32_t pgm_wls_last_launches(pgm_ctx *ctx);     /* kernels it launched */
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,6 +27,7 @@
 #include "pgm_dist_kernels.h"
 #include "pgm_merge_kernels.h"
 #include "pgm_parsimony_kernels.h"
+#include "pgm_wls_kernels.h"
 #include "pgm_pool.h"
 
 static thread_local std::string g_err;
@@ -58,10 +59,11 @@ struct pgm_ctx {
     void *cache_ptr[C_SLOTS] = {};
     size_t cache_bytes[C_SLOTS] = {};
     hipDeviceProp_t prop;
-    float nw_ms = 0, cs_ms = 0, ml_ms = 0, merge_ms = 0, pars_ms = 0;
+    float nw_ms = 0, cs_ms = 0, ml_ms = 0, merge_ms = 0, pars_ms = 0, wls_ms = 0;
+    uint32_t wls_n = 0, wls_launches = 0;   // the WLS refinement: size of the loaded matrices (0 = none), kernels of the last call
     // grow-only scratch buffers of the all-pairs / context-profile calls (slot = position in the call's buffer list): a
     // guide-tree stage issues many calls (one per pair tile), hipMalloc / hipFree of up to 2 GB per call would dominate them
-    enum { SC_DEV = 24, SC_HOST = 4 };
+    enum { SC_DEV = 28, SC_HOST = 4 };
     void *sc_dev[SC_DEV] = {};
     size_t sc_dev_bytes[SC_DEV] = {};
     void *sc_host[SC_HOST] = {};      // pinned
@@ -1559,3 +1561,4 @@ int pgm_align_batch_read_matrices(pgm_ctx *ctx, pgm_align_batch *b, uint32_t job
 #include "pgm_dist_capi.inc"
 #include "pgm_merge_capi.inc"
 #include "pgm_parsimony_capi.inc"
+#include "pgm_wls_capi.inc"

@@ -113,6 +113,17 @@ struct HipBackend : Backend {
         if (rc != PGM_OK) error("pgm_gapmask_extend_batch failed (%d): %s", rc, pgm_last_error());
         return true;
     }
+    void wls_load(uint32_t n, const double *D, const double *W, int worker) override {
+        int rc = pgm_wls_load(ctx_of(worker), n, D, W);
+        if (rc != PGM_OK) error("pgm_wls_load failed (%d): %s", rc, pgm_last_error());
+    }
+    void wls_pair_sums_batch(uint32_t njobs, const pgm_wls_job *jobs, double *out, int worker) override {
+        pgm_ctx *c = ctx_of(worker);
+        int rc = pgm_wls_pair_sums_batch(c, njobs, jobs, out);
+        if (rc != PGM_OK) error("pgm_wls_pair_sums_batch failed (%d): %s", rc, pgm_last_error());
+        seconds_wls_kernels += pgm_wls_last_kernel_ms(c) * 1e-3;
+        wls_launches += pgm_wls_last_launches(c);
+    }
     bool gap_parsimony_batch(uint32_t njobs, const pgm_parsimony_job *jobs, uint32_t *scores, int worker) override {
         int rc = pgm_gap_parsimony_batch(ctx_of(worker), njobs, jobs, scores);
         if (rc != PGM_OK) error("pgm_gap_parsimony_batch failed (%d): %s", rc, pgm_last_error());

@@ -21,9 +21,11 @@ static void usage() {
     std::cerr << "USAGE: pgmsa [-f|--fasta] [-t|--tree <newick>] [-o <file>] [-T] [-I] [-a] [-m] [-M]\n"
                  "             [--codon] [-c|--cs_profile <lib>] [-i <iters>] [-g rate] [-e prob] [-E prob]\n"
                  "             [-s prob] [-A] [--early_refinement] [--ancestral_seqs] [--profile_out <file>] [-R] [--read_repeats <file>]\n"
-                 "             [-r|--reroot [-r]] [--dump_jobs <file>] [--dump_dist <file>] [--stats] <fasta file>\n"
+                 "             [-r|--reroot [-r]] [-W|--wls_refine [-W]] [--dump_jobs <file>] [--dump_dist <file>] [--stats] <fasta file>\n"
                  "  -r, --reroot  realign with the guide tree rooted on every branch and keep the alignment of the lowest gap\n"
-                 "                parsimony score; given twice (-rr), a hill climb over neighbouring branches instead\n";
+                 "                parsimony score; given twice (-rr), a hill climb over neighbouring branches instead\n"
+                 "  -W, --wls_refine  refine every guide tree estimated from distances by weighted least squares (nearest-neighbour\n"
+                 "                interchanges of quartets); given twice (-WW), quintet moves as well\n";
 }
 
 // The backend (device contexts: the HIP runtime's start-up takes 80-400 ms) is created on a thread of its own while the
@@ -167,6 +169,13 @@ static int doAlign(const Alphabet &a, const std::map<std::string, std::string> &
                             "\"reroot_align_s\": %.6f, \"reroot_host_merge_s\": %.6f, \"reroot_gapmask_s\": %.6f, \"reroot_parsimony_s\": %.6f, \"reroot_rows_s\": %.6f",
                     cmdlineopts.reroot_flag, r.merges, r.candidates, r.heights, r.batches, r.align_s, r.host_merge_s, r.gapmask_s, r.parsimony_s, r.select_s);
         }
+        if (cmdlineopts.wlsrefine_flag) {   // (keys of the refinement only when it ran)
+            const WlsStats &w = wls_stats;
+            fprintf(stderr, ", \"wls_refine\": %d, \"wls_trees\": %d, \"wls_s\": %.6f, \"wls_pair_sums_s\": %.6f, \"wls_kernels_s\": %.6f, \"wls_sweeps\": %d, "
+                            "\"wls_quartets\": %llu, \"wls_quintets\": %llu, \"wls_batches\": %llu, \"wls_launches\": %llu",
+                    cmdlineopts.wlsrefine_flag, w.trees, w.seconds, w.pair_sums_s, be.seconds_wls_kernels, w.sweeps, (unsigned long long)w.quartets,
+                    (unsigned long long)w.quintets, (unsigned long long)w.batches, (unsigned long long)be.wls_launches);
+        }
         fprintf(stderr, "}\n");
     }
     return 0;
@@ -219,6 +228,8 @@ int main(int argc, char **argv) {
             else if (s == "--dump_dist") dist_dump = val();
             else if (s == "--stats") stats = true;
             else if (s == "--reroot") ++cmdlineopts.reroot_flag;
+            else if (s == "--wls_refine") ++cmdlineopts.wlsrefine_flag;
+            else if (s.size() >= 2 && s[0] == '-' && s.find_first_not_of('W', 1) == std::string::npos) cmdlineopts.wlsrefine_flag += (int)s.size() - 1;   // -W, -WW
             else if (s.size() >= 2 && s[0] == '-' && s.find_first_not_of('r', 1) == std::string::npos) cmdlineopts.reroot_flag += (int)s.size() - 1;   // -r, -rr (TCLAP's MultiSwitchArg)
             else if (s == "-h" || s == "--help") { usage(); return 0; }
             else if (!s.empty() && s[0] == '-') { std::cerr << "Command line error: unknown flag " << s << std::endl; return 1; }

@@ -39,6 +39,7 @@ struct cmdlineopts_t {
     bool mldist_flag = false, mldist_gap_flag = false, codon_flag = false, inputorder_flag = false;
     bool ancestral_flag = false;
     bool earlyref_flag = false;       // --early_refinement (ProgressiveAlignment.h:102-110)
+    int wlsrefine_flag = 0;           // -W / --wls_refine, counted (main.cpp:120): 1 = quartet moves, 2 or more = quintet moves too (LeastSquares.cpp:683)
     int reroot_flag = 0;              // -r / --reroot, counted (main.cpp:117): 1 = every branch, 2 or more = hill climbing (FindRoot.h:276-320)
     std::string profile_file;   // --profile_out (main.cpp:132)
     std::string readreps_file;  // --read_repeats (main.cpp:108)
@@ -292,6 +293,13 @@ struct Backend {
     // the candidate alignments (include/pgm_hip.h); false = this backend has no such kernel (the host's own code runs)
     virtual bool gapmask_extend_batch(uint32_t, const pgm_gapmask_job *, int = 0) { return false; }
     virtual bool gap_parsimony_batch(uint32_t, const pgm_parsimony_job *, uint32_t *, int = 0) { return false; }
+    // the weighted least-squares refinement of a guide tree (LeastSquares.cpp): the n x n distance and weight matrices are
+    // loaded once per refined tree, then the subtree pair sums of many edges (include/pgm_hip.h: pgm_wls_pair_sums_batch).  The
+    // defaults are the host's own statement of the kernels' summation order (wls_pair_sums_host): the same bits.
+    virtual void wls_load(uint32_t n, const double *D, const double *W, int worker = 0);
+    virtual void wls_pair_sums_batch(uint32_t njobs, const pgm_wls_job *jobs, double *out, int worker = 0);
+    uint64_t wls_launches = 0;   // kernels the pair sums launched (0 for the host defaults)
+    double seconds_wls_kernels = 0;
     virtual void csprofile_create_batch(const class CSProfile &lib, uint32_t nseq, const int8_t *syms, const uint32_t *offs,
                                         const double *tau, const double *pi, const double *p_uniform, double *out,
                                         const uint64_t *out_offs, int worker = 0) = 0;
@@ -300,6 +308,8 @@ struct Backend {
     // ... left on the device of `worker` (resident pass): dev[s] = the 20 x (len + 2) matrix of sequence s; false = not available
     virtual bool csprofile_create_batch_res(const class CSProfile &, uint32_t, const int8_t *, const uint32_t *, const double *, const double *,
                                             const double *, const double **, int = 0) { return false; }
+    std::vector<double> wls_D, wls_W;   // the host defaults' copy of the loaded matrices
+    uint32_t wls_n = 0;
     int farm_workers = 0, farm_tiles = 0;   // what the last all-pairs farm used (logs / --stats)
     int farm_level_workers = 0, farm_leaf_workers = 0;   // most workers a guide-tree level's jobs / the leaves' profiles were dealt to
     bool resident_pass = false; int resident_imports = 0;   // the last progressive pass kept its profiles on the devices; matrices copied between them
@@ -484,6 +494,17 @@ public:
                                       const std::vector<std::string> &order);
 };
 PhyTree *buildNJTree(std::vector<std::string> seqs_order, DistanceMatrix dist);   // TreeNJ.cpp:132-281 (no topology plan)
+// LeastSquares::refineTree (LeastSquares.cpp:661-710; TreeNJ.h:52-54 when -W is given): nearest-neighbour interchanges by weighted
+// least squares on the unrooted tree, quartets (and with -WW quintets) swept until the fit stops falling, then every edge's support
+struct WlsStats {
+    int trees = 0, sweeps = 0;
+    uint64_t quartets = 0, quintets = 0, batches = 0;
+    double seconds = 0, pair_sums_s = 0;
+};
+extern WlsStats wls_stats;
+PhyTree *refineTree(PhyTree *tree, const std::vector<std::string> &leaf_order, const DistanceMatrix &dist);
+// the pair sums of pgm_wls_pair_sums_batch in the kernels' order (D, W: n x n row-major)
+void wls_pair_sums_host(uint32_t n, const double *D, const double *W, uint32_t njobs, const pgm_wls_job *jobs, double *out);
 // TreeNJ.h:27-59: distances from an all-pairs alignment (-a, prealigned == false) or induced by an existing alignment
 // (prealigned == true, the guide-tree re-estimation of main.cpp:404-430)
 PhyTree *TreeNJ(const Alphabet &a, const std::map<std::string, sequence_t> &seqs, const ModelFactory *mf, bool prealigned = false);
