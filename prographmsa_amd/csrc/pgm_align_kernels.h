@@ -50,7 +50,7 @@ __device__ __forceinline__ float pgm_emission_finish(float num, float ay, float 
 // A workgroup takes NODES consecutive nodes: their profile columns (doubles, D per node) are one contiguous run, read
 // coalesced and converted into LDS; every thread then works on its node from LDS (padded stride: conflict free), and the
 // results go back through LDS so that the stores are coalesced too.  The sums keep the reference's sequential order (one
-// multiply and one add per term, no FMA).  DMAX = 20 for amino acids (NODES = 256), 64 for codons (NODES = 64).
+// multiply and one add per term, no FMA).  DMAX = 4 for nucleotides and 20 for amino acids (NODES = 256), 64 for codons (NODES = 64).
 // The kernel also zeroes the batch's sync block (progress words, tickets, abort flag) for the fill stage two kernels later: a
 // hipMemsetAsync between the emission kernel and the sweeps cost 55 us of fill kernel plus its dependency per step.
 template <int DMAX, int NODES>
@@ -244,19 +244,22 @@ __global__ void __launch_bounds__(4 * PGM_ROWS) pgm_emission_skew_kernel(const P
     auto sblock_of = [&](uint32_t v, uint32_t tb_) { return ((((size_t)(v >> rsh) * J.nblk + tb_) << rsh) | (v & ((1u << rsh) - 1u))); };
     const uint32_t t0 = tb0 * PGM_BLOCK;
     const int cbase = (int)t0 - 63;
-    if (DP == 20 && RB == 1) {
+    if ((DP == 20 || DP == 4) && RB == 1) {
         // Rows of a sequence graph (a leaf of the guide tree: half of the cells of a progressive pass) hold a single 1.0, START
         // and the rows beyond the graph hold nothing.  The sum of such a row with column c is ((+0 + 0 T[c][0]) + ...) + 1 T[c][s]
         // + ... = 0.0f + T[c][s] (the other terms are zeros of either sign), and a1 depends on s alone: the score of a cell is
-        // a function of (s, c).  If every row of the workgroup is of that kind, the 21 x COLS scores are evaluated once (the
+        // a function of (s, c).  If every row of the workgroup is of that kind, the (DP + 1) x COLS scores are evaluated once (the
         // same operations on the same operands as below) and the cells look them up.
-        float *const tab = (float *)tp;      // [COLS][21], in the space of the staged columns (not staged on this path)
-        static_assert(COLS * 21 <= (COLS + 1) * STR * 2, "score table must fit the column staging area");
+        // (entry DP: a row without a 1.0; DP = 4 for nucleotides, 20 for amino acids)
+        constexpr int TE = DP + 1;
+        float *const tab = (float *)tp;      // [COLS][TE], in the space of the staged columns (not staged on this path)
+        static_assert(COLS * TE <= (COLS + 1) * STR * 2, "score table must fit the column staging area");
+        static_assert(DP > 20 || TE <= 32, "row classes must fit As");
         __shared__ float As[32];
         const uint32_t fb0 = 4u * blockIdx.y + threadIdx.x / PGM_ROWS;
         const uint32_t fl = threadIdx.x % PGM_ROWS;
         const bool active = fb0 < nvb;
-        int sym = 20;
+        int sym = DP;
         bool plain = true;
         float a_row = 0.f;
         if (active) {
@@ -280,20 +283,20 @@ __global__ void __launch_bounds__(4 * PGM_ROWS) pgm_emission_skew_kernel(const P
             if (active) As[sym] = a_row;   // (rows with the same content have the same a1: any of them writes it)
             __syncthreads();
             const float mi = J.sc.match_init;
-            constexpr int NE = (COLS * 21 + 4 * PGM_ROWS - 1) / (4 * PGM_ROWS);   // table entries per thread: all loads first
+            constexpr int NE = (COLS * TE + 4 * PGM_ROWS - 1) / (4 * PGM_ROWS);   // table entries per thread: all loads first
             float tt[NE], tb2[NE];
 #pragma unroll
             for (int e = 0; e < NE; ++e) {
                 const int i = (int)threadIdx.x + e * 4 * PGM_ROWS;
-                const int ci = i / 21, k = i % 21, c = cbase + ci;
-                const bool in = i < COLS * 21 && c >= 0 && c <= (int)J.ncol;
+                const int ci = i / TE, k = i % TE, c = cbase + ci;
+                const bool in = i < COLS * TE && c >= 0 && c <= (int)J.ncol;
                 tb2[e] = in ? J.b2[c] : 0.f;
-                tt[e] = (in && k < 20) ? J.t2[(size_t)DP * c + k] : 0.f;
+                tt[e] = (in && k < DP) ? J.t2[(size_t)DP * c + k] : 0.f;
             }
 #pragma unroll
             for (int e = 0; e < NE; ++e) {
                 const int i = (int)threadIdx.x + e * 4 * PGM_ROWS;
-                if (i < COLS * 21) tab[i] = pgm_emission_finish(0.0f + tt[e], As[i % 21], tb2[e], mi);
+                if (i < COLS * TE) tab[i] = pgm_emission_finish(0.0f + tt[e], As[i % TE], tb2[e], mi);
             }
             __syncthreads();
             if (!active) return;
@@ -305,7 +308,7 @@ __global__ void __launch_bounds__(4 * PGM_ROWS) pgm_emission_skew_kernel(const P
                 if (tb >= J.nblk) break;
                 float out[PGM_BLOCK];
 #pragma unroll
-                for (int i = 0; i < PGM_BLOCK; ++i) out[i] = tab[((int)(tb * PGM_BLOCK) + i - l - cbase) * 21 + sym];
+                for (int i = 0; i < PGM_BLOCK; ++i) out[i] = tab[((int)(tb * PGM_BLOCK) + i - l - cbase) * TE + sym];
                 PGM_GLOBAL pgm_v4f *dst = Sq + (sblock_of(fb0, tb) * 64u + (uint32_t)l) * (PGM_BLOCK / 4);
 #pragma unroll
                 for (int q = 0; q < PGM_BLOCK / 4; ++q) dst[q] = pgm_v4f{out[4 * q], out[4 * q + 1], out[4 * q + 2], out[4 * q + 3]};

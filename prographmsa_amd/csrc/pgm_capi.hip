@@ -661,7 +661,11 @@ static hipError_t launch_all(pgm_ctx *ctx, pgm_align_batch *b, bool timed) {
     hipError_t e;
     for (uint32_t i = 0; i < b->njobs; ++i) ((PgmJob::Result *)(b->h_out + b->res_off[i]))->status = PGM_STATUS_PENDING;
     if (timed && (e = hipEventRecord(b->ev[0], s)) != hipSuccess) return e;
-    if (b->maxdim <= 20) {
+    // (the tiers of batch_dp in pgm_align_batch_create_res: 4 for nucleotides, 20 for amino acids, 64 for codons)
+    if (b->maxdim <= 4) {
+        const size_t prep_lds = ((size_t)b->maxdim * b->maxdim + b->maxdim + 256 * ((size_t)b->maxdim + 1)) * sizeof(float);
+        hipLaunchKernelGGL((pgm_prep_kernel<4, 256>), dim3(b->njobs, 2, (b->maxn + 255) / 256), dim3(256), prep_lds, s, b->d_jobs, b->d_sync, (uint32_t)b->sync_ints);
+    } else if (b->maxdim <= 20) {
         const size_t prep_lds = ((size_t)b->maxdim * b->maxdim + b->maxdim + 256 * ((size_t)b->maxdim + 1)) * sizeof(float);
         hipLaunchKernelGGL((pgm_prep_kernel<20, 256>), dim3(b->njobs, 2, (b->maxn + 255) / 256), dim3(256), prep_lds, s, b->d_jobs, b->d_sync, (uint32_t)b->sync_ints);
     } else {
@@ -672,7 +676,8 @@ static hipError_t launch_all(pgm_ctx *ctx, pgm_align_batch *b, bool timed) {
     if (timed && (e = hipEventRecord(b->ev[1], s)) != hipSuccess) return e;
     // (RB = 2 bands per thread — one LDS read of a column pair for four cells — was measured at half the speed: 0.55 -> 1.13 ms)
     const dim3 eg((b->maxnblk + PGM_EM_TB - 1) / PGM_EM_TB, (b->maxnb + 3) / 4, b->njobs);
-    if (b->maxdim <= 20) hipLaunchKernelGGL((pgm_emission_skew_kernel<20, 1>), eg, dim3(4 * PGM_ROWS), 0, s, b->d_jobs);
+    if (b->maxdim <= 4) hipLaunchKernelGGL((pgm_emission_skew_kernel<4, 1>), eg, dim3(4 * PGM_ROWS), 0, s, b->d_jobs);
+    else if (b->maxdim <= 20) hipLaunchKernelGGL((pgm_emission_skew_kernel<20, 1>), eg, dim3(4 * PGM_ROWS), 0, s, b->d_jobs);
     else hipLaunchKernelGGL((pgm_emission_skew_kernel<64, 1>), eg, dim3(4 * PGM_ROWS), 0, s, b->d_jobs);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (timed && (e = hipEventRecord(b->ev[2], s)) != hipSuccess) return e;
@@ -790,10 +795,11 @@ int pgm_align_batch_create_res(pgm_ctx *ctx, uint32_t njobs, const pgm_graph *co
         two_chains[i] = (a && c && a->n >= 2 && c->n >= 2 && a->e_rowptr && c->e_rowptr && a->e_col && c->e_col && a->e_val && c->e_val && graph_is_chain(a) && graph_is_chain(c)) ? 1 : 0;
     });
     // The prep and emission kernels are instantiated once per batch for its largest alphabet and read every job's converted
-    // profiles with that padded stride: all jobs of a batch get it, whatever their own alphabet.
+    // profiles with that padded stride: all jobs of a batch get it, whatever their own alphabet.  Three tiers: 4 (nucleotides: a
+    // node's profile is one float4), 20 (amino acids), 64 (codons).  launch_all picks the kernels by b->maxdim, the same maximum.
     uint32_t batch_dim = 0;
     for (uint32_t i = 0; i < njobs; ++i) if (g1[i]) batch_dim = std::max(batch_dim, g1[i]->dim);
-    const uint32_t batch_dp = batch_dim <= 20 ? 20u : 64u;
+    const uint32_t batch_dp = batch_dim <= 4 ? 4u : batch_dim <= 20 ? 20u : 64u;
     for (uint32_t i = 0; i < njobs; ++i) {
         const pgm_graph *a = g1[i], *c = g2[i];
         if (!a || !c || !model[i] || a->dim != c->dim || a->dim == 0 || a->dim > PGM_MAX_DIM || a->n < 2 || c->n < 2 || !model[i]->M || !model[i]->pi ||

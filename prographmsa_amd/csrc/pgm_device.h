@@ -87,7 +87,7 @@ struct PgmTbNode {
 
 struct PgmJob {
     uint32_t n1, n2;       // node counts incl. START/END
-    uint32_t dim, dp;      // alphabet size and padded size (multiple of 4): the same for every job of a batch, 20 or 64 after its largest alphabet
+    uint32_t dim, dp;      // alphabet size and padded size (multiple of 4): the same for every job of a batch, 4, 20 or 64 after its largest alphabet
     uint32_t nb;           // number of row bands = ceil((n1-1)/(64 R))
     uint32_t ncol;         // stored columns = n2-1
     uint32_t tsteps;       // steps per band = ncol + 63

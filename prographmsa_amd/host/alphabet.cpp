@@ -54,6 +54,23 @@ static int aa_value(int8_t data) {
     return p ? (int)(p - order) : 20;
 }
 
+// ---- DNA -------------------------------------------------------------------------------
+// dna_translation_table (Alphabet.cpp:22-40): T/U=0 C=1 A=2 G=3 X=4; here N and the IUPAC ambiguity letters R Y S W K M B D H V
+// read as unknown too, and any other character is refused when the sequence is read (the reference's DNA::value()
+// reads the amino-acid table instead).
+static int dna_value(int8_t data) {
+    switch (data) {
+        case 'T': case 't': case 'U': case 'u': return 0;
+        case 'C': case 'c': return 1;
+        case 'A': case 'a': return 2;
+        case 'G': case 'g': return 3;
+        case 'X': case 'x': case 'N': case 'n':
+        case 'R': case 'r': case 'Y': case 'y': case 'S': case 's': case 'W': case 'w': case 'K': case 'k':
+        case 'M': case 'm': case 'B': case 'b': case 'D': case 'd': case 'H': case 'h': case 'V': case 'v': return 4;
+        default: return -1;
+    }
+}
+
 // ---- Codon -----------------------------------------------------------------------------
 // nucleotide code T/U=0 C=1 A=2 G=3 X=4 else -1 (dna_translation_table, Alphabet.cpp:22-36)
 static int nt_value(char ch) {
@@ -102,31 +119,33 @@ static char codon_aa(int idx) {  // codon_inv3_translation_table (standard genet
 
 int Alphabet::value(int8_t data) const {
     if (kind == ALPHA_AA) return aa_value(data);
+    if (kind == ALPHA_DNA) return dna_value(data);
     if (data == CODON_DIM + 1) return -1;  // gap
     return data;
 }
-int8_t Alphabet::gap() const { return kind == ALPHA_AA ? (int8_t)'-' : (int8_t)(CODON_DIM + 1); }
-int8_t Alphabet::unknown() const { return kind == ALPHA_AA ? (int8_t)'X' : (int8_t)CODON_DIM; }
+int8_t Alphabet::gap() const { return rawChars() ? (int8_t)'-' : (int8_t)(CODON_DIM + 1); }
+int8_t Alphabet::unknown() const { return rawChars() ? (int8_t)'X' : (int8_t)CODON_DIM; }
 char Alphabet::asChar(int8_t data) const {
-    if (kind == ALPHA_AA) return (char)data;
+    if (rawChars()) return (char)data;
     if (isGap(data)) return '-';
     if (!isValid(data)) return 'X';
     return codon_aa(data);
 }
 std::string Alphabet::asString(int8_t data) const {
-    if (kind == ALPHA_AA) return std::string(1, (char)data);
+    if (rawChars()) return std::string(1, (char)data);
     if (isGap(data)) return "---";
     if (!isValid(data)) return "XXX";
     return codon_string(data);
 }
 bool Alphabet::stripsStart(int8_t first) const {
-    // AA::stripStart = 'M', Codon::stripStart = ATG (Alphabet.cpp:94-96)
+    // AA::stripStart = 'M', Codon::stripStart = ATG, DNA::stripStart = GAP (disabled) (Alphabet.cpp:86-88)
     if (kind == ALPHA_AA) return first == (int8_t)'M';
+    if (kind == ALPHA_DNA) return false;
     return first == codon_data('A', 'T', 'G');
 }
 bool Alphabet::stripsEnd(int8_t last) const {
-    // AA::stripEnd = GAP (disabled), Codon::stripEnd = XXX (Alphabet.cpp:98-100)
-    if (kind == ALPHA_AA) return false;
+    // AA::stripEnd = GAP (disabled), Codon::stripEnd = XXX, DNA::stripEnd = GAP (disabled) (Alphabet.cpp:90-92)
+    if (kind != ALPHA_CODON) return false;
     return last == (int8_t)CODON_DIM;
 }
 
@@ -136,6 +155,13 @@ sequence_t sequenceFromString(const Alphabet &a, const std::string &str) {
         seq.reserve(str.size());
         for (char ch : str) {
             if (ch == '_' || ch == '-' || ch == '.' || ch == ' ') error("No support for gapped sequences (yet)");
+            seq += (int8_t)ch;
+        }
+    } else if (a.kind == ALPHA_DNA) {
+        seq.reserve(str.size());
+        for (char ch : str) {
+            if (ch == '_' || ch == '-' || ch == '.' || ch == ' ') error("No support for gapped sequences (yet)");
+            if (dna_value((int8_t)ch) < 0) error("invalid character '%c' (0x%02x) in a DNA sequence", ch, (unsigned)(unsigned char)ch);
             seq += (int8_t)ch;
         }
     } else {  // Alphabet.cpp:258-275
@@ -153,7 +179,7 @@ sequence_t sequenceFromString(const Alphabet &a, const std::string &str) {
 std::string stringFromSequence(const Alphabet &a, const sequence_t &seq) {
     std::string s;
     for (int8_t c : seq) {
-        if (a.kind == ALPHA_AA) s += a.asChar(c); else s += a.asString(c);
+        if (a.rawChars()) s += a.asChar(c); else s += a.asString(c);
     }
     return s;
 }
@@ -161,7 +187,7 @@ std::string stringFromSequence(const Alphabet &a, const sequence_t &seq) {
 std::string stringFromSequence(const Alphabet &a, const sequence_t &seq, const std::string &orig) {
     std::string s;
     s.reserve(orig.size());
-    if (a.kind == ALPHA_AA) {  // Alphabet.h:148-165
+    if (a.rawChars()) {  // Alphabet.h:148-165
         size_t j = 0;
         for (int8_t c : seq) {
             if (a.isGap(c)) s += a.asChar(c); else s += orig[j++];

@@ -16,8 +16,8 @@
 namespace pgm {
 
 // ---- DistanceFactoryML ---------------------------------------------------------------------
-static void consts(const Alphabet &a, double &DIST_MAX, double &VAR_MAX, double &VAR_MIN) {  // DistanceFactoryML.cpp
-    if (a.kind == ALPHA_AA) { DIST_MAX = 2.2; VAR_MAX = 1e3; VAR_MIN = 1e-5; }
+static void consts(const Alphabet &a, double &DIST_MAX, double &VAR_MAX, double &VAR_MIN) {  // DistanceFactoryML.cpp:5-32
+    if (a.kind == ALPHA_AA || a.kind == ALPHA_DNA) { DIST_MAX = 2.2; VAR_MAX = 1e3; VAR_MIN = 1e-5; }
     else { DIST_MAX = 5.2; VAR_MAX = 5e3; VAR_MIN = 1e-5; }
 }
 
@@ -177,7 +177,18 @@ void DistanceFactoryML::computeDistances(const int32_t *counts, const uint32_t *
 
 // ---- DistanceFactoryAlign ---------------------------------------------------------------------
 DistanceFactoryAlign::DistanceFactoryAlign(const Alphabet &a, const ModelFactory *mf) : DistanceFactoryML(a, mf) {
-    const int sd = a.DIM + 1;  // initMatrix (DistanceFactoryAlign.cpp:5-35, 38-235)
+    const int sd = a.DIM + 1;  // initMatrix (DistanceFactoryAlign.cpp:5-35, 38-235, 238-249)
+    if (a.kind == ALPHA_DNA) {
+        // transition / transversion scores over {T, C, A, G, X}: a match +1, a transition (T-C, A-G) -1, a transversion -2,
+        // anything against X 0
+        scoring_matrix_.resize((size_t)sd * sd);
+        for (int i = 0; i < sd; ++i)
+            for (int j = 0; j < sd; ++j)
+                scoring_matrix_[(size_t)i + (size_t)sd * j] = (i == 4 || j == 4) ? 0 : i == j ? 1 : (i / 2 == j / 2) ? -1 : -2;
+        gap_open = -5;
+        gap_extend = -2;
+        return;
+    }
     std::string file = data_dir() + (a.kind == ALPHA_AA ? "/nw_aa.imat" : "/nw_codon.imat");
     std::ifstream in(file.c_str());
     int r = 0, c = 0;
@@ -194,14 +205,16 @@ DistanceMatrix DistanceFactoryAlign::computePwDistances(const std::map<std::stri
     const uint32_t n = (uint32_t)order.size();
     const uint32_t D = (uint32_t)alphabet.DIM;
     DistanceMatrix distances((int)n);
-    // symbols: value(), negative -> 20 for every alphabet (the reference's quirk, DistanceFactoryAlign.h:72,79)
+    // symbols: value(), negative -> 20 for amino acids and codons (the reference's quirk, DistanceFactoryAlign.h:72,79); DNA has no
+    // negative values (sequenceFromString refuses other characters) and its unknown is DIM, the X row of its scoring matrix
+    const int unknown_sym = alphabet.kind == ALPHA_DNA ? (int)D : 20;
     std::vector<int8_t> syms;
     std::vector<uint32_t> offs(n + 1, 0);
     for (uint32_t i = 0; i < n; ++i) {
         const sequence_t &s = sequences.at(order[i]);
         for (int8_t c : s) {
             int v = alphabet.value(c);
-            syms.push_back((int8_t)(v < 0 ? 20 : v));
+            syms.push_back((int8_t)(v < 0 ? unknown_sym : v));
         }
         offs[i + 1] = (uint32_t)syms.size();
     }
@@ -454,23 +467,30 @@ DistanceMatrix DistanceFactoryPrealigned::computePwDistances(const std::map<std:
     bool done = false;
     if (!host_switches().host_counts && np) {
         // the N^2 L column scan on the device (integer counts, bit-exact: on by default, unlike the ML estimates that follow):
-        // value() per residue, -1 for a gap, -2 for a residue without a value
+        // value() per residue, -1 for a gap, -2 for a residue without a value (and for the DNA unknown, value 4: the kernel counts
+        // every value below 20)
         auto t0 = std::chrono::steady_clock::now();
+        const bool dna = alphabet.kind == ALPHA_DNA;
         std::vector<int8_t> mat((size_t)n * L);
         for (uint32_t i = 0; i < n; ++i)
             for (size_t k = 0; k < L; ++k) {
                 const int8_t c = (*rows[i])[k];
                 const int v = alphabet.isGap(c) ? -1 : alphabet.value(c);
-                mat[(size_t)i * L + k] = (int8_t)(alphabet.isGap(c) ? -1 : (v < 0 ? -2 : v));
+                mat[(size_t)i * L + k] = (int8_t)(alphabet.isGap(c) ? -1 : (v < 0 || (dna && v >= (int)D) ? -2 : v));
             }
         {
-            // every pair costs the same (one scan of the columns): contiguous ranges of pairs, one per device context
+            // every pair costs the same (one scan of the columns): contiguous ranges of pairs, one per device context.  The entry
+            // point takes 20 to 64 states: DNA rows (values 0..3, -2) are counted as 20-state rows and the 4 x 4 corner of each
+            // 20 x 20 matrix is kept
+            const uint32_t Dk = std::max<uint32_t>(D, 20u);
+            std::vector<int32_t> wide(Dk != D ? (size_t)np * Dk * Dk : 0, 0);
+            int32_t *const cdst = Dk != D ? wide.data() : counts.data();
             const int nw = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, be.workers()), np));
             std::vector<char> ok((size_t)nw, 0);
             auto part = [&](int w) {
                 const uint32_t p0 = (uint32_t)((uint64_t)np * (uint32_t)w / (uint32_t)nw), p1 = (uint32_t)((uint64_t)np * ((uint32_t)w + 1u) / (uint32_t)nw);
-                ok[(size_t)w] = (p1 == p0 || be.prealigned_counts_batch(D, n, (uint32_t)L, mat.data(), p1 - p0, pi.data() + p0, pj.data() + p0,
-                                                                       counts.data() + (size_t)p0 * D * D, gaps.data() + p0, w)) ? 1 : 0;
+                ok[(size_t)w] = (p1 == p0 || be.prealigned_counts_batch(Dk, n, (uint32_t)L, mat.data(), p1 - p0, pi.data() + p0, pj.data() + p0,
+                                                                       cdst + (size_t)p0 * Dk * Dk, gaps.data() + p0, w)) ? 1 : 0;
             };
             std::vector<std::thread> th;
             for (int w = 1; w < nw; ++w) th.emplace_back(part, w);
@@ -478,6 +498,10 @@ DistanceMatrix DistanceFactoryPrealigned::computePwDistances(const std::map<std:
             for (auto &t : th) t.join();
             done = true;
             for (char c : ok) done = done && c;
+            if (done && Dk != D)
+                for (size_t p = 0; p < np; ++p)
+                    for (uint32_t b = 0; b < D; ++b)
+                        for (uint32_t a = 0; a < D; ++a) counts[p * D * D + a + (size_t)D * b] = wide[p * Dk * Dk + a + (size_t)Dk * b];
         }
         be.seconds_mldist += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
@@ -487,6 +511,7 @@ DistanceMatrix DistanceFactoryPrealigned::computePwDistances(const std::map<std:
         if (const char *e = getenv("PGM_HOST_THREADS")) nt = (unsigned)atoi(e);
         nt = std::max(1u, std::min(nt, 16u));
         nt = (unsigned)std::min<size_t>(nt, std::max<size_t>(1, np));
+        const int cmax = alphabet.kind == ALPHA_DNA ? (int)D : 20;   // (the DNA unknown is not counted: see the device rows above)
         auto work = [&](unsigned t) {
             for (size_t p = t; p < np; p += nt) {
                 const sequence_t &s1 = *rows[pi[p]], &s2 = *rows[pj[p]];
@@ -497,7 +522,7 @@ DistanceMatrix DistanceFactoryPrealigned::computePwDistances(const std::map<std:
                     const bool g1 = alphabet.isGap(s1[k]), g2 = alphabet.isGap(s2[k]);
                     if (!g1 && !g2) {
                         const int c1 = alphabet.value(s1[k]), c2 = alphabet.value(s2[k]);
-                        if (c1 >= 0 && c1 < 20 && c2 >= 0 && c2 < 20) ++c[(size_t)c1 + (size_t)D * c2];
+                        if (c1 >= 0 && c1 < cmax && c2 >= 0 && c2 < cmax) ++c[(size_t)c1 + (size_t)D * c2];
                         open1 = false; open2 = false;
                     } else if (g1 && g2) {
                         // skip
@@ -527,21 +552,24 @@ DistanceMatrix DistanceFactoryPrealigned::computePwDistances(const std::map<std:
 }
 
 DistanceMatrix angleDistances(const Alphabet &a, const std::map<std::string, sequence_t> &sequences, const std::vector<std::string> &order) {
-    const uint32_t n = (uint32_t)order.size(), D = (uint32_t)a.DIM, ncols = D * D;   // K = 2 for both alphabets
+    // K = 2 for amino acids and codons, 6 for DNA (DistanceFactory.cpp:9-60): ncols = D^K = 400, 3721, 4096
+    const uint32_t n = (uint32_t)order.size(), D = (uint32_t)a.DIM, K = a.kind == ALPHA_DNA ? 6u : 2u;
+    uint32_t ncols = 1;
+    for (uint32_t k = 0; k < K; ++k) ncols *= D;
     DistanceMatrix distances((int)n);
     std::vector<int32_t> counts((size_t)n * ncols, 0);
     std::vector<double> seq_len(n);
-    for (uint32_t i = 0; i < n; ++i) {   // DistanceFactoryAngle.h:63-94
+    parallel_for((size_t)n, [&](size_t i) {   // DistanceFactoryAngle.h:63-94: the index of the last K values, none of them invalid
         const sequence_t &seq = sequences.at(order[i]);
         seq_len[i] = (double)seq.size();
-        int prev = -1;
+        uint32_t index = 0, run = 0;   // (run: valid values at the end of the window so far)
         for (size_t j = 0; j < seq.size(); ++j) {
-            int v = a.value(seq[j]);
-            if (v < 0 || v >= (int)D) v = -1;
-            if (prev != -1 && v != -1) counts[(size_t)i * ncols + (size_t)prev * D + (size_t)v] += 1;
-            prev = v;
+            const int v = a.value(seq[j]);
+            if (v < 0 || v >= (int)D) { run = 0; index = 0; continue; }
+            index = (index * D + (uint32_t)v) % ncols;
+            if (++run >= K) counts[i * ncols + index] += 1;
         }
-    }
+    });
     Backend &be = default_backend();
     const auto t0 = std::chrono::steady_clock::now();
     be.kmer_cosine(n, ncols, counts.data(), distances.distances.data());   // :100

@@ -21,7 +21,17 @@ static void usage() {
     std::cerr << "USAGE: pgmsa [-f|--fasta] [-t|--tree <newick>] [-o <file>] [-T] [-I] [-a] [-m] [-M]\n"
                  "             [--codon] [-c|--cs_profile <lib>] [-i <iters>] [-g rate] [-e prob] [-E prob]\n"
                  "             [-s prob] [-A] [--early_refinement] [--ancestral_seqs] [--profile_out <file>] [-R] [--read_repeats <file>]\n"
-                 "             [-r|--reroot [-r]] [-W|--wls_refine [-W]] [--dump_jobs <file>] [--dump_dist <file>] [--stats] <fasta file>\n"
+                 "             [-r|--reroot [-r]] [-W|--wls_refine [-W]] [--dna] [--custom_model <file>] [-F|--estimate_aafreqs]\n"
+                 "             [-C|--aafreqs_pseudocount <count>] [--dump_jobs <file>] [--dump_dist <file>] [--stats] <fasta file>\n"
+                 "  --dna         align DNA sequences (T C A G; U reads as T; N, X and the IUPAC ambiguity codes as unknown); needs\n"
+                 "                --custom_model\n"
+                 "  --custom_model <file>  custom substitution model: the strict lower triangle of the symmetric exchangeability\n"
+                 "                matrix row by row (rows 1 .. D-1, columns below the diagonal), then the D equilibrium frequencies,\n"
+                 "                separated by white space, in the alphabet's own order: TCAG for --dna, ACDEFGHIKLMNPQRSTVWY for amino\n"
+                 "                acids (alphabetical by one-letter code, not PAML's ARNDCQEGHILKMFPSTWYV), the 61 sense codons in TCAG\n"
+                 "                order for --codon\n"
+                 "  -F, --estimate_aafreqs  estimate the equilibrium frequencies from the input sequences\n"
+                 "  -C, --aafreqs_pseudocount <count>  pseudo-count of the model's own frequencies in that estimate (default 1000)\n"
                  "  -r, --reroot  realign with the guide tree rooted on every branch and keep the alignment of the lowest gap\n"
                  "                parsimony score; given twice (-rr), a hill climb over neighbouring branches instead\n"
                  "  -W, --wls_refine  refine every guide tree estimated from distances by weighted least squares (nearest-neighbour\n"
@@ -55,6 +65,7 @@ static std::string value_name(const Alphabet &a, int j) {   // ALPHABET(j).asStr
     static const char *aa = "ACDEFGHIKLMNPQRSTVWY";
     if (a.kind == ALPHA_AA) return std::string(1, aa[j]);
     static const char nt[] = "TCAG";
+    if (a.kind == ALPHA_DNA) return std::string(1, nt[j]);   // dna_inv_translation_table
     int k = -1;
     for (int c = 0; c < 64; ++c) {
         const std::string cod = {nt[c >> 4], nt[(c >> 2) & 3], nt[c & 3]};
@@ -80,7 +91,7 @@ static int doAlign(const Alphabet &a, const std::map<std::string, std::string> &
         }
         seqs2[kv.first] = seq;
     }
-    std::unique_ptr<ModelFactory> model_factory(ModelFactory::getDefault(a));
+    std::unique_ptr<ModelFactory> model_factory(ModelFactory::getDefault(a, seqs2));
     std::unique_ptr<CSProfile> csprofile;
     if (!cmdlineopts.cs_file.empty()) csprofile.reset(new CSProfile(cmdlineopts.cs_file));
 
@@ -207,6 +218,10 @@ int main(int argc, char **argv) {
             else if (s == "-M" || s == "--mldist_gap") cmdlineopts.mldist_gap_flag = true;
             else if (s == "-A" || s == "--no_force_align") cmdlineopts.noforcealign_flag = true;
             else if (s == "--codon") cmdlineopts.codon_flag = true;
+            else if (s == "--dna") cmdlineopts.dna_flag = true;
+            else if (s == "--custom_model") cmdlineopts.cmodel_file = val();
+            else if (s == "-F" || s == "--estimate_aafreqs") cmdlineopts.aafreqs_flag = true;
+            else if (s == "-C" || s == "--aafreqs_pseudocount") cmdlineopts.pseudo_count = atof(val().c_str());
             else if (s == "-c" || s == "--cs_profile") cmdlineopts.cs_file = val();
             else if (s == "-i" || s == "--iterations") { cmdlineopts.iters = atoi(val().c_str()); iters_set = true; }
             else if (s == "-g" || s == "--indel_rate") { cmdlineopts.indel_rate = atof(val().c_str()); indel_set = true; }
@@ -240,6 +255,10 @@ int main(int argc, char **argv) {
             std::cerr << "ERROR:--ancestral_seqs and --profile_out cannot be combined with -r (the root search keeps no ancestral profiles)" << std::endl;
             return 2;
         }
+        if (cmdlineopts.dna_flag && (cmdlineopts.codon_flag || !cmdlineopts.cs_file.empty())) {
+            std::cerr << "ERROR:--dna cannot be combined with " << (cmdlineopts.codon_flag ? "--codon" : "-c (context-specific profiles are amino-acid profiles)") << std::endl;
+            return 2;
+        }
         if (cmdlineopts.codon_flag) {  // main.cpp:225-241
             if (!indel_set) cmdlineopts.indel_rate /= 2.6;
             if (!edgehl_set) cmdlineopts.edge_halflife *= 2.6;
@@ -264,7 +283,7 @@ int main(int argc, char **argv) {
         }
         std::map<std::string, std::string> aligned;
         PhyTree *tree = nullptr;
-        Alphabet a(cmdlineopts.codon_flag ? ALPHA_CODON : ALPHA_AA);
+        Alphabet a(cmdlineopts.codon_flag ? ALPHA_CODON : cmdlineopts.dna_flag ? ALPHA_DNA : ALPHA_AA);
         doAlign(a, seqs, aligned, tree, stats);
         if (!cmdlineopts.onlytree_flag) {
             std::vector<std::string> order = input_order;

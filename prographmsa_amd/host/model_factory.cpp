@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cmath>
 #include <fstream>
+#include <memory>
 
 namespace pgm {
 
@@ -136,8 +137,12 @@ ModelFactory::ModelFactory(int dim, const std::string &qmat_file) : dim_(dim) {
     for (int j = 0; j < n; ++j) A[(n - 1) + n * j] = 1.0;
     b[n - 1] = 1.0;
     freqs_ = solve(A, b, n);
+    normalise();
+}
 
-    // normalise rate (ModelFactoryWag.cpp:432-435)
+void ModelFactory::normalise() {
+    const int n = dim_;
+    // normalise rate (ModelFactoryWag.cpp:432-435, ModelFactoryCustom.h:62-65, ModelFactoryPlusF.h:97-100)
     for (int i = 0; i < n; ++i) Q_[i + n * i] = 0;
     for (int i = 0; i < n; ++i) {
         double s = 0;
@@ -187,9 +192,67 @@ ModelFactory::ModelFactory(int dim, const std::string &qmat_file) : dim_(dim) {
         }
 }
 
-ModelFactory *ModelFactory::getDefault(const Alphabet &a) {
-    if (a.kind == ALPHA_AA) return new ModelFactory(20, data_dir() + "/wag.qmat");
-    return new ModelFactory(61, data_dir() + "/ecm.qmat");
+// A custom model (ModelFactoryCustom.h:36-70): the strict lower triangle of the symmetric exchangeability matrix row by row
+// (i = 1 .. D-1, j < i), then D frequencies, in the alphabet's value order.  Q stays the exchangeability matrix itself (it is not
+// multiplied by the frequencies, as in the reference), so it is symmetric and takes the eigen form.
+ModelFactory *ModelFactory::readCustom(int dim, const std::string &file) {
+    const int n = dim;
+    std::unique_ptr<ModelFactory> mf(new ModelFactory(dim));
+    std::ifstream in(file.c_str());
+    mf->Q_.assign((size_t)n * n, 0.0);
+    for (int i = 1; i < n; ++i)
+        for (int j = 0; j < i; ++j) {
+            double value = 0;
+            in >> value;
+            if (!in) error("error reading exchangeability matrix from file");
+            if (!(value > 0 && value < INFINITY)) error("negative/infinity/zero value in exchangeability matrix");
+            mf->Q_[i + n * j] = mf->Q_[j + n * i] = value;
+        }
+    mf->freqs_.assign(n, 0.0);
+    for (int i = 0; i < n; ++i) {
+        double value = 0;
+        in >> value;
+        if (!in) error("error reading amino acid frequencies");
+        if (!(value > 0 && value < INFINITY)) error("negative/infinity/zero value in amino acid frequencies");
+        mf->freqs_[i] = value;
+    }
+    double sum = 0;
+    for (int i = 0; i < n; ++i) sum += mf->freqs_[i];
+    for (double &f : mf->freqs_) f /= sum;
+    mf->normalise();
+    return mf.release();
+}
+
+// +F (ModelFactoryPlusF.h:72-105): frequencies = (base frequencies * pseudo-count + counts of the valid residues), normalised;
+// Q <- Q diag(f / f_base), then the diagonal reset and the rate normalisation again.  Delta and epsilon are the base model's
+// (here the same functions for every model).
+void ModelFactory::estimateFreqs(const Alphabet &a, const std::map<std::string, sequence_t> &seqs) {
+    const int n = dim_;
+    const std::vector<double> old = freqs_;
+    std::vector<double> f(n);
+    for (int i = 0; i < n; ++i) f[i] = old[i] * cmdlineopts.pseudo_count;
+    for (const auto &kv : seqs)
+        for (int8_t c : kv.second)
+            if (a.isValid(c)) f[a.value(c)] += 1;
+    double sum = 0;
+    for (int i = 0; i < n; ++i) sum += f[i];
+    for (int i = 0; i < n; ++i) freqs_[i] = f[i] / sum;
+    for (int j = 0; j < n; ++j) {
+        const double w = freqs_[j] / old[j];
+        for (int i = 0; i < n; ++i) Q_[i + n * j] *= w;
+    }
+    V_.clear(); Vi_.clear(); sigma_.clear();
+    normalise();
+}
+
+ModelFactory *ModelFactory::getDefault(const Alphabet &a, const std::map<std::string, sequence_t> &seqs) {
+    std::unique_ptr<ModelFactory> mf;
+    if (!cmdlineopts.cmodel_file.empty()) mf.reset(readCustom(a.DIM, cmdlineopts.cmodel_file));
+    else if (a.kind == ALPHA_DNA) error("custom model file necessary for DNA alignments");
+    else if (a.kind == ALPHA_AA) mf.reset(new ModelFactory(20, data_dir() + "/wag.qmat"));
+    else mf.reset(new ModelFactory(61, data_dir() + "/ecm.qmat"));
+    if (cmdlineopts.aafreqs_flag) mf->estimateFreqs(a, seqs);
+    return mf.release();
 }
 
 double ModelFactory::getDelta(distance_t distance) const {

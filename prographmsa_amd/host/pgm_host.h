@@ -55,6 +55,9 @@ struct cmdlineopts_t {
     double repeatext_prob = 0.3;
     double max_dist = 2.2, min_dist = 0.05, max_pdist = 0.8, min_pdist = 0.05;
     std::string output_file, sequence_file, tree_file, cs_file;
+    bool dna_flag = false;      // --dna (main.cpp:55-57, 219-223)
+    std::string cmodel_file;    // --custom_model (main.cpp:135, 178)
+    bool aafreqs_flag = false;  // -F / --estimate_aafreqs (main.cpp:138, 204); -C / --aafreqs_pseudocount sets pseudo_count
 };
 extern cmdlineopts_t cmdlineopts;
 
@@ -67,12 +70,14 @@ struct pgm_exception : std::runtime_error {
 
 // ---------------------------------------------------------------------------------------
 // Alphabets (Alphabet.h:37-115).  A symbol is stored as the reference stores it in `data`:
-// AA keeps the raw character, Codon keeps the codon index (61 = unknown, 62 = gap, -1 = invalid).
-enum AlphabetKind { ALPHA_AA = 0, ALPHA_CODON = 1 };
+// AA and DNA keep the raw character, Codon keeps the codon index (61 = unknown, 62 = gap, -1 = invalid).
+// DNA values follow dna_translation_table (Alphabet.cpp:22-40): T=0 C=1 A=2 G=3, unknown 4.
+enum AlphabetKind { ALPHA_AA = 0, ALPHA_CODON = 1, ALPHA_DNA = 2 };
 struct Alphabet {
     AlphabetKind kind;
     int DIM;
-    explicit Alphabet(AlphabetKind k) : kind(k), DIM(k == ALPHA_AA ? 20 : 61) {}
+    explicit Alphabet(AlphabetKind k) : kind(k), DIM(k == ALPHA_AA ? 20 : k == ALPHA_DNA ? 4 : 61) {}
+    bool rawChars() const { return kind != ALPHA_CODON; }   // one character per symbol, kept as read
     int value(int8_t data) const;                  // AA::value / Codon::value
     bool isValid(int8_t data) const { int v = value(data); return v >= 0 && v < DIM; }
     int8_t gap() const;                            // ALPHABET::GAP
@@ -98,11 +103,13 @@ struct Model {
 };
 
 // ModelFactory (ModelFactory.h:11-34) with the WAG (ModelFactoryWag.cpp) and ECM
-// (ModelFactoryEcm.cpp) rate matrices.  P(t) = exp(Q t) by scaling-and-squaring instead of Eigen's
+// (ModelFactoryEcm.cpp) rate matrices, a custom model read from a file (ModelFactoryCustom.h) and frequencies
+// estimated from the input (ModelFactoryPlusF.h).  P(t) = exp(Q t) by scaling-and-squaring instead of Eigen's
 // general EigenSolver; agrees to ~1e-14.
 class ModelFactory {
 public:
-    static ModelFactory *getDefault(const Alphabet &a);          // ModelFactory.cpp:11-36
+    // ModelFactory.cpp:11-90: --custom_model, else WAG / ECM (DNA: a custom model is required); -F then re-estimates the frequencies
+    static ModelFactory *getDefault(const Alphabet &a, const std::map<std::string, sequence_t> &seqs);
     Model getModel(distance_t distance) const;                   // ModelFactory.h:48-67
     Model getModel(distance_t distance, distance_t gap_distance) const;  // :70-90
     double getEpsilon(distance_t) const { return cmdlineopts.gapext_prob; }
@@ -118,6 +125,10 @@ public:
 
 private:
     ModelFactory(int dim, const std::string &qmat_file);
+    explicit ModelFactory(int dim) : dim_(dim) {}
+    static ModelFactory *readCustom(int dim, const std::string &file);                      // ModelFactoryCustom.h:36-70
+    void estimateFreqs(const Alphabet &a, const std::map<std::string, sequence_t> &seqs);   // ModelFactoryPlusF.h:72-105
+    void normalise();   // diagonal reset, rate normalisation and the choice of the eigen form (Q_ off the diagonal and freqs_ set)
     static void parseDistance(distance_t distance, Model &model);  // ModelFactory.h:104-127
     void fillP(Model &model) const;
     int dim_;

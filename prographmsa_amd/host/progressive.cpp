@@ -61,6 +61,7 @@ static int8_t symbol_of(const Alphabet &a, int j) {   // ALPHABET(j): the symbol
     static const char *aa = "ACDEFGHIKLMNPQRSTVWY";
     if (a.kind == ALPHA_AA) return sequenceFromString(a, std::string(1, aa[j]))[0];
     static const char nt[] = "TCAG";   // the 61 sense codons in TCAG order (Alphabet.cpp)
+    if (a.kind == ALPHA_DNA) return j < 4 ? (int8_t)nt[j] : a.unknown();   // dna_inv_translation_table
     int k = -1;
     for (int c = 0; c < 64; ++c) {
         const std::string cod = {nt[c >> 4], nt[(c >> 2) & 3], nt[c & 3]};
