@@ -170,6 +170,23 @@ int pgm_align_batch_test_stall(pgm_align_batch *b, uint32_t job, uint32_t band, 
  * of sweeps in microseconds.  Every queue with work gets at least one CU and the shares never exceed `cus`. */
 int pgm_test_cu_shares(uint32_t cus, double lean_cost, uint32_t nlean, double band_cost, uint32_t nbands, double rest_cost,
                        uint32_t nrest, uint32_t ncrit, double longest_chain, uint32_t *out4);
+/* Test hook (host arithmetic only, no device call): the plan pgm_align_batch_create_res makes for these jobs on a device of `cus`
+ * compute units, through the same functions (csrc/pgm_plan.h), in caller memory.  Invalid input: the codes and messages of create.
+ *   head   PGM_PLAN_HEAD words: dp of the jobs (0: no job), promote_bands, nitems, ncrit, nbands, nbands_narrow, nlean, ntb, ntb_c, ntb_b,
+ *          the workers nworkers, nlean, nband, nwide, ncrit, ntb, ntb_b, then crit_c3, rest_c3 and of the PGM_HOST_PROFILE "work lists:"
+ *          line the main launch's CUs, the narrow bands, the main launch's items, the items of the longest chains
+ *   dhead  PGM_PLAN_DHEAD doubles, the rest of that line: longest chain of sweeps, goal, lean cost, band cost, simulated end of the bands,
+ *          cost and simulated end of the items, simulated end of the longest chains; then longest_crit_chain
+ *   job_fields  PGM_PLAN_JOB words per job: lean, has_extras, mode2, hD, hDX, slot_bytes, aux_off, ov_off, rh_off, c3_off, nov2, has_far,
+ *          long1, long2, crit3, far_slack, nslots, generic nodes, kill nodes
+ *   items, bands  {job, band, prio, count} per entry, room for one entry per band of 64 rows of the batch;  lean_list  njobs words;
+ *   tblist  {job, last item} per entry, njobs entries */
+#define PGM_PLAN_HEAD 23
+#define PGM_PLAN_DHEAD 9
+#define PGM_PLAN_JOB 19
+int pgm_test_batch_plan(uint32_t njobs, const pgm_graph *const *g1, const pgm_graph *const *g2, const pgm_model *const *model,
+                        const pgm_scores *scores, uint32_t flags, const pgm_site_ref *res1, const pgm_site_ref *res2, uint32_t cus,
+                        uint32_t *head, double *dhead, uint32_t *job_fields, uint32_t *items, uint32_t *bands, uint32_t *lean_list, int32_t *tblist);
 /* Test hook: copy one job's DP matrices back as the reference lays them out (n1 x n2,
  * column-major, element (y,x) at y + x*n1).  Only rows < n1-1 and columns < n2-1 are
  * defined (the END row/column are never written by the reference's fill either).
