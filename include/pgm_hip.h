@@ -282,6 +282,17 @@ int pgm_prealigned_counts_batch(pgm_ctx *ctx, uint32_t dim, uint32_t nrows, uint
  * depth blocks of the reference's GEMM — L1d / 128 terms each, L1d = 49152 bytes unless the environment names the size the
  * reference's host reports (PGM_EIGEN_L1D).  The matrix is NOT symmetric in its last bits; element (i, j) is at i + nseq j. */
 int pgm_kmer_cosine(pgm_ctx *ctx, uint32_t nseq, uint32_t ncols, const int32_t *counts, double *cosine);
+/* ---- (f3, f4) for many families in one launch (pgmsa --batch).
+ * pgm_kmer_cosine_multi: counts holds the families' count rows back to back (sum of nseq[f] rows of ncols int32), cosine their
+ * nseq[f] x nseq[f] column-major matrices back to back; every element has the bits pgm_kmer_cosine gives the family alone.
+ * pgm_prealigned_counts_multi: rows holds every family's nrows[f] x ncols[f] int8 matrix back to back; pair p compares rows pi[p],
+ * pj[p] of family fam[p]; counts and gaps are laid out as pgm_prealigned_counts_batch lays them out (1 <= dim <= 64; a result
+ * matrix smaller than 20 x 20 keeps that corner of the counts).  PGM_ERR_INVALID: a null pointer, nfam == 0, a family with fewer
+ * than 2 rows, fam[p] >= nfam, a pair index outside its family. */
+int pgm_kmer_cosine_multi(pgm_ctx *ctx, uint32_t nfam, const uint32_t *nseq, uint32_t ncols, const int32_t *counts, double *cosine);
+int pgm_prealigned_counts_multi(pgm_ctx *ctx, uint32_t dim, uint32_t nfam, const uint32_t *nrows, const uint32_t *ncols,
+                                const int8_t *rows, uint32_t npairs, const uint32_t *fam, const uint32_t *pi, const uint32_t *pj,
+                                int32_t *counts, uint32_t *gaps);
 /* Device time of the kernel of the last pgm_mldist_batch / pgm_prealigned_counts_batch / pgm_kmer_cosine call on this context (ms). */
 float pgm_dist_last_kernel_ms(pgm_ctx *ctx);
 

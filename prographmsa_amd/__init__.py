@@ -77,6 +77,7 @@ EXPORTS = [
     "pgm_align_batch_destroy", "pgm_align_batch_cells", "pgm_align_batch_test_stall", "pgm_test_cu_shares", "pgm_test_batch_plan", "pgm_align_batch_stage_times", "pgm_align_batch_job_times", "pgm_align_batch_time", "pgm_align_batch_read_matrices",
     "pgm_nw_pairs_batch", "pgm_nw_pairs_submit", "pgm_nw_pairs_wait", "pgm_nw_last_kernel_ms", "pgm_host_alloc", "pgm_host_free", "pgm_csprofile_load", "pgm_csprofile_create_batch", "pgm_csprofile_create_batch_res",
     "pgm_csprofile_last_kernel_ms", "pgm_mldist_batch", "pgm_prealigned_counts_batch", "pgm_kmer_cosine", "pgm_dist_last_kernel_ms",
+    "pgm_kmer_cosine_multi", "pgm_prealigned_counts_multi",
     "pgm_merge_profiles_batch", "pgm_merge_profiles_batch_ex", "pgm_resident_reset", "pgm_resident_onehot", "pgm_resident_import", "pgm_merge_last_kernel_ms",
     "pgm_gapmask_extend_batch", "pgm_gap_parsimony_batch", "pgm_parsimony_last_kernel_ms",
     "pgm_wls_load", "pgm_wls_pair_sums_batch", "pgm_wls_last_kernel_ms", "pgm_wls_last_launches",
@@ -131,6 +132,9 @@ def _load():
         "pgm_prealigned_counts_batch": (C.c_int, [vp, u32, u32, u32, C.POINTER(C.c_int8), u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(i32), C.POINTER(u32)]),
         "pgm_kmer_cosine": (C.c_int, [vp, u32, u32, C.POINTER(i32), C.POINTER(C.c_double)]),
         "pgm_dist_last_kernel_ms": (C.c_float, [vp]),
+        "pgm_kmer_cosine_multi": (C.c_int, [vp, u32, C.POINTER(u32), u32, C.POINTER(i32), C.POINTER(C.c_double)]),
+        "pgm_prealigned_counts_multi": (C.c_int, [vp, u32, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_int8), u32, C.POINTER(u32), C.POINTER(u32),
+                                                  C.POINTER(u32), C.POINTER(i32), C.POINTER(u32)]),
         "pgm_merge_profiles_batch": (C.c_int, [vp, u32, C.POINTER(pgm_merge_job)]),
         "pgm_merge_profiles_batch_ex": (C.c_int, [vp, u32, C.POINTER(pgm_merge_job), u32, C.POINTER(C.POINTER(C.c_double))]),
         "pgm_resident_reset": (C.c_int, [vp]),

@@ -86,6 +86,14 @@ extern "C" int pgm_prealigned_counts_batch(pgm_ctx *ctx, uint32_t dim, uint32_t 
 
 extern "C" float pgm_dist_last_kernel_ms(pgm_ctx *ctx) { return ctx ? ctx->ml_ms : 0.f; }
 
+// depth block of the reference's GEMM: L1d / 128 terms, L1d as Eigen reads it from cpuid where the reference runs (48 KB on the
+// host of the golden files; PGM_EIGEN_L1D = bytes for another)
+static uint32_t kmer_depth_block() {
+    const char *l1e = getenv("PGM_EIGEN_L1D");
+    const long l1d = l1e ? atol(l1e) : 49152;
+    return (uint32_t)std::max(1L, l1d / 128);
+}
+
 extern "C" int pgm_kmer_cosine(pgm_ctx *ctx, uint32_t nseq, uint32_t ncols, const int32_t *counts, double *cosine) {
     if (!ctx || (nseq && (!counts || !cosine)) || ncols == 0) return fail(PGM_ERR_INVALID, "bad argument");
     ctx->ml_ms = 0;
@@ -104,11 +112,7 @@ extern "C" int pgm_kmer_cosine(pgm_ctx *ctx, uint32_t nseq, uint32_t ncols, cons
         e = hipEventRecord(ctx->sc_ev[0], s);
         hipLaunchKernelGGL(pgm_kmer_norm_kernel, dim3((nseq + 255) / 256), dim3(256), 0, s, nseq, ncols, d_counts, d_inv);
         const uint32_t tiles = (nseq + PGM_KC_TILE - 1) / PGM_KC_TILE;
-        // depth block of the reference's GEMM: L1d / 128 terms, L1d as Eigen reads it from cpuid where the reference runs (48 KB on the
-        // host of the golden files; PGM_EIGEN_L1D = bytes for another)
-        const char *l1e = getenv("PGM_EIGEN_L1D");
-        const long l1d = l1e ? atol(l1e) : 49152;
-        const uint32_t kc = (uint32_t)std::max(1L, l1d / 128);
+        const uint32_t kc = kmer_depth_block();
         hipLaunchKernelGGL(pgm_kmer_cosine_kernel, dim3(tiles, tiles), dim3(PGM_KC_TILE * PGM_KC_TILE), 0, s, nseq, ncols, d_counts, d_inv, d_out, kc);
         if (e == hipSuccess) e = hipGetLastError();
         if (e == hipSuccess) e = hipEventRecord(ctx->sc_ev[1], s);
@@ -117,5 +121,104 @@ extern "C" int pgm_kmer_cosine(pgm_ctx *ctx, uint32_t nseq, uint32_t ncols, cons
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e == hipSuccess) (void)hipEventElapsedTime(&ctx->ml_ms, ctx->sc_ev[0], ctx->sc_ev[1]);
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("kmer cosine: ") + hipGetErrorString(e));
+    return PGM_OK;
+}
+
+// ---- many families per launch (pgmsa --batch) ----
+extern "C" int pgm_kmer_cosine_multi(pgm_ctx *ctx, uint32_t nfam, const uint32_t *nseq, uint32_t ncols, const int32_t *counts, double *cosine) {
+    if (!ctx || !nseq || !counts || !cosine || nfam == 0 || ncols == 0) return fail(PGM_ERR_INVALID, "bad argument");
+    ctx->ml_ms = 0;
+    std::vector<uint32_t> tile0(nfam + 1, 0), row0(nfam + 1, 0);
+    std::vector<uint64_t> out0(nfam + 1, 0);
+    for (uint32_t f = 0; f < nfam; ++f) {
+        if (nseq[f] < 2) return fail(PGM_ERR_INVALID, "a family needs at least 2 sequences");
+        const uint64_t tiles = (nseq[f] + PGM_KC_TILE - 1) / PGM_KC_TILE;
+        const uint64_t t = (uint64_t)tile0[f] + tiles * tiles, r = (uint64_t)row0[f] + nseq[f];
+        if (t > 0x7fffffffull || r > 0x7fffffffull) return fail(PGM_ERR_INVALID, "too many sequences for one call");
+        tile0[f + 1] = (uint32_t)t; row0[f + 1] = (uint32_t)r;
+        out0[f + 1] = out0[f] + (uint64_t)nseq[f] * nseq[f];
+    }
+    const uint32_t nrows = row0[nfam];
+    HIPCHK(hipSetDevice(ctx->device));
+    int32_t *d_counts = nullptr;
+    double *d_inv = nullptr, *d_out = nullptr;
+    uint32_t *d_tile0 = nullptr, *d_row0 = nullptr;
+    uint64_t *d_out0 = nullptr;
+    hipStream_t s = ctx->stream;
+    hipError_t e = scratch_dev(ctx, 0, 4 * (size_t)nrows * ncols, (void **)&d_counts);
+    if (e == hipSuccess) e = scratch_dev(ctx, 1, 8 * (size_t)nrows, (void **)&d_inv);
+    if (e == hipSuccess) e = scratch_dev(ctx, 2, 8 * (size_t)out0[nfam], (void **)&d_out);
+    if (e == hipSuccess) e = scratch_dev(ctx, 3, 4 * (size_t)(nfam + 1), (void **)&d_tile0);
+    if (e == hipSuccess) e = scratch_dev(ctx, 4, 4 * (size_t)(nfam + 1), (void **)&d_row0);
+    if (e == hipSuccess) e = scratch_dev(ctx, 5, 8 * (size_t)(nfam + 1), (void **)&d_out0);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_counts, counts, 4 * (size_t)nrows * ncols, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tile0, tile0.data(), 4 * (size_t)(nfam + 1), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_row0, row0.data(), 4 * (size_t)(nfam + 1), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_out0, out0.data(), 8 * (size_t)(nfam + 1), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = scratch_events(ctx);
+    if (e == hipSuccess) {
+        e = hipEventRecord(ctx->sc_ev[0], s);
+        hipLaunchKernelGGL(pgm_kmer_norm_kernel, dim3((nrows + 255) / 256), dim3(256), 0, s, nrows, ncols, d_counts, d_inv);   // (every row has ncols counts)
+        hipLaunchKernelGGL(pgm_kmer_cosine_multi_kernel, dim3(tile0[nfam]), dim3(PGM_KC_TILE * PGM_KC_TILE), 0, s, nfam, d_tile0, d_row0, d_out0, ncols, d_counts,
+                           d_inv, d_out, kmer_depth_block());
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = hipEventRecord(ctx->sc_ev[1], s);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(cosine, d_out, 8 * (size_t)out0[nfam], hipMemcpyDeviceToHost, s);
+    const hipError_t es = hipStreamSynchronize(s);   // (also after a failure: the copies read this call's vectors)
+    if (e == hipSuccess) e = es;
+    if (e == hipSuccess) (void)hipEventElapsedTime(&ctx->ml_ms, ctx->sc_ev[0], ctx->sc_ev[1]);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("kmer cosine (multi): ") + hipGetErrorString(e));
+    return PGM_OK;
+}
+
+extern "C" int pgm_prealigned_counts_multi(pgm_ctx *ctx, uint32_t dim, uint32_t nfam, const uint32_t *nrows, const uint32_t *ncols, const int8_t *rows,
+                                           uint32_t npairs, const uint32_t *fam, const uint32_t *pi, const uint32_t *pj, int32_t *counts, uint32_t *gaps) {
+    if (!ctx || dim == 0 || dim > 64 || nfam == 0 || !nrows || !ncols || !rows || !fam || !pi || !pj || !counts || !gaps) return fail(PGM_ERR_INVALID, "bad argument");
+    ctx->ml_ms = 0;
+    std::vector<uint64_t> base(nfam + 1, 0);
+    for (uint32_t f = 0; f < nfam; ++f) {
+        if (nrows[f] < 2) return fail(PGM_ERR_INVALID, "a family needs at least 2 rows");
+        base[f + 1] = base[f] + (uint64_t)nrows[f] * ncols[f];
+    }
+    for (uint32_t p = 0; p < npairs; ++p) {
+        if (fam[p] >= nfam) return fail(PGM_ERR_INVALID, "family index out of range");
+        if (pi[p] >= nrows[fam[p]] || pj[p] >= nrows[fam[p]]) return fail(PGM_ERR_INVALID, "pair index out of range");
+    }
+    if (npairs == 0) return PGM_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    int8_t *d_rows = nullptr;
+    uint64_t *d_base = nullptr;
+    uint32_t *d_ncols = nullptr, *d_fam = nullptr, *d_pi = nullptr, *d_pj = nullptr, *d_gaps = nullptr;
+    int32_t *d_counts = nullptr;
+    const size_t cbytes = 4 * (size_t)npairs * dim * dim;
+    struct Buf { void **p; size_t bytes; const void *src; };
+    Buf bufs[] = {{(void **)&d_rows, (size_t)base[nfam], rows}, {(void **)&d_pi, 4 * (size_t)npairs, pi}, {(void **)&d_pj, 4 * (size_t)npairs, pj},
+                  {(void **)&d_counts, cbytes, nullptr}, {(void **)&d_gaps, 4 * (size_t)npairs, nullptr}, {(void **)&d_fam, 4 * (size_t)npairs, fam},
+                  {(void **)&d_base, 8 * (size_t)nfam, base.data()}, {(void **)&d_ncols, 4 * (size_t)nfam, ncols}};
+    hipError_t e = hipSuccess;
+    hipStream_t s = ctx->stream;
+    int slot_ix = 0;
+    for (auto &b : bufs) {
+        if (e == hipSuccess) e = scratch_dev(ctx, slot_ix++, b.bytes, b.p);
+        if (e == hipSuccess && b.src && b.bytes) e = hipMemcpyAsync(*b.p, b.src, b.bytes, hipMemcpyHostToDevice, s);
+    }
+    if (e == hipSuccess) e = scratch_events(ctx);
+    if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, cbytes, s);
+    if (e == hipSuccess) {
+        PgmPaMultiArgs A;
+        A.dim = dim; A.npairs = npairs; A.rows = d_rows; A.base = d_base; A.ncols = d_ncols; A.fam = d_fam; A.pi = d_pi; A.pj = d_pj; A.counts = d_counts; A.gaps = d_gaps;
+        const uint32_t blocks = std::min<uint32_t>((npairs + 3) / 4, (uint32_t)ctx->prop.multiProcessorCount * 8u);
+        e = hipEventRecord(ctx->sc_ev[0], s);
+        hipLaunchKernelGGL(pgm_prealigned_multi_kernel, dim3(blocks), dim3(256), 0, s, A);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = hipEventRecord(ctx->sc_ev[1], s);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, cbytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(gaps, d_gaps, 4 * (size_t)npairs, hipMemcpyDeviceToHost, s);
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = es;
+    if (e == hipSuccess) (void)hipEventElapsedTime(&ctx->ml_ms, ctx->sc_ev[0], ctx->sc_ev[1]);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("prealigned (multi): ") + hipGetErrorString(e));
     return PGM_OK;
 }

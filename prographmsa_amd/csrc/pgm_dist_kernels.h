@@ -161,49 +161,75 @@ struct PgmPaArgs {
     uint32_t *gaps;      // npairs
 };
 
+// one pair on one wavefront: rows r1, r2 of L columns; cnt: the wavefront's 400 LDS counters
+__device__ __forceinline__ void pgm_prealigned_pair(const int8_t *__restrict__ r1, const int8_t *__restrict__ r2, uint32_t L, uint32_t D, int *cnt,
+                                                    int32_t *__restrict__ out, uint32_t *__restrict__ gaps_out, int lane) {
+    const uint32_t chunk = (L + 63u) / 64u;
+    for (int i = lane; i < 400; i += 64) cnt[i] = 0;
+    __builtin_amdgcn_wave_barrier();
+    // type of a column: 0 both residues, 1 only row 1 has a residue, 2 only row 2, 3 both gaps (skipped)
+    int first = 3, last = 3;
+    uint32_t g = 0;
+    const uint32_t k0 = min(L, (uint32_t)lane * chunk), k1 = min(L, k0 + chunk);
+    for (uint32_t k = k0; k < k1; ++k) {
+        const int c1 = r1[k], c2 = r2[k];
+        const bool g1 = c1 == -1, g2 = c2 == -1;
+        const int ty = (!g1 && !g2) ? 0 : ((g1 && g2) ? 3 : (!g1 ? 1 : 2));
+        if (ty == 3) continue;
+        if (ty == 0) { if (c1 >= 0 && c1 < 20 && c2 >= 0 && c2 < 20) atomicAdd(&cnt[c1 + 20 * c2], 1); }
+        else if (ty != last) ++g;            // a run opens (the previous non-skipped column was of another type)
+        if (first == 3) first = ty;
+        last = ty;
+    }
+    // chunk boundaries: a chunk whose first non-skipped column continues the run the previous non-empty chunk ended in
+    // has counted one opening too many
+    int prev_last = 3;
+    uint32_t total = 0;
+    for (int l = 0; l < 64; ++l) {
+        const int f = __builtin_amdgcn_readlane(first, l), la = __builtin_amdgcn_readlane(last, l);
+        total += (uint32_t)__builtin_amdgcn_readlane((int)g, l);
+        if (f != 3) {
+            if (f != 0 && f == prev_last) --total;
+            prev_last = la;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    for (int i = lane; i < 400; i += 64) {
+        const int c1 = i % 20, c2 = i / 20;
+        if ((uint32_t)c1 < D && (uint32_t)c2 < D) out[c1 + D * c2] = cnt[i];
+    }
+    if (lane == 0) *gaps_out = total;
+    __builtin_amdgcn_wave_barrier();
+}
+
 __global__ void __launch_bounds__(256) pgm_prealigned_kernel(PgmPaArgs A) {
     __shared__ int cnt[4][400];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t D = A.dim, L = A.ncols;
-    const uint32_t chunk = (L + 63u) / 64u;
+    for (uint32_t pair = blockIdx.x * 4 + w; pair < A.npairs; pair += gridDim.x * 4)
+        pgm_prealigned_pair(A.rows + (size_t)A.pi[pair] * L, A.rows + (size_t)A.pj[pair] * L, L, D, cnt[w], A.counts + (size_t)pair * D * D, A.gaps + pair, lane);
+}
+
+// The same for the alignments of many families in one launch (pgm_prealigned_counts_multi): pair p compares rows pi[p], pj[p] of
+// family fam[p], whose matrix starts at rows + base[fam[p]] and has ncols[fam[p]] columns.  The per-pair code is the one above.
+struct PgmPaMultiArgs {
+    uint32_t dim, npairs;
+    const int8_t *rows;
+    const uint64_t *base;     // per family: offset of its matrix in rows
+    const uint32_t *ncols;    // per family
+    const uint32_t *fam, *pi, *pj;
+    int32_t *counts;          // npairs x dim x dim, zero-initialised
+    uint32_t *gaps;           // npairs
+};
+
+__global__ void __launch_bounds__(256) pgm_prealigned_multi_kernel(PgmPaMultiArgs A) {
+    __shared__ int cnt[4][400];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t D = A.dim;
     for (uint32_t pair = blockIdx.x * 4 + w; pair < A.npairs; pair += gridDim.x * 4) {
-        for (int i = lane; i < 400; i += 64) cnt[w][i] = 0;
-        __builtin_amdgcn_wave_barrier();
-        const int8_t *r1 = A.rows + (size_t)A.pi[pair] * L, *r2 = A.rows + (size_t)A.pj[pair] * L;
-        // type of a column: 0 both residues, 1 only row 1 has a residue, 2 only row 2, 3 both gaps (skipped)
-        int first = 3, last = 3;
-        uint32_t g = 0;
-        const uint32_t k0 = (uint32_t)lane * chunk, k1 = min(L, k0 + chunk);
-        for (uint32_t k = k0; k < k1; ++k) {
-            const int c1 = r1[k], c2 = r2[k];
-            const bool g1 = c1 == -1, g2 = c2 == -1;
-            const int ty = (!g1 && !g2) ? 0 : ((g1 && g2) ? 3 : (!g1 ? 1 : 2));
-            if (ty == 3) continue;
-            if (ty == 0) { if (c1 >= 0 && c1 < 20 && c2 >= 0 && c2 < 20) atomicAdd(&cnt[w][c1 + 20 * c2], 1); }
-            else if (ty != last) ++g;            // a run opens (the previous non-skipped column was of another type)
-            if (first == 3) first = ty;
-            last = ty;
-        }
-        // chunk boundaries: a chunk whose first non-skipped column continues the run the previous non-empty chunk ended in
-        // has counted one opening too many
-        int prev_last = 3;
-        uint32_t total = 0;
-        for (int l = 0; l < 64; ++l) {
-            const int f = __builtin_amdgcn_readlane(first, l), la = __builtin_amdgcn_readlane(last, l);
-            total += (uint32_t)__builtin_amdgcn_readlane((int)g, l);
-            if (f != 3) {
-                if (f != 0 && f == prev_last) --total;
-                prev_last = la;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-        int32_t *out = A.counts + (size_t)pair * D * D;
-        for (int i = lane; i < 400; i += 64) {
-            const int c1 = i % 20, c2 = i / 20;
-            if ((uint32_t)c1 < D && (uint32_t)c2 < D) out[c1 + D * c2] = cnt[w][i];
-        }
-        if (lane == 0) A.gaps[pair] = total;
-        __builtin_amdgcn_wave_barrier();
+        const uint32_t f = A.fam[pair], L = A.ncols[f];
+        const int8_t *m = A.rows + A.base[f];
+        pgm_prealigned_pair(m + (size_t)A.pi[pair] * L, m + (size_t)A.pj[pair] * L, L, D, cnt[w], A.counts + (size_t)pair * D * D, A.gaps + pair, lane);
     }
 }
 
@@ -218,17 +244,18 @@ __global__ void __launch_bounds__(256) pgm_prealigned_kernel(PgmPaArgs A) {
 // chunks of 64 columns (the i-slab already scaled).
 #define PGM_KC_TILE 16
 #define PGM_KC_CHUNK 64
-__global__ void __launch_bounds__(PGM_KC_TILE * PGM_KC_TILE) pgm_kmer_cosine_kernel(uint32_t nseq, uint32_t ncols, const int32_t *__restrict__ counts,
-                                                                                 const double *__restrict__ inv_norm, double *__restrict__ out, uint32_t kc) {
-    __shared__ double sa[PGM_KC_TILE][PGM_KC_CHUNK + 1], sb[PGM_KC_TILE][PGM_KC_CHUNK + 1];
+// the 16 x 16 tile (by, bx) of one nseq x nseq matrix
+__device__ __forceinline__ void pgm_kmer_cosine_tile(uint32_t nseq, uint32_t ncols, const int32_t *__restrict__ counts, const double *__restrict__ inv_norm,
+                                                     double *__restrict__ out, uint32_t kc, uint32_t bx, uint32_t by,
+                                                     double (*sa)[PGM_KC_CHUNK + 1], double (*sb)[PGM_KC_CHUNK + 1]) {
     const uint32_t tx = threadIdx.x % PGM_KC_TILE, ty = threadIdx.x / PGM_KC_TILE;
-    const uint32_t i = blockIdx.y * PGM_KC_TILE + ty, j = blockIdx.x * PGM_KC_TILE + tx;
+    const uint32_t i = by * PGM_KC_TILE + ty, j = bx * PGM_KC_TILE + tx;
     double acc = 0.0, res = 0.0;
     uint32_t left = kc;   // terms left in the depth block
     for (uint32_t k0 = 0; k0 < ncols; k0 += PGM_KC_CHUNK) {
         for (uint32_t e = threadIdx.x; e < PGM_KC_TILE * PGM_KC_CHUNK; e += PGM_KC_TILE * PGM_KC_TILE) {
             const uint32_t r = e / PGM_KC_CHUNK, c = e % PGM_KC_CHUNK, k = k0 + c;
-            const uint32_t ri = blockIdx.y * PGM_KC_TILE + r, rj = blockIdx.x * PGM_KC_TILE + r;
+            const uint32_t ri = by * PGM_KC_TILE + r, rj = bx * PGM_KC_TILE + r;
             sa[r][c] = (ri < nseq && k < ncols) ? __dmul_rn((double)counts[(size_t)ri * ncols + k], inv_norm[ri]) : 0.0;
             sb[r][c] = (rj < nseq && k < ncols) ? (double)counts[(size_t)rj * ncols + k] : 0.0;
         }
@@ -242,6 +269,29 @@ __global__ void __launch_bounds__(PGM_KC_TILE * PGM_KC_TILE) pgm_kmer_cosine_ker
     }
     if (left != kc) res = __dadd_rn(res, acc);   // the last, shorter block
     if (i < nseq && j < nseq) out[(size_t)i + (size_t)nseq * j] = __dmul_rn(res, inv_norm[j]);
+}
+__global__ void __launch_bounds__(PGM_KC_TILE * PGM_KC_TILE) pgm_kmer_cosine_kernel(uint32_t nseq, uint32_t ncols, const int32_t *__restrict__ counts,
+                                                                                 const double *__restrict__ inv_norm, double *__restrict__ out, uint32_t kc) {
+    __shared__ double sa[PGM_KC_TILE][PGM_KC_CHUNK + 1], sb[PGM_KC_TILE][PGM_KC_CHUNK + 1];
+    pgm_kmer_cosine_tile(nseq, ncols, counts, inv_norm, out, kc, blockIdx.x, blockIdx.y, sa, sb);
+}
+// The cosine matrices of many families in one launch (pgm_kmer_cosine_multi): a block-diagonal grid.  Family f has
+// ceil(nseq_f / 16)^2 tiles; tile0[f] is the number of tiles of the families before it (tile0[nfam]: the grid), row0[f] its first
+// row in counts and inv_norm, out0[f] the offset of its matrix in out.  A workgroup finds its family by binary search in tile0;
+// every element is computed by the code above, so it has the bits pgm_kmer_cosine gives the family alone.
+__global__ void __launch_bounds__(PGM_KC_TILE * PGM_KC_TILE) pgm_kmer_cosine_multi_kernel(uint32_t nfam, const uint32_t *__restrict__ tile0, const uint32_t *__restrict__ row0,
+                                                                                       const uint64_t *__restrict__ out0, uint32_t ncols, const int32_t *__restrict__ counts,
+                                                                                       const double *__restrict__ inv_norm, double *__restrict__ out, uint32_t kc) {
+    __shared__ double sa[PGM_KC_TILE][PGM_KC_CHUNK + 1], sb[PGM_KC_TILE][PGM_KC_CHUNK + 1];
+    const uint32_t b = blockIdx.x;
+    uint32_t lo = 0, hi = nfam;   // the family with tile0[f] <= b < tile0[f + 1] (uniform over the workgroup)
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (tile0[mid] <= b) lo = mid; else hi = mid;
+    }
+    const uint32_t f = lo, r0 = row0[f], nseq = row0[f + 1] - r0;
+    const uint32_t tiles = (nseq + PGM_KC_TILE - 1) / PGM_KC_TILE, t = b - tile0[f];
+    pgm_kmer_cosine_tile(nseq, ncols, counts + (size_t)r0 * ncols, inv_norm + r0, out + out0[f], kc, t % tiles, t / tiles, sa, sb);
 }
 __global__ void pgm_kmer_norm_kernel(uint32_t nseq, uint32_t ncols, const int32_t *__restrict__ counts, double *__restrict__ inv_norm) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -108,6 +108,16 @@ struct HipBackend : Backend {
         int rc = pgm_kmer_cosine(ctx_of(worker), nseq, ncols, counts, cosine);
         if (rc != PGM_OK) error("pgm_kmer_cosine failed (%d): %s", rc, pgm_last_error());
     }
+    void kmer_cosine_multi(uint32_t nfam, const uint32_t *nseq, uint32_t ncols, const int32_t *counts, double *cosine, int worker) override {
+        int rc = pgm_kmer_cosine_multi(ctx_of(worker), nfam, nseq, ncols, counts, cosine);
+        if (rc != PGM_OK) error("pgm_kmer_cosine_multi failed (%d): %s", rc, pgm_last_error());
+    }
+    bool prealigned_counts_multi(uint32_t dim, uint32_t nfam, const uint32_t *nrows, const uint32_t *ncols, const int8_t *rows, uint32_t npairs,
+                                 const uint32_t *fam, const uint32_t *pi, const uint32_t *pj, int32_t *counts, uint32_t *gaps, int worker) override {
+        int rc = pgm_prealigned_counts_multi(ctx_of(worker), dim, nfam, nrows, ncols, rows, npairs, fam, pi, pj, counts, gaps);
+        if (rc != PGM_OK) error("pgm_prealigned_counts_multi failed (%d): %s", rc, pgm_last_error());
+        return true;
+    }
     bool gapmask_extend_batch(uint32_t njobs, const pgm_gapmask_job *jobs, int worker) override {
         int rc = pgm_gapmask_extend_batch(ctx_of(worker), njobs, jobs);
         if (rc != PGM_OK) error("pgm_gapmask_extend_batch failed (%d): %s", rc, pgm_last_error());

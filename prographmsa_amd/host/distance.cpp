@@ -144,6 +144,7 @@ void DistanceFactoryML::computeDistances(const int32_t *counts, const uint32_t *
         m.min_dist = cmdlineopts.min_dist; m.max_dist = cmdlineopts.max_dist; m.indel_rate = cmdlineopts.indel_rate;
         m.mldist = cmdlineopts.mldist_flag ? 1 : 0; m.mldist_gap = cmdlineopts.mldist_gap_flag ? 1 : 0;
         std::vector<double> dist(np), var(np);
+        ++be.calls_dist;
         done = be.mldist_batch(m, np, counts, gaps, seqlen.data(), dist.data(), var.data());
         if (done)
             for (uint32_t p = 0; p < np; ++p) {
@@ -261,6 +262,7 @@ DistanceMatrix DistanceFactoryAlign::computePwDistances(const std::map<std::stri
                 const uint32_t t = next_tile.fetch_add(1);
                 if (t >= ntiles) break;
                 const uint32_t p0 = t * tile, cnt = std::min(tile, np - p0);
+                ++be.calls_dist;
                 const int ticket = be.nw_pairs_submit(D, scoring_matrix_.data(), gap_open, gap_extend, n, syms.data(), offs.data(), cnt, pi.data() + p0,
                                                       pj.data() + p0, reduced ? 1u : 0u, counts + (size_t)p0 * per, gaps + p0, w);
                 if (pending >= 0) be.nw_pairs_wait(pending, w);
@@ -448,6 +450,17 @@ PhyTree *buildNJTree(std::vector<std::string> seqs_order, DistanceMatrix dist) {
 // ---- distances induced by an alignment (DistanceFactoryPrealigned.h:34-90) -----------------------------------------
 // Pair counts over the columns where both rows have a residue (only residues with value() in 0..19, for every alphabet:
 // the reference's literal 20), one gap per opening of a run in which exactly one of the two rows has a residue.
+// a row of an alignment as the pair-count kernels read it: value() per residue, -1 for a gap, -2 for a residue without a value (and
+// for the DNA unknown, value 4: the kernel counts every value below 20)
+static void prealigned_row(const Alphabet &alphabet, const sequence_t &row, int8_t *out) {
+    const bool dna = alphabet.kind == ALPHA_DNA;
+    for (size_t k = 0; k < row.size(); ++k) {
+        const int8_t c = row[k];
+        const int v = alphabet.isGap(c) ? -1 : alphabet.value(c);
+        out[k] = (int8_t)(alphabet.isGap(c) ? -1 : (v < 0 || (dna && v >= alphabet.DIM) ? -2 : v));
+    }
+}
+
 DistanceMatrix DistanceFactoryPrealigned::computePwDistances(const std::map<std::string, sequence_t> &aligned,
                                                             const std::vector<std::string> &order) {
     const uint32_t n = (uint32_t)order.size(), D = (uint32_t)alphabet.DIM;
@@ -470,14 +483,8 @@ DistanceMatrix DistanceFactoryPrealigned::computePwDistances(const std::map<std:
         // value() per residue, -1 for a gap, -2 for a residue without a value (and for the DNA unknown, value 4: the kernel counts
         // every value below 20)
         auto t0 = std::chrono::steady_clock::now();
-        const bool dna = alphabet.kind == ALPHA_DNA;
         std::vector<int8_t> mat((size_t)n * L);
-        for (uint32_t i = 0; i < n; ++i)
-            for (size_t k = 0; k < L; ++k) {
-                const int8_t c = (*rows[i])[k];
-                const int v = alphabet.isGap(c) ? -1 : alphabet.value(c);
-                mat[(size_t)i * L + k] = (int8_t)(alphabet.isGap(c) ? -1 : (v < 0 || (dna && v >= (int)D) ? -2 : v));
-            }
+        for (uint32_t i = 0; i < n; ++i) prealigned_row(alphabet, *rows[i], mat.data() + (size_t)i * L);
         {
             // every pair costs the same (one scan of the columns): contiguous ranges of pairs, one per device context.  The entry
             // point takes 20 to 64 states: DNA rows (values 0..3, -2) are counted as 20-state rows and the 4 x 4 corner of each
@@ -489,6 +496,7 @@ DistanceMatrix DistanceFactoryPrealigned::computePwDistances(const std::map<std:
             std::vector<char> ok((size_t)nw, 0);
             auto part = [&](int w) {
                 const uint32_t p0 = (uint32_t)((uint64_t)np * (uint32_t)w / (uint32_t)nw), p1 = (uint32_t)((uint64_t)np * ((uint32_t)w + 1u) / (uint32_t)nw);
+                if (p1 != p0) ++be.calls_dist;
                 ok[(size_t)w] = (p1 == p0 || be.prealigned_counts_batch(Dk, n, (uint32_t)L, mat.data(), p1 - p0, pi.data() + p0, pj.data() + p0,
                                                                        cdst + (size_t)p0 * Dk * Dk, gaps.data() + p0, w)) ? 1 : 0;
             };
@@ -551,34 +559,33 @@ DistanceMatrix DistanceFactoryPrealigned::computePwDistances(const std::map<std:
     return distances;
 }
 
-DistanceMatrix angleDistances(const Alphabet &a, const std::map<std::string, sequence_t> &sequences, const std::vector<std::string> &order) {
-    // K = 2 for amino acids and codons, 6 for DNA (DistanceFactory.cpp:9-60): ncols = D^K = 400, 3721, 4096
-    const uint32_t n = (uint32_t)order.size(), D = (uint32_t)a.DIM, K = a.kind == ALPHA_DNA ? 6u : 2u;
+// K = 2 for amino acids and codons, 6 for DNA (DistanceFactory.cpp:9-60): ncols = D^K = 400, 3721, 4096
+static uint32_t angle_ncols(const Alphabet &a) {
+    const uint32_t D = (uint32_t)a.DIM, K = a.kind == ALPHA_DNA ? 6u : 2u;
     uint32_t ncols = 1;
     for (uint32_t k = 0; k < K; ++k) ncols *= D;
-    DistanceMatrix distances((int)n);
-    std::vector<int32_t> counts((size_t)n * ncols, 0);
-    std::vector<double> seq_len(n);
-    parallel_for((size_t)n, [&](size_t i) {   // DistanceFactoryAngle.h:63-94: the index of the last K values, none of them invalid
-        const sequence_t &seq = sequences.at(order[i]);
-        seq_len[i] = (double)seq.size();
-        uint32_t index = 0, run = 0;   // (run: valid values at the end of the window so far)
-        for (size_t j = 0; j < seq.size(); ++j) {
-            const int v = a.value(seq[j]);
-            if (v < 0 || v >= (int)D) { run = 0; index = 0; continue; }
-            index = (index * D + (uint32_t)v) % ncols;
-            if (++run >= K) counts[i * ncols + index] += 1;
-        }
-    });
-    Backend &be = default_backend();
-    const auto t0 = std::chrono::steady_clock::now();
-    be.kmer_cosine(n, ncols, counts.data(), distances.distances.data());   // :100
+    return ncols;
+}
+// DistanceFactoryAngle.h:63-94: the index of the last K values, none of them invalid (counts: one zeroed row of ncols)
+static void angle_count_row(const Alphabet &a, const sequence_t &seq, uint32_t ncols, int32_t *counts) {
+    const uint32_t D = (uint32_t)a.DIM, K = a.kind == ALPHA_DNA ? 6u : 2u;
+    uint32_t index = 0, run = 0;   // (run: valid values at the end of the window so far)
+    for (size_t j = 0; j < seq.size(); ++j) {
+        const int v = a.value(seq[j]);
+        if (v < 0 || v >= (int)D) { run = 0; index = 0; continue; }
+        index = (index * D + (uint32_t)v) % ncols;
+        if (++run >= K) counts[index] += 1;
+    }
+}
+// from the cosine matrix as kmer_cosine wrote it to the distances and variances (DistanceFactoryAngle.h:100-113); `spread`: the rows
+// on the host threads
+static void angle_finish(DistanceMatrix &distances, const std::vector<double> &seq_len, bool spread) {
+    const uint32_t n = (uint32_t)distances.dim;
     // kmer_cosine writes element (i, j) at i + n j (the reference's column-major matrix); DistanceMatrix::D(i, j) reads i n + j.  The
     // matrix is NOT symmetric in its last bits — ((c_i / |c_i|) . c_j) / |c_j| is rounded differently from the (j, i) element — and
     // BioNJ reads it by rows, by columns and at (index1, index2) / (index2, index1): the orientation has to be the reference's.
     for (uint32_t i = 0; i < n; ++i)
         for (uint32_t j = i + 1; j < n; ++j) std::swap(distances.distances[(size_t)i * n + j], distances.distances[(size_t)j * n + i]);
-    be.seconds_mldist += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     const bool ml = cmdlineopts.mldist_flag || cmdlineopts.mldist_gap_flag;
     // log and exp of the reference binary are those of the glibc it is linked with statically (2.17: IBM's correctly rounded ones);
     // today's libm is within 0.52 ulp, which moved the exact final tie of 3 trees in 60.  Correctly rounded here: the long double
@@ -589,7 +596,7 @@ DistanceMatrix angleDistances(const Alphabet &a, const std::map<std::string, seq
     };
     auto cr_log = [&](double x) { return correctly_rounded(logl((long double)x), logq, x); };
     auto cr_exp = [&](double x) { return correctly_rounded(expl((long double)x), expq, x); };
-    parallel_for((size_t)n, [&](size_t r) {   // :101-105, row by row on the host threads
+    auto row = [&](size_t r) {   // :101-105, row by row
         for (uint32_t c = 0; c < n; ++c) {
             double &d = distances.distances[r * n + c];
             d = -1.0 * cr_log((d * d + 0.4) / 1.4);
@@ -598,13 +605,33 @@ DistanceMatrix angleDistances(const Alphabet &a, const std::map<std::string, seq
                 d = -0.5 * (5.0 * e - std::sqrt(45.0 * (e * e) - 20.0 * e)) * (1.0 / e);
             }
         }
-    });
+    };
+    if (spread) parallel_for((size_t)n, row);
+    else for (size_t r = 0; r < n; ++r) row(r);
     for (uint32_t j = 0; j < n; ++j)   // :107-113: variances = distances / ((len_i + len_j) / 2), at least 1e-5
         for (uint32_t i = 0; i < n; ++i) {
             double v = 1.0 / ((seq_len[j] + seq_len[i]) / 2);
             v *= distances.D((int)i, (int)j);
             distances.V((int)i, (int)j) = std::max(v, 1e-5);
         }
+}
+
+DistanceMatrix angleDistances(const Alphabet &a, const std::map<std::string, sequence_t> &sequences, const std::vector<std::string> &order) {
+    const uint32_t n = (uint32_t)order.size(), ncols = angle_ncols(a);
+    DistanceMatrix distances((int)n);
+    std::vector<int32_t> counts((size_t)n * ncols, 0);
+    std::vector<double> seq_len(n);
+    parallel_for((size_t)n, [&](size_t i) {
+        const sequence_t &seq = sequences.at(order[i]);
+        seq_len[i] = (double)seq.size();
+        angle_count_row(a, seq, ncols, counts.data() + i * ncols);
+    });
+    Backend &be = default_backend();
+    const auto t0 = std::chrono::steady_clock::now();
+    ++be.calls_dist;
+    be.kmer_cosine(n, ncols, counts.data(), distances.distances.data());   // :100
+    be.seconds_mldist += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    angle_finish(distances, seq_len, true);
     dump_distances(distances);
     return distances;
 }
@@ -1125,6 +1152,302 @@ PhyTree *TreeNJ(const Alphabet &a, const std::map<std::string, sequence_t> &seqs
     PhyTree *tree = buildNJTree(order, dist);
     if (cmdlineopts.wlsrefine_flag) tree = refineTree(tree, order, dist);
     return midpointRoot(tree);
+}
+
+// ==== many families per call (--batch) ================================================================================
+// The defaults of the two multi-family entries: the per-family entries, one family after the other (a backend without segmented
+// kernels of its own: the CPU oracle).
+void Backend::kmer_cosine_multi(uint32_t nfam, const uint32_t *nseq, uint32_t ncols, const int32_t *counts, double *cosine, int worker) {
+    size_t row0 = 0, out0 = 0;
+    for (uint32_t f = 0; f < nfam; ++f) {
+        kmer_cosine(nseq[f], ncols, counts + row0 * ncols, cosine + out0, worker);
+        row0 += nseq[f];
+        out0 += (size_t)nseq[f] * nseq[f];
+    }
+}
+
+bool Backend::prealigned_counts_multi(uint32_t dim, uint32_t nfam, const uint32_t *nrows, const uint32_t *ncols, const int8_t *rows, uint32_t npairs,
+                                      const uint32_t *fam, const uint32_t *pi, const uint32_t *pj, int32_t *counts, uint32_t *gaps, int worker) {
+    std::vector<size_t> base(nfam + 1, 0);
+    for (uint32_t f = 0; f < nfam; ++f) base[f + 1] = base[f] + (size_t)nrows[f] * ncols[f];
+    std::vector<std::vector<uint32_t>> of_family(nfam);
+    for (uint32_t p = 0; p < npairs; ++p) of_family[fam[p]].push_back(p);
+    const size_t dd = (size_t)dim * dim;
+    for (uint32_t f = 0; f < nfam; ++f) {
+        const std::vector<uint32_t> &mine = of_family[f];
+        if (mine.empty()) continue;
+        const uint32_t m = (uint32_t)mine.size();
+        std::vector<uint32_t> qi(m), qj(m), g(m, 0);
+        std::vector<int32_t> c((size_t)m * dd, 0);
+        for (uint32_t k = 0; k < m; ++k) { qi[k] = pi[mine[k]]; qj[k] = pj[mine[k]]; }
+        if (!prealigned_counts_batch(dim, nrows[f], ncols[f], rows + base[f], m, qi.data(), qj.data(), c.data(), g.data(), worker)) return false;
+        for (uint32_t k = 0; k < m; ++k) {
+            std::copy(c.begin() + (std::ptrdiff_t)(k * dd), c.begin() + (std::ptrdiff_t)((k + 1) * dd), counts + (size_t)mine[k] * dd);
+            gaps[mine[k]] = g[k];
+        }
+    }
+    return true;
+}
+
+namespace {
+// the pairs [p0, p0 + np) of a chunk's shared pair arrays are those of one family
+struct PairBlock {
+    const DistanceFactoryML *df;
+    const ModelFactory *model_factory;
+    size_t p0;
+    uint32_t np;
+    DistanceMatrix *out;
+};
+}  // namespace
+
+// DistanceFactoryML::computeDistances for the families of a chunk.  On the device (PGM_DEVICE_MLDIST): one call over the pairs of all
+// families that share a model — every family without -F, one call per family with it.  On the host: the pairs of all families dealt
+// to the host threads; every pair's arithmetic is computeDistance's.
+static void compute_distances_multi(const Alphabet &a, const std::vector<PairBlock> &blocks, const int32_t *counts, const uint32_t *gaps,
+                                    const double *seqlen, const uint32_t *pi, const uint32_t *pj) {
+    if (blocks.empty()) return;
+    const uint32_t D = (uint32_t)a.DIM;
+    const size_t dd = (size_t)D * D;
+    Backend &be = default_backend();
+    const auto t1 = std::chrono::steady_clock::now();
+    bool eigen = true;
+    for (const PairBlock &b : blocks) eigen = eigen && b.model_factory->has_eigen();
+    bool done = false;
+    if (host_switches().device_mldist && eigen && D <= 20) {
+        double DIST_MAX, VAR_MAX, VAR_MIN;
+        consts(a, DIST_MAX, VAR_MAX, VAR_MIN);
+        done = true;
+        for (size_t b0 = 0; b0 < blocks.size() && done;) {
+            const size_t b1 = cmdlineopts.aafreqs_flag ? b0 + 1 : blocks.size();   // (the blocks are contiguous in the pair arrays)
+            const ModelFactory *mf = blocks[b0].model_factory;
+            const size_t p0 = blocks[b0].p0, p1 = blocks[b1 - 1].p0 + blocks[b1 - 1].np;
+            pgm_mldist_model m;
+            m.dim = D; m.Q = mf->Qmat().data(); m.V = mf->eigV().data(); m.Vi = mf->eigVi().data(); m.sigma = mf->eigSigma().data();
+            m.dist_max = DIST_MAX; m.var_max = VAR_MAX; m.var_min = VAR_MIN; m.cutoff_dist = cmdlineopts.cutoff_dist;
+            m.min_dist = cmdlineopts.min_dist; m.max_dist = cmdlineopts.max_dist; m.indel_rate = cmdlineopts.indel_rate;
+            m.mldist = cmdlineopts.mldist_flag ? 1 : 0; m.mldist_gap = cmdlineopts.mldist_gap_flag ? 1 : 0;
+            std::vector<double> dist(p1 - p0), var(p1 - p0);
+            if (p1 > p0) {
+                ++be.calls_dist;
+                done = be.mldist_batch(m, (uint32_t)(p1 - p0), counts + p0 * dd, gaps + p0, seqlen + p0, dist.data(), var.data());
+            }
+            for (size_t b = b0; b < b1 && done; ++b)
+                for (size_t p = blocks[b].p0; p < blocks[b].p0 + blocks[b].np; ++p) {
+                    DistanceMatrix &dm = *blocks[b].out;
+                    dm.D(pi[p], pj[p]) = dm.D(pj[p], pi[p]) = dist[p - p0];
+                    dm.V(pi[p], pj[p]) = dm.V(pj[p], pi[p]) = var[p - p0];
+                }
+            b0 = b1;
+        }
+    }
+    if (!done) {
+        std::vector<std::pair<uint32_t, uint32_t>> work;   // (block, pair of the block)
+        for (size_t b = 0; b < blocks.size(); ++b)
+            for (uint32_t k = 0; k < blocks[b].np; ++k) work.emplace_back((uint32_t)b, k);
+        const size_t grain = 16;   // pairs per index handed out
+        parallel_for((work.size() + grain - 1) / grain, [&](size_t g) {
+            std::vector<int32_t> c(dd);
+            for (size_t q = g * grain; q < std::min(work.size(), (g + 1) * grain); ++q) {
+                const PairBlock &b = blocks[work[q].first];
+                const size_t p = b.p0 + work[q].second;
+                std::copy(counts + p * dd, counts + (p + 1) * dd, c.begin());
+                const distvar_t dv = b.df->computeDistance(c, gaps[p], seqlen[p]);
+                b.out->D(pi[p], pj[p]) = b.out->D(pj[p], pi[p]) = dv.dist;
+                b.out->V(pi[p], pj[p]) = b.out->V(pj[p], pi[p]) = dv.var;
+            }
+        });
+    }
+    be.seconds_mldist += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+}
+
+void TreeNJ_multi(const Alphabet &a, std::vector<TreeJob> &jobs, bool prealigned) {
+    std::vector<size_t> act;
+    for (size_t j = 0; j < jobs.size(); ++j) {
+        jobs[j].tree = nullptr;
+        jobs[j].error.clear();
+        if (jobs[j].seqs->size() < 2) { jobs[j].error = "cannot construct tree from < 2 sequences"; continue; }
+        if (prealigned) {
+            const size_t L = jobs[j].seqs->begin()->second.size();
+            bool same = true;
+            for (const auto &kv : *jobs[j].seqs) same = same && kv.second.size() == L;
+            if (!same) { jobs[j].error = "prealigned distances: rows of different length"; continue; }
+        }
+        act.push_back(j);
+    }
+    if (act.empty()) return;
+    Backend &be = default_backend();
+    const uint32_t nfam = (uint32_t)act.size(), D = (uint32_t)a.DIM;
+    const size_t dd = (size_t)D * D;
+    std::vector<std::vector<std::string>> order(nfam);   // std::map key order (TreeNJ.h:34-39)
+    std::vector<std::vector<const sequence_t *>> seq(nfam);
+    std::vector<DistanceMatrix> dist;
+    dist.reserve(nfam);
+    std::vector<uint32_t> nseq(nfam);
+    for (uint32_t f = 0; f < nfam; ++f) {
+        for (const auto &kv : *jobs[act[f]].seqs) { order[f].push_back(kv.first); seq[f].push_back(&kv.second); }
+        nseq[f] = (uint32_t)order[f].size();
+        dist.emplace_back((int)nseq[f]);
+    }
+    std::vector<DistanceFactoryML> dfml;
+    dfml.reserve(nfam);
+    for (uint32_t f = 0; f < nfam; ++f) dfml.emplace_back(a, jobs[act[f]].model_factory);
+    // the pairs i < j of every family, the families one after the other
+    std::vector<uint32_t> pfam, pi, pj;
+    std::vector<PairBlock> blocks(nfam);
+    auto all_pairs = [&](const std::function<void(uint32_t, std::vector<std::pair<uint32_t, uint32_t>> &)> &arrange) {
+        for (uint32_t f = 0; f < nfam; ++f) {
+            std::vector<std::pair<uint32_t, uint32_t>> pr;
+            for (uint32_t i = 0; i < nseq[f]; ++i)
+                for (uint32_t j = i + 1; j < nseq[f]; ++j) pr.push_back({i, j});
+            arrange(f, pr);
+            blocks[f] = PairBlock{&dfml[f], jobs[act[f]].model_factory, pi.size(), (uint32_t)pr.size(), &dist[f]};
+            for (const auto &p : pr) { pfam.push_back(f); pi.push_back(p.first); pj.push_back(p.second); }
+        }
+    };
+    bool solo = false;   // a stage this call cannot share: every family through TreeNJ alone
+    if (prealigned) {
+        if (host_switches().host_counts) solo = true;
+        else {
+            all_pairs([](uint32_t, std::vector<std::pair<uint32_t, uint32_t>> &) {});
+            const uint32_t np = (uint32_t)pi.size();
+            std::vector<uint32_t> ncols(nfam);
+            std::vector<size_t> base(nfam + 1, 0);
+            for (uint32_t f = 0; f < nfam; ++f) { ncols[f] = (uint32_t)seq[f][0]->size(); base[f + 1] = base[f] + (size_t)nseq[f] * ncols[f]; }
+            std::vector<int8_t> mat(base[nfam]);
+            parallel_for(nfam, [&](size_t f) {
+                for (uint32_t i = 0; i < nseq[f]; ++i) prealigned_row(a, *seq[f][i], mat.data() + base[f] + (size_t)i * ncols[f]);
+            });
+            // (the entry point takes 20 to 64 states: DNA rows are counted as 20-state rows and the 4 x 4 corner is kept)
+            const uint32_t Dk = std::max<uint32_t>(D, 20u);
+            std::vector<int32_t> counts((size_t)np * dd, 0), wide(Dk != D ? (size_t)np * Dk * Dk : 0, 0);
+            std::vector<uint32_t> gaps(np, 0);
+            const auto t0 = std::chrono::steady_clock::now();
+            ++be.calls_dist;
+            const bool done = be.prealigned_counts_multi(Dk, nfam, nseq.data(), ncols.data(), mat.data(), np, pfam.data(), pi.data(), pj.data(),
+                                                         Dk != D ? wide.data() : counts.data(), gaps.data());
+            be.seconds_mldist += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            if (!done) solo = true;
+            else {
+                if (Dk != D)
+                    for (size_t p = 0; p < np; ++p)
+                        for (uint32_t b = 0; b < D; ++b)
+                            for (uint32_t c = 0; c < D; ++c) counts[p * dd + c + (size_t)D * b] = wide[p * Dk * Dk + c + (size_t)Dk * b];
+                std::vector<double> seqlen(np);
+                for (size_t p = 0; p < np; ++p) seqlen[p] = ((double)ncols[pfam[p]] + (double)ncols[pfam[p]]) / 2.0;
+                compute_distances_multi(a, blocks, counts.data(), gaps.data(), seqlen.data(), pi.data(), pj.data());
+            }
+        }
+    } else if (!cmdlineopts.nwdist_flag) {
+        // the k-mer angle distances: the count rows of all families back to back, one cosine call
+        const uint32_t ncols = angle_ncols(a);
+        std::vector<size_t> row0(nfam + 1, 0), out0(nfam + 1, 0);
+        for (uint32_t f = 0; f < nfam; ++f) { row0[f + 1] = row0[f] + nseq[f]; out0[f + 1] = out0[f] + (size_t)nseq[f] * nseq[f]; }
+        std::vector<int32_t> counts(row0[nfam] * ncols, 0);
+        std::vector<double> cosine(out0[nfam], 0.0);
+        parallel_for(nfam, [&](size_t f) {
+            for (uint32_t i = 0; i < nseq[f]; ++i) angle_count_row(a, *seq[f][i], ncols, counts.data() + (row0[f] + i) * ncols);
+        });
+        const auto t0 = std::chrono::steady_clock::now();
+        ++be.calls_dist;
+        be.kmer_cosine_multi(nfam, nseq.data(), ncols, counts.data(), cosine.data());
+        be.seconds_mldist += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        parallel_for(nfam, [&](size_t f) {
+            std::copy(cosine.begin() + (std::ptrdiff_t)out0[f], cosine.begin() + (std::ptrdiff_t)out0[f + 1], dist[f].distances.begin());
+            std::vector<double> seq_len(nseq[f]);
+            for (uint32_t i = 0; i < nseq[f]; ++i) seq_len[i] = (double)seq[f][i]->size();
+            angle_finish(dist[f], seq_len, false);
+        });
+    } else {
+        // -a: one farm of alignPair tiles over the sequences of all families, within-family pairs only
+        DistanceFactoryAlign dfa(a, jobs[act[0]].model_factory);   // (the scoring matrix and the gap costs: the run's)
+        const int unknown_sym = a.kind == ALPHA_DNA ? (int)D : 20;
+        std::vector<int8_t> syms;
+        std::vector<uint32_t> offs{0};
+        std::vector<uint32_t> first(nfam);   // a family's first sequence among all
+        for (uint32_t f = 0; f < nfam; ++f) {
+            first[f] = (uint32_t)offs.size() - 1;
+            for (const sequence_t *sq : seq[f]) {
+                for (int8_t c : *sq) { const int v = a.value(c); syms.push_back((int8_t)(v < 0 ? unknown_sym : v)); }
+                offs.push_back((uint32_t)syms.size());
+            }
+        }
+        const uint32_t ntot = (uint32_t)offs.size() - 1;
+        auto len = [&](uint32_t f, uint32_t i) { return offs[first[f] + i + 1] - offs[first[f] + i]; };
+        all_pairs([&](uint32_t f, std::vector<std::pair<uint32_t, uint32_t>> &pr) {   // (longest first within the family, as alone)
+            auto cost = [&](const std::pair<uint32_t, uint32_t> &p) { return (uint64_t)len(f, p.first) * len(f, p.second); };
+            std::stable_sort(pr.begin(), pr.end(), [&](const std::pair<uint32_t, uint32_t> &x, const std::pair<uint32_t, uint32_t> &y) { return cost(x) > cost(y); });
+        });
+        const uint32_t np = (uint32_t)pi.size();
+        std::vector<uint32_t> gi(np), gj(np);   // the pairs by their sequences' places among all
+        for (uint32_t p = 0; p < np; ++p) { gi[p] = first[pfam[p]] + pi[p]; gj[p] = first[pfam[p]] + pj[p]; }
+        const bool reduced = !(cmdlineopts.mldist_flag || cmdlineopts.mldist_gap_flag);
+        const size_t per = reduced ? 2 : dd;
+        int32_t *counts = (int32_t *)be.host_alloc(std::max<size_t>(sizeof(int32_t) * (size_t)np * per, 16));
+        uint32_t *gaps = (uint32_t *)be.host_alloc(std::max<size_t>(4 * (size_t)np, 16));
+        for (uint32_t p = 0; p < np; ++p) be.cells_nw += (uint64_t)(offs[gi[p] + 1] - offs[gi[p]]) * (offs[gj[p] + 1] - offs[gj[p]]);
+        const auto t0 = std::chrono::steady_clock::now();
+        {
+            const int nw = std::max(1, be.workers());
+            uint32_t tile = std::max<uint32_t>(256u, (np + 3u * (uint32_t)nw - 1u) / (3u * (uint32_t)nw));   // (computePwDistances' rule)
+            if (const char *e = getenv("PGM_NW_TILE")) tile = (uint32_t)std::max(1, atoi(e));
+            const uint32_t ntiles = np ? (np + tile - 1) / tile : 0;
+            std::atomic<uint32_t> next_tile(0);
+            std::vector<std::string> errs((size_t)nw);
+            auto farm = [&](int w) {
+                try {
+                    int pending = -1;
+                    for (;;) {
+                        const uint32_t t = next_tile.fetch_add(1);
+                        if (t >= ntiles) break;
+                        const uint32_t p0 = t * tile, cnt = std::min(tile, np - p0);
+                        ++be.calls_dist;
+                        const int ticket = be.nw_pairs_submit(D, dfa.scoring_matrix().data(), dfa.gap_open, dfa.gap_extend, ntot, syms.data(), offs.data(), cnt,
+                                                              gi.data() + p0, gj.data() + p0, reduced ? 1u : 0u, counts + (size_t)p0 * per, gaps + p0, w);
+                        if (pending >= 0) be.nw_pairs_wait(pending, w);
+                        pending = ticket;
+                    }
+                    if (pending >= 0) be.nw_pairs_wait(pending, w);
+                } catch (std::exception &e) { errs[(size_t)w] = e.what(); }
+            };
+            std::vector<std::thread> devs;
+            for (int w = 1; w < nw; ++w) devs.emplace_back(farm, w);
+            farm(0);
+            for (auto &th : devs) th.join();
+            be.farm_workers = nw; be.farm_tiles = (int)ntiles;
+            for (const std::string &e : errs) if (!e.empty()) { be.host_free(counts); be.host_free(gaps); throw pgm_exception(e); }
+        }
+        be.seconds_nw += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        std::vector<double> seqlen(np);
+        for (uint32_t p = 0; p < np; ++p) seqlen[p] = ((double)(offs[gi[p] + 1] - offs[gi[p]]) + (double)(offs[gj[p] + 1] - offs[gj[p]])) / 2.0;
+        if (reduced) {
+            for (uint32_t p = 0; p < np; ++p) {
+                const distvar_t dv = dfml[pfam[p]].computeDistance((double)counts[2 * (size_t)p], (double)counts[2 * (size_t)p + 1], nullptr, gaps[p], seqlen[p]);
+                DistanceMatrix &dm = dist[pfam[p]];
+                dm.D(pi[p], pj[p]) = dm.D(pj[p], pi[p]) = dv.dist;
+                dm.V(pi[p], pj[p]) = dm.V(pj[p], pi[p]) = dv.var;
+            }
+        } else {
+            compute_distances_multi(a, blocks, counts, gaps, seqlen.data(), pi.data(), pj.data());
+        }
+        be.host_free(counts);
+        be.host_free(gaps);
+    }
+    if (solo) {   // (one after the other: the calls of a device context are serial)
+        for (size_t j : act) {
+            try { jobs[j].tree = TreeNJ(a, *jobs[j].seqs, jobs[j].model_factory, prealigned); }
+            catch (pgm_exception &e) { jobs[j].error = e.what(); }
+        }
+        return;
+    }
+    // BioNJ and the rooting: per family on the host threads
+    parallel_for(nfam, [&](size_t f) {
+        TreeJob &job = jobs[act[f]];
+        try {
+            DistanceMatrix &d = dist[f];
+            for (int i = 0; i < d.dim; ++i) { d.D(i, i) = 0; d.V(i, i) = 0; }
+            job.tree = midpointRoot(buildNJTree(order[f], d));
+        } catch (std::exception &e) { job.error = e.what(); }
+    });
 }
 
 }  // namespace pgm

@@ -201,6 +201,7 @@ std::vector<AlignmentResult> alignGraphsBatch(const std::vector<const Graph *> &
     size_t used = 0;
     for (const auto &sh : shards) used += !sh.empty();
     if (shards.size() <= 1) {
+        ++be.calls_align;
         be.align_graphs_batch(n, p1.data(), p2.data(), pm.data(), sc.data(), out.data(), 0, res1.empty() ? nullptr : res1.data(), res2.empty() ? nullptr : res2.data());
     } else if (worker_of) {
         farm_run(shards, [&](int w) {
@@ -216,6 +217,7 @@ std::vector<AlignmentResult> alignGraphsBatch(const std::vector<const Graph *> &
                 if (!res1.empty()) r1[k] = res1[sh[k]];
                 if (!res2.empty()) r2[k] = res2[sh[k]];
             }
+            ++be.calls_align;
             be.align_graphs_batch(m, q1.data(), q2.data(), qm.data(), qs.data(), qo.data(), w, r1.empty() ? nullptr : r1.data(), r2.empty() ? nullptr : r2.data());
             for (uint32_t k = 0; k < m; ++k) out[sh[k]] = qo[k];
         });
@@ -229,6 +231,7 @@ std::vector<AlignmentResult> alignGraphsBatch(const std::vector<const Graph *> &
             std::vector<pgm_scores> qs(m);
             std::vector<pgm_align_out> qo(m);
             for (uint32_t k = 0; k < m; ++k) { q1[k] = p1[sh[k]]; q2[k] = p2[sh[k]]; qm[k] = pm[sh[k]]; qs[k] = sc[sh[k]]; qo[k] = out[sh[k]]; }
+            ++be.calls_align;
             be.align_graphs_batch(m, q1.data(), q2.data(), qm.data(), qs.data(), qo.data(), w);
             for (uint32_t k = 0; k < m; ++k) out[sh[k]] = qo[k];
         });

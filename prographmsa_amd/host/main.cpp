@@ -23,6 +23,13 @@ static void usage() {
                  "             [-s prob] [-A] [--early_refinement] [--ancestral_seqs] [--profile_out <file>] [-R] [--read_repeats <file>]\n"
                  "             [-r|--reroot [-r]] [-W|--wls_refine [-W]] [--dna] [--custom_model <file>] [-F|--estimate_aafreqs]\n"
                  "             [-C|--aafreqs_pseudocount <count>] [--dump_jobs <file>] [--dump_dist <file>] [--stats] <fasta file>\n"
+                 "       pgmsa --batch <list> [--batch_cells <cells>] [options]\n"
+                 "  --batch <list>  align many families in one run: every line of <list> is input.fa<TAB>output[<TAB>guide_tree.nwk] (blank\n"
+                 "                lines and lines starting with # are skipped); the other options apply to every family and every output is\n"
+                 "                what the same options write for that family alone.  Not with a positional file, -o, -t, -r, -W, -R,\n"
+                 "                --read_repeats, --profile_out, --dump_jobs, --dump_dist\n"
+                 "  --batch_cells <cells>  families share the device stages in chunks of at most this many estimated DP cells per pass\n"
+                 "                (default 2e9); a larger family is a chunk of its own\n"
                  "  --dna         align DNA sequences (T C A G; U reads as T; N, X and the IUPAC ambiguity codes as unknown); needs\n"
                  "                --custom_model\n"
                  "  --custom_model <file>  custom substitution model: the strict lower triangle of the symmetric exchangeability\n"
@@ -75,28 +82,104 @@ static std::string value_name(const Alphabet &a, int j) {   // ALPHABET(j).asStr
     return "?";
 }
 
-static int doAlign(const Alphabet &a, const std::map<std::string, std::string> &seqs,
-                   std::map<std::string, std::string> &out_aligned, PhyTree *&out_tree, bool stats) {
-    // strip start/stop (main.cpp:332-353)
+// What doAlign keeps for one family (main.cpp:332-482): the solo run is this state for one family, `--batch` walks the states of
+// a chunk of families through the same stages together.
+namespace {
+struct Family {
+    std::string input, output, tree_file;   // (--batch: the fields of the family's line of the list)
+    int iters = 0;
+    std::vector<std::string> input_order;
+    std::map<std::string, std::string> seqs;   // as read
     bool any_start = false, any_end = false;
     std::map<std::string, bool> startStripped, endStripped;
-    std::map<std::string, sequence_t> seqs2;
-    for (const auto &kv : seqs) {
-        sequence_t seq = sequenceFromString(a, kv.second);
-        if (!cmdlineopts.noforcealign_flag) {
-            if (!seq.empty() && a.stripsStart(seq[0])) { seq = seq.substr(1); any_start = true; startStripped[kv.first] = true; }
-            else startStripped[kv.first] = false;
-            if (!seq.empty() && a.stripsEnd(seq[seq.size() - 1])) { seq = seq.substr(0, seq.size() - 1); any_end = true; endStripped[kv.first] = true; }
-            else endStripped[kv.first] = false;
-        }
-        seqs2[kv.first] = seq;
-    }
-    std::unique_ptr<ModelFactory> model_factory(ModelFactory::getDefault(a, seqs2));
-    std::unique_ptr<CSProfile> csprofile;
-    if (!cmdlineopts.cs_file.empty()) csprofile.reset(new CSProfile(cmdlineopts.cs_file));
+    std::map<std::string, sequence_t> seqs2;   // start / stop stripped
+    std::unique_ptr<ModelFactory> model_factory;   // (per family: -F estimates the frequencies from the family's sequences)
+    PhyTree *tree = nullptr;
+    ProgressiveAlignmentResult result, old_result;
+    bool done = false;   // converged: takes no further part in the iterations
+    std::string failure;   // --batch: the message the solo run would have ended with
+    double cells = 0;    // --batch: estimated DP cells of one pass
+    int worker = 0;
+    std::map<std::string, std::string> aligned;
+    ~Family() { delete tree; }
 
-    // the device contexts (HIP runtime start-up, code object load) exist before the clocks of the stages start; init_s is the
-    // time their creation took (it ran beside the set-up above), init_wait_s what of it was left to wait for here
+    // strip start/stop (main.cpp:332-353) and set the models up
+    void prepare(const Alphabet &a) {
+        for (const auto &kv : seqs) {
+            sequence_t seq = sequenceFromString(a, kv.second);
+            if (!cmdlineopts.noforcealign_flag) {
+                if (!seq.empty() && a.stripsStart(seq[0])) { seq = seq.substr(1); any_start = true; startStripped[kv.first] = true; }
+                else startStripped[kv.first] = false;
+                if (!seq.empty() && a.stripsEnd(seq[seq.size() - 1])) { seq = seq.substr(0, seq.size() - 1); any_end = true; endStripped[kv.first] = true; }
+                else endStripped[kv.first] = false;
+            }
+            seqs2[kv.first] = seq;
+        }
+        model_factory.reset(ModelFactory::getDefault(a, seqs2));
+    }
+    void read_tree() {
+        std::ifstream ts(tree_file.c_str());
+        if (!ts) error("cannot open tree file %s", tree_file.c_str());
+        tree = parse_newick(ts);
+    }
+    void drop_ancestral_rows() {
+        for (auto it = result.aligned_sequences.begin(); it != result.aligned_sequences.end();)   // ancestral sequences
+            if (!it->first.empty() && it->first[0] == '(') it = result.aligned_sequences.erase(it); else ++it;
+    }
+    // re-insert start/stop (main.cpp:459-482)
+    void finish(const Alphabet &a) {
+        for (auto &kv : result.aligned_sequences) {
+            sequence_t aseq = kv.second;
+            if (any_start) aseq.insert(aseq.begin(), startStripped[kv.first] ? a.unknown() : a.gap());
+            if (any_end) aseq.insert(aseq.end(), endStripped[kv.first] ? a.unknown() : a.gap());
+            aligned[kv.first] = seqs.count(kv.first) ? stringFromSequence(a, aseq, seqs.at(kv.first)) : stringFromSequence(a, aseq);   // (ancestral rows have no original)
+        }
+    }
+    void write(std::ostream &out) const {
+        if (!cmdlineopts.onlytree_flag) {
+            std::vector<std::string> order = input_order;
+            if (!cmdlineopts.inputorder_flag) order = get_tree_order(tree);
+            write_fasta(aligned, order, out);
+        } else {
+            out << tree->formatNewick() << std::endl;
+        }
+    }
+};
+
+struct BatchRun { int families = 0, failed = 0, chunks = 0; };
+}  // namespace
+
+static void print_stats(double t_init, double t_tree, double t_prog, const BatchRun *batch) {
+    Backend &be = default_backend();
+    fprintf(stderr,
+            "{\"backend\": \"%s\", \"init_s\": %.6f, \"tree_s\": %.6f, \"progressive_s\": %.6f, \"align_cells\": %llu, \"align_s\": %.6f, "
+            "\"nw_cells\": %llu, \"nw_s\": %.6f, \"mldist_s\": %.6f, \"merge_profiles_s\": %.6f, \"farm_workers\": %d, \"farm_tiles\": %d, \"farm_level_workers\": %d, \"farm_leaf_workers\": %d, \"resident\": %s, \"resident_imports\": %d, \"switches\": \"%s\"",
+            be.name(), t_init, t_tree, t_prog, (unsigned long long)be.cells_aligned, be.seconds_align,
+            (unsigned long long)be.cells_nw, be.seconds_nw, be.seconds_mldist, be.seconds_merge_profiles, be.farm_workers, be.farm_tiles, be.farm_level_workers, be.farm_leaf_workers, be.resident_pass ? "true" : "false", be.resident_imports, host_switches().describe().c_str());
+    if (cmdlineopts.reroot_flag) {   // (keys of the root search only when it ran)
+        const RootSearchStats &r = root_search_stats;
+        fprintf(stderr, ", \"reroot\": %d, \"reroot_merges\": %d, \"reroot_candidates\": %d, \"reroot_heights\": %d, \"reroot_batches\": %d, "
+                        "\"reroot_align_s\": %.6f, \"reroot_host_merge_s\": %.6f, \"reroot_gapmask_s\": %.6f, \"reroot_parsimony_s\": %.6f, \"reroot_rows_s\": %.6f",
+                cmdlineopts.reroot_flag, r.merges, r.candidates, r.heights, r.batches, r.align_s, r.host_merge_s, r.gapmask_s, r.parsimony_s, r.select_s);
+    }
+    if (cmdlineopts.wlsrefine_flag) {   // (keys of the refinement only when it ran)
+        const WlsStats &w = wls_stats;
+        fprintf(stderr, ", \"wls_refine\": %d, \"wls_trees\": %d, \"wls_s\": %.6f, \"wls_pair_sums_s\": %.6f, \"wls_kernels_s\": %.6f, \"wls_sweeps\": %d, "
+                        "\"wls_quartets\": %llu, \"wls_quintets\": %llu, \"wls_batches\": %llu, \"wls_launches\": %llu",
+                cmdlineopts.wlsrefine_flag, w.trees, w.seconds, w.pair_sums_s, be.seconds_wls_kernels, w.sweeps, (unsigned long long)w.quartets,
+                (unsigned long long)w.quintets, (unsigned long long)w.batches, (unsigned long long)be.wls_launches);
+    }
+    if (batch)   // (keys of --batch only)
+        fprintf(stderr, ", \"batch_families\": %d, \"batch_failed\": %d, \"batch_chunks\": %d, \"batch_passes\": %llu, \"batch_levels\": %llu, "
+                        "\"batch_align_calls\": %llu, \"batch_dist_calls\": %llu",
+                batch->families, batch->failed, batch->chunks, (unsigned long long)batch_stats.passes, (unsigned long long)batch_stats.levels,
+                (unsigned long long)be.calls_align.load(), (unsigned long long)be.calls_dist.load());
+    fprintf(stderr, "}\n");
+}
+
+// the device contexts (HIP runtime start-up, code object load) exist before the clocks of the stages start; init_s is the
+// time their creation took (it ran beside the set-up), init_wait_s what of it was left to wait for here
+static double wait_for_backend(const CSProfile *csprofile) {
     auto t0 = std::chrono::steady_clock::now();
     g_startup.wait();
     default_backend();
@@ -110,48 +193,43 @@ static int doAlign(const Alphabet &a, const std::map<std::string, std::string> &
     if (host_switches().profile)
         fprintf(stderr, "backend start-up %.1f ms, of which %.1f ms waited for after the set-up\n", t_init * 1e3,
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    return t_init;
+}
+
+static int doAlign(const Alphabet &a, Family &fam, bool stats) {
+    fam.prepare(a);
+    std::unique_ptr<CSProfile> csprofile;
+    if (!cmdlineopts.cs_file.empty()) csprofile.reset(new CSProfile(cmdlineopts.cs_file));
+    const double t_init = wait_for_backend(csprofile.get());
     std::map<std::string, std::vector<repeat_t>> reps;   // main.cpp:367-370 (detection by T-REKS itself is not built here: --read_repeats only)
-    if (!cmdlineopts.readreps_file.empty()) reps = read_repeats(a, cmdlineopts.readreps_file, seqs2);
-    PhyTree *tree = nullptr;
-    t0 = std::chrono::steady_clock::now();
-    if (!cmdlineopts.tree_file.empty()) {
-        std::ifstream ts(cmdlineopts.tree_file.c_str());
-        if (!ts) error("cannot open tree file %s", cmdlineopts.tree_file.c_str());
-        tree = parse_newick(ts);
-    } else {
-        tree = TreeNJ(a, seqs2, model_factory.get());
-    }
+    if (!cmdlineopts.readreps_file.empty()) reps = read_repeats(a, cmdlineopts.readreps_file, fam.seqs2);
+    auto t0 = std::chrono::steady_clock::now();
+    if (!fam.tree_file.empty()) fam.read_tree();
+    else fam.tree = TreeNJ(a, fam.seqs2, fam.model_factory.get());
     double t_tree = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    ProgressiveAlignmentResult result, old_result;
+    ProgressiveAlignmentResult &result = fam.result;
     t0 = std::chrono::steady_clock::now();
     // further rounds of alignment followed by estimation of an improved tree from the induced pairwise distances
     // (main.cpp:404-430; the default is two such rounds when no tree is given)
-    for (int i = 0; i < cmdlineopts.iters; ++i) {
-        result = progressive_alignment(a, seqs2, *tree, csprofile.get(), *model_factory, &reps);
-        for (auto it = result.aligned_sequences.begin(); it != result.aligned_sequences.end();)   // ancestral sequences
-            if (!it->first.empty() && it->first[0] == '(') it = result.aligned_sequences.erase(it); else ++it;
-        if (i > 0 && result.aligned_sequences == old_result.aligned_sequences) break;   // converged
-        delete tree;
+    for (int i = 0; i < fam.iters; ++i) {
+        result = progressive_alignment(a, fam.seqs2, *fam.tree, csprofile.get(), *fam.model_factory, &reps);
+        fam.drop_ancestral_rows();
+        if (i > 0 && result.aligned_sequences == fam.old_result.aligned_sequences) break;   // converged
+        delete fam.tree;
+        fam.tree = nullptr;
         const auto tt0 = std::chrono::steady_clock::now();
-        tree = TreeNJ(a, result.aligned_sequences, model_factory.get(), true);
+        fam.tree = TreeNJ(a, result.aligned_sequences, fam.model_factory.get(), true);
         if (host_switches().profile) fprintf(stderr, "guide tree from the alignment: %.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tt0).count());
-        old_result = result;
+        fam.old_result = result;
     }
     // the final alignment (main.cpp:433-440): with -r the guide tree rerooted on the branch of the lowest gap parsimony
     if (!cmdlineopts.onlytree_flag)
-        result = cmdlineopts.reroot_flag ? progressive_alignment_find_root(a, seqs2, *tree, *model_factory, &reps)
-                                         : progressive_alignment(a, seqs2, *tree, csprofile.get(), *model_factory, &reps);
+        result = cmdlineopts.reroot_flag ? progressive_alignment_find_root(a, fam.seqs2, *fam.tree, *fam.model_factory, &reps)
+                                         : progressive_alignment(a, fam.seqs2, *fam.tree, csprofile.get(), *fam.model_factory, &reps);
     if (host_switches().profile) fprintf(stderr, "[%.1f ms] back in main\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     double t_prog = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    out_tree = tree;
 
-    // re-insert start/stop (main.cpp:459-482)
-    for (auto &kv : result.aligned_sequences) {
-        sequence_t aseq = kv.second;
-        if (any_start) aseq.insert(aseq.begin(), startStripped[kv.first] ? a.unknown() : a.gap());
-        if (any_end) aseq.insert(aseq.end(), endStripped[kv.first] ? a.unknown() : a.gap());
-        out_aligned[kv.first] = seqs.count(kv.first) ? stringFromSequence(a, aseq, seqs.at(kv.first)) : stringFromSequence(a, aseq);   // (ancestral rows have no original)
-    }
+    fam.finish(a);
     if (cmdlineopts.repeats_flag) {
         if (cmdlineopts.readreps_file.empty()) error("-R: tandem-repeat detection (T-REKS, a Java program) is not built here; supply the repeats with --read_repeats");
         std::cerr << "TR indels: " << result.n_tr_indels << std::endl;   // main.cpp:447-449
@@ -167,29 +245,176 @@ static int doAlign(const Alphabet &a, const std::map<std::string, std::string> &
             }
         }
     }
-    if (stats) {
-        Backend &be = default_backend();
-        fprintf(stderr,
-                "{\"backend\": \"%s\", \"init_s\": %.6f, \"tree_s\": %.6f, \"progressive_s\": %.6f, \"align_cells\": %llu, \"align_s\": %.6f, "
-                "\"nw_cells\": %llu, \"nw_s\": %.6f, \"mldist_s\": %.6f, \"merge_profiles_s\": %.6f, \"farm_workers\": %d, \"farm_tiles\": %d, \"farm_level_workers\": %d, \"farm_leaf_workers\": %d, \"resident\": %s, \"resident_imports\": %d, \"switches\": \"%s\"",
-                be.name(), t_init, t_tree, t_prog, (unsigned long long)be.cells_aligned, be.seconds_align,
-                (unsigned long long)be.cells_nw, be.seconds_nw, be.seconds_mldist, be.seconds_merge_profiles, be.farm_workers, be.farm_tiles, be.farm_level_workers, be.farm_leaf_workers, be.resident_pass ? "true" : "false", be.resident_imports, host_switches().describe().c_str());
-        if (cmdlineopts.reroot_flag) {   // (keys of the root search only when it ran)
-            const RootSearchStats &r = root_search_stats;
-            fprintf(stderr, ", \"reroot\": %d, \"reroot_merges\": %d, \"reroot_candidates\": %d, \"reroot_heights\": %d, \"reroot_batches\": %d, "
-                            "\"reroot_align_s\": %.6f, \"reroot_host_merge_s\": %.6f, \"reroot_gapmask_s\": %.6f, \"reroot_parsimony_s\": %.6f, \"reroot_rows_s\": %.6f",
-                    cmdlineopts.reroot_flag, r.merges, r.candidates, r.heights, r.batches, r.align_s, r.host_merge_s, r.gapmask_s, r.parsimony_s, r.select_s);
-        }
-        if (cmdlineopts.wlsrefine_flag) {   // (keys of the refinement only when it ran)
-            const WlsStats &w = wls_stats;
-            fprintf(stderr, ", \"wls_refine\": %d, \"wls_trees\": %d, \"wls_s\": %.6f, \"wls_pair_sums_s\": %.6f, \"wls_kernels_s\": %.6f, \"wls_sweeps\": %d, "
-                            "\"wls_quartets\": %llu, \"wls_quintets\": %llu, \"wls_batches\": %llu, \"wls_launches\": %llu",
-                    cmdlineopts.wlsrefine_flag, w.trees, w.seconds, w.pair_sums_s, be.seconds_wls_kernels, w.sweeps, (unsigned long long)w.quartets,
-                    (unsigned long long)w.quintets, (unsigned long long)w.batches, (unsigned long long)be.wls_launches);
-        }
-        fprintf(stderr, "}\n");
-    }
+    if (stats) print_stats(t_init, t_tree, t_prog, nullptr);
     return 0;
+}
+
+// ---- --batch ----------------------------------------------------------------------------------------------------------
+// Estimated DP cells of one pass over a family: the sum over the internal nodes of its tree of (residues below the left child) x
+// (residues below the right child) — an over-estimate that needs no alignment —, (N - 1) x (mean length)^2 before a tree exists.
+static double subtree_cells(const PhyTree &t, const std::map<std::string, sequence_t> &seqs, double &cells) {
+    if (t.isLeaf()) { auto it = seqs.find(t.getName()); return it == seqs.end() ? 0.0 : (double)it->second.size(); }
+    std::vector<double> below;
+    double sum = 0;
+    for (index_t c = 0; c < t.n_children(); ++c) { below.push_back(subtree_cells(t[(int)c], seqs, cells)); sum += below.back(); }
+    if (below.size() == 2) cells += below[0] * below[1];
+    return sum;
+}
+static double estimate_cells(const Family &fam) {
+    double cells = 0;
+    if (fam.tree) { subtree_cells(*fam.tree, fam.seqs2, cells); return cells; }
+    if (fam.seqs2.empty()) return 0;
+    double total = 0;
+    for (const auto &kv : fam.seqs2) total += (double)kv.second.size();
+    const double mean = total / (double)fam.seqs2.size();
+    return ((double)fam.seqs2.size() - 1.0) * mean * mean;
+}
+
+// One forest pass over the families of `act`; a family the pass refuses gets its message and leaves the run.
+static void forest_pass(const Alphabet &a, const std::vector<Family *> &act, const CSProfile *csprofile) {
+    std::vector<ForestFamily> ff(act.size());
+    for (size_t k = 0; k < act.size(); ++k) {
+        ff[k].sequences = &act[k]->seqs2; ff[k].tree = act[k]->tree; ff[k].model_factory = act[k]->model_factory.get();
+        ff[k].result = &act[k]->result; ff[k].worker = act[k]->worker;
+    }
+    progressive_alignment_forest(a, ff, csprofile);
+    for (size_t k = 0; k < act.size(); ++k) if (!ff[k].error.empty()) act[k]->failure = ff[k].error;
+}
+static void trees_for(const Alphabet &a, const std::vector<Family *> &act, bool prealigned) {
+    std::vector<TreeJob> jobs(act.size());
+    for (size_t k = 0; k < act.size(); ++k) {
+        jobs[k].seqs = prealigned ? &act[k]->result.aligned_sequences : &act[k]->seqs2;
+        jobs[k].model_factory = act[k]->model_factory.get();
+    }
+    TreeNJ_multi(a, jobs, prealigned);
+    for (size_t k = 0; k < act.size(); ++k) {
+        if (!jobs[k].error.empty()) act[k]->failure = jobs[k].error;
+        else act[k]->tree = jobs[k].tree;
+    }
+}
+static std::vector<Family *> alive(const std::vector<Family *> &v) {
+    std::vector<Family *> out;
+    for (Family *f : v) if (f->failure.empty()) out.push_back(f);
+    return out;
+}
+
+// The families of a chunk through the stages of doAlign in lock-step: every device stage once for all of them.
+static void run_chunk(const Alphabet &a, const std::vector<Family *> &chunk, const CSProfile *csprofile) {
+    {   // the families dealt to the device contexts, longest first (a family never spans contexts)
+        std::vector<uint64_t> cost(chunk.size());
+        for (size_t k = 0; k < chunk.size(); ++k) cost[k] = (uint64_t)chunk[k]->cells + 1u;
+        const std::vector<std::vector<uint32_t>> shards = farm_shards(cost, default_backend().workers());
+        for (size_t w = 0; w < shards.size(); ++w) for (uint32_t k : shards[w]) chunk[k]->worker = (int)w;
+    }
+    // 1. initial trees
+    std::vector<Family *> need;
+    for (Family *f : chunk) if (!f->tree) need.push_back(f);
+    if (!need.empty()) trees_for(a, need, false);
+    // 2. rounds of alignment followed by a tree from the alignment (main.cpp:404-430), per family as far as its own loop goes
+    int max_iters = 0;
+    for (Family *f : chunk) max_iters = std::max(max_iters, f->iters);
+    for (int i = 0; i < max_iters; ++i) {
+        std::vector<Family *> act;
+        for (Family *f : chunk) if (f->failure.empty() && !f->done && i < f->iters) act.push_back(f);
+        if (act.empty()) break;
+        forest_pass(a, act, csprofile);
+        act = alive(act);
+        std::vector<Family *> go_on;
+        for (Family *f : act) {
+            f->drop_ancestral_rows();
+            if (i > 0 && f->result.aligned_sequences == f->old_result.aligned_sequences) { f->done = true; continue; }   // converged
+            delete f->tree;
+            f->tree = nullptr;
+            go_on.push_back(f);
+        }
+        if (!go_on.empty()) trees_for(a, go_on, true);
+        for (Family *f : alive(go_on)) f->old_result = f->result;
+    }
+    // 3. the final alignment
+    if (!cmdlineopts.onlytree_flag) forest_pass(a, alive(chunk), csprofile);
+}
+
+static int doBatch(const Alphabet &a, const std::string &list_file, bool iters_set, double batch_cells, bool stats) {
+    std::vector<std::unique_ptr<Family>> fams;
+    {
+        std::ifstream in(list_file.c_str());
+        if (!in) error("cannot open the list of families %s", list_file.c_str());
+        std::string line;
+        for (int lineno = 1; std::getline(in, line); ++lineno) {
+            if (!line.empty() && line[line.size() - 1] == '\r') line.erase(line.size() - 1);
+            if (line.empty() || line[0] == '#') continue;
+            std::vector<std::string> field(1);
+            for (char c : line) { if (c == '\t') field.emplace_back(); else field.back() += c; }
+            bool blank = true;
+            for (char c : line) blank = blank && (c == '\t' || c == ' ');
+            if (blank) continue;
+            if (field.size() < 2 || field.size() > 3 || field[0].empty() || field[1].empty())
+                error("--batch: line %d of %s: expected input<TAB>output[<TAB>tree], found %zu field(s)", lineno, list_file.c_str(), field.size());
+            std::unique_ptr<Family> f(new Family);
+            f->input = field[0]; f->output = field[1];
+            if (field.size() == 3) f->tree_file = field[2];
+            f->iters = (!iters_set && !f->tree_file.empty()) ? 0 : cmdlineopts.iters;   // no iterations with a guide tree (main.cpp:243-246)
+            fams.push_back(std::move(f));
+        }
+    }
+    BatchRun run;
+    run.families = (int)fams.size();
+    g_startup.start();
+    parallel_for(64, [](size_t) {});   // (the driver's host threads start while the device runtime does)
+    std::unique_ptr<CSProfile> csprofile;
+    if (!cmdlineopts.cs_file.empty()) csprofile.reset(new CSProfile(cmdlineopts.cs_file));
+    parallel_for(fams.size(), [&](size_t k) {
+        Family &f = *fams[k];
+        try {
+            f.seqs = read_fasta(f.input, f.input_order);
+            f.prepare(a);
+            if (!f.tree_file.empty()) f.read_tree();
+            f.cells = estimate_cells(f);
+        } catch (std::exception &e) { f.failure = e.what(); }
+    });
+    const double t_init = wait_for_backend(csprofile.get());
+    const auto t0 = std::chrono::steady_clock::now();
+    auto report = [&](Family &f) {
+        std::cerr << "family " << f.input << ": ERROR:" << f.failure << std::endl;
+        ++run.failed;
+    };
+    // chunks: families in list order while the estimated cells of a pass stay within the bound; a larger family alone
+    std::vector<std::vector<Family *>> chunks;
+    {
+        double cells = 0;
+        for (auto &f : fams) {
+            if (!f->failure.empty()) continue;
+            if (chunks.empty() || (!chunks.back().empty() && cells + f->cells > batch_cells)) { chunks.emplace_back(); cells = 0; }
+            chunks.back().push_back(f.get());
+            cells += f->cells;
+        }
+    }
+    run.chunks = (int)chunks.size();
+    for (auto &f : fams) if (!f->failure.empty()) report(*f);
+    for (const std::vector<Family *> &chunk : chunks) {
+        try { run_chunk(a, chunk, csprofile.get()); }
+        catch (std::exception &e) { for (Family *f : chunk) if (f->failure.empty()) f->failure = e.what(); }   // (a stage all its families share)
+        const std::vector<Family *> ok = alive(chunk);
+        parallel_for(ok.size(), [&](size_t k) {
+            Family &f = *ok[k];
+            try {
+                f.finish(a);
+                std::ofstream out(f.output.c_str());
+                if (!out) error("error opening output file");
+                f.write(out);
+            } catch (std::exception &e) { f.failure = e.what(); }
+        });
+        for (Family *f : chunk) {
+            if (!f->failure.empty()) report(*f);
+            f->seqs.clear(); f->seqs2.clear(); f->aligned.clear();
+            f->result = ProgressiveAlignmentResult(); f->old_result = ProgressiveAlignmentResult();
+            delete f->tree; f->tree = nullptr;
+            f->model_factory.reset();
+        }
+    }
+    const double t_prog = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (stats) print_stats(t_init, 0.0, t_prog, &run);
+    return run.failed ? 2 : 0;
 }
 
 int main(int argc, char **argv) {
@@ -204,7 +429,8 @@ int main(int argc, char **argv) {
     }
     try {
         bool iters_set = false, stats = false, indel_set = false, edgehl_set = false, maxdist_set = false, cutdist_set = false;
-        std::string dump, dist_dump;
+        std::string dump, dist_dump, batch_list;
+        double batch_cells = 2e9;
         for (int i = 1; i < argc; ++i) {
             std::string s = argv[i];
             auto val = [&]() -> std::string { if (i + 1 >= argc) { usage(); exit(1); } return argv[++i]; };
@@ -242,6 +468,8 @@ int main(int argc, char **argv) {
             else if (s == "--dump_jobs") dump = val();
             else if (s == "--dump_dist") dist_dump = val();
             else if (s == "--stats") stats = true;
+            else if (s == "--batch") batch_list = val();
+            else if (s == "--batch_cells") batch_cells = atof(val().c_str());
             else if (s == "--reroot") ++cmdlineopts.reroot_flag;
             else if (s == "--wls_refine") ++cmdlineopts.wlsrefine_flag;
             else if (s.size() >= 2 && s[0] == '-' && s.find_first_not_of('W', 1) == std::string::npos) cmdlineopts.wlsrefine_flag += (int)s.size() - 1;   // -W, -WW
@@ -250,7 +478,16 @@ int main(int argc, char **argv) {
             else if (!s.empty() && s[0] == '-') { std::cerr << "Command line error: unknown flag " << s << std::endl; return 1; }
             else cmdlineopts.sequence_file = s;
         }
-        if (cmdlineopts.sequence_file.empty()) { usage(); return 1; }
+        if (!batch_list.empty()) {   // what belongs to one family or is a search loop of its own is refused
+            const char *refused = !cmdlineopts.sequence_file.empty() ? "a positional sequence file (the families come from the list)"
+                                  : !cmdlineopts.output_file.empty() ? "-o (every line of the list names its output)"
+                                  : !cmdlineopts.tree_file.empty() ? "-t (a guide tree is the third field of a family's line)"
+                                  : cmdlineopts.reroot_flag ? "-r" : cmdlineopts.wlsrefine_flag ? "-W"
+                                  : cmdlineopts.repeats_flag ? "-R" : !cmdlineopts.readreps_file.empty() ? "--read_repeats"
+                                  : !cmdlineopts.profile_file.empty() ? "--profile_out" : !dump.empty() ? "--dump_jobs" : !dist_dump.empty() ? "--dump_dist" : nullptr;
+            if (refused) { std::cerr << "ERROR:--batch cannot be combined with " << refused << std::endl; return 2; }
+        }
+        if (cmdlineopts.sequence_file.empty() && batch_list.empty()) { usage(); return 1; }
         if (cmdlineopts.reroot_flag && (cmdlineopts.ancestral_flag || !cmdlineopts.profile_file.empty())) {
             std::cerr << "ERROR:--ancestral_seqs and --profile_out cannot be combined with -r (the root search keeps no ancestral profiles)" << std::endl;
             return 2;
@@ -269,11 +506,22 @@ int main(int argc, char **argv) {
         if (!iters_set && !cmdlineopts.tree_file.empty()) cmdlineopts.iters = 0;   // do not iterate when a guide tree is provided (main.cpp:243-246)
         if (!dump.empty()) set_job_dump(dump);
         if (!dist_dump.empty()) set_dist_dump(dist_dump);
+        if (!batch_list.empty()) {
+            Alphabet a(cmdlineopts.codon_flag ? ALPHA_CODON : cmdlineopts.dna_flag ? ALPHA_DNA : ALPHA_AA);
+            if (!cmdlineopts.fasta_flag && !cmdlineopts.onlytree_flag) std::cerr << "note: Stockholm output is not built here; writing FASTA" << std::endl;
+            const int rc = doBatch(a, batch_list, iters_set, batch_cells, stats);
+            if (!getenv("PGM_FULL_EXIT") && std::string(default_backend().name()) == "hip") {   // (as below: the outputs are complete)
+                std::cout.flush(); std::cerr.flush(); fflush(nullptr);
+                _exit(rc);
+            }
+            return rc;
+        }
 
         g_startup.start();
         parallel_for(64, [](size_t) {});   // (the driver's host threads start while the device runtime does)
-        std::vector<std::string> input_order;
-        std::map<std::string, std::string> seqs = read_fasta(cmdlineopts.sequence_file, input_order);
+        Family fam;
+        fam.input = cmdlineopts.sequence_file; fam.tree_file = cmdlineopts.tree_file; fam.iters = cmdlineopts.iters;
+        fam.seqs = read_fasta(cmdlineopts.sequence_file, fam.input_order);
         std::ofstream custom_out;
         std::ostream *out = &std::cout;
         if (!cmdlineopts.output_file.empty()) {
@@ -281,19 +529,10 @@ int main(int argc, char **argv) {
             if (!custom_out) error("error opening output file");
             out = &custom_out;
         }
-        std::map<std::string, std::string> aligned;
-        PhyTree *tree = nullptr;
         Alphabet a(cmdlineopts.codon_flag ? ALPHA_CODON : cmdlineopts.dna_flag ? ALPHA_DNA : ALPHA_AA);
-        doAlign(a, seqs, aligned, tree, stats);
-        if (!cmdlineopts.onlytree_flag) {
-            std::vector<std::string> order = input_order;
-            if (!cmdlineopts.inputorder_flag) order = get_tree_order(tree);
-            if (!cmdlineopts.fasta_flag) std::cerr << "note: Stockholm output is not built here; writing FASTA" << std::endl;
-            write_fasta(aligned, order, *out);
-        } else {
-            *out << tree->formatNewick() << std::endl;
-        }
-        delete tree;
+        doAlign(a, fam, stats);
+        if (!cmdlineopts.onlytree_flag && !cmdlineopts.fasta_flag) std::cerr << "note: Stockholm output is not built here; writing FASTA" << std::endl;
+        fam.write(*out);
         if (host_switches().profile)
             fprintf(stderr, "main: output written %.1f ms after its start\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_main).count());
         // The output is complete.  Releasing the contexts' gigabytes of device memory and pinned blocks and shutting the HIP runtime

@@ -13,6 +13,7 @@
 #ifndef PGM_HOST_H_
 #define PGM_HOST_H_
 
+#include <atomic>
 #include <cstdint>
 #include <map>
 #include <memory>
@@ -297,6 +298,17 @@ struct Backend {
     virtual bool prealigned_counts_batch(uint32_t, uint32_t, uint32_t, const int8_t *, uint32_t, const uint32_t *, const uint32_t *, int32_t *, uint32_t *, int = 0) { return false; }
     // cosine matrix of the k-mer count vectors (DistanceFactoryAngle.h:100): counts nseq x ncols row-major -> nseq x nseq column-major
     virtual void kmer_cosine(uint32_t nseq, uint32_t ncols, const int32_t *counts, double *cosine, int worker = 0) = 0;
+    // The two stages above for many families in one call (--batch; include/pgm_hip.h: pgm_kmer_cosine_multi,
+    // pgm_prealigned_counts_multi).  counts: the families' count rows back to back, cosine: their nseq_f x nseq_f column-major blocks
+    // back to back.  rows: every family's nrows_f x ncols_f matrix back to back; pair p compares rows pi[p], pj[p] of family fam[p].
+    // The defaults loop over the families through the per-family entries above: a backend without kernels of its own computes
+    // the same values one family at a time.
+    virtual void kmer_cosine_multi(uint32_t nfam, const uint32_t *nseq, uint32_t ncols, const int32_t *counts, double *cosine, int worker = 0);
+    virtual bool prealigned_counts_multi(uint32_t dim, uint32_t nfam, const uint32_t *nrows, const uint32_t *ncols, const int8_t *rows, uint32_t npairs,
+                                         const uint32_t *fam, const uint32_t *pi, const uint32_t *pj, int32_t *counts, uint32_t *gaps, int worker = 0);
+    // calls the host code made of the align-batch entry and of the distance entries (all-pairs tiles, pair counts, cosine, ML
+    // distances): `pgmsa --batch --stats` shows with them that a stage was shared by the families of a chunk
+    std::atomic<uint64_t> calls_align{0}, calls_dist{0};
     // node profiles of a batch of merged graphs on the device (numeric part); false = host arithmetic
     virtual bool merge_profiles_batch(uint32_t, const pgm_merge_job *, int = 0) { return false; }
     double seconds_merge_profiles = 0;
@@ -447,6 +459,26 @@ ProgressiveAlignmentResult progressive_alignment(const Alphabet &a, const std::m
                                                  const PhyTree &tree, const CSProfile *csprofile,
                                                  const ModelFactory &model_factory,
                                                  const std::map<std::string, std::vector<repeat_t>> *repeats = nullptr);
+// The same pass over many guide trees at once (--batch): the nodes of all trees in one set, one batch per height.  Per family the
+// sequences, the tree, the model factory (-F estimates the frequencies per family) and where the result goes; the alphabet and the
+// profile library are the run's.  `worker`: the device context the family's nodes run on (a family never spans contexts).
+// `error`: set by the pass for a family whose tree cannot be used (the message the solo pass throws); that family gets no result.
+// progressive_alignment is this pass for one tree.
+struct ForestFamily {
+    const std::map<std::string, sequence_t> *sequences = nullptr;
+    const PhyTree *tree = nullptr;
+    const ModelFactory *model_factory = nullptr;
+    const std::map<std::string, std::vector<repeat_t>> *repeats = nullptr;
+    ProgressiveAlignmentResult *result = nullptr;
+    int worker = 0;
+    std::string error;
+};
+void progressive_alignment_forest(const Alphabet &a, std::vector<ForestFamily> &families, const CSProfile *csprofile);
+struct BatchStats {   // `pgmsa --batch --stats`
+    int families = 0, failed = 0, chunks = 0;
+    uint64_t passes = 0, levels = 0;   // forest passes; run_level calls of all passes
+};
+extern BatchStats batch_stats;
 // progressive_alignment_find_root (FindRoot.h:236-336): the alignment of the guide tree rerooted on the branch of the lowest gap
 // parsimony score, every branch (cmdlineopts.reroot_flag == 1) or a hill climb over neighbouring branches; prints the score.
 // The directed subtree merges of all candidates run as one DAG, height by height, through the level machinery of the plain pass.
@@ -519,6 +551,17 @@ void wls_pair_sums_host(uint32_t n, const double *D, const double *W, uint32_t n
 // TreeNJ.h:27-59: distances from an all-pairs alignment (-a, prealigned == false) or induced by an existing alignment
 // (prealigned == true, the guide-tree re-estimation of main.cpp:404-430)
 PhyTree *TreeNJ(const Alphabet &a, const std::map<std::string, sequence_t> &seqs, const ModelFactory *mf, bool prealigned = false);
+
+// TreeNJ for the families of a --batch chunk: the distance stages run once for all families (one cosine call, one farm of
+// all-pairs tiles over the concatenated sequences, one pair-count call), BioNJ and the rooting per family on the host threads.
+// Every family's tree is the one TreeNJ gives it alone.  `error`: the message TreeNJ would have thrown for this family.
+struct TreeJob {
+    const std::map<std::string, sequence_t> *seqs = nullptr;
+    const ModelFactory *model_factory = nullptr;
+    PhyTree *tree = nullptr;
+    std::string error;
+};
+void TreeNJ_multi(const Alphabet &a, std::vector<TreeJob> &jobs, bool prealigned = false);
 
 std::string data_dir();   // directory holding wag.qmat etc.
 

@@ -111,6 +111,7 @@ namespace {
 struct Node {
     std::string tr_note;   // -R: "TR indels at (...): n" of this internal node
     const PhyTree *tree;   // the guide-tree node (a merge of the root search's DAG has none; its leaves have theirs)
+    int fam = 0;           // the family (tree of a forest pass) the node belongs to: LevelEnv::fams
     int child[2] = {-1, -1};
     double len[2] = {0, 0}, sup[2] = {1, 1};   // length and support of the branches to the two children
     int height = 0;
@@ -277,7 +278,16 @@ static std::vector<int> assign_owners(const std::vector<Node> &nodes, int root, 
 // (:170), on the graphs as they are, not cleaned — and rebuilt from those alignments one descendant at a time
 // (mergeGraphsIncremental); nodes no descendant maps to are dropped.  The 2-4 alignments of a node read only the node's old graph,
 // so the whole level goes to the backend as ONE batch; the merges are per node, in the reference's order.
-static void early_refinement(const Alphabet &a, std::vector<Node> &nodes, const std::vector<int> &level, const ModelFactory &model_factory, bool with_repeats) {
+namespace {
+// what differs between the families of a forest pass: the models (-F estimates the frequencies per family) and the repeats
+struct FamEnv {
+    const ModelFactory *model_factory;
+    const std::map<std::string, std::vector<repeat_t>> *repeats;
+    bool with_repeats() const { return repeats && !repeats->empty(); }
+};
+}  // namespace
+
+static void early_refinement(const Alphabet &a, std::vector<Node> &nodes, const std::vector<int> &level, const std::vector<FamEnv> &fams) {
     const index_t NONE = (index_t)-1;
     struct Desc { int node; double distance, gap_distance; };
     std::vector<std::vector<Desc>> desc(level.size());
@@ -300,6 +310,7 @@ static void early_refinement(const Alphabet &a, std::vector<Node> &nodes, const 
                 }
             }
         }
+        const ModelFactory &model_factory = *fams[(size_t)nd.fam].model_factory;
         for (size_t i = 0; i < desc[k].size(); ++i) { models.push_back(model_factory.getModel(desc[k][i].distance, desc[k][i].gap_distance)); job_of.emplace_back(k, i); }
     }
     if (job_of.empty()) return;
@@ -362,7 +373,7 @@ static void early_refinement(const Alphabet &a, std::vector<Node> &nodes, const 
             extend_alignment(a, result, mappings[i], dr.aligned_sequences, false);
             extend_tr_homologies(result, mappings[i], dr.tr_homologies, dr.tr_source);
         }
-        if (with_repeats) result.graph.addRepeats(result.tr_homologies);
+        if (fams[(size_t)nd.fam].with_repeats()) result.graph.addRepeats(result.tr_homologies);
         nd.res = std::move(result);
     });
 }
@@ -371,8 +382,7 @@ namespace {
 // what a level of merges needs besides the nodes: the plain pass and the root search's DAG run the same code
 struct LevelEnv {
     const Alphabet &a;
-    const ModelFactory &model_factory;
-    const std::map<std::string, std::vector<repeat_t>> *repeats;
+    std::vector<FamEnv> fams;   // indexed by Node::fam (one entry for a single tree and for the root search)
     bool resident_pass;
     bool earlyref;   // early refinement of every merged node (the plain pass with --early_refinement)
     bool dag;        // the root search: merges keep their mappings instead of extending rows; children released by reference count
@@ -383,8 +393,6 @@ struct LevelEnv {
 // align_progressive_results (ProgressiveAlignment.h:413-476) of every node of `level` (their children are done) in one batch
 static void run_level(const LevelEnv &env, std::vector<Node> &nodes, std::vector<int> &owner, const std::vector<int> &level, int h) {
     const Alphabet &a = env.a;
-    const ModelFactory &model_factory = env.model_factory;
-    const std::map<std::string, std::vector<repeat_t>> *repeats = env.repeats;
     const bool resident_pass = env.resident_pass;
     const auto tl0 = env.tl0;
     const size_t L = level.size();
@@ -412,6 +420,7 @@ static void run_level(const LevelEnv &env, std::vector<Node> &nodes, std::vector
         if (r1.is_csprofile) distance1 = 0;
         if (r2.is_csprofile) distance2 = 0;
         Pending &p = pend[k];
+        const ModelFactory &model_factory = *env.fams[(size_t)nd.fam].model_factory;
         p.model = model_factory.getModel(distance1 + distance2, gap_distance1 + gap_distance2);
         p.model1 = model_factory.getModel(distance1, gap_distance1);
         p.model2 = model_factory.getModel(distance2, gap_distance2);
@@ -560,7 +569,7 @@ static void run_level(const LevelEnv &env, std::vector<Node> &nodes, std::vector
             ancestral_seq(a, result, create_ancestral_seq_name(result.aligned_sequences), result.graph, nullptr, anc.is_matched, p.model);
         }
         if (cmdlineopts.repeats_flag && !env.dag) nd.tr_note = "TR indels at " + create_ancestral_seq_name(result.aligned_sequences) + ": " + std::to_string(ar[k].n_tr_indels);   // (:470-473)
-        if (repeats && !repeats->empty()) result.graph.addRepeats(result.tr_homologies);   // (:468; with no annotation at all the merged graph has no repeat edges either way)
+        if (env.fams[(size_t)nd.fam].with_repeats()) result.graph.addRepeats(result.tr_homologies);   // (:468; with no annotation at all the merged graph has no repeat edges either way)
         // children are no longer needed (the reference copies them by value and drops them)
         if (!env.earlyref && !env.dag) {   // (the reference's alignment_cache, ProgressiveAlignment.h:107-109: the parent's refinement reads them again)
             r1 = ProgressiveAlignmentResult();
@@ -581,7 +590,7 @@ static void run_level(const LevelEnv &env, std::vector<Node> &nodes, std::vector
                 Node &ch = nodes[(size_t)nodes[level[k]].child[c]];
                 if (--ch.refs == 0) ch.res = ProgressiveAlignmentResult();
             }
-    if (env.earlyref) early_refinement(a, nodes, level, model_factory, repeats && !repeats->empty());
+    if (env.earlyref) early_refinement(a, nodes, level, env.fams);
     const auto tp3 = std::chrono::steady_clock::now();
     if (host_switches().profile)
         fprintf(stderr, "[%.1f ms] level %d: %zu nodes, host pre %.1f ms, alignGraphsBatch %.1f ms, host post (merge, extend) %.1f ms\n",
@@ -592,22 +601,46 @@ static void run_level(const LevelEnv &env, std::vector<Node> &nodes, std::vector
                 std::chrono::duration<double, std::milli>(tq1 - tq0).count(), std::chrono::duration<double, std::milli>(tp3 - tq1).count(), ns_merge.load() / 1e6, ns_extend.load() / 1e6);
 }
 
-ProgressiveAlignmentResult progressive_alignment(const Alphabet &a, const std::map<std::string, sequence_t> &sequences,
-                                                 const PhyTree &tree, const CSProfile *csprofile,
-                                                 const ModelFactory &model_factory,
-                                                 const std::map<std::string, std::vector<repeat_t>> *repeats) {
+BatchStats batch_stats;
+
+// The pass over a forest: the nodes of every family's guide tree in one `nodes` vector, the leaf stage once for all of them, and one
+// run_level per height over the nodes of that height of all trees.  A node reads its own children and its own family's models
+// only, so what a family gets does not depend on the families it shares the pass with.  A family whose tree cannot be used (not
+// bifurcating, a leaf that names no sequence) gets the solo pass's message in its `error` and takes no part.
+void progressive_alignment_forest(const Alphabet &a, std::vector<ForestFamily> &families, const CSProfile *csprofile) {
     const auto tl0 = std::chrono::steady_clock::now();
     default_backend().resident_reset();   // (merged profiles a previous pass left on the device)
+    ++batch_stats.passes;
     std::vector<Node> nodes;
-    int root = collect(tree, nodes);
-    int maxh = nodes[root].height;
+    std::vector<FamEnv> fenv(families.size());
+    std::vector<int> roots(families.size(), -1);
+    int maxh = 0;
+    const bool forest = families.size() > 1;
+    for (size_t f = 0; f < families.size(); ++f) {
+        ForestFamily &ff = families[f];
+        fenv[f] = FamEnv{ff.model_factory, ff.repeats};
+        ff.error.clear();
+        const size_t first = nodes.size();
+        try {
+            const int root = collect(*ff.tree, nodes);
+            for (size_t i = first; i < nodes.size(); ++i) {
+                nodes[i].fam = (int)f;
+                if (nodes[i].tree->isLeaf() && ff.sequences->find(nodes[i].tree->getName()) == ff.sequences->end()) error("unknown sequence name: %s", nodes[i].tree->getName().c_str());
+            }
+            roots[f] = root;
+            maxh = std::max(maxh, nodes[(size_t)root].height);
+        } catch (pgm_exception &e) {
+            nodes.erase(nodes.begin() + (std::ptrdiff_t)first, nodes.end());
+            ff.error = e.what();
+        }
+    }
+    if (nodes.empty()) return;
+    auto sequence_of = [&](int v) -> const sequence_t & { return families[(size_t)nodes[(size_t)v].fam].sequences->at(nodes[(size_t)v].tree->getName()); };
 
     // ---- leaves (ProgressiveAlignment.cpp:17-46) ----
     std::vector<int> leaves;
     for (size_t i = 0; i < nodes.size(); ++i)
         if (nodes[i].tree->isLeaf()) leaves.push_back((int)i);
-    for (int li : leaves)
-        if (sequences.find(nodes[li].tree->getName()) == sequences.end()) error("unknown sequence name: %s", nodes[li].tree->getName().c_str());
     // A pass whose merged profiles stay on the device (see the level loop) builds its leaf graphs there too: the host keeps
     // their edges only (SequenceGraph's profile matrix is 160 bytes per residue: 41 MB for 256 x 1000, otherwise built here,
     // copied into the staging block and uploaded for the alignments, and once more for the merges)
@@ -616,17 +649,19 @@ ProgressiveAlignmentResult progressive_alignment(const Alphabet &a, const std::m
     const bool resident_leaves = resident_pass && !csprofile;
     // where the profiles of every node live (worker = device context): all 0 with one context
     std::vector<int> owner(nodes.size(), 0);
-    if (resident_pass && default_backend().workers() > 1) {
+    if (forest && default_backend().workers() > 1) {   // a family never spans workers: nothing is copied between them
+        for (size_t i = 0; i < nodes.size(); ++i) owner[i] = families[(size_t)nodes[i].fam].worker % default_backend().workers();
+    } else if (resident_pass && default_backend().workers() > 1) {
         std::vector<double> leaf_len(nodes.size(), 0.0);
-        for (int li : leaves) leaf_len[(size_t)li] = (double)sequences.at(nodes[li].tree->getName()).size();
-        owner = assign_owners(nodes, root, default_backend().workers(), leaf_len);
+        for (int li : leaves) leaf_len[(size_t)li] = (double)sequence_of(li).size();
+        owner = assign_owners(nodes, roots[(size_t)nodes[0].fam], default_backend().workers(), leaf_len);
     }
     default_backend().resident_pass = resident_pass;
     default_backend().resident_imports = 0;
     const auto tl1 = std::chrono::steady_clock::now();
     parallel_for(leaves.size(), [&](size_t k) {   // (independent leaves: a thousand SequenceGraphs are 50 ms on one thread)
         Node &nd = nodes[leaves[k]];
-        auto it = sequences.find(nd.tree->getName());
+        auto it = families[(size_t)nd.fam].sequences->find(nd.tree->getName());
         nd.res.aligned_sequences[it->first] = it->second;
         nd.res.score = 0;
         nd.res.n_tr_indels = 0;
@@ -652,7 +687,7 @@ ProgressiveAlignmentResult progressive_alignment(const Alphabet &a, const std::m
             std::vector<uint32_t> offs(mine.size() + 1, 0);
             std::vector<const sequence_t *> seqs(mine.size());
             for (size_t s = 0; s < mine.size(); ++s) {
-                seqs[s] = &sequences.at(nodes[mine[s]].tree->getName());
+                seqs[s] = &sequence_of(mine[s]);
                 offs[s + 1] = offs[s] + (uint32_t)seqs[s]->size();
             }
             std::vector<int8_t> syms(offs[mine.size()]);
@@ -665,7 +700,8 @@ ProgressiveAlignmentResult progressive_alignment(const Alphabet &a, const std::m
             for (size_t s = 0; s < mine.size(); ++s) nodes[mine[s]].res.graph.setDevSites(dev[s]);
         }
     }
-    if (csprofile) {
+    // (the leaves of a group share the model's frequencies: all leaves of the pass, or a family's when -F estimates them per family)
+    auto leaf_profiles = [&](const std::vector<int> &leaves) {
         // SequenceGraph(seq, csprofile, model_factory.getModel(branch_length)) for every leaf in one
         // createProfile batch (SequenceGraph.h:111-121, CSProfile.cpp:175-225).
         if (a.kind != ALPHA_AA) error("context-specific profiles need the AA alphabet");
@@ -675,7 +711,7 @@ ProgressiveAlignmentResult progressive_alignment(const Alphabet &a, const std::m
         std::vector<double> tau(ns), p_uniform((size_t)ns * 20), pi(20, 0.0);
         std::vector<const sequence_t *> seqs(ns);
         for (uint32_t s = 0; s < ns; ++s) {
-            seqs[s] = &sequences.at(nodes[leaves[s]].tree->getName());
+            seqs[s] = &sequence_of(leaves[s]);
             offs[s + 1] = offs[s] + (uint32_t)seqs[s]->size();
             out_offs[s + 1] = out_offs[s] + (uint64_t)20 * (seqs[s]->size() + 2);
         }
@@ -683,7 +719,7 @@ ProgressiveAlignmentResult progressive_alignment(const Alphabet &a, const std::m
         parallel_for(ns, [&](size_t s) {   // (a model per leaf — its branch length —: P(t) from the eigen form, 20 us each)
             int8_t *o = syms.data() + offs[s];
             for (int8_t c : *seqs[s]) *o++ = a.isValid(c) ? (int8_t)a.value(c) : (int8_t)20;
-            Model m = model_factory.getModel(nodes[leaves[s]].tree->getBranchLength());
+            Model m = fenv[(size_t)nodes[leaves[s]].fam].model_factory->getModel(nodes[leaves[s]].tree->getBranchLength());
             tau[s] = m.divergence / 0.8;
             if (s == 0) pi = m.pi;   // (the same for every leaf)
             for (int i = 0; i < 20; ++i) {  // model.P * Constant(1/20)
@@ -761,28 +797,54 @@ ProgressiveAlignmentResult progressive_alignment(const Alphabet &a, const std::m
             nd.res.graph = SequenceGraphFromProfile(20, nn, sites);
             nd.res.is_csprofile = true;
         }
+    };
+    if (csprofile) {
+        if (forest && cmdlineopts.aafreqs_flag) {
+            std::vector<std::vector<int>> of_family(families.size());
+            for (int li : leaves) of_family[(size_t)nodes[(size_t)li].fam].push_back(li);
+            for (const std::vector<int> &group : of_family) if (!group.empty()) leaf_profiles(group);
+        } else leaf_profiles(leaves);
     }
 
-    attach_repeats(nodes, leaves, repeats);
+    for (size_t f = 0; f < families.size(); ++f) {
+        if (!fenv[f].with_repeats() || roots[f] < 0) continue;
+        std::vector<int> mine;
+        for (int li : leaves) if (nodes[(size_t)li].fam == (int)f) mine.push_back(li);
+        attach_repeats(nodes, mine, fenv[f].repeats);
+    }
     if (host_switches().profile)
         fprintf(stderr, "leaves: %zu, %.1f ms (names / owners %.2f, graphs %.2f, profiles %.2f)\n", leaves.size(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count(),
                 std::chrono::duration<double, std::milli>(tl1 - tl0).count(), std::chrono::duration<double, std::milli>(tl2 - tl1).count(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl2).count());
     // ---- internal nodes, one guide-tree level per batch (ProgressiveAlignment.h:413-476) ----
-    const LevelEnv env{a, model_factory, repeats, resident_pass, cmdlineopts.earlyref_flag, false, tl0};
+    const LevelEnv env{a, fenv, resident_pass, cmdlineopts.earlyref_flag, false, tl0};
     for (int h = 1; h <= maxh; ++h) {
         std::vector<int> level;
         for (size_t i = 0; i < nodes.size(); ++i)
             if (nodes[i].height == h) level.push_back((int)i);
         run_level(env, nodes, owner, level, h);
+        ++batch_stats.levels;
     }
     if (cmdlineopts.repeats_flag)   // the reference prints them as its recursion returns: post-order, which is the order of `nodes`
         for (const Node &nd : nodes) if (!nd.tr_note.empty()) std::cerr << nd.tr_note << std::endl;
-    ProgressiveAlignmentResult out = std::move(nodes[root].res);
+    for (size_t f = 0; f < families.size(); ++f)
+        if (roots[f] >= 0) *families[f].result = std::move(nodes[(size_t)roots[f]].res);
     if (host_switches().profile)
         fprintf(stderr, "[%.1f ms] root result taken\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count());
     nodes.clear();
     if (host_switches().profile)
         fprintf(stderr, "[%.1f ms] nodes released\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count());
+}
+
+// the forest of one tree
+ProgressiveAlignmentResult progressive_alignment(const Alphabet &a, const std::map<std::string, sequence_t> &sequences,
+                                                 const PhyTree &tree, const CSProfile *csprofile,
+                                                 const ModelFactory &model_factory,
+                                                 const std::map<std::string, std::vector<repeat_t>> *repeats) {
+    ProgressiveAlignmentResult out;
+    std::vector<ForestFamily> one(1);
+    one[0].sequences = &sequences; one[0].tree = &tree; one[0].model_factory = &model_factory; one[0].repeats = repeats; one[0].result = &out;
+    progressive_alignment_forest(a, one, csprofile);
+    if (!one[0].error.empty()) throw pgm_exception(one[0].error);
     return out;
 }
 
@@ -1023,7 +1085,7 @@ struct RootSearch {
             if (!default_backend().resident_onehot((uint32_t)a.DIM, (uint32_t)leaves.size(), syms.data(), offs.data(), dev.data(), 0)) error("the backend could not build the leaf graphs on the device");
             for (size_t s = 0; s < leaves.size(); ++s) nodes[(size_t)leaves[s]].res.graph.setDevSites(dev[s]);
         }
-        attach_repeats(nodes, leaves, env.repeats);
+        attach_repeats(nodes, leaves, env.fams[0].repeats);
     }
 
     // the gap masks of a height's merges: each child's rows through the merge's mapping, in one backend call
@@ -1194,7 +1256,7 @@ ProgressiveAlignmentResult progressive_alignment_find_root(const Alphabet &a, co
     be.resident_imports = 0;
     root_search_stats = RootSearchStats();
     root_search_stats.ran = true;
-    const LevelEnv env{a, model_factory, repeats, resident_pass, false, true, t0};
+    const LevelEnv env{a, {FamEnv{&model_factory, repeats}}, resident_pass, false, true, t0};
     RootSearch rs(a, sequences, env, tree);
     for (size_t n = 0; n < rs.g.nodes.size(); ++n)
         if (rs.g.isLeaf((int)n) && !sequences.count(rs.g.nodes[n].tree->getName())) error("unknown sequence name: %s", rs.g.nodes[n].tree->getName().c_str());
