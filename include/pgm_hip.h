@@ -255,13 +255,15 @@ float pgm_csprofile_last_kernel_ms(pgm_ctx *ctx);
  * and of DistanceFactoryPrealigned, src/DistanceFactoryPrealigned.h:84-88).  The substitution model is handed over in the
  * eigen form the reference builds in ModelFactory (src/ModelFactory.h:48-67): P(d) = V diag(exp(sigma d)) V^-1, all
  * dim x dim matrices column-major double; dim <= 20: the kernel keeps P(d) and its two derivatives of one pair in the registers
- * of one wavefront (20 x 20 / 64 lanes); the 61-state codon models are refused (PGM_ERR_INVALID) and the host mirror keeps its
- * estimator for them (host/distance.cpp: 16 host threads; 8128 pairs of config 4 take 0.1 s).  min_dist / max_dist are the clamps of parseDistance
+ * of one wavefront (20 x 20 / 64 lanes).  Or in the general form: Q alone, V == Vi == sigma == NULL, dim <= 64 (the 61-state
+ * codon model, any generator without a usable eigen form): P(d) = exp(Q d) by scaling and squaring with 20 Taylor terms, the
+ * steps and the order of host/model_factory.cpp's expm, one workgroup per pair.  PGM_ERR_INVALID: an eigen form with
+ * dim > 20, a general form with dim > 64, only some of V, Vi, sigma given.  min_dist / max_dist are the clamps of parseDistance
  * (src/ModelFactory.h:125), dist_max / var_max / var_min the constants of DistanceFactoryML.cpp:3-32.
  * counts[p * dim * dim + s1 + dim * s2], gaps[p], seqlen[p] = (L1 + L2) / 2 per pair -> dist[p], var[p]. */
 typedef struct pgm_mldist_model {
     uint32_t dim;
-    const double *Q, *V, *Vi, *sigma;
+    const double *Q, *V, *Vi, *sigma;   /* general form: V == Vi == sigma == NULL */
     double dist_max, var_max, var_min, cutoff_dist, min_dist, max_dist, indel_rate;
     int32_t mldist, mldist_gap; /* cmdlineopts.mldist_flag / mldist_gap_flag */
 } pgm_mldist_model;

@@ -1,7 +1,10 @@
 // pgm_dist_capi.inc — C ABI of the distance-estimation stages (included by pgm_capi.hip).
 extern "C" int pgm_mldist_batch(pgm_ctx *ctx, const pgm_mldist_model *m, uint32_t npairs, const int32_t *counts, const uint32_t *gaps,
                                 const double *seqlen, double *dist, double *var) {
-    if (!ctx || !m || !m->Q || !m->V || !m->Vi || !m->sigma || m->dim == 0 || m->dim > PGM_ML_DMAX) return fail(PGM_ERR_INVALID, "bad model (dim must be <= 20, eigen form required)");
+    // two forms of the model: the eigen form (V, Vi, sigma all given, dim <= 20) and the general form (none of them given, dim <= 64)
+    const bool eigen = m && m->V && m->Vi && m->sigma, general = m && !m->V && !m->Vi && !m->sigma;
+    if (!ctx || !m || !m->Q || m->dim == 0 || !((eigen && m->dim <= PGM_ML_DMAX) || (general && m->dim <= PGM_MLG_DMAX)))
+        return fail(PGM_ERR_INVALID, "bad model (eigen form: Q, V, Vi, sigma and dim <= 20; general form: Q alone, V == Vi == sigma == NULL, and dim <= 64)");
     if (npairs && (!counts || !gaps || !seqlen || !dist || !var)) return fail(PGM_ERR_INVALID, "null argument");
     ctx->ml_ms = 0;
     if (npairs == 0) return PGM_OK;
@@ -11,7 +14,7 @@ extern "C" int pgm_mldist_batch(pgm_ctx *ctx, const pgm_mldist_model *m, uint32_
     int32_t *d_counts = nullptr;
     uint32_t *d_gaps = nullptr;
     struct Buf { void **p; size_t bytes; const void *src; };
-    Buf bufs[] = {{(void **)&d_Q, 8 * nn, m->Q}, {(void **)&d_V, 8 * nn, m->V}, {(void **)&d_Vi, 8 * nn, m->Vi}, {(void **)&d_sig, 8 * (size_t)m->dim, m->sigma},
+    Buf bufs[] = {{(void **)&d_Q, 8 * nn, m->Q}, {(void **)&d_V, eigen ? 8 * nn : 0, m->V}, {(void **)&d_Vi, eigen ? 8 * nn : 0, m->Vi}, {(void **)&d_sig, eigen ? 8 * (size_t)m->dim : 0, m->sigma},
                   {(void **)&d_counts, 4 * nn * npairs, counts}, {(void **)&d_gaps, 4 * (size_t)npairs, gaps}, {(void **)&d_len, 8 * (size_t)npairs, seqlen},
                   {(void **)&d_dist, 8 * (size_t)npairs, nullptr}, {(void **)&d_var, 8 * (size_t)npairs, nullptr}};
     hipError_t e = hipSuccess;
@@ -31,7 +34,8 @@ extern "C" int pgm_mldist_batch(pgm_ctx *ctx, const pgm_mldist_model *m, uint32_
         A.dist = d_dist; A.var = d_var;
         const uint32_t blocks = std::min<uint32_t>((npairs + PGM_ML_WAVES - 1) / PGM_ML_WAVES, (uint32_t)ctx->prop.multiProcessorCount * 2u);
         e = hipEventRecord(ctx->sc_ev[0], s);
-        hipLaunchKernelGGL(pgm_mldist_kernel, dim3(blocks), dim3(PGM_ML_WAVES * 64), 0, s, A);
+        if (eigen) hipLaunchKernelGGL(pgm_mldist_kernel, dim3(blocks), dim3(PGM_ML_WAVES * 64), 0, s, A);
+        else hipLaunchKernelGGL(pgm_mldist_general_kernel, dim3(npairs), dim3(PGM_MLG_THREADS), 0, s, A);   // one workgroup per pair
         if (e == hipSuccess) e = hipGetLastError();
         if (e == hipSuccess) e = hipEventRecord(ctx->sc_ev[1], s);
     }

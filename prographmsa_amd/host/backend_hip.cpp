@@ -96,8 +96,11 @@ struct HipBackend : Backend {
                       double *dist, double *var, int worker) override {
         int rc = pgm_mldist_batch(ctxs[(size_t)worker % ctxs.size()], &m, npairs, counts, gaps, seqlen, dist, var);
         if (rc != PGM_OK) error("pgm_mldist_batch failed (%d): %s", rc, pgm_last_error());
+        mldist_device_pairs += npairs;
+        mldist_kernel_ms += pgm_dist_last_kernel_ms(ctxs[(size_t)worker % ctxs.size()]);
         return true;
     }
+    bool mldist_general() const override { return true; }
     bool prealigned_counts_batch(uint32_t dim, uint32_t nrows, uint32_t ncols, const int8_t *rows, uint32_t npairs, const uint32_t *pi,
                                  const uint32_t *pj, int32_t *counts, uint32_t *gaps, int worker) override {
         int rc = pgm_prealigned_counts_batch(ctx_of(worker), dim, nrows, ncols, rows, npairs, pi, pj, counts, gaps);

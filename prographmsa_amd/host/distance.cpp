@@ -132,14 +132,19 @@ void DistanceFactoryML::computeDistances(const int32_t *counts, const uint32_t *
     Backend &be = default_backend();
     auto t1 = std::chrono::steady_clock::now();
     bool done = false;
-    if (host_switches().device_mldist && model_factory->has_eigen() && D <= 20 && np) {
-        // the whole batch in one kernel (one wavefront per pair); same arithmetic as computeDistance below except for the
-        // device library's exp / log (last-bit differences: see csrc/pgm_dist_kernels.h)
+    // the model goes over in eigen form when it has one of at most 20 states, else in general form (Q alone: the 61-state ECM
+    // model, a generator that is not reversible) if the backend's kernel takes that
+    const bool eigen_form = model_factory->has_eigen() && D <= 20;
+    if (host_switches().device_mldist && (eigen_form || (be.mldist_general() && D <= 64)) && np) {
+        // the whole batch in one kernel (eigen form: one wavefront per pair, general form: one workgroup per pair); same arithmetic
+        // as computeDistance below except for the device library's exp / log (last-bit differences: see csrc/pgm_dist_kernels.h) and,
+        // for a model of more than 20 states that has an eigen form, P(d) = exp(Q d) by expm instead of that form
         double DIST_MAX, VAR_MAX, VAR_MIN;
         consts(alphabet, DIST_MAX, VAR_MAX, VAR_MIN);
         pgm_mldist_model m;
-        m.dim = D; m.Q = model_factory->Qmat().data(); m.V = model_factory->eigV().data(); m.Vi = model_factory->eigVi().data();
-        m.sigma = model_factory->eigSigma().data();
+        m.dim = D; m.Q = model_factory->Qmat().data();
+        m.V = eigen_form ? model_factory->eigV().data() : nullptr; m.Vi = eigen_form ? model_factory->eigVi().data() : nullptr;
+        m.sigma = eigen_form ? model_factory->eigSigma().data() : nullptr;
         m.dist_max = DIST_MAX; m.var_max = VAR_MAX; m.var_min = VAR_MIN; m.cutoff_dist = cmdlineopts.cutoff_dist;
         m.min_dist = cmdlineopts.min_dist; m.max_dist = cmdlineopts.max_dist; m.indel_rate = cmdlineopts.indel_rate;
         m.mldist = cmdlineopts.mldist_flag ? 1 : 0; m.mldist_gap = cmdlineopts.mldist_gap_flag ? 1 : 0;
@@ -1210,40 +1215,47 @@ static void compute_distances_multi(const Alphabet &a, const std::vector<PairBlo
     const size_t dd = (size_t)D * D;
     Backend &be = default_backend();
     const auto t1 = std::chrono::steady_clock::now();
-    bool eigen = true;
-    for (const PairBlock &b : blocks) eigen = eigen && b.model_factory->has_eigen();
+    // per group of families that share a model: on the device in the form computeDistances would choose for that model alone (so a
+    // family's estimates are those of its solo run), else on the host
+    std::vector<char> on_device(blocks.size(), 0);
     bool done = false;
-    if (host_switches().device_mldist && eigen && D <= 20) {
+    if (host_switches().device_mldist) {
         double DIST_MAX, VAR_MAX, VAR_MIN;
         consts(a, DIST_MAX, VAR_MAX, VAR_MIN);
         done = true;
-        for (size_t b0 = 0; b0 < blocks.size() && done;) {
+        for (size_t b0 = 0; b0 < blocks.size();) {
             const size_t b1 = cmdlineopts.aafreqs_flag ? b0 + 1 : blocks.size();   // (the blocks are contiguous in the pair arrays)
             const ModelFactory *mf = blocks[b0].model_factory;
+            const bool eigen = mf->has_eigen() && D <= 20;
             const size_t p0 = blocks[b0].p0, p1 = blocks[b1 - 1].p0 + blocks[b1 - 1].np;
-            pgm_mldist_model m;
-            m.dim = D; m.Q = mf->Qmat().data(); m.V = mf->eigV().data(); m.Vi = mf->eigVi().data(); m.sigma = mf->eigSigma().data();
-            m.dist_max = DIST_MAX; m.var_max = VAR_MAX; m.var_min = VAR_MIN; m.cutoff_dist = cmdlineopts.cutoff_dist;
-            m.min_dist = cmdlineopts.min_dist; m.max_dist = cmdlineopts.max_dist; m.indel_rate = cmdlineopts.indel_rate;
-            m.mldist = cmdlineopts.mldist_flag ? 1 : 0; m.mldist_gap = cmdlineopts.mldist_gap_flag ? 1 : 0;
+            bool ok = eigen || (be.mldist_general() && D <= 64);
             std::vector<double> dist(p1 - p0), var(p1 - p0);
-            if (p1 > p0) {
+            if (ok && p1 > p0) {
+                pgm_mldist_model m;
+                m.dim = D; m.Q = mf->Qmat().data();
+                m.V = eigen ? mf->eigV().data() : nullptr; m.Vi = eigen ? mf->eigVi().data() : nullptr; m.sigma = eigen ? mf->eigSigma().data() : nullptr;
+                m.dist_max = DIST_MAX; m.var_max = VAR_MAX; m.var_min = VAR_MIN; m.cutoff_dist = cmdlineopts.cutoff_dist;
+                m.min_dist = cmdlineopts.min_dist; m.max_dist = cmdlineopts.max_dist; m.indel_rate = cmdlineopts.indel_rate;
+                m.mldist = cmdlineopts.mldist_flag ? 1 : 0; m.mldist_gap = cmdlineopts.mldist_gap_flag ? 1 : 0;
                 ++be.calls_dist;
-                done = be.mldist_batch(m, (uint32_t)(p1 - p0), counts + p0 * dd, gaps + p0, seqlen + p0, dist.data(), var.data());
+                ok = be.mldist_batch(m, (uint32_t)(p1 - p0), counts + p0 * dd, gaps + p0, seqlen + p0, dist.data(), var.data());
             }
-            for (size_t b = b0; b < b1 && done; ++b)
+            for (size_t b = b0; b < b1 && ok; ++b) {
+                on_device[b] = 1;
                 for (size_t p = blocks[b].p0; p < blocks[b].p0 + blocks[b].np; ++p) {
                     DistanceMatrix &dm = *blocks[b].out;
                     dm.D(pi[p], pj[p]) = dm.D(pj[p], pi[p]) = dist[p - p0];
                     dm.V(pi[p], pj[p]) = dm.V(pj[p], pi[p]) = var[p - p0];
                 }
+            }
+            done = done && ok;
             b0 = b1;
         }
     }
     if (!done) {
         std::vector<std::pair<uint32_t, uint32_t>> work;   // (block, pair of the block)
         for (size_t b = 0; b < blocks.size(); ++b)
-            for (uint32_t k = 0; k < blocks[b].np; ++k) work.emplace_back((uint32_t)b, k);
+            for (uint32_t k = 0; k < blocks[b].np && !on_device[b]; ++k) work.emplace_back((uint32_t)b, k);
         const size_t grain = 16;   // pairs per index handed out
         parallel_for((work.size() + grain - 1) / grain, [&](size_t g) {
             std::vector<int32_t> c(dd);

@@ -39,6 +39,10 @@ static void usage() {
                  "                order for --codon\n"
                  "  -F, --estimate_aafreqs  estimate the equilibrium frequencies from the input sequences\n"
                  "  -C, --aafreqs_pseudocount <count>  pseudo-count of the model's own frequencies in that estimate (default 1000)\n"
+                 "  -m, -M        maximum-likelihood distances (-M: with the gap term).  The host estimates them unless the environment\n"
+                 "                sets PGM_DEVICE_MLDIST=1; the device then estimates them where the backend has the kernel: a model\n"
+                 "                with an eigen form of up to 20 states, and, on the GPU backend, any model of up to 64 states, --codon\n"
+                 "                and a model without an eigen form included (last-bit differences to the host's values)\n"
                  "  -r, --reroot  realign with the guide tree rooted on every branch and keep the alignment of the lowest gap\n"
                  "                parsimony score; given twice (-rr), a hill climb over neighbouring branches instead\n"
                  "  -W, --wls_refine  refine every guide tree estimated from distances by weighted least squares (nearest-neighbour\n"
@@ -169,6 +173,8 @@ static void print_stats(double t_init, double t_tree, double t_prog, const Batch
                 cmdlineopts.wlsrefine_flag, w.trees, w.seconds, w.pair_sums_s, be.seconds_wls_kernels, w.sweeps, (unsigned long long)w.quartets,
                 (unsigned long long)w.quintets, (unsigned long long)w.batches, (unsigned long long)be.wls_launches);
     }
+    if (host_switches().device_mldist)   // (keys of PGM_DEVICE_MLDIST only: pairs estimated by the device kernel, its time)
+        fprintf(stderr, ", \"mldist_device_pairs\": %llu, \"mldist_kernel_ms\": %.3f", (unsigned long long)be.mldist_device_pairs, be.mldist_kernel_ms);
     if (batch)   // (keys of --batch only)
         fprintf(stderr, ", \"batch_families\": %d, \"batch_failed\": %d, \"batch_chunks\": %d, \"batch_passes\": %llu, \"batch_levels\": %llu, "
                         "\"batch_align_calls\": %llu, \"batch_dist_calls\": %llu",

@@ -295,6 +295,11 @@ struct Backend {
     // batched DistanceFactoryML::computeDistance and the pair counts of an alignment on the device;
     // false = this backend has no such kernel (the host estimator is used)
     virtual bool mldist_batch(const pgm_mldist_model &, uint32_t, const int32_t *, const uint32_t *, const double *, double *, double *, int = 0) { return false; }
+    // mldist_batch also takes a model in general form (Q alone, V == Vi == sigma == NULL, dim <= 64: the codon model, a generator
+    // that is not reversible); false = eigen form with dim <= 20 only, the host estimator keeps the other models
+    virtual bool mldist_general() const { return false; }
+    uint64_t mldist_device_pairs = 0;     // pairs whose estimate came from mldist_batch (--stats, with PGM_DEVICE_MLDIST)
+    double mldist_kernel_ms = 0;          // device time of their kernels
     virtual bool prealigned_counts_batch(uint32_t, uint32_t, uint32_t, const int8_t *, uint32_t, const uint32_t *, const uint32_t *, int32_t *, uint32_t *, int = 0) { return false; }
     // cosine matrix of the k-mer count vectors (DistanceFactoryAngle.h:100): counts nseq x ncols row-major -> nseq x nseq column-major
     virtual void kmer_cosine(uint32_t nseq, uint32_t ncols, const int32_t *counts, double *cosine, int worker = 0) = 0;
