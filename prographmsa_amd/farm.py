@@ -1,6 +1,6 @@
 """Work sharing for the embarrassingly parallel stages across GPUs (bench / test plumbing; no data-path collective).
 
-The product's farm lives in C++ (`host/distance.cpp`, computePwDistances): one host thread per device context pulls
+The product's farm lives in C++ (`host/distance.cpp`, nw_farm): one host thread per device context pulls
 pair tiles from an atomic counter.  `bench.py` runs one PROCESS per GPU (the launch contract), so the same queue is
 rebuilt here on top of the rendezvous store of `torch.distributed` (`TCPStore.add` is an atomic fetch-and-add served
 by rank 0): every rank pulls the next tile number until the tiles run out.  Same tiles, same order, same tile size

@@ -1,7 +1,8 @@
 // distance.cpp — pairwise distances and the BioNJ guide tree for the `-a` path
 // (reference src/DistanceFactoryAlign.{h,cpp}, DistanceFactoryML.{h,cpp}, TreeNJ.{h,cpp}).
-// The O(L^2) Needleman-Wunsch of every pair (alignPair) runs behind the C ABI
-// (pgm_nw_pairs_batch); ML distance estimation and neighbour joining stay on the host.
+// The O(L^2) Needleman-Wunsch of every pair (alignPair), the pair counts of an alignment and the k-mer cosine matrix run behind the
+// C ABI, and so does ML distance estimation when PGM_DEVICE_MLDIST is set (pgm_mldist_batch; on the host threads otherwise);
+// neighbour joining stays on the host.  TreeNJ (one family) and TreeNJ_multi (--batch) are one implementation: the last section.
 #include "pgm_host.h"
 #include "nnls.h"
 #include <quadmath.h>
@@ -126,61 +127,6 @@ static void dump_distances(const DistanceMatrix &d) {
     f.write((const char *)d.variances.data(), 8 * d.variances.size());
 }
 
-void DistanceFactoryML::computeDistances(const int32_t *counts, const uint32_t *gaps, const std::vector<double> &seqlen,
-                                         const std::vector<uint32_t> &pi, const std::vector<uint32_t> &pj, DistanceMatrix &distances) const {
-    const uint32_t np = (uint32_t)pi.size(), D = (uint32_t)alphabet.DIM;
-    Backend &be = default_backend();
-    auto t1 = std::chrono::steady_clock::now();
-    bool done = false;
-    // the model goes over in eigen form when it has one of at most 20 states, else in general form (Q alone: the 61-state ECM
-    // model, a generator that is not reversible) if the backend's kernel takes that
-    const bool eigen_form = model_factory->has_eigen() && D <= 20;
-    if (host_switches().device_mldist && (eigen_form || (be.mldist_general() && D <= 64)) && np) {
-        // the whole batch in one kernel (eigen form: one wavefront per pair, general form: one workgroup per pair); same arithmetic
-        // as computeDistance below except for the device library's exp / log (last-bit differences: see csrc/pgm_dist_kernels.h) and,
-        // for a model of more than 20 states that has an eigen form, P(d) = exp(Q d) by expm instead of that form
-        double DIST_MAX, VAR_MAX, VAR_MIN;
-        consts(alphabet, DIST_MAX, VAR_MAX, VAR_MIN);
-        pgm_mldist_model m;
-        m.dim = D; m.Q = model_factory->Qmat().data();
-        m.V = eigen_form ? model_factory->eigV().data() : nullptr; m.Vi = eigen_form ? model_factory->eigVi().data() : nullptr;
-        m.sigma = eigen_form ? model_factory->eigSigma().data() : nullptr;
-        m.dist_max = DIST_MAX; m.var_max = VAR_MAX; m.var_min = VAR_MIN; m.cutoff_dist = cmdlineopts.cutoff_dist;
-        m.min_dist = cmdlineopts.min_dist; m.max_dist = cmdlineopts.max_dist; m.indel_rate = cmdlineopts.indel_rate;
-        m.mldist = cmdlineopts.mldist_flag ? 1 : 0; m.mldist_gap = cmdlineopts.mldist_gap_flag ? 1 : 0;
-        std::vector<double> dist(np), var(np);
-        ++be.calls_dist;
-        done = be.mldist_batch(m, np, counts, gaps, seqlen.data(), dist.data(), var.data());
-        if (done)
-            for (uint32_t p = 0; p < np; ++p) {
-                distances.D(pi[p], pj[p]) = distances.D(pj[p], pi[p]) = dist[p];
-                distances.V(pi[p], pj[p]) = distances.V(pj[p], pi[p]) = var[p];
-            }
-    }
-    if (!done) {
-        // ML distance per pair (Newton on d, each step a 20x20 P(d)): independent per pair, so the pairs are dealt to host
-        // threads; every pair's arithmetic is the single-threaded one, the matrix entries written are disjoint
-        unsigned nt = std::thread::hardware_concurrency();
-        if (const char *e = getenv("PGM_HOST_THREADS")) nt = (unsigned)atoi(e);
-        nt = std::max(1u, std::min(nt, 16u));
-        nt = (unsigned)std::min<uint32_t>(nt, std::max(1u, np));
-        auto work = [&](unsigned t) {
-            std::vector<int32_t> c((size_t)D * D);
-            for (uint32_t p = t; p < np; p += nt) {
-                std::copy(counts + (size_t)p * D * D, counts + (size_t)(p + 1) * D * D, c.begin());
-                distvar_t dv = computeDistance(c, gaps[p], seqlen[p]);
-                distances.D(pi[p], pj[p]) = distances.D(pj[p], pi[p]) = dv.dist;
-                distances.V(pi[p], pj[p]) = distances.V(pj[p], pi[p]) = dv.var;
-            }
-        };
-        std::vector<std::thread> pool;
-        for (unsigned t = 1; t < nt; ++t) pool.emplace_back(work, t);
-        work(0);
-        for (auto &th : pool) th.join();
-    }
-    be.seconds_mldist += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
-}
-
 // ---- DistanceFactoryAlign ---------------------------------------------------------------------
 DistanceFactoryAlign::DistanceFactoryAlign(const Alphabet &a, const ModelFactory *mf) : DistanceFactoryML(a, mf) {
     const int sd = a.DIM + 1;  // initMatrix (DistanceFactoryAlign.cpp:5-35, 38-235, 238-249)
@@ -204,99 +150,6 @@ DistanceFactoryAlign::DistanceFactoryAlign(const Alphabet &a, const ModelFactory
     for (int32_t &v : scoring_matrix_) in >> v;
     gap_open = -10;
     gap_extend = -2;
-}
-
-DistanceMatrix DistanceFactoryAlign::computePwDistances(const std::map<std::string, sequence_t> &sequences,
-                                                        const std::vector<std::string> &order) {
-    const uint32_t n = (uint32_t)order.size();
-    const uint32_t D = (uint32_t)alphabet.DIM;
-    DistanceMatrix distances((int)n);
-    // symbols: value(), negative -> 20 for amino acids and codons (the reference's quirk, DistanceFactoryAlign.h:72,79); DNA has no
-    // negative values (sequenceFromString refuses other characters) and its unknown is DIM, the X row of its scoring matrix
-    const int unknown_sym = alphabet.kind == ALPHA_DNA ? (int)D : 20;
-    std::vector<int8_t> syms;
-    std::vector<uint32_t> offs(n + 1, 0);
-    for (uint32_t i = 0; i < n; ++i) {
-        const sequence_t &s = sequences.at(order[i]);
-        for (int8_t c : s) {
-            int v = alphabet.value(c);
-            syms.push_back((int8_t)(v < 0 ? unknown_sym : v));
-        }
-        offs[i + 1] = (uint32_t)syms.size();
-    }
-    // The reference's i < j double loop (DistanceFactoryAlign.h:35-53) is a farm of independent alignPair jobs.  Here: the
-    // pairs sorted by cost (longest first), cut into tiles, and one host thread per device context pulling tile numbers from
-    // an atomic counter (no collective, no static partition: a slower device simply takes fewer tiles).  Every tile is one
-    // pgm_nw_pairs_batch call on the worker's own context; the outputs of a pair land at the pair's position in the sorted
-    // order, whoever computed it, so the result does not depend on the number of workers.
-    std::vector<uint32_t> pi, pj;
-    {
-        std::vector<std::pair<uint32_t, uint32_t>> pr;
-        for (uint32_t i = 0; i < n; ++i)
-            for (uint32_t j = i + 1; j < n; ++j) pr.push_back({i, j});
-        auto cost = [&](const std::pair<uint32_t, uint32_t> &p) { return (uint64_t)(offs[p.first + 1] - offs[p.first]) * (offs[p.second + 1] - offs[p.second]); };
-        std::stable_sort(pr.begin(), pr.end(), [&](const std::pair<uint32_t, uint32_t> &a, const std::pair<uint32_t, uint32_t> &b2) { return cost(a) > cost(b2); });
-        for (auto &p : pr) { pi.push_back(p.first); pj.push_back(p.second); }
-    }
-    const uint32_t np = (uint32_t)pi.size();
-    Backend &be = default_backend();
-    // Without --mldist / --mldist_gap the distance of a pair reads (ident, total) of its count matrix and nothing else
-    // (DistanceFactoryML.h:143-146, 175-178): the device reduces them and 8 B per pair come back instead of 4 D^2.
-    const bool reduced = !(cmdlineopts.mldist_flag || cmdlineopts.mldist_gap_flag);
-    const size_t per = reduced ? 2 : (size_t)D * D;
-    // result buffers in pinned memory (the D2H copies write them directly), not zero-filled: every pair's slice is written by its tile
-    int32_t *counts = (int32_t *)be.host_alloc(std::max<size_t>(sizeof(int32_t) * (size_t)np * per, 16));
-    uint32_t *gaps = (uint32_t *)be.host_alloc(std::max<size_t>(4 * (size_t)np, 16));
-    for (uint32_t p = 0; p < np; ++p)
-        be.cells_nw += (uint64_t)(offs[pi[p] + 1] - offs[pi[p]]) * (offs[pj[p] + 1] - offs[pj[p]]);
-    auto t0 = std::chrono::steady_clock::now();
-    {
-        const int nw = std::max(1, be.workers());
-        // Tile size.  A call costs ~0.3 ms beside its kernel (staging of the inputs, launch, the last D2H: bench.py all_pairs_nw
-        // rank0_fixed_ms_per_call) and a worker hides that of tile k under the kernel of tile k+1 (two tiles in flight), so what
-        // matters is (a) that a tile fills a device — its persistent grid holds 7168 pairs at once; fewer pairs leave CUs idle —
-        // and (b) that the last tiles of the ticket queue are small against a worker's share.  Three tiles per worker, at least
-        // 256 pairs; the pairs are sorted by cost, so the last tiles are also the cheapest.  PGM_NW_TILE overrides.
-        uint32_t tile = std::max<uint32_t>(256u, (np + 3u * (uint32_t)nw - 1u) / (3u * (uint32_t)nw));
-        if (const char *e = getenv("PGM_NW_TILE")) tile = (uint32_t)std::max(1, atoi(e));
-        const uint32_t ntiles = np ? (np + tile - 1) / tile : 0;
-        std::atomic<uint32_t> next_tile(0);
-        auto farm = [&](int w) {
-            int pending = -1;
-            for (;;) {
-                const uint32_t t = next_tile.fetch_add(1);
-                if (t >= ntiles) break;
-                const uint32_t p0 = t * tile, cnt = std::min(tile, np - p0);
-                ++be.calls_dist;
-                const int ticket = be.nw_pairs_submit(D, scoring_matrix_.data(), gap_open, gap_extend, n, syms.data(), offs.data(), cnt, pi.data() + p0,
-                                                      pj.data() + p0, reduced ? 1u : 0u, counts + (size_t)p0 * per, gaps + p0, w);
-                if (pending >= 0) be.nw_pairs_wait(pending, w);
-                pending = ticket;
-            }
-            if (pending >= 0) be.nw_pairs_wait(pending, w);
-        };
-        std::vector<std::thread> devs;
-        for (int w = 1; w < nw; ++w) devs.emplace_back(farm, w);
-        farm(0);
-        for (auto &th : devs) th.join();
-        be.farm_workers = nw; be.farm_tiles = (int)ntiles;
-    }
-    be.seconds_nw += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    std::vector<double> seqlen(np);
-    for (uint32_t p = 0; p < np; ++p) seqlen[p] = ((double)(offs[pi[p] + 1] - offs[pi[p]]) + (double)(offs[pj[p] + 1] - offs[pj[p]])) / 2.0;
-    if (reduced) {
-        for (uint32_t p = 0; p < np; ++p) {
-            const distvar_t dv = computeDistance((double)counts[2 * (size_t)p], (double)counts[2 * (size_t)p + 1], nullptr, gaps[p], seqlen[p]);
-            distances.D(pi[p], pj[p]) = distances.D(pj[p], pi[p]) = dv.dist;
-            distances.V(pi[p], pj[p]) = distances.V(pj[p], pi[p]) = dv.var;
-        }
-    } else {
-        computeDistances(counts, gaps, seqlen, pi, pj, distances);
-    }
-    be.host_free(counts);
-    be.host_free(gaps);
-    dump_distances(distances);
-    return distances;
 }
 
 // ---- BioNJ (TreeNJ.cpp:22-29, 132-281; no fixed-topology plan) --------------------------------------
@@ -466,102 +319,28 @@ static void prealigned_row(const Alphabet &alphabet, const sequence_t &row, int8
     }
 }
 
-DistanceMatrix DistanceFactoryPrealigned::computePwDistances(const std::map<std::string, sequence_t> &aligned,
-                                                            const std::vector<std::string> &order) {
-    const uint32_t n = (uint32_t)order.size(), D = (uint32_t)alphabet.DIM;
-    DistanceMatrix distances((int)n);
-    std::vector<const sequence_t *> rows(n);
-    for (uint32_t i = 0; i < n; ++i) rows[i] = &aligned.at(order[i]);
-    std::vector<uint32_t> pi, pj;
-    for (uint32_t i = 0; i < n; ++i)
-        for (uint32_t j = i + 1; j < n; ++j) { pi.push_back(i); pj.push_back(j); }
-    const uint32_t np = (uint32_t)pi.size();
-    const size_t L = n ? rows[0]->size() : 0;
-    for (uint32_t i = 0; i < n; ++i)
-        if (rows[i]->size() != L) error("prealigned distances: rows of different length");
-    std::vector<int32_t> counts((size_t)np * D * D, 0);
-    std::vector<uint32_t> gaps(np, 0);
-    Backend &be = default_backend();
-    bool done = false;
-    if (!host_switches().host_counts && np) {
-        // the N^2 L column scan on the device (integer counts, bit-exact: on by default, unlike the ML estimates that follow):
-        // value() per residue, -1 for a gap, -2 for a residue without a value (and for the DNA unknown, value 4: the kernel counts
-        // every value below 20)
-        auto t0 = std::chrono::steady_clock::now();
-        std::vector<int8_t> mat((size_t)n * L);
-        for (uint32_t i = 0; i < n; ++i) prealigned_row(alphabet, *rows[i], mat.data() + (size_t)i * L);
-        {
-            // every pair costs the same (one scan of the columns): contiguous ranges of pairs, one per device context.  The entry
-            // point takes 20 to 64 states: DNA rows (values 0..3, -2) are counted as 20-state rows and the 4 x 4 corner of each
-            // 20 x 20 matrix is kept
-            const uint32_t Dk = std::max<uint32_t>(D, 20u);
-            std::vector<int32_t> wide(Dk != D ? (size_t)np * Dk * Dk : 0, 0);
-            int32_t *const cdst = Dk != D ? wide.data() : counts.data();
-            const int nw = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, be.workers()), np));
-            std::vector<char> ok((size_t)nw, 0);
-            auto part = [&](int w) {
-                const uint32_t p0 = (uint32_t)((uint64_t)np * (uint32_t)w / (uint32_t)nw), p1 = (uint32_t)((uint64_t)np * ((uint32_t)w + 1u) / (uint32_t)nw);
-                if (p1 != p0) ++be.calls_dist;
-                ok[(size_t)w] = (p1 == p0 || be.prealigned_counts_batch(Dk, n, (uint32_t)L, mat.data(), p1 - p0, pi.data() + p0, pj.data() + p0,
-                                                                       cdst + (size_t)p0 * Dk * Dk, gaps.data() + p0, w)) ? 1 : 0;
-            };
-            std::vector<std::thread> th;
-            for (int w = 1; w < nw; ++w) th.emplace_back(part, w);
-            part(0);
-            for (auto &t : th) t.join();
-            done = true;
-            for (char c : ok) done = done && c;
-            if (done && Dk != D)
-                for (size_t p = 0; p < np; ++p)
-                    for (uint32_t b = 0; b < D; ++b)
-                        for (uint32_t a = 0; a < D; ++a) counts[p * D * D + a + (size_t)D * b] = wide[p * Dk * Dk + a + (size_t)Dk * b];
+// the same scan on the host (PGM_HOST_COUNTS, or a backend without the kernel): c is the pair's zeroed D x D count matrix; returns
+// the gap openings
+static uint32_t prealigned_count_pair(const Alphabet &alphabet, const sequence_t &s1, const sequence_t &s2, int32_t *c) {
+    const size_t D = (size_t)alphabet.DIM;
+    const int cmax = alphabet.kind == ALPHA_DNA ? (int)D : 20;   // (the DNA unknown is not counted: see the device rows above)
+    uint32_t g = 0;
+    bool open1 = false, open2 = false;
+    for (size_t k = 0; k < s1.size(); ++k) {
+        const bool g1 = alphabet.isGap(s1[k]), g2 = alphabet.isGap(s2[k]);
+        if (!g1 && !g2) {
+            const int c1 = alphabet.value(s1[k]), c2 = alphabet.value(s2[k]);
+            if (c1 >= 0 && c1 < cmax && c2 >= 0 && c2 < cmax) ++c[(size_t)c1 + D * (size_t)c2];
+            open1 = false; open2 = false;
+        } else if (g1 && g2) {
+            // skip
+        } else if (!g1 && !open1) {
+            ++g; open1 = true; open2 = false;
+        } else if (!g2 && !open2) {
+            ++g; open1 = false; open2 = true;
         }
-        be.seconds_mldist += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
-    if (!done) {
-        auto t1 = std::chrono::steady_clock::now();
-        unsigned nt = std::thread::hardware_concurrency();
-        if (const char *e = getenv("PGM_HOST_THREADS")) nt = (unsigned)atoi(e);
-        nt = std::max(1u, std::min(nt, 16u));
-        nt = (unsigned)std::min<size_t>(nt, std::max<size_t>(1, np));
-        const int cmax = alphabet.kind == ALPHA_DNA ? (int)D : 20;   // (the DNA unknown is not counted: see the device rows above)
-        auto work = [&](unsigned t) {
-            for (size_t p = t; p < np; p += nt) {
-                const sequence_t &s1 = *rows[pi[p]], &s2 = *rows[pj[p]];
-                int32_t *c = counts.data() + p * D * D;
-                index_t g = 0;
-                bool open1 = false, open2 = false;
-                for (size_t k = 0; k < s1.size(); ++k) {
-                    const bool g1 = alphabet.isGap(s1[k]), g2 = alphabet.isGap(s2[k]);
-                    if (!g1 && !g2) {
-                        const int c1 = alphabet.value(s1[k]), c2 = alphabet.value(s2[k]);
-                        if (c1 >= 0 && c1 < cmax && c2 >= 0 && c2 < cmax) ++c[(size_t)c1 + (size_t)D * c2];
-                        open1 = false; open2 = false;
-                    } else if (g1 && g2) {
-                        // skip
-                    } else if (!g1 && !open1) {
-                        ++g; open1 = true; open2 = false;
-                    } else if (!g2 && !open2) {
-                        ++g; open1 = false; open2 = true;
-                    }
-                }
-                gaps[p] = g;
-            }
-        };
-        std::vector<std::thread> pool;
-        for (unsigned t = 1; t < nt; ++t) pool.emplace_back(work, t);
-        work(0);
-        for (auto &th : pool) th.join();
-        be.seconds_mldist += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
-    }
-    std::vector<double> seqlen(np, ((double)L + (double)L) / 2.0);
-    const auto tq0 = std::chrono::steady_clock::now();
-    computeDistances(counts.data(), gaps.data(), seqlen, pi, pj, distances);
-    if (host_switches().profile)
-        fprintf(stderr, "  prealigned distances: pair counts %s, estimates %.1f ms\n", done ? "on the device" : "on the host",
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tq0).count());
-    dump_distances(distances);
-    return distances;
+    return g;
 }
 
 // K = 2 for amino acids and codons, 6 for DNA (DistanceFactory.cpp:9-60): ncols = D^K = 400, 3721, 4096
@@ -619,26 +398,6 @@ static void angle_finish(DistanceMatrix &distances, const std::vector<double> &s
             v *= distances.D((int)i, (int)j);
             distances.V((int)i, (int)j) = std::max(v, 1e-5);
         }
-}
-
-DistanceMatrix angleDistances(const Alphabet &a, const std::map<std::string, sequence_t> &sequences, const std::vector<std::string> &order) {
-    const uint32_t n = (uint32_t)order.size(), ncols = angle_ncols(a);
-    DistanceMatrix distances((int)n);
-    std::vector<int32_t> counts((size_t)n * ncols, 0);
-    std::vector<double> seq_len(n);
-    parallel_for((size_t)n, [&](size_t i) {
-        const sequence_t &seq = sequences.at(order[i]);
-        seq_len[i] = (double)seq.size();
-        angle_count_row(a, seq, ncols, counts.data() + i * ncols);
-    });
-    Backend &be = default_backend();
-    const auto t0 = std::chrono::steady_clock::now();
-    ++be.calls_dist;
-    be.kmer_cosine(n, ncols, counts.data(), distances.distances.data());   // :100
-    be.seconds_mldist += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    angle_finish(distances, seq_len, true);
-    dump_distances(distances);
-    return distances;
 }
 
 // ---- LeastSquares::refineTree (LeastSquares.cpp) ----------------------------------------------------------------------
@@ -1124,42 +883,8 @@ PhyTree *refineTree(PhyTree *tree, const std::vector<std::string> &leaf_order, c
     return tree;
 }
 
-PhyTree *TreeNJ(const Alphabet &a, const std::map<std::string, sequence_t> &seqs, const ModelFactory *mf, bool prealigned) {
-    if (seqs.size() < 2) error("cannot construct tree from < 2 sequences");
-    if (prealigned) {
-        std::vector<std::string> order;
-        for (const auto &kv : seqs) order.push_back(kv.first);
-        DistanceFactoryPrealigned df(a, mf);
-        const auto tq0 = std::chrono::steady_clock::now();
-        DistanceMatrix dist = df.computePwDistances(seqs, order);
-        for (int i = 0; i < dist.dim; ++i) { dist.D(i, i) = 0; dist.V(i, i) = 0; }
-        const auto tq1 = std::chrono::steady_clock::now();
-        PhyTree *t = buildNJTree(order, dist);
-        if (cmdlineopts.wlsrefine_flag) t = refineTree(t, order, dist);   // TreeNJ.h:52-54
-        t = midpointRoot(t);
-        if (host_switches().profile)
-            fprintf(stderr, "  TreeNJ: distances %.1f ms, BioNJ + rooting %.1f ms\n", std::chrono::duration<double, std::milli>(tq1 - tq0).count(),
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tq1).count());
-        return t;
-    }
-    std::vector<std::string> order;
-    for (const auto &kv : seqs) order.push_back(kv.first);  // std::map key order (TreeNJ.h:34-39)
-    if (!cmdlineopts.nwdist_flag) {   // DistanceFactory::getDefault (DistanceFactory.cpp:9-20): the k-mer angle distances
-        DistanceMatrix dist = angleDistances(a, seqs, order);
-        for (int i = 0; i < dist.dim; ++i) { dist.D(i, i) = 0; dist.V(i, i) = 0; }
-        PhyTree *tree = buildNJTree(order, dist);
-        if (cmdlineopts.wlsrefine_flag) tree = refineTree(tree, order, dist);
-        return midpointRoot(tree);
-    }
-    DistanceFactoryAlign df(a, mf);
-    DistanceMatrix dist = df.computePwDistances(seqs, order);
-    for (int i = 0; i < dist.dim; ++i) { dist.D(i, i) = 0; dist.V(i, i) = 0; }
-    PhyTree *tree = buildNJTree(order, dist);
-    if (cmdlineopts.wlsrefine_flag) tree = refineTree(tree, order, dist);
-    return midpointRoot(tree);
-}
 
-// ==== many families per call (--batch) ================================================================================
+// ==== the guide tree: TreeNJ for one family, TreeNJ_multi for the families of a --batch chunk ===========================
 // The defaults of the two multi-family entries: the per-family entries, one family after the other (a backend without segmented
 // kernels of its own: the CPU oracle).
 void Backend::kmer_cosine_multi(uint32_t nfam, const uint32_t *nseq, uint32_t ncols, const int32_t *counts, double *cosine, int worker) {
@@ -1195,84 +920,329 @@ bool Backend::prealigned_counts_multi(uint32_t dim, uint32_t nfam, const uint32_
 }
 
 namespace {
-// the pairs [p0, p0 + np) of a chunk's shared pair arrays are those of one family
+// the pairs [p0, p0 + np) of a call's shared pair arrays are those of one family
 struct PairBlock {
-    const DistanceFactoryML *df;
     const ModelFactory *model_factory;
     size_t p0;
     uint32_t np;
-    DistanceMatrix *out;
 };
-}  // namespace
 
-// DistanceFactoryML::computeDistances for the families of a chunk.  On the device (PGM_DEVICE_MLDIST): one call over the pairs of all
-// families that share a model — every family without -F, one call per family with it.  On the host: the pairs of all families dealt
-// to the host threads; every pair's arithmetic is computeDistance's.
-static void compute_distances_multi(const Alphabet &a, const std::vector<PairBlock> &blocks, const int32_t *counts, const uint32_t *gaps,
-                                    const double *seqlen, const uint32_t *pi, const uint32_t *pj) {
-    if (blocks.empty()) return;
+// The families of one call.  Their sequences stand one after the other in `seq` (family f: first[f] .. first[f + 1], in std::map key
+// order like TreeNJ.h:34-39), their pairs i < j one after the other in pfam / pi / pj (family f: blocks[f]; pi, pj count within the
+// family; df[f] estimates them into dist[f]).  One family is the solo run: first[0] = p0 = 0.
+struct Families {
+    uint32_t nfam = 0;
+    std::vector<uint32_t> nseq, first;
+    std::vector<const sequence_t *> seq;
+    std::vector<std::vector<std::string>> order;
+    std::vector<DistanceFactoryML> df;
+    std::vector<DistanceMatrix> dist;
+    std::vector<uint32_t> pfam, pi, pj;
+    std::vector<PairBlock> blocks;
+    const sequence_t &row(uint32_t f, uint32_t i) const { return *seq[first[f] + i]; }
+    uint32_t np() const { return (uint32_t)pi.size(); }
+
+    // the pairs i < j of every family, in row-major order or (the all-pairs farm) the longest pairs of a family first
+    void all_pairs(bool longest_first) {
+        for (uint32_t f = 0; f < nfam; ++f) {
+            std::vector<std::pair<uint32_t, uint32_t>> pr;
+            for (uint32_t i = 0; i < nseq[f]; ++i)
+                for (uint32_t j = i + 1; j < nseq[f]; ++j) pr.push_back({i, j});
+            if (longest_first) {
+                auto cost = [&](const std::pair<uint32_t, uint32_t> &p) { return (uint64_t)row(f, p.first).size() * row(f, p.second).size(); };
+                std::stable_sort(pr.begin(), pr.end(), [&](const std::pair<uint32_t, uint32_t> &x, const std::pair<uint32_t, uint32_t> &y) { return cost(x) > cost(y); });
+            }
+            blocks[f].p0 = pi.size();
+            blocks[f].np = (uint32_t)pr.size();
+            for (const auto &p : pr) { pfam.push_back(f); pi.push_back(p.first); pj.push_back(p.second); }
+        }
+    }
+    void set(uint32_t p, double d, double v) {   // the estimate of pair p into its family's symmetric matrices
+        DistanceMatrix &dm = dist[pfam[p]];
+        dm.D(pi[p], pj[p]) = dm.D(pj[p], pi[p]) = d;
+        dm.V(pi[p], pj[p]) = dm.V(pj[p], pi[p]) = v;
+    }
+};
+
+// The model as pgm_mldist_batch takes it: in eigen form when it has one of at most 20 states, else in general form (Q alone: the
+// 61-state ECM model, a generator that is not reversible)
+pgm_mldist_model mldist_model(const Alphabet &a, const ModelFactory &mf, bool eigen_form) {
+    double DIST_MAX, VAR_MAX, VAR_MIN;
+    consts(a, DIST_MAX, VAR_MAX, VAR_MIN);
+    pgm_mldist_model m;
+    m.dim = (uint32_t)a.DIM; m.Q = mf.Qmat().data();
+    m.V = eigen_form ? mf.eigV().data() : nullptr; m.Vi = eigen_form ? mf.eigVi().data() : nullptr;
+    m.sigma = eigen_form ? mf.eigSigma().data() : nullptr;
+    m.dist_max = DIST_MAX; m.var_max = VAR_MAX; m.var_min = VAR_MIN; m.cutoff_dist = cmdlineopts.cutoff_dist;
+    m.min_dist = cmdlineopts.min_dist; m.max_dist = cmdlineopts.max_dist; m.indel_rate = cmdlineopts.indel_rate;
+    m.mldist = cmdlineopts.mldist_flag ? 1 : 0; m.mldist_gap = cmdlineopts.mldist_gap_flag ? 1 : 0;
+    return m;
+}
+
+// computeDistance of every pair from its count matrix.  On the device (PGM_DEVICE_MLDIST): one pgm_mldist_batch call over the pairs
+// of all families that share a model — every family without -F, one call per family with it —, in the form that model takes (eigen
+// form: one wavefront per pair, general form: one workgroup per pair, if the backend's kernel takes that); the arithmetic is
+// computeDistance's except for the device library's exp / log (last-bit differences: see csrc/pgm_dist_kernels.h) and, for a model
+// of more than 20 states that has an eigen form, P(d) = exp(Q d) by expm instead of that form.  Else on the host: Newton on d per
+// pair, each step a P(d), independent per pair, so the pairs are dealt to the host threads; every pair's arithmetic is the
+// single-threaded one, the matrix entries written are disjoint.
+void estimate_distances(const Alphabet &a, Families &F, const int32_t *counts, const uint32_t *gaps, const double *seqlen) {
     const uint32_t D = (uint32_t)a.DIM;
     const size_t dd = (size_t)D * D;
+    const std::vector<PairBlock> &blocks = F.blocks;
     Backend &be = default_backend();
     const auto t1 = std::chrono::steady_clock::now();
-    // per group of families that share a model: on the device in the form computeDistances would choose for that model alone (so a
-    // family's estimates are those of its solo run), else on the host
     std::vector<char> on_device(blocks.size(), 0);
-    bool done = false;
-    if (host_switches().device_mldist) {
-        double DIST_MAX, VAR_MAX, VAR_MIN;
-        consts(a, DIST_MAX, VAR_MAX, VAR_MIN);
-        done = true;
+    if (host_switches().device_mldist)
         for (size_t b0 = 0; b0 < blocks.size();) {
             const size_t b1 = cmdlineopts.aafreqs_flag ? b0 + 1 : blocks.size();   // (the blocks are contiguous in the pair arrays)
-            const ModelFactory *mf = blocks[b0].model_factory;
-            const bool eigen = mf->has_eigen() && D <= 20;
+            const ModelFactory &mf = *blocks[b0].model_factory;
+            const bool eigen_form = mf.has_eigen() && D <= 20;
             const size_t p0 = blocks[b0].p0, p1 = blocks[b1 - 1].p0 + blocks[b1 - 1].np;
-            bool ok = eigen || (be.mldist_general() && D <= 64);
+            bool ok = eigen_form || (be.mldist_general() && D <= 64);
             std::vector<double> dist(p1 - p0), var(p1 - p0);
             if (ok && p1 > p0) {
-                pgm_mldist_model m;
-                m.dim = D; m.Q = mf->Qmat().data();
-                m.V = eigen ? mf->eigV().data() : nullptr; m.Vi = eigen ? mf->eigVi().data() : nullptr; m.sigma = eigen ? mf->eigSigma().data() : nullptr;
-                m.dist_max = DIST_MAX; m.var_max = VAR_MAX; m.var_min = VAR_MIN; m.cutoff_dist = cmdlineopts.cutoff_dist;
-                m.min_dist = cmdlineopts.min_dist; m.max_dist = cmdlineopts.max_dist; m.indel_rate = cmdlineopts.indel_rate;
-                m.mldist = cmdlineopts.mldist_flag ? 1 : 0; m.mldist_gap = cmdlineopts.mldist_gap_flag ? 1 : 0;
+                const pgm_mldist_model m = mldist_model(a, mf, eigen_form);
                 ++be.calls_dist;
                 ok = be.mldist_batch(m, (uint32_t)(p1 - p0), counts + p0 * dd, gaps + p0, seqlen + p0, dist.data(), var.data());
             }
-            for (size_t b = b0; b < b1 && ok; ++b) {
-                on_device[b] = 1;
-                for (size_t p = blocks[b].p0; p < blocks[b].p0 + blocks[b].np; ++p) {
-                    DistanceMatrix &dm = *blocks[b].out;
-                    dm.D(pi[p], pj[p]) = dm.D(pj[p], pi[p]) = dist[p - p0];
-                    dm.V(pi[p], pj[p]) = dm.V(pj[p], pi[p]) = var[p - p0];
-                }
-            }
-            done = done && ok;
+            for (size_t b = b0; b < b1 && ok; ++b) on_device[b] = 1;
+            for (size_t p = p0; p < p1 && ok; ++p) F.set((uint32_t)p, dist[p - p0], var[p - p0]);
             b0 = b1;
         }
-    }
-    if (!done) {
-        std::vector<std::pair<uint32_t, uint32_t>> work;   // (block, pair of the block)
-        for (size_t b = 0; b < blocks.size(); ++b)
-            for (uint32_t k = 0; k < blocks[b].np && !on_device[b]; ++k) work.emplace_back((uint32_t)b, k);
-        const size_t grain = 16;   // pairs per index handed out
-        parallel_for((work.size() + grain - 1) / grain, [&](size_t g) {
-            std::vector<int32_t> c(dd);
-            for (size_t q = g * grain; q < std::min(work.size(), (g + 1) * grain); ++q) {
-                const PairBlock &b = blocks[work[q].first];
-                const size_t p = b.p0 + work[q].second;
-                std::copy(counts + p * dd, counts + (p + 1) * dd, c.begin());
-                const distvar_t dv = b.df->computeDistance(c, gaps[p], seqlen[p]);
-                b.out->D(pi[p], pj[p]) = b.out->D(pj[p], pi[p]) = dv.dist;
-                b.out->V(pi[p], pj[p]) = b.out->V(pj[p], pi[p]) = dv.var;
-            }
-        });
-    }
+    std::vector<uint32_t> work;   // the pairs left to the host
+    for (size_t b = 0; b < blocks.size(); ++b)
+        for (uint32_t k = 0; k < blocks[b].np && !on_device[b]; ++k) work.push_back((uint32_t)blocks[b].p0 + k);
+    const size_t grain = 16;   // pairs per index handed out
+    parallel_for((work.size() + grain - 1) / grain, [&](size_t g) {
+        std::vector<int32_t> c(dd);
+        for (size_t q = g * grain; q < std::min(work.size(), (g + 1) * grain); ++q) {
+            const size_t p = work[q];
+            std::copy(counts + p * dd, counts + (p + 1) * dd, c.begin());
+            const distvar_t dv = F.df[F.pfam[p]].computeDistance(c, gaps[p], seqlen[p]);
+            F.set((uint32_t)p, dv.dist, dv.var);
+        }
+    });
     be.seconds_mldist += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
 }
 
-void TreeNJ_multi(const Alphabet &a, std::vector<TreeJob> &jobs, bool prealigned) {
+// fn(w) for every worker w < nw, one host thread per device context (worker 0 on this thread).  An exception does not leave its
+// thread (that would end the process): the first one is thrown here once all have joined.
+void on_workers(int nw, const std::function<void(int)> &fn) {
+    std::vector<std::string> errs((size_t)nw);
+    auto run = [&](int w) { try { fn(w); } catch (std::exception &e) { errs[(size_t)w] = e.what(); } };
+    std::vector<std::thread> th;
+    for (int w = 1; w < nw; ++w) th.emplace_back(run, w);
+    run(0);
+    for (auto &t : th) t.join();
+    for (const std::string &e : errs) if (!e.empty()) throw pgm_exception(e);
+}
+
+// symbols of the all-pairs alignment: value(), negative -> 20 for amino acids and codons (the reference's quirk,
+// DistanceFactoryAlign.h:72,79); DNA has no negative values (sequenceFromString refuses other characters) and its unknown is DIM, the
+// X row of its scoring matrix
+void nw_symbols(const Alphabet &a, const std::vector<const sequence_t *> &seq, std::vector<int8_t> &syms, std::vector<uint32_t> &offs) {
+    const int unknown_sym = a.kind == ALPHA_DNA ? a.DIM : 20;
+    offs.assign(1, 0);
+    for (const sequence_t *s : seq) {
+        for (int8_t c : *s) {
+            const int v = a.value(c);
+            syms.push_back((int8_t)(v < 0 ? unknown_sym : v));
+        }
+        offs.push_back((uint32_t)syms.size());
+    }
+}
+
+// The reference's i < j double loop (DistanceFactoryAlign.h:35-53) is a farm of independent alignPair jobs.  Here: the pairs (gi, gj:
+// by their sequences' places among the nseq of the call) cut into tiles, and one host thread per device context pulling tile numbers
+// from an atomic counter (no collective, no static partition: a slower device simply takes fewer tiles).  Every tile is one
+// pgm_nw_pairs_submit call on the worker's own context; the outputs of a pair land at the pair's position, whoever computed it, so
+// the result does not depend on the number of workers.
+void nw_farm(const DistanceFactoryAlign &dfa, uint32_t D, uint32_t nseq, const std::vector<int8_t> &syms, const std::vector<uint32_t> &offs,
+             const std::vector<uint32_t> &gi, const std::vector<uint32_t> &gj, bool reduced, int32_t *counts, uint32_t *gaps) {
+    Backend &be = default_backend();
+    const uint32_t np = (uint32_t)gi.size();
+    const size_t per = reduced ? 2 : (size_t)D * D;
+    const int nw = std::max(1, be.workers());
+    // Tile size.  A call costs ~0.3 ms beside its kernel (staging of the inputs, launch, the last D2H: bench.py all_pairs_nw
+    // rank0_fixed_ms_per_call) and a worker hides that of tile k under the kernel of tile k+1 (two tiles in flight), so what
+    // matters is (a) that a tile fills a device — its persistent grid holds 7168 pairs at once; fewer pairs leave CUs idle —
+    // and (b) that the last tiles of the ticket queue are small against a worker's share.  Three tiles per worker, at least
+    // 256 pairs; the pairs are sorted by cost, so the last tiles are also the cheapest.  PGM_NW_TILE overrides.
+    uint32_t tile = std::max<uint32_t>(256u, (np + 3u * (uint32_t)nw - 1u) / (3u * (uint32_t)nw));
+    if (const char *e = getenv("PGM_NW_TILE")) tile = (uint32_t)std::max(1, atoi(e));
+    const uint32_t ntiles = np ? (np + tile - 1) / tile : 0;
+    std::atomic<uint32_t> next_tile(0);
+    be.farm_workers = nw; be.farm_tiles = (int)ntiles;
+    on_workers(nw, [&](int w) {
+        int pending = -1;
+        for (;;) {
+            const uint32_t t = next_tile.fetch_add(1);
+            if (t >= ntiles) break;
+            const uint32_t p0 = t * tile, cnt = std::min(tile, np - p0);
+            ++be.calls_dist;
+            const int ticket = be.nw_pairs_submit(D, dfa.scoring_matrix().data(), dfa.gap_open, dfa.gap_extend, nseq, syms.data(), offs.data(), cnt,
+                                                  gi.data() + p0, gj.data() + p0, reduced ? 1u : 0u, counts + (size_t)p0 * per, gaps + p0, w);
+            if (pending >= 0) be.nw_pairs_wait(pending, w);
+            pending = ticket;
+        }
+        if (pending >= 0) be.nw_pairs_wait(pending, w);
+    });
+}
+
+// -a (DistanceFactoryAlign.h:29-56): one farm of alignPair tiles over the sequences of all families, within-family pairs only
+void nw_distances(const Alphabet &a, Families &F) {
+    const uint32_t D = (uint32_t)a.DIM;
+    Backend &be = default_backend();
+    DistanceFactoryAlign dfa(a, F.blocks[0].model_factory);   // (the scoring matrix and the gap costs: the run's)
+    std::vector<int8_t> syms;
+    std::vector<uint32_t> offs;
+    nw_symbols(a, F.seq, syms, offs);
+    F.all_pairs(true);
+    const uint32_t np = F.np();
+    std::vector<uint32_t> gi(np), gj(np);
+    for (uint32_t p = 0; p < np; ++p) { gi[p] = F.first[F.pfam[p]] + F.pi[p]; gj[p] = F.first[F.pfam[p]] + F.pj[p]; }
+    auto len = [&](uint32_t s) { return offs[s + 1] - offs[s]; };
+    // Without --mldist / --mldist_gap the distance of a pair reads (ident, total) of its count matrix and nothing else
+    // (DistanceFactoryML.h:143-146, 175-178): the device reduces them and 8 B per pair come back instead of 4 D^2.
+    const bool reduced = !(cmdlineopts.mldist_flag || cmdlineopts.mldist_gap_flag);
+    const size_t per = reduced ? 2 : (size_t)D * D;
+    // result buffers in pinned memory (the D2H copies write them directly), not zero-filled: every pair's slice is written by its tile
+    int32_t *counts = (int32_t *)be.host_alloc(std::max<size_t>(sizeof(int32_t) * (size_t)np * per, 16));
+    uint32_t *gaps = (uint32_t *)be.host_alloc(std::max<size_t>(4 * (size_t)np, 16));
+    try {
+        for (uint32_t p = 0; p < np; ++p) be.cells_nw += (uint64_t)len(gi[p]) * len(gj[p]);
+        const auto t0 = std::chrono::steady_clock::now();
+        nw_farm(dfa, D, (uint32_t)F.seq.size(), syms, offs, gi, gj, reduced, counts, gaps);
+        be.seconds_nw += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        std::vector<double> seqlen(np);
+        for (uint32_t p = 0; p < np; ++p) seqlen[p] = ((double)len(gi[p]) + (double)len(gj[p])) / 2.0;
+        if (reduced) {
+            for (uint32_t p = 0; p < np; ++p) {
+                const distvar_t dv = F.df[F.pfam[p]].computeDistance((double)counts[2 * (size_t)p], (double)counts[2 * (size_t)p + 1], nullptr, gaps[p], seqlen[p]);
+                F.set(p, dv.dist, dv.var);
+            }
+        } else {
+            estimate_distances(a, F, counts, gaps, seqlen.data());
+        }
+    } catch (...) {
+        be.host_free(counts);
+        be.host_free(gaps);
+        throw;
+    }
+    be.host_free(counts);
+    be.host_free(gaps);
+}
+
+// Distances induced by the families' alignments: pair counts on the device (integer counts, bit-exact: on by default, unlike the ML
+// estimates that follow), on the host threads with PGM_HOST_COUNTS or a backend without the kernel, then the estimates.
+// per_family_calls: see tree_nj.
+void prealigned_distances(const Alphabet &a, Families &F, bool per_family_calls) {
+    const uint32_t D = (uint32_t)a.DIM, nfam = F.nfam;
+    const size_t dd = (size_t)D * D;
+    Backend &be = default_backend();
+    F.all_pairs(false);
+    const uint32_t np = F.np();
+    std::vector<uint32_t> ncols(nfam);
+    for (uint32_t f = 0; f < nfam; ++f) ncols[f] = (uint32_t)F.row(f, 0).size();
+    std::vector<int32_t> counts((size_t)np * dd, 0);
+    std::vector<uint32_t> gaps(np, 0);
+    bool done = false;
+    if (!host_switches().host_counts) {
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<size_t> base(nfam + 1, 0);   // every family's nseq x ncols matrix, back to back
+        for (uint32_t f = 0; f < nfam; ++f) base[f + 1] = base[f] + (size_t)F.nseq[f] * ncols[f];
+        std::vector<int8_t> mat(base[nfam]);
+        parallel_for(nfam, [&](size_t f) {
+            for (uint32_t i = 0; i < F.nseq[f]; ++i) prealigned_row(a, F.row((uint32_t)f, i), mat.data() + base[f] + (size_t)i * ncols[f]);
+        });
+        // The entry points take 20 to 64 states: DNA rows (values 0..3, -2) are counted as 20-state rows and the 4 x 4 corner of each
+        // 20 x 20 matrix is kept
+        const uint32_t Dk = std::max<uint32_t>(D, 20u);
+        std::vector<int32_t> wide(Dk != D ? (size_t)np * Dk * Dk : 0, 0);
+        int32_t *const cdst = Dk != D ? wide.data() : counts.data();
+        done = true;
+        if (!per_family_calls) {
+            ++be.calls_dist;
+            done = be.prealigned_counts_multi(Dk, nfam, F.nseq.data(), ncols.data(), mat.data(), np, F.pfam.data(), F.pi.data(), F.pj.data(), cdst, gaps.data());
+        } else
+            for (uint32_t f = 0; f < nfam; ++f) {
+                // every pair costs the same (one scan of the columns): contiguous ranges of the family's pairs, one per device context
+                const size_t q0 = F.blocks[f].p0;
+                const uint32_t nq = F.blocks[f].np;
+                const int nw = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, be.workers()), nq));
+                std::vector<char> ok((size_t)nw, 0);
+                on_workers(nw, [&](int w) {
+                    const uint32_t p0 = (uint32_t)((uint64_t)nq * (uint32_t)w / (uint32_t)nw), p1 = (uint32_t)((uint64_t)nq * ((uint32_t)w + 1u) / (uint32_t)nw);
+                    if (p1 != p0) ++be.calls_dist;
+                    ok[(size_t)w] = (p1 == p0 || be.prealigned_counts_batch(Dk, F.nseq[f], ncols[f], mat.data() + base[f], p1 - p0, F.pi.data() + q0 + p0,
+                                                                           F.pj.data() + q0 + p0, cdst + (q0 + p0) * Dk * Dk, gaps.data() + q0 + p0, w)) ? 1 : 0;
+                });
+                for (char c : ok) done = done && c;
+            }
+        if (done && Dk != D)
+            for (size_t p = 0; p < np; ++p)
+                for (uint32_t b = 0; b < D; ++b)
+                    for (uint32_t c = 0; c < D; ++c) counts[p * dd + c + (size_t)D * b] = wide[p * Dk * Dk + c + (size_t)Dk * b];
+        be.seconds_mldist += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+    if (!done) {
+        const auto t1 = std::chrono::steady_clock::now();
+        const size_t grain = 16;   // pairs per index handed out
+        parallel_for(((size_t)np + grain - 1) / grain, [&](size_t g) {
+            for (size_t p = g * grain; p < std::min<size_t>(np, (g + 1) * grain); ++p) {
+                std::fill(counts.begin() + (std::ptrdiff_t)(p * dd), counts.begin() + (std::ptrdiff_t)((p + 1) * dd), 0);   // (a device call that failed may have written)
+                gaps[p] = prealigned_count_pair(a, F.row(F.pfam[p], F.pi[p]), F.row(F.pfam[p], F.pj[p]), counts.data() + p * dd);
+            }
+        });
+        be.seconds_mldist += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+    }
+    std::vector<double> seqlen(np);
+    for (size_t p = 0; p < np; ++p) seqlen[p] = ((double)ncols[F.pfam[p]] + (double)ncols[F.pfam[p]]) / 2.0;
+    const auto tq0 = std::chrono::steady_clock::now();
+    estimate_distances(a, F, counts.data(), gaps.data(), seqlen.data());
+    if (host_switches().profile && nfam == 1)
+        fprintf(stderr, "  prealigned distances: pair counts %s, estimates %.1f ms\n", done ? "on the device" : "on the host",
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tq0).count());
+}
+
+// DistanceFactory::getDefault (DistanceFactory.cpp:9-20), DistanceFactoryAngle<ALPHABET, K> (DistanceFactoryAngle.h:55-131): the
+// default initial distances (no -a), the cosine of the k-mer count vectors turned into a distance.  The count rows of all families
+// back to back; per_family_calls: see tree_nj.
+void angle_distances(const Alphabet &a, Families &F, bool per_family_calls) {
+    const uint32_t nfam = F.nfam, ncols = angle_ncols(a);
+    Backend &be = default_backend();
+    std::vector<size_t> out0(nfam + 1, 0);
+    for (uint32_t f = 0; f < nfam; ++f) out0[f + 1] = out0[f] + (size_t)F.nseq[f] * F.nseq[f];
+    std::vector<int32_t> counts(F.seq.size() * ncols, 0);
+    std::vector<double> cosine(out0[nfam], 0.0);
+    parallel_for(F.seq.size(), [&](size_t s) { angle_count_row(a, *F.seq[s], ncols, counts.data() + s * ncols); });
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!per_family_calls) {
+        ++be.calls_dist;
+        be.kmer_cosine_multi(nfam, F.nseq.data(), ncols, counts.data(), cosine.data());
+    } else
+        for (uint32_t f = 0; f < nfam; ++f) {
+            ++be.calls_dist;
+            be.kmer_cosine(F.nseq[f], ncols, counts.data() + (size_t)F.first[f] * ncols, cosine.data() + out0[f]);   // :100
+        }
+    be.seconds_mldist += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    // one family: its rows on the host threads; several: the families
+    parallel_for(nfam, [&](size_t f) {
+        std::copy(cosine.begin() + (std::ptrdiff_t)out0[f], cosine.begin() + (std::ptrdiff_t)out0[f + 1], F.dist[f].distances.begin());
+        std::vector<double> seq_len(F.nseq[f]);
+        for (uint32_t i = 0; i < F.nseq[f]; ++i) seq_len[i] = (double)F.row((uint32_t)f, i).size();
+        angle_finish(F.dist[f], seq_len, nfam == 1);
+    });
+}
+
+// TreeNJ.h:27-59 for a list of families: one of the three distance stages over the pairs of all of them, then BioNJ, the -W
+// refinement (TreeNJ.h:52-54) and the rooting per family.  per_family_calls is all that tells the two entry points apart: the
+// cosine matrix and the pair counts of an alignment through the per-family entries of the backend (TreeNJ: kmer_cosine, and
+// prealigned_counts_batch over every device context), or through the entries that take all families in one call on worker 0
+// (TreeNJ_multi).  Either way a family's matrices, and so its tree, are the same.
+void tree_nj(const Alphabet &a, std::vector<TreeJob> &jobs, bool prealigned, bool per_family_calls) {
+    const auto tq0 = std::chrono::steady_clock::now();
     std::vector<size_t> act;
     for (size_t j = 0; j < jobs.size(); ++j) {
         jobs[j].tree = nullptr;
@@ -1287,179 +1257,50 @@ void TreeNJ_multi(const Alphabet &a, std::vector<TreeJob> &jobs, bool prealigned
         act.push_back(j);
     }
     if (act.empty()) return;
-    Backend &be = default_backend();
-    const uint32_t nfam = (uint32_t)act.size(), D = (uint32_t)a.DIM;
-    const size_t dd = (size_t)D * D;
-    std::vector<std::vector<std::string>> order(nfam);   // std::map key order (TreeNJ.h:34-39)
-    std::vector<std::vector<const sequence_t *>> seq(nfam);
-    std::vector<DistanceMatrix> dist;
-    dist.reserve(nfam);
-    std::vector<uint32_t> nseq(nfam);
+    Families F;
+    const uint32_t nfam = F.nfam = (uint32_t)act.size();
+    F.nseq.resize(nfam); F.first.resize(nfam); F.order.resize(nfam); F.blocks.resize(nfam);
     for (uint32_t f = 0; f < nfam; ++f) {
-        for (const auto &kv : *jobs[act[f]].seqs) { order[f].push_back(kv.first); seq[f].push_back(&kv.second); }
-        nseq[f] = (uint32_t)order[f].size();
-        dist.emplace_back((int)nseq[f]);
+        const TreeJob &job = jobs[act[f]];
+        F.first[f] = (uint32_t)F.seq.size();
+        for (const auto &kv : *job.seqs) { F.order[f].push_back(kv.first); F.seq.push_back(&kv.second); }
+        F.nseq[f] = (uint32_t)F.order[f].size();
+        F.df.emplace_back(a, job.model_factory);
+        F.dist.emplace_back((int)F.nseq[f]);
+        F.blocks[f] = PairBlock{job.model_factory, 0, 0};
     }
-    std::vector<DistanceFactoryML> dfml;
-    dfml.reserve(nfam);
-    for (uint32_t f = 0; f < nfam; ++f) dfml.emplace_back(a, jobs[act[f]].model_factory);
-    // the pairs i < j of every family, the families one after the other
-    std::vector<uint32_t> pfam, pi, pj;
-    std::vector<PairBlock> blocks(nfam);
-    auto all_pairs = [&](const std::function<void(uint32_t, std::vector<std::pair<uint32_t, uint32_t>> &)> &arrange) {
-        for (uint32_t f = 0; f < nfam; ++f) {
-            std::vector<std::pair<uint32_t, uint32_t>> pr;
-            for (uint32_t i = 0; i < nseq[f]; ++i)
-                for (uint32_t j = i + 1; j < nseq[f]; ++j) pr.push_back({i, j});
-            arrange(f, pr);
-            blocks[f] = PairBlock{&dfml[f], jobs[act[f]].model_factory, pi.size(), (uint32_t)pr.size(), &dist[f]};
-            for (const auto &p : pr) { pfam.push_back(f); pi.push_back(p.first); pj.push_back(p.second); }
-        }
-    };
-    bool solo = false;   // a stage this call cannot share: every family through TreeNJ alone
-    if (prealigned) {
-        if (host_switches().host_counts) solo = true;
-        else {
-            all_pairs([](uint32_t, std::vector<std::pair<uint32_t, uint32_t>> &) {});
-            const uint32_t np = (uint32_t)pi.size();
-            std::vector<uint32_t> ncols(nfam);
-            std::vector<size_t> base(nfam + 1, 0);
-            for (uint32_t f = 0; f < nfam; ++f) { ncols[f] = (uint32_t)seq[f][0]->size(); base[f + 1] = base[f] + (size_t)nseq[f] * ncols[f]; }
-            std::vector<int8_t> mat(base[nfam]);
-            parallel_for(nfam, [&](size_t f) {
-                for (uint32_t i = 0; i < nseq[f]; ++i) prealigned_row(a, *seq[f][i], mat.data() + base[f] + (size_t)i * ncols[f]);
-            });
-            // (the entry point takes 20 to 64 states: DNA rows are counted as 20-state rows and the 4 x 4 corner is kept)
-            const uint32_t Dk = std::max<uint32_t>(D, 20u);
-            std::vector<int32_t> counts((size_t)np * dd, 0), wide(Dk != D ? (size_t)np * Dk * Dk : 0, 0);
-            std::vector<uint32_t> gaps(np, 0);
-            const auto t0 = std::chrono::steady_clock::now();
-            ++be.calls_dist;
-            const bool done = be.prealigned_counts_multi(Dk, nfam, nseq.data(), ncols.data(), mat.data(), np, pfam.data(), pi.data(), pj.data(),
-                                                         Dk != D ? wide.data() : counts.data(), gaps.data());
-            be.seconds_mldist += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            if (!done) solo = true;
-            else {
-                if (Dk != D)
-                    for (size_t p = 0; p < np; ++p)
-                        for (uint32_t b = 0; b < D; ++b)
-                            for (uint32_t c = 0; c < D; ++c) counts[p * dd + c + (size_t)D * b] = wide[p * Dk * Dk + c + (size_t)Dk * b];
-                std::vector<double> seqlen(np);
-                for (size_t p = 0; p < np; ++p) seqlen[p] = ((double)ncols[pfam[p]] + (double)ncols[pfam[p]]) / 2.0;
-                compute_distances_multi(a, blocks, counts.data(), gaps.data(), seqlen.data(), pi.data(), pj.data());
-            }
-        }
-    } else if (!cmdlineopts.nwdist_flag) {
-        // the k-mer angle distances: the count rows of all families back to back, one cosine call
-        const uint32_t ncols = angle_ncols(a);
-        std::vector<size_t> row0(nfam + 1, 0), out0(nfam + 1, 0);
-        for (uint32_t f = 0; f < nfam; ++f) { row0[f + 1] = row0[f] + nseq[f]; out0[f + 1] = out0[f] + (size_t)nseq[f] * nseq[f]; }
-        std::vector<int32_t> counts(row0[nfam] * ncols, 0);
-        std::vector<double> cosine(out0[nfam], 0.0);
-        parallel_for(nfam, [&](size_t f) {
-            for (uint32_t i = 0; i < nseq[f]; ++i) angle_count_row(a, *seq[f][i], ncols, counts.data() + (row0[f] + i) * ncols);
-        });
-        const auto t0 = std::chrono::steady_clock::now();
-        ++be.calls_dist;
-        be.kmer_cosine_multi(nfam, nseq.data(), ncols, counts.data(), cosine.data());
-        be.seconds_mldist += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        parallel_for(nfam, [&](size_t f) {
-            std::copy(cosine.begin() + (std::ptrdiff_t)out0[f], cosine.begin() + (std::ptrdiff_t)out0[f + 1], dist[f].distances.begin());
-            std::vector<double> seq_len(nseq[f]);
-            for (uint32_t i = 0; i < nseq[f]; ++i) seq_len[i] = (double)seq[f][i]->size();
-            angle_finish(dist[f], seq_len, false);
-        });
-    } else {
-        // -a: one farm of alignPair tiles over the sequences of all families, within-family pairs only
-        DistanceFactoryAlign dfa(a, jobs[act[0]].model_factory);   // (the scoring matrix and the gap costs: the run's)
-        const int unknown_sym = a.kind == ALPHA_DNA ? (int)D : 20;
-        std::vector<int8_t> syms;
-        std::vector<uint32_t> offs{0};
-        std::vector<uint32_t> first(nfam);   // a family's first sequence among all
-        for (uint32_t f = 0; f < nfam; ++f) {
-            first[f] = (uint32_t)offs.size() - 1;
-            for (const sequence_t *sq : seq[f]) {
-                for (int8_t c : *sq) { const int v = a.value(c); syms.push_back((int8_t)(v < 0 ? unknown_sym : v)); }
-                offs.push_back((uint32_t)syms.size());
-            }
-        }
-        const uint32_t ntot = (uint32_t)offs.size() - 1;
-        auto len = [&](uint32_t f, uint32_t i) { return offs[first[f] + i + 1] - offs[first[f] + i]; };
-        all_pairs([&](uint32_t f, std::vector<std::pair<uint32_t, uint32_t>> &pr) {   // (longest first within the family, as alone)
-            auto cost = [&](const std::pair<uint32_t, uint32_t> &p) { return (uint64_t)len(f, p.first) * len(f, p.second); };
-            std::stable_sort(pr.begin(), pr.end(), [&](const std::pair<uint32_t, uint32_t> &x, const std::pair<uint32_t, uint32_t> &y) { return cost(x) > cost(y); });
-        });
-        const uint32_t np = (uint32_t)pi.size();
-        std::vector<uint32_t> gi(np), gj(np);   // the pairs by their sequences' places among all
-        for (uint32_t p = 0; p < np; ++p) { gi[p] = first[pfam[p]] + pi[p]; gj[p] = first[pfam[p]] + pj[p]; }
-        const bool reduced = !(cmdlineopts.mldist_flag || cmdlineopts.mldist_gap_flag);
-        const size_t per = reduced ? 2 : dd;
-        int32_t *counts = (int32_t *)be.host_alloc(std::max<size_t>(sizeof(int32_t) * (size_t)np * per, 16));
-        uint32_t *gaps = (uint32_t *)be.host_alloc(std::max<size_t>(4 * (size_t)np, 16));
-        for (uint32_t p = 0; p < np; ++p) be.cells_nw += (uint64_t)(offs[gi[p] + 1] - offs[gi[p]]) * (offs[gj[p] + 1] - offs[gj[p]]);
-        const auto t0 = std::chrono::steady_clock::now();
-        {
-            const int nw = std::max(1, be.workers());
-            uint32_t tile = std::max<uint32_t>(256u, (np + 3u * (uint32_t)nw - 1u) / (3u * (uint32_t)nw));   // (computePwDistances' rule)
-            if (const char *e = getenv("PGM_NW_TILE")) tile = (uint32_t)std::max(1, atoi(e));
-            const uint32_t ntiles = np ? (np + tile - 1) / tile : 0;
-            std::atomic<uint32_t> next_tile(0);
-            std::vector<std::string> errs((size_t)nw);
-            auto farm = [&](int w) {
-                try {
-                    int pending = -1;
-                    for (;;) {
-                        const uint32_t t = next_tile.fetch_add(1);
-                        if (t >= ntiles) break;
-                        const uint32_t p0 = t * tile, cnt = std::min(tile, np - p0);
-                        ++be.calls_dist;
-                        const int ticket = be.nw_pairs_submit(D, dfa.scoring_matrix().data(), dfa.gap_open, dfa.gap_extend, ntot, syms.data(), offs.data(), cnt,
-                                                              gi.data() + p0, gj.data() + p0, reduced ? 1u : 0u, counts + (size_t)p0 * per, gaps + p0, w);
-                        if (pending >= 0) be.nw_pairs_wait(pending, w);
-                        pending = ticket;
-                    }
-                    if (pending >= 0) be.nw_pairs_wait(pending, w);
-                } catch (std::exception &e) { errs[(size_t)w] = e.what(); }
-            };
-            std::vector<std::thread> devs;
-            for (int w = 1; w < nw; ++w) devs.emplace_back(farm, w);
-            farm(0);
-            for (auto &th : devs) th.join();
-            be.farm_workers = nw; be.farm_tiles = (int)ntiles;
-            for (const std::string &e : errs) if (!e.empty()) { be.host_free(counts); be.host_free(gaps); throw pgm_exception(e); }
-        }
-        be.seconds_nw += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        std::vector<double> seqlen(np);
-        for (uint32_t p = 0; p < np; ++p) seqlen[p] = ((double)(offs[gi[p] + 1] - offs[gi[p]]) + (double)(offs[gj[p] + 1] - offs[gj[p]])) / 2.0;
-        if (reduced) {
-            for (uint32_t p = 0; p < np; ++p) {
-                const distvar_t dv = dfml[pfam[p]].computeDistance((double)counts[2 * (size_t)p], (double)counts[2 * (size_t)p + 1], nullptr, gaps[p], seqlen[p]);
-                DistanceMatrix &dm = dist[pfam[p]];
-                dm.D(pi[p], pj[p]) = dm.D(pj[p], pi[p]) = dv.dist;
-                dm.V(pi[p], pj[p]) = dm.V(pj[p], pi[p]) = dv.var;
-            }
-        } else {
-            compute_distances_multi(a, blocks, counts, gaps, seqlen.data(), pi.data(), pj.data());
-        }
-        be.host_free(counts);
-        be.host_free(gaps);
-    }
-    if (solo) {   // (one after the other: the calls of a device context are serial)
-        for (size_t j : act) {
-            try { jobs[j].tree = TreeNJ(a, *jobs[j].seqs, jobs[j].model_factory, prealigned); }
-            catch (pgm_exception &e) { jobs[j].error = e.what(); }
-        }
-        return;
-    }
-    // BioNJ and the rooting: per family on the host threads
+    if (prealigned) prealigned_distances(a, F, per_family_calls);
+    else if (!cmdlineopts.nwdist_flag) angle_distances(a, F, per_family_calls);
+    else nw_distances(a, F);
+    for (const DistanceMatrix &d : F.dist) dump_distances(d);   // (--dump_dist: refused with --batch, so one matrix per call)
+    const auto tq1 = std::chrono::steady_clock::now();
+    // one family: on this thread, BioNJ's sections on the host threads; several: the families on the host threads (-W is refused
+    // with --batch: refineTree loads one tree's matrices into the backend)
     parallel_for(nfam, [&](size_t f) {
         TreeJob &job = jobs[act[f]];
         try {
-            DistanceMatrix &d = dist[f];
+            DistanceMatrix &d = F.dist[f];
             for (int i = 0; i < d.dim; ++i) { d.D(i, i) = 0; d.V(i, i) = 0; }
-            job.tree = midpointRoot(buildNJTree(order[f], d));
+            PhyTree *tree = buildNJTree(F.order[f], d);
+            if (cmdlineopts.wlsrefine_flag) tree = refineTree(tree, F.order[f], d);
+            job.tree = midpointRoot(tree);
         } catch (std::exception &e) { job.error = e.what(); }
     });
+    if (host_switches().profile && prealigned && nfam == 1)
+        fprintf(stderr, "  TreeNJ: distances %.1f ms, BioNJ + rooting %.1f ms\n", std::chrono::duration<double, std::milli>(tq1 - tq0).count(),
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tq1).count());
 }
+}  // namespace
+
+PhyTree *TreeNJ(const Alphabet &a, const std::map<std::string, sequence_t> &seqs, const ModelFactory *mf, bool prealigned) {
+    std::vector<TreeJob> job(1);
+    job[0].seqs = &seqs;
+    job[0].model_factory = mf;
+    tree_nj(a, job, prealigned, true);
+    if (!job[0].error.empty()) throw pgm_exception(job[0].error);
+    return job[0].tree;
+}
+
+void TreeNJ_multi(const Alphabet &a, std::vector<TreeJob> &jobs, bool prealigned) { tree_nj(a, jobs, prealigned, false); }
 
 }  // namespace pgm

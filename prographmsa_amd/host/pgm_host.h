@@ -513,33 +513,18 @@ public:
     DistanceFactoryML(const Alphabet &a, const ModelFactory *mf) : alphabet(a), model_factory(mf) {}
     distvar_t computeDistance(const std::vector<int32_t> &counts, index_t gaps, double seqlen) const;  // :137-190
     distvar_t computeDistance(double ident, double total, const std::vector<int32_t> *counts, index_t gaps, double seqlen) const;
-    // computeDistance of every pair: on the device when PGM_DEVICE_MLDIST is set, the backend has the kernel and the model is
-    // in eigen form (20 states), else on host threads; fills the symmetric matrices
-    void computeDistances(const int32_t *counts, const uint32_t *gaps, const std::vector<double> &seqlen,
-                          const std::vector<uint32_t> &pi, const std::vector<uint32_t> &pj, DistanceMatrix &distances) const;
 protected:
     distvar_t computeMLDist(const std::vector<int32_t> &counts, index_t gaps, double seqlen, double dist0, double var0) const;  // :66-135
     Alphabet alphabet;
     const ModelFactory *model_factory;
 };
-class DistanceFactoryAlign : public DistanceFactoryML {   // DistanceFactoryAlign.h
+class DistanceFactoryAlign : public DistanceFactoryML {   // DistanceFactoryAlign.h: the scores of alignPair (the farm itself: distance.cpp)
 public:
     DistanceFactoryAlign(const Alphabet &a, const ModelFactory *mf);
-    DistanceMatrix computePwDistances(const std::map<std::string, sequence_t> &sequences,
-                                      const std::vector<std::string> &order);   // :29-56
     const std::vector<int32_t> &scoring_matrix() const { return scoring_matrix_; }
     int gap_open = -10, gap_extend = -2;
 private:
     std::vector<int32_t> scoring_matrix_;   // (DIM+1)^2 column-major
-};
-// DistanceFactoryAngle<ALPHABET, 2> (DistanceFactoryAngle.h:55-131): the default initial distances (no -a): cosine of the 2-mer
-// count vectors, turned into a distance
-DistanceMatrix angleDistances(const Alphabet &a, const std::map<std::string, sequence_t> &sequences, const std::vector<std::string> &order);
-class DistanceFactoryPrealigned : public DistanceFactoryML {   // DistanceFactoryPrealigned.h:34-90
-public:
-    DistanceFactoryPrealigned(const Alphabet &a, const ModelFactory *mf) : DistanceFactoryML(a, mf) {}
-    DistanceMatrix computePwDistances(const std::map<std::string, sequence_t> &aligned,
-                                      const std::vector<std::string> &order);
 };
 PhyTree *buildNJTree(std::vector<std::string> seqs_order, DistanceMatrix dist);   // TreeNJ.cpp:132-281 (no topology plan)
 // LeastSquares::refineTree (LeastSquares.cpp:661-710; TreeNJ.h:52-54 when -W is given): nearest-neighbour interchanges by weighted
@@ -553,13 +538,16 @@ extern WlsStats wls_stats;
 PhyTree *refineTree(PhyTree *tree, const std::vector<std::string> &leaf_order, const DistanceMatrix &dist);
 // the pair sums of pgm_wls_pair_sums_batch in the kernels' order (D, W: n x n row-major)
 void wls_pair_sums_host(uint32_t n, const double *D, const double *W, uint32_t njobs, const pgm_wls_job *jobs, double *out);
-// TreeNJ.h:27-59: distances from an all-pairs alignment (-a, prealigned == false) or induced by an existing alignment
-// (prealigned == true, the guide-tree re-estimation of main.cpp:404-430)
+// TreeNJ.h:27-59: distances from the k-mer count vectors (DistanceFactoryAngle.h:55-131, the default), from an all-pairs alignment
+// (-a; both prealigned == false) or induced by an existing alignment (prealigned == true, the guide-tree re-estimation of
+// main.cpp:404-430), the estimate of every pair on the host threads or, with PGM_DEVICE_MLDIST, on the device for the models the
+// backend's kernels take; then BioNJ, with -W the least-squares refinement, and the midpoint rooting.
 PhyTree *TreeNJ(const Alphabet &a, const std::map<std::string, sequence_t> &seqs, const ModelFactory *mf, bool prealigned = false);
 
-// TreeNJ for the families of a --batch chunk: the distance stages run once for all families (one cosine call, one farm of
-// all-pairs tiles over the concatenated sequences, one pair-count call), BioNJ and the rooting per family on the host threads.
-// Every family's tree is the one TreeNJ gives it alone.  `error`: the message TreeNJ would have thrown for this family.
+// TreeNJ for the families of a --batch chunk.  Both are one implementation over a list of families (TreeNJ: a list of one), so every
+// family's tree is the one TreeNJ gives it alone; the distance stage runs once for all families (one farm of all-pairs tiles over the
+// concatenated sequences; one cosine call or one pair-count call where TreeNJ makes the per-family calls), BioNJ and the rooting per
+// family on the host threads.  `error`: the message TreeNJ throws for this family.
 struct TreeJob {
     const std::map<std::string, sequence_t> *seqs = nullptr;
     const ModelFactory *model_factory = nullptr;

@@ -58,6 +58,18 @@ def test_batch_equals_solo(exe, fams, trees, tmp_path, flow):
     assert st["batch_families"] == 12 and st["batch_failed"] == 0 and st["batch_chunks"] == 1
 
 
+@pytest.mark.parametrize("flow", ["fasta", "fasta_M_i1"])
+def test_host_counts_batch_equals_solo(exe, fams, tmp_path, flow):
+    """PGM_HOST_COUNTS=1: the pair counts of the re-estimated guide trees come from the host threads, in one pass over the pairs of
+    all families (the counting loop the solo run uses), and every file is that of the solo run with the same variable."""
+    env = dict(os.environ, PGM_HOST_COUNTS="1")
+    opts, _ = FLOWS[flow]
+    outs, st, _ = bu.run_batch(exe, fams, opts, tmp_path, "hc_" + flow, env=env)
+    bu.assert_identical(outs, bu.solo_outputs(exe, fams, opts, env=env))
+    assert st["batch_families"] == 12 and st["batch_failed"] == 0 and st["batch_chunks"] == 1
+    assert st["batch_dist_calls"] == 1   # the cosine call: no pair-count call was made
+
+
 def test_dna_custom_model(exe, tmp_path):
     fams = bu.dna_families(tmp_path)
     opts = ["--fasta", "--dna", "--custom_model", bu.hky_model(tmp_path)]

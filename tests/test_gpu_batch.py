@@ -51,6 +51,17 @@ def test_batch_equals_solo(exe, fams, trees, tmp_path, flow):
     assert st["backend"] == "hip" and st["batch_families"] == 12 and st["batch_failed"] == 0 and st["batch_chunks"] == 1
 
 
+@pytest.mark.parametrize("opts", [["--fasta"], ["--fasta", "-M", "-i", "1"]], ids=["fasta", "fasta_M_i1"])
+def test_host_counts_batch_equals_solo(exe, fams, tmp_path, opts):
+    """PGM_HOST_COUNTS=1 on the four smallest families (2, 2, 3 and 3 sequences: one pair and several pairs per block, and blocks that
+    do not start at pair 0): the host counting loop over the pairs of all families gives every family the file of its solo run."""
+    env = dict(os.environ, PGM_HOST_COUNTS="1")
+    small = fams[:4]
+    outs, st, _ = bu.run_batch(exe, small, opts, tmp_path, "hc%d" % len(opts), env=env)
+    bu.assert_identical(outs, bu.solo_outputs(exe, small, opts, env=env))
+    assert st["backend"] == "hip" and st["batch_families"] == 4 and st["batch_failed"] == 0
+
+
 def test_dna_custom_model(exe, tmp_path):
     fams = bu.dna_families(tmp_path)
     opts = ["--fasta", "--dna", "--custom_model", bu.hky_model(tmp_path)]
