@@ -589,7 +589,9 @@ int pgmo_csprofile_create(uint32_t K, uint32_t ncols, const double *lprofiles, c
         const double *ce = centre + (size_t)k * 20;
         for (uint32_t i = 0; i < L; ++i) {
             double pk = priors[k];
-            for (int j = -center; j <= center; ++j) {
+            /* (a window of an even width has the columns -center .. center - 1: the reference's loop reads one row past its
+             * ncols x 21 matrix there, which no library it ships reaches — their widths are odd) */
+            for (int j = -center; j <= center && j + center < (int)ncols; ++j) {
                 if ((int)i + j >= 0 && i + j < L) {
                     int cj = seq[i + j];
                     pk += lp[(size_t)(j + center) * 21 + cj];

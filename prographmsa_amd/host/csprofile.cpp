@@ -34,7 +34,7 @@ CSProfile::CSProfile(const std::string &filename) {
     centre_.assign((size_t)K * 20, 0.0);
     priors_.assign(K, 0.0);
     std::vector<double> weights(C);
-    for (int j = -center; j <= center; ++j) weights[center + j] = std::exp(w_center + beta * std::abs(j));
+    for (int j = -center; j <= center && center + j < C; ++j) weights[center + j] = std::exp(w_center + beta * std::abs(j));   // (an even width: columns -center .. center - 1)
 
     do {
         if (line.empty() || line[0] == '#') continue;

@@ -1,6 +1,7 @@
 """The independent statement of the ML distance estimator for a general generator Q (no eigen form), in numpy float64, and the
 helpers the tests of pgm_mldist_general_kernel share (tests/test_gpu_mldist_general.py, tests/test_gpu_mldist_codon_e2e.py,
-tests/test_cpu_mldist_general.py).
+tests/test_cpu_mldist_general.py), and the models and pairs of the eigen-form kernel's dims-and-rounds test (tests/test_gpu_dist.py)
+and of its CPU companion.
 
 P(d) = exp(Q d) by the recipe of host/model_factory.cpp's expm: scale by 2^-s (s from the 1-norm rule), 20 Taylor terms, s
 squarings.  Around it the Newton iteration of DistanceFactoryML.h:66-190 (computeDistance / computeMLDist).  The matrix products
@@ -208,3 +209,95 @@ def kernel_test_pairs(Q, seed):
     gaps[0] = 7
     seqlen = rng.uniform(50, 1200, NPAIRS)
     return counts, gaps, seqlen
+
+
+# ---- the inputs of the eigen-form kernel's dims-and-rounds test (tests/test_gpu_dist.py) and of its CPU companion ------------
+EIGEN_DIMS = (2, 4, 19, 20)
+EIGEN_FLAGS = ((1, 0), (0, 1))
+EIGEN_KINDS = ("near", "empty", "far", "identical", "saturated")
+_eigen_cache = {}
+
+
+def eigen_model(dim):
+    """A random reversible model in eigen form, built as tests/test_gpu_dist.py builds its 20-state one: symmetric exchangeabilities
+    times pi, normalised to rate 1, then numpy's eig.  Returns (Q, V, Vi, sigma)."""
+    rng = np.random.default_rng(900 + dim)
+    pi = rng.dirichlet(np.ones(dim) * 5)
+    S = rng.gamma(0.5, 1.0, (dim, dim)); S = (S + S.T) / 2; np.fill_diagonal(S, 0)
+    Q = S * pi[None, :]
+    np.fill_diagonal(Q, -Q.sum(1))
+    Q /= -(pi * np.diag(Q)).sum()
+    sig, V = np.linalg.eig(Q)
+    assert np.all(sig.imag == 0) and np.all(V.imag == 0)
+    sig, V = sig.real, V.real
+    return Q, V, np.linalg.inv(V), sig
+
+
+def eigen_ctypes_model(dim, flags, par=None):
+    """pgm_mldist_model of eigen_model(dim) with the amino-acid constants; returns (model, the arrays it points into)."""
+    import ctypes as C
+    import prographmsa_amd as pg
+    Q, V, Vi, sig = eigen_model(dim)
+    keep = [np.asfortranarray(Q), np.asfortranarray(V), np.asfortranarray(Vi), np.ascontiguousarray(sig)]
+    m = pg.pgm_mldist_model()
+    m.dim = dim
+    m.Q, m.V, m.Vi, m.sigma = [a.ctypes.data_as(C.POINTER(C.c_double)) for a in keep]
+    for k, v in (par or AA_PAR).items():
+        setattr(m, k, v)
+    m.mldist, m.mldist_gap = flags
+    return m, keep
+
+
+def eigen_pool(dim):
+    """The distinct pairs of the test, by kind (computed once per dim): a dict kind -> (counts (m, n * n) int32 in the C ABI's
+    layout, gaps, seqlen).  `near` / `far`: counts_at at distances 0.02 .. 0.3 / 0.5 .. 3; `empty`: no column; `identical`: only
+    diagonal counts; `saturated`: p-distance above 0.85 (the start at DIST_MAX)."""
+    if dim in _eigen_cache:
+        return _eigen_cache[dim]
+    Q = eigen_model(dim)[0]
+    rng = np.random.default_rng(7000 + dim)
+    cs = {k: [] for k in EIGEN_KINDS}
+    for d in (0.02, 0.05, 0.1, 0.2, 0.3):
+        for _ in range(6):
+            cs["near"].append(counts_at(Q, d, int(rng.integers(60, 400)), rng))
+    for d in (0.5, 0.8, 1.2, 2.0, 3.0):
+        for _ in range(6):
+            cs["far"].append(counts_at(Q, d, int(rng.integers(60, 400)), rng))
+    for _ in range(4):
+        cs["empty"].append(np.zeros((dim, dim), np.int32))
+    for _ in range(6):
+        cs["identical"].append(counts_at(Q, 0.0, int(rng.integers(1, 500)), rng, identical=True))
+    for _ in range(6):
+        c = rng.integers(1, 40, (dim, dim)).astype(np.int32)
+        np.fill_diagonal(c, 0)
+        c[0, 0] = int(rng.integers(0, 3))
+        cs["saturated"].append(c)
+    pool = {}
+    for k in EIGEN_KINDS:
+        m = len(cs[k])
+        pool[k] = (np.ascontiguousarray(np.stack([c.reshape(-1, order="F") for c in cs[k]]).astype(np.int32)),
+                   rng.integers(0, 30, m).astype(np.uint32), rng.uniform(50, 1200, m))
+    _eigen_cache[dim] = pool
+    return pool
+
+
+def eigen_schedule(npairs, stride):
+    """Which pool entry pair p of the launch is: (kind index, entry index) arrays.  `stride` is the number of pairs of one round of
+    the grid (4 wavefronts x the blocks of the launch): pairs p and p + stride run on the same wavefront in consecutive rounds, and
+    the kind advances by one from round to round, so they are always of different kinds."""
+    p = np.arange(npairs)
+    kind = (p % stride + p // stride) % len(EIGEN_KINDS)
+    return kind, p // len(EIGEN_KINDS)
+
+
+def eigen_pairs(dim, npairs, stride):
+    """counts (npairs, n * n), gaps, seqlen and the kind of every pair, drawn from the pool by eigen_schedule."""
+    pool = eigen_pool(dim)
+    kind, ent = eigen_schedule(npairs, stride)
+    counts = np.zeros((npairs, dim * dim), np.int32); gaps = np.zeros(npairs, np.uint32); seqlen = np.zeros(npairs)
+    for k, name in enumerate(EIGEN_KINDS):
+        c, g, l = pool[name]
+        sel = kind == k
+        ix = ent[sel] % len(g)
+        counts[sel], gaps[sel], seqlen[sel] = c[ix], g[ix], l[ix]
+    return counts, gaps, seqlen, kind

@@ -11,6 +11,7 @@ import os
 import subprocess
 
 import numpy as np
+import pytest
 
 import gen
 import mldist_general_ref as R
@@ -75,3 +76,59 @@ def test_numpy_statement_matches_the_host_estimator(oracle_build, tmp_path):
     wv = R.rel_diff(V[off], vh.reshape(12, 12)[off])
     print("numpy statement vs host estimator: max rel diff dist %.3e var %.3e (%d of 66 pairs converged)" % (wd, wv, sum(i["exit"] == "converged" for i in info)))
     assert wd <= BOUND and wv <= BOUND, (wd, wv)
+
+
+# ---- the CPU companion of tests/test_gpu_dist.py::test_mldist_eigen_kernel_dims_and_grid_rounds --------------------------------
+# The GPU test compares the eigen-form kernel with the oracle's pgmo_mldist to 1e-12 (distances) and 1e-9 (variances) on pairs it
+# draws from R.eigen_pool.  Two independent evaluations of the estimator may legitimately part where a pair sits on one of its
+# branch edges (the MAXITER exit, the 0.85 switch of the start value, the final clamps).  That no pool entry does is checked here
+# with a second witness: the oracle given the eigen form against the numpy statement given Q alone (P(d) by Taylor series and
+# squarings instead of V exp(sigma d) V^-1), to a tenth of the GPU test's tolerances.  Every entry of the pool is compared.
+EIGEN_DIST_BOUND = 1e-12 / 10
+EIGEN_VAR_BOUND = 1e-9 / 10
+
+
+@pytest.mark.parametrize("flags", R.EIGEN_FLAGS)
+@pytest.mark.parametrize("dim", R.EIGEN_DIMS)
+def test_eigen_pool_sits_on_no_branch_edge(oracle_build, dim, flags):
+    import oracle_lib
+    Q = R.eigen_model(dim)[0]
+    m, keep = R.eigen_ctypes_model(dim, flags)
+    pool = R.eigen_pool(dim)
+    worst_d = worst_v = 0.0
+    for kind in R.EIGEN_KINDS:
+        counts, gaps, seqlen = pool[kind]
+        od, ov = oracle_lib.mldist(m, counts.reshape(-1), gaps, seqlen)
+        sd, sv, info = R.estimate_batch(Q, counts, gaps, seqlen, R.AA_PAR, *flags)
+        # the kinds are what their names say (the statement's record of each pair)
+        tot = counts.sum(1)
+        if kind == "near":
+            assert all(i["start"] == "pdist" and i["newton"] > 0 for i in info)
+        elif kind == "far":      # (at 19 and 20 states a pair at distance 3 has a p-distance above 0.85 and starts at DIST_MAX)
+            assert all(i["newton"] > 0 for i in info)
+        elif kind == "empty":
+            assert not tot.any() and all(i["newton"] == 0 for i in info)
+        elif kind == "identical":
+            assert tot.all() and all(i["start"] == "pdist" and i["newton"] == 0 for i in info)
+        else:
+            assert all(i["start"] == "dist_max" and i["newton"] > 0 for i in info)
+        wd, wv = R.rel_diff(sd, od), R.rel_diff(sv, ov)
+        print("eigen pool dim %d -m %d -M %d %-9s: %d pairs, oracle eigen form vs numpy statement max rel diff dist %.3e var %.3e" % (dim, flags[0], flags[1], kind, len(gaps), wd, wv))
+        worst_d, worst_v = max(worst_d, wd), max(worst_v, wv)
+    assert worst_d <= EIGEN_DIST_BOUND and worst_v <= EIGEN_VAR_BOUND, (worst_d, worst_v)
+
+
+def test_eigen_schedule_changes_kind_between_rounds():
+    """Pairs p and p + stride (one wavefront, consecutive rounds of the grid) are of different kinds, every kind and every pool entry
+    is used, for the strides of 4 .. 304 CUs (stride = 4 wavefronts x 2 blocks per CU)."""
+    for cus in (1, 4, 80, 104, 256, 304):
+        stride = 8 * cus
+        npairs = int(2.5 * stride) + 3
+        kind, ent = R.eigen_schedule(npairs, stride)
+        assert np.all(kind[:-stride] != kind[stride:])
+        assert set(kind.tolist()) == set(range(len(R.EIGEN_KINDS)))
+    counts, gaps, seqlen, kind = R.eigen_pairs(4, int(2.5 * 2048), 2048)
+    pool = R.eigen_pool(4)
+    for k, name in enumerate(R.EIGEN_KINDS):
+        got = {c.tobytes() for c in counts[kind == k]}
+        assert got == {c.tobytes() for c in pool[name][0]}

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import gen
+import mldist_general_ref as R
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -170,6 +171,57 @@ def test_mldist_kernel_against_the_oracle(ctx, flags):
     else:
         assert np.max(np.abs(dist - rd) / np.maximum(np.abs(rd), 1e-300)) <= 1e-12
         assert np.max(np.abs(var - rv) / np.maximum(np.abs(rv), 1e-300)) <= 1e-9   # (the variance is -1 / f'' of the last Newton step: a difference of two large sums)
+
+
+@pytest.mark.parametrize("flags", R.EIGEN_FLAGS)
+@pytest.mark.parametrize("dim", R.EIGEN_DIMS)
+def test_mldist_eigen_kernel_dims_and_grid_rounds(ctx, dim, flags):
+    """pgm_mldist_kernel below its 20 states (2: two of 64 lanes own an entry, 4: the DNA models, 19) and over more than two rounds
+    of its grid-stride loop: the launch is min(ceil(npairs / 4), 2 cus) blocks of 4 wavefronts, so with npairs >= 2.5 x 8 cus a
+    wavefront takes a second and a third pair and reuses its LDS rows E, P, PP, T1, T2.  The pairs (tests/mldist_general_ref.py:
+    eigen_pool / eigen_schedule) are ordered so that the pairs of one wavefront in consecutive rounds, p and p + 8 cus, are of
+    different kinds: counts at distances 0.02 .. 0.3, an empty pair, counts at 0.5 .. 3, an identical pair, a p-distance above
+    0.85.  Every pair against the oracle's pgmo_mldist with the tolerances of test_mldist_kernel_against_the_oracle;
+    tests/test_cpu_mldist_general.py checks without a GPU that no pair of the pool sits on a branch edge of the estimator.
+    Measured on an MI355X (256 CUs, 5123 pairs): at most 3.8e-15 in the distances and 3.0e-14 in the variances."""
+    import oracle_lib
+    import prographmsa_amd as pg
+    cus = ctx.device_info()[1]
+    stride = 2 * cus * 4                              # pairs per round: 4 wavefronts x 2 cus blocks
+    npairs = int(np.ceil(2.5 * stride)) + 3           # (+ 3: the last block is not full)
+    assert npairs > stride and npairs >= 2.5 * stride
+    counts, gaps, seqlen, kind = R.eigen_pairs(dim, npairs, stride)
+    assert np.all(kind[:-stride] != kind[stride:]) and len(set(kind.tolist())) == len(R.EIGEN_KINDS)
+    m, keep = R.eigen_ctypes_model(dim, flags)
+    cflat = np.ascontiguousarray(counts.reshape(-1))
+    rd, rv = oracle_lib.mldist(m, cflat, gaps, seqlen)
+    dist = np.full(npairs, -7.0); var = np.full(npairs, -7.0)
+    P = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+    pg.check(pg.lib.pgm_mldist_batch(ctx.handle, C.byref(m), npairs, P(cflat, C.c_int32), P(gaps, C.c_uint32), P(seqlen, C.c_double), P(dist, C.c_double), P(var, C.c_double)))
+    wd, wv = R.rel_diff(dist, rd), R.rel_diff(var, rv)
+    print("mldist eigen kernel dim %d -m %d -M %d, %d pairs on %d CUs (%.2f rounds): max rel diff dist %.3e var %.3e, %d of %d distances bit-identical"
+          % (dim, flags[0], flags[1], npairs, cus, npairs / stride, wd, wv, int((dist.view(np.uint64) == rd.view(np.uint64)).sum()), npairs))
+    assert wd <= 1e-12 and wv <= 1e-9, (wd, wv)
+
+
+def test_mldist_eigen_form_is_refused_above_20_states(ctx):
+    """The eigen-form kernel holds 20 x 20 matrices in LDS: dim = 21 with V, Vi and sigma is PGM_ERR_INVALID (the same model in
+    general form, Q alone, is accepted: tests/test_gpu_mldist_general.py)."""
+    import prographmsa_amd as pg
+    D = 21
+    Q = R.random_generator(D, D)
+    keep = [np.asfortranarray(Q), np.asfortranarray(np.eye(D)), np.asfortranarray(np.eye(D)), np.zeros(D)]
+    P = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+    m = pg.pgm_mldist_model()
+    m.dim = D
+    m.Q, m.V, m.Vi, m.sigma = [P(a, C.c_double) for a in keep]
+    for k, v in R.AA_PAR.items():
+        setattr(m, k, v)
+    m.mldist, m.mldist_gap = 1, 0
+    counts = np.ascontiguousarray(R.counts_at(Q, 0.3, 100, np.random.default_rng(1)).reshape(-1, order="F").astype(np.int32))
+    gaps = np.array([1], np.uint32); seqlen = np.array([100.0]); dist = np.zeros(1); var = np.zeros(1)
+    rc = pg.lib.pgm_mldist_batch(ctx.handle, C.byref(m), 1, P(counts, C.c_int32), P(gaps, C.c_uint32), P(seqlen, C.c_double), P(dist, C.c_double), P(var, C.c_double))
+    assert rc == pg.PGM_ERR_INVALID
 
 
 @pytest.mark.parametrize("nseq,ncols", [(1, 400), (7, 400), (64, 400), (257, 400), (33, 3721)])
