@@ -391,6 +391,24 @@ int pgm_wls_pair_sums_batch(pgm_ctx *ctx, uint32_t njobs, const pgm_wls_job *job
 float pgm_wls_last_kernel_ms(pgm_ctx *ctx);       /* device time of the last pair-sums call */
 uint32_t pgm_wls_last_launches(pgm_ctx *ctx);     /* kernels it launched */
 
+/* ---- BioNJ guide trees (reference src/TreeNJ.cpp:132-281) ------------------------------------------------------------ */
+/* The joins of BioNJ on the device: every value is the expression of the host loop (bionj_joins_host, host/distance.cpp), the
+ * column sums in Eigen's association, the joined pair the first strict minimum of the criterion in column-major order, so the
+ * join record and final_d equal the host's bit for bit.  Three kernels per join of the largest family.
+ * PGM_ERR_INVALID, before anything is launched: a NULL pointer, nfam == 0, a family with n < 4 or n > PGM_BIONJ_MAX_N, an
+ * entry of D or V that is not finite. */
+typedef struct pgm_bionj_join { uint32_t index1, index2; double dist1, dist2; } pgm_bionj_join;
+#define PGM_BIONJ_MAX_N 32768
+/* D, V: n x n row-major (entry (i,j) at i*n+j), as DistanceMatrix holds them; not modified.
+ * joins: n-3 records in join order (reduced indices, index1 < index2, as buildNJTree uses them);
+ * final_d: the 3 x 3 row-major D of the three clusters left, as the host's last formula reads it. */
+int pgm_bionj(pgm_ctx *ctx, uint32_t n, const double *D, const double *V, pgm_bionj_join *joins, double *final_d);
+/* nfam matrices back to back (n[f]^2 doubles each), joins back to back (n[f]-3 each), final_d 9 per family */
+int pgm_bionj_multi(pgm_ctx *ctx, uint32_t nfam, const uint32_t *n, const double *D, const double *V,
+                    pgm_bionj_join *joins, double *final_d);
+uint32_t pgm_bionj_last_launches(pgm_ctx *ctx);   /* kernels of the last call */
+float pgm_bionj_last_kernel_ms(pgm_ctx *ctx);     /* device time from its first kernel to its last */
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,10 @@ class pgm_wls_job(C.Structure):
     _fields_ = [("label", C.POINTER(C.c_int8)), ("offset", C.POINTER(C.c_double)), ("nsub", C.c_uint32)]
 
 
+class pgm_bionj_join(C.Structure):
+    _fields_ = [("index1", C.c_uint32), ("index2", C.c_uint32), ("dist1", C.c_double), ("dist2", C.c_double)]
+
+
 class pgm_align_out(C.Structure):
     _fields_ = [("score", C.c_float), ("n_tr_indels", C.c_uint32), ("len", C.c_uint32), ("status", C.c_int32),
                 ("map1", C.POINTER(C.c_uint32)), ("map2", C.POINTER(C.c_uint32))]
@@ -81,6 +85,7 @@ EXPORTS = [
     "pgm_merge_profiles_batch", "pgm_merge_profiles_batch_ex", "pgm_resident_reset", "pgm_resident_onehot", "pgm_resident_import", "pgm_merge_last_kernel_ms",
     "pgm_gapmask_extend_batch", "pgm_gap_parsimony_batch", "pgm_parsimony_last_kernel_ms",
     "pgm_wls_load", "pgm_wls_pair_sums_batch", "pgm_wls_last_kernel_ms", "pgm_wls_last_launches",
+    "pgm_bionj", "pgm_bionj_multi", "pgm_bionj_last_launches", "pgm_bionj_last_kernel_ms",
 ]
 
 
@@ -148,6 +153,10 @@ def _load():
         "pgm_wls_pair_sums_batch": (C.c_int, [vp, u32, C.POINTER(pgm_wls_job), C.POINTER(C.c_double)]),
         "pgm_wls_last_kernel_ms": (C.c_float, [vp]),
         "pgm_wls_last_launches": (C.c_uint32, [vp]),
+        "pgm_bionj": (C.c_int, [vp, u32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(pgm_bionj_join), C.POINTER(C.c_double)]),
+        "pgm_bionj_multi": (C.c_int, [vp, u32, C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(pgm_bionj_join), C.POINTER(C.c_double)]),
+        "pgm_bionj_last_launches": (C.c_uint32, [vp]),
+        "pgm_bionj_last_kernel_ms": (C.c_float, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = the library does not export a declared symbol

@@ -1,0 +1,91 @@
+// pgm_bionj_capi.inc — C ABI of the BioNJ joins (included by pgm_capi.hip).  A call uploads the families' matrices, the family
+// descriptors and the identity index lists, runs the three kernels of pgm_bionj_kernels.h once per join of the largest family
+// (plain launches on the context's stream: stream order is the only dependency), and copies the join log and final_d back in
+// one copy behind one synchronisation.
+namespace {
+// scratch slots (see scratch_dev): 28 = D, T, V; 29 = sums, column minima, descriptors, index lists; 30 = join log + final_d
+enum { SC_BIONJ_MAT = 28, SC_BIONJ_VEC = 29, SC_BIONJ_OUT = 30 };
+}  // namespace
+
+extern "C" float pgm_bionj_last_kernel_ms(pgm_ctx *ctx) { return ctx ? ctx->bionj_ms : 0.0f; }
+extern "C" uint32_t pgm_bionj_last_launches(pgm_ctx *ctx) { return ctx ? ctx->bionj_launches : 0u; }
+
+extern "C" int pgm_bionj_multi(pgm_ctx *ctx, uint32_t nfam, const uint32_t *n, const double *D, const double *V,
+                               pgm_bionj_join *joins, double *final_d) {
+    if (ctx) { ctx->bionj_ms = 0; ctx->bionj_launches = 0; }
+    if (!ctx || !n || !D || !V || !joins || !final_d) return fail(PGM_ERR_INVALID, "null argument");
+    if (nfam == 0) return fail(PGM_ERR_INVALID, "bionj: no family");
+    std::vector<PgmBionjFam> fam(nfam);
+    uint64_t sum_nn = 0, sum_n = 0, sum_j = 0;
+    uint32_t nmax = 0;
+    for (uint32_t f = 0; f < nfam; ++f) {
+        if (n[f] < 4 || n[f] > PGM_BIONJ_MAX_N)
+            return fail(PGM_ERR_INVALID, "bionj: family " + std::to_string(f) + ": n = " + std::to_string(n[f]) + " outside [4, " + std::to_string(PGM_BIONJ_MAX_N) + "]");
+        fam[f] = PgmBionjFam{n[f], sum_nn, sum_n, sum_j};
+        sum_nn += (uint64_t)n[f] * n[f]; sum_n += n[f]; sum_j += n[f] - 3u;
+        nmax = std::max(nmax, n[f]);
+    }
+    {   // a NaN or an infinity: std::max / std::min of the host loop propagate them in ways the parallel minimum does not
+        const uint64_t grain = (uint64_t)1 << 16, nchunks = (sum_nn + grain - 1) / grain;
+        std::atomic<int> bad(0);
+        (void)lib_pool().run((size_t)nchunks, nchunks >= 16 ? 16u : 1u, [&](size_t c) {
+            const uint64_t e0 = c * grain, e1 = std::min<uint64_t>(sum_nn, e0 + grain);
+            bool ok = true;
+            for (uint64_t e = e0; e < e1; ++e) ok = ok && std::isfinite(D[e]) && std::isfinite(V[e]);
+            if (!ok) bad.store(1);
+        });
+        if (bad.load()) return fail(PGM_ERR_INVALID, "bionj: a distance or variance is not finite");
+    }
+    // the vector buffer: sums, best_q (doubles), the descriptors, act[0], act[1], best_row; descriptors and act[0] are uploaded
+    const size_t o_sums = 0, o_bq = o_sums + 8 * sum_n, o_fam = o_bq + 8 * sum_n, o_act0 = o_fam + sizeof(PgmBionjFam) * nfam,
+                 o_act1 = o_act0 + 4 * sum_n, o_brow = o_act1 + 4 * sum_n, vec_bytes = o_brow + 4 * sum_n;
+    const size_t out_joins = sizeof(pgm_bionj_join) * sum_j, out_bytes = out_joins + 8 * 9 * (size_t)nfam;
+    std::vector<uint8_t> img(o_act0 - o_fam + 4 * sum_n);
+    memcpy(img.data(), fam.data(), sizeof(PgmBionjFam) * nfam);
+    {
+        uint32_t *a = (uint32_t *)(img.data() + (o_act0 - o_fam));
+        for (uint32_t f = 0; f < nfam; ++f)
+            for (uint32_t i = 0; i < n[f]; ++i) a[fam[f].voff + i] = i;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    uint8_t *d_mat = nullptr, *d_vec = nullptr, *d_out = nullptr;
+    hipError_t e = scratch_dev(ctx, SC_BIONJ_MAT, 3 * 8 * (size_t)sum_nn, (void **)&d_mat);
+    if (e == hipSuccess) e = scratch_dev(ctx, SC_BIONJ_VEC, vec_bytes, (void **)&d_vec);
+    if (e == hipSuccess) e = scratch_dev(ctx, SC_BIONJ_OUT, out_bytes, (void **)&d_out);
+    if (e == hipSuccess) e = scratch_events(ctx);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("bionj: ") + hipGetErrorString(e));
+    PgmBionjDev S;
+    S.fam = (const PgmBionjFam *)(d_vec + o_fam); S.nfam = nfam;
+    S.D = (double *)d_mat; S.T = S.D + sum_nn; S.V = S.T + sum_nn;
+    S.act[0] = (uint32_t *)(d_vec + o_act0); S.act[1] = (uint32_t *)(d_vec + o_act1);
+    S.sums = (double *)(d_vec + o_sums); S.best_q = (double *)(d_vec + o_bq); S.best_row = (uint32_t *)(d_vec + o_brow);
+    S.joins = (pgm_bionj_join *)d_out; S.final_d = (double *)(d_out + out_joins);
+    hipStream_t s = ctx->stream;
+    HIPCHK(hipMemcpyAsync(S.D, D, 8 * (size_t)sum_nn, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(S.V, V, 8 * (size_t)sum_nn, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_vec + o_fam, img.data(), img.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(ctx->sc_ev[0], s));
+    const uint32_t gy = std::min(nfam, 65535u), gz = (nfam + gy - 1) / gy;
+    uint32_t launches = 0;
+    for (uint32_t step = 0; step + 3u < nmax; ++step) {
+        const dim3 cols((nmax - step + PGM_BIONJ_COLS - 1) / PGM_BIONJ_COLS, gy, gz);
+        hipLaunchKernelGGL(pgm_bionj_sums_kernel, cols, dim3(64 * PGM_BIONJ_COLS), 0, s, S, step);
+        hipLaunchKernelGGL(pgm_bionj_scan_kernel, cols, dim3(64 * PGM_BIONJ_COLS), 0, s, S, step);
+        hipLaunchKernelGGL(pgm_bionj_join_kernel, dim3(1, gy, gz), dim3(256), 0, s, S, step);
+        HIPCHK(hipGetLastError());
+        launches += 3;
+    }
+    HIPCHK(hipEventRecord(ctx->sc_ev[1], s));
+    std::vector<uint8_t> back(out_bytes);
+    HIPCHK(hipMemcpyAsync(back.data(), d_out, out_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipEventElapsedTime(&ctx->bionj_ms, ctx->sc_ev[0], ctx->sc_ev[1]));
+    memcpy(joins, back.data(), out_joins);
+    memcpy(final_d, back.data() + out_joins, out_bytes - out_joins);
+    ctx->bionj_launches = launches;
+    return PGM_OK;
+}
+
+extern "C" int pgm_bionj(pgm_ctx *ctx, uint32_t n, const double *D, const double *V, pgm_bionj_join *joins, double *final_d) {
+    return pgm_bionj_multi(ctx, 1, &n, D, V, joins, final_d);
+}

@@ -2,7 +2,7 @@
 // (reference src/DistanceFactoryAlign.{h,cpp}, DistanceFactoryML.{h,cpp}, TreeNJ.{h,cpp}).
 // The O(L^2) Needleman-Wunsch of every pair (alignPair), the pair counts of an alignment and the k-mer cosine matrix run behind the
 // C ABI, and so does ML distance estimation when PGM_DEVICE_MLDIST is set (pgm_mldist_batch; on the host threads otherwise);
-// neighbour joining stays on the host.  TreeNJ (one family) and TreeNJ_multi (--batch) are one implementation: the last section.
+// the joins of neighbour joining run on the host threads or, from kBionjDeviceMin taxa on, behind pgm_bionj_multi.  TreeNJ (one family) and TreeNJ_multi (--batch) are one implementation: the last section.
 #include "pgm_host.h"
 #include "nnls.h"
 #include <quadmath.h>
@@ -127,6 +127,21 @@ static void dump_distances(const DistanceMatrix &d) {
     f.write((const char *)d.variances.data(), 8 * d.variances.size());
 }
 
+static std::string g_joins_dump;
+void set_joins_dump(const std::string &path) { g_joins_dump = path; }
+static void dump_joins(int32_t n, const std::vector<pgm_bionj_join> &joins, const double *final_d) {
+    if (g_joins_dump.empty()) return;
+    std::ofstream f(g_joins_dump.c_str(), std::ios::binary | std::ios::app);
+    f.write((const char *)&n, 4);
+    for (const pgm_bionj_join &j : joins) {
+        const int32_t idx[2] = {(int32_t)j.index1, (int32_t)j.index2};
+        const double d[2] = {j.dist1, j.dist2};
+        f.write((const char *)idx, 8);
+        f.write((const char *)d, 16);
+    }
+    f.write((const char *)final_d, 8 * 9);
+}
+
 // ---- DistanceFactoryAlign ---------------------------------------------------------------------
 DistanceFactoryAlign::DistanceFactoryAlign(const Alphabet &a, const ModelFactory *mf) : DistanceFactoryML(a, mf) {
     const int sd = a.DIM + 1;  // initMatrix (DistanceFactoryAlign.cpp:5-35, 38-235, 238-249)
@@ -199,11 +214,13 @@ static double eigen_column_sum(const std::vector<double> &tr, size_t ld, const s
 // clamped when they were written, and nothing reads an entry between its join and the next clamp), sums and scan on the host
 // threads from 512 clusters on (ranges of columns; the scan keeps the FIRST minimum in column-major order like Eigen's
 // minCoeff: a range keeps its first, the ranges are combined in order with the same strict comparison), and no copy.
-PhyTree *buildNJTree(std::vector<std::string> seqs_order, DistanceMatrix dist) {
+// The loop records its joins (reduced indices, index1 < index2, and the two branch lengths) and, when it ends, the D of the
+// clusters left (final_d: 3 x 3 row-major; for n0 < 4 the matrix as it came, nothing clamped): all bionj_tree needs to assemble
+// the tree, and what pgm_bionj_multi computes on the device (same bits: DESIGN.md 3.11).
+void bionj_joins_host(DistanceMatrix dist, std::vector<pgm_bionj_join> &joins, double *final_d) {
     const double MIN_DIST = 1e-4, MIN_VAR = 1e-5;
-    const int n0 = (int)seqs_order.size();
-    std::vector<PhyTree *> subtrees;
-    for (const std::string &s : seqs_order) subtrees.push_back(new PhyTree(s));
+    const int n0 = dist.dim;
+    joins.clear();
     std::vector<int> act((size_t)n0);
     for (int i = 0; i < n0; ++i) act[(size_t)i] = i;
     auto D = [&](int i, int j) -> double & { return dist.D(act[(size_t)i], act[(size_t)j]); };   // (reduced indices)
@@ -256,7 +273,6 @@ PhyTree *buildNJTree(std::vector<std::string> seqs_order, DistanceMatrix dist) {
         double min = INFINITY;
         for (size_t r = 0; r < nranges; ++r) if (best[r].min < min) { min = best[r].min; index2 = best[r].row; index1 = best[r].col; }
         if (index2 < index1) std::swap(index1, index2);
-        std::string name1 = seqs_order[index1], name2 = seqs_order[index2];
         double dist1 = (D(index1, index2) + (sums[index1] - sums[index2]) / (dim - 2.0)) / 2.0;
         dist1 = std::min(std::max(dist1, MIN_DIST), D(index1, index2));
         double dist2 = std::max(D(index2, index1) - dist1, MIN_DIST);
@@ -278,14 +294,31 @@ PhyTree *buildNJTree(std::vector<std::string> seqs_order, DistanceMatrix dist) {
         }
         act.erase(act.begin() + index2);
         fresh = index1;   // (index1 < index2: its reduced index stays)
-        seqs_order.erase(seqs_order.begin() + index2);
+        joins.push_back(pgm_bionj_join{(uint32_t)index1, (uint32_t)index2, dist1, dist2});
+    }
+    const int left = std::min(n0, 3);
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) final_d[3 * r + c] = r < left && c < left ? D(r, c) : 0.0;
+}
+
+// The tree of a join record (TreeNJ.cpp:196-228 per join, :264-281 for the two or three clusters left)
+PhyTree *bionj_tree(std::vector<std::string> seqs_order, const std::vector<pgm_bionj_join> &joins, const double *final_d) {
+    const double MIN_DIST = 1e-4;
+    std::vector<PhyTree *> subtrees;
+    for (const std::string &s : seqs_order) subtrees.push_back(new PhyTree(s));
+    for (const pgm_bionj_join &j : joins) {
+        const size_t index1 = j.index1, index2 = j.index2;
+        if (index1 >= index2 || index2 >= seqs_order.size()) error("BioNJ: join record out of range");
+        std::string name1 = seqs_order[index1], name2 = seqs_order[index2];
+        seqs_order.erase(seqs_order.begin() + (std::ptrdiff_t)index2);
         seqs_order[index1] = name1 + "," + name2;
         PhyTree *tree = new PhyTree(seqs_order[index1]);
-        tree->addChild(subtrees[index1], dist1, support(dist1));
-        tree->addChild(subtrees[index2], dist2, support(dist2));
-        subtrees.erase(subtrees.begin() + index2);
+        tree->addChild(subtrees[index1], j.dist1, support(j.dist1));
+        tree->addChild(subtrees[index2], j.dist2, support(j.dist2));
+        subtrees.erase(subtrees.begin() + (std::ptrdiff_t)index2);
         subtrees[index1] = tree;
     }
+    auto D = [&](int i, int j) { return final_d[3 * i + j]; };
     PhyTree *tree = new PhyTree("root");
     if (seqs_order.size() == 2) {
         double d = D(0, 1) / 2;
@@ -303,6 +336,13 @@ PhyTree *buildNJTree(std::vector<std::string> seqs_order, DistanceMatrix dist) {
         tree->addChild(tree2, d2 / 2, support(d2));
     }
     return tree;
+}
+
+PhyTree *buildNJTree(std::vector<std::string> seqs_order, DistanceMatrix dist) {
+    std::vector<pgm_bionj_join> joins;
+    double final_d[9];
+    bionj_joins_host(std::move(dist), joins, final_d);
+    return bionj_tree(std::move(seqs_order), joins, final_d);
 }
 
 // ---- distances induced by an alignment (DistanceFactoryPrealigned.h:34-90) -----------------------------------------
@@ -1274,14 +1314,78 @@ void tree_nj(const Alphabet &a, std::vector<TreeJob> &jobs, bool prealigned, boo
     else nw_distances(a, F);
     for (const DistanceMatrix &d : F.dist) dump_distances(d);   // (--dump_dist: refused with --batch, so one matrix per call)
     const auto tq1 = std::chrono::steady_clock::now();
-    // one family: on this thread, BioNJ's sections on the host threads; several: the families on the host threads (-W is refused
-    // with --batch: refineTree loads one tree's matrices into the backend)
+    Backend &be_bionj = default_backend();
+    // BioNJ's joins: one bionj_multi call over the families of 4 taxa and more on worker 0 (PGM_DEVICE_BIONJ, or by default when
+    // the largest family has kBionjDeviceMin taxa and every entry is finite: the device entry takes no NaN or infinity), or the
+    // host loop per family (one family: on this thread, the loop's sections on the host threads; several: the families on the
+    // host threads).  Either way the same join records, and so the same trees.
+    std::vector<std::vector<pgm_bionj_join>> joins(nfam);
+    std::vector<double> final_d((size_t)9 * nfam, 0.0);
+    for (DistanceMatrix &d : F.dist)
+        for (int i = 0; i < d.dim; ++i) { d.D(i, i) = 0; d.V(i, i) = 0; }
+    bool on_device = false;
+    {
+        std::vector<uint32_t> dev;   // the families of the device call
+        uint32_t nmax = 0;
+        for (uint32_t f = 0; f < nfam; ++f)
+            if (F.nseq[f] >= 4 && F.nseq[f] <= PGM_BIONJ_MAX_N) { dev.push_back(f); nmax = std::max(nmax, F.nseq[f]); }
+        const HostSwitches &sw = host_switches();
+        if (!dev.empty() && !sw.host_bionj && (sw.device_bionj || nmax >= kBionjDeviceMin)) {
+            std::vector<char> finite(dev.size(), 1);
+            parallel_for(dev.size(), [&](size_t k) {
+                const DistanceMatrix &d = F.dist[dev[k]];
+                bool ok = true;
+                for (size_t e = 0; e < d.distances.size(); ++e) ok = ok && std::isfinite(d.distances[e]) && std::isfinite(d.variances[e]);
+                finite[k] = ok ? 1 : 0;
+            });
+            bool all_finite = true;
+            for (char c : finite) all_finite = all_finite && c;
+            if (all_finite) {
+                std::vector<uint32_t> ns(dev.size());
+                std::vector<size_t> m0(dev.size() + 1, 0), j0(dev.size() + 1, 0);
+                for (size_t k = 0; k < dev.size(); ++k) {
+                    ns[k] = F.nseq[dev[k]];
+                    m0[k + 1] = m0[k] + (size_t)ns[k] * ns[k];
+                    j0[k + 1] = j0[k] + ns[k] - 3;
+                }
+                std::vector<double> Dcat, Vcat;   // (one family: its own matrices)
+                if (dev.size() > 1) {
+                    Dcat.resize(m0[dev.size()]); Vcat.resize(m0[dev.size()]);
+                    parallel_for(dev.size(), [&](size_t k) {
+                        const DistanceMatrix &d = F.dist[dev[k]];
+                        std::copy(d.distances.begin(), d.distances.end(), Dcat.begin() + (std::ptrdiff_t)m0[k]);
+                        std::copy(d.variances.begin(), d.variances.end(), Vcat.begin() + (std::ptrdiff_t)m0[k]);
+                    });
+                }
+                const DistanceMatrix &d0 = F.dist[dev[0]];
+                std::vector<pgm_bionj_join> jcat(j0[dev.size()]);
+                std::vector<double> fcat((size_t)9 * dev.size());
+                on_device = be_bionj.bionj_multi((uint32_t)dev.size(), ns.data(), dev.size() > 1 ? Dcat.data() : d0.distances.data(),
+                                                 dev.size() > 1 ? Vcat.data() : d0.variances.data(), jcat.data(), fcat.data(), 0);
+                if (on_device)
+                    for (size_t k = 0; k < dev.size(); ++k) {
+                        joins[dev[k]].assign(jcat.begin() + (std::ptrdiff_t)j0[k], jcat.begin() + (std::ptrdiff_t)j0[k + 1]);
+                        std::copy(fcat.begin() + (std::ptrdiff_t)(9 * k), fcat.begin() + (std::ptrdiff_t)(9 * k + 9), final_d.begin() + (std::ptrdiff_t)(9 * (size_t)dev[k]));
+                    }
+            }
+        }
+    }
+    std::vector<std::string> join_error(nfam);
+    parallel_for(nfam, [&](size_t f) {
+        if (on_device && F.nseq[f] >= 4 && F.nseq[f] <= PGM_BIONJ_MAX_N) return;
+        try { bionj_joins_host(F.dist[f], joins[f], &final_d[9 * f]); }
+        catch (std::exception &e) { join_error[f] = e.what(); }
+    });
+    be_bionj.seconds_bionj += std::chrono::duration<double>(std::chrono::steady_clock::now() - tq1).count();
+    for (uint32_t f = 0; f < nfam; ++f) dump_joins((int32_t)F.nseq[f], joins[f], &final_d[9 * (size_t)f]);   // (--dump_joins: refused with --batch)
+    // the trees, -W and the rooting per family on the host threads (-W is refused with --batch: refineTree loads one tree's
+    // matrices into the backend)
     parallel_for(nfam, [&](size_t f) {
         TreeJob &job = jobs[act[f]];
         try {
+            if (!join_error[f].empty()) throw pgm_exception(join_error[f]);
             DistanceMatrix &d = F.dist[f];
-            for (int i = 0; i < d.dim; ++i) { d.D(i, i) = 0; d.V(i, i) = 0; }
-            PhyTree *tree = buildNJTree(F.order[f], d);
+            PhyTree *tree = bionj_tree(F.order[f], joins[f], &final_d[9 * f]);
             if (cmdlineopts.wlsrefine_flag) tree = refineTree(tree, F.order[f], d);
             job.tree = midpointRoot(tree);
         } catch (std::exception &e) { job.error = e.what(); }

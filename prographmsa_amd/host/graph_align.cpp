@@ -84,6 +84,8 @@ const HostSwitches &host_switches() {
         h.no_resident = getenv("PGM_NO_RESIDENT") != nullptr;
         h.host_counts = getenv("PGM_HOST_COUNTS") != nullptr;
         h.device_mldist = getenv("PGM_DEVICE_MLDIST") != nullptr;
+        h.device_bionj = getenv("PGM_DEVICE_BIONJ") != nullptr;
+        h.host_bionj = getenv("PGM_HOST_BIONJ") != nullptr;
         return h;
     }();
     return sw;
@@ -92,6 +94,7 @@ std::string HostSwitches::describe() const {
     std::string s;
     auto add = [&](bool on, const char *name) { if (on) { if (!s.empty()) s += ","; s += name; } };
     add(host_merge, "PGM_HOST_MERGE"); add(no_resident, "PGM_NO_RESIDENT"); add(host_counts, "PGM_HOST_COUNTS"); add(device_mldist, "PGM_DEVICE_MLDIST");
+    add(device_bionj, "PGM_DEVICE_BIONJ"); add(host_bionj, "PGM_HOST_BIONJ");
     return s;
 }
 

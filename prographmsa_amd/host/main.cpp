@@ -22,12 +22,12 @@ static void usage() {
                  "             [--codon] [-c|--cs_profile <lib>] [-i <iters>] [-g rate] [-e prob] [-E prob]\n"
                  "             [-s prob] [-A] [--early_refinement] [--ancestral_seqs] [--profile_out <file>] [-R] [--read_repeats <file>]\n"
                  "             [-r|--reroot [-r]] [-W|--wls_refine [-W]] [--dna] [--custom_model <file>] [-F|--estimate_aafreqs]\n"
-                 "             [-C|--aafreqs_pseudocount <count>] [--dump_jobs <file>] [--dump_dist <file>] [--stats] <fasta file>\n"
+                 "             [-C|--aafreqs_pseudocount <count>] [--dump_jobs <file>] [--dump_dist <file>] [--dump_joins <file>] [--stats] <fasta file>\n"
                  "       pgmsa --batch <list> [--batch_cells <cells>] [options]\n"
                  "  --batch <list>  align many families in one run: every line of <list> is input.fa<TAB>output[<TAB>guide_tree.nwk] (blank\n"
                  "                lines and lines starting with # are skipped); the other options apply to every family and every output is\n"
                  "                what the same options write for that family alone.  Not with a positional file, -o, -t, -r, -W, -R,\n"
-                 "                --read_repeats, --profile_out, --dump_jobs, --dump_dist\n"
+                 "                --read_repeats, --profile_out, --dump_jobs, --dump_dist, --dump_joins\n"
                  "  --batch_cells <cells>  families share the device stages in chunks of at most this many estimated DP cells per pass\n"
                  "                (default 2e9); a larger family is a chunk of its own\n"
                  "  --dna         align DNA sequences (T C A G; U reads as T; N, X and the IUPAC ambiguity codes as unknown); needs\n"
@@ -157,9 +157,10 @@ static void print_stats(double t_init, double t_tree, double t_prog, const Batch
     Backend &be = default_backend();
     fprintf(stderr,
             "{\"backend\": \"%s\", \"init_s\": %.6f, \"tree_s\": %.6f, \"progressive_s\": %.6f, \"align_cells\": %llu, \"align_s\": %.6f, "
-            "\"nw_cells\": %llu, \"nw_s\": %.6f, \"mldist_s\": %.6f, \"merge_profiles_s\": %.6f, \"farm_workers\": %d, \"farm_tiles\": %d, \"farm_level_workers\": %d, \"farm_leaf_workers\": %d, \"resident\": %s, \"resident_imports\": %d, \"switches\": \"%s\"",
+            "\"nw_cells\": %llu, \"nw_s\": %.6f, \"mldist_s\": %.6f, \"merge_profiles_s\": %.6f, \"farm_workers\": %d, \"farm_tiles\": %d, \"farm_level_workers\": %d, \"farm_leaf_workers\": %d, \"resident\": %s, \"resident_imports\": %d, \"bionj_s\": %.6f, \"bionj_device_calls\": %llu, \"bionj_launches\": %llu, \"switches\": \"%s\"",
             be.name(), t_init, t_tree, t_prog, (unsigned long long)be.cells_aligned, be.seconds_align,
-            (unsigned long long)be.cells_nw, be.seconds_nw, be.seconds_mldist, be.seconds_merge_profiles, be.farm_workers, be.farm_tiles, be.farm_level_workers, be.farm_leaf_workers, be.resident_pass ? "true" : "false", be.resident_imports, host_switches().describe().c_str());
+            (unsigned long long)be.cells_nw, be.seconds_nw, be.seconds_mldist, be.seconds_merge_profiles, be.farm_workers, be.farm_tiles, be.farm_level_workers, be.farm_leaf_workers, be.resident_pass ? "true" : "false", be.resident_imports,
+            be.seconds_bionj, (unsigned long long)be.bionj_device_calls, (unsigned long long)be.bionj_launches, host_switches().describe().c_str());
     if (cmdlineopts.reroot_flag) {   // (keys of the root search only when it ran)
         const RootSearchStats &r = root_search_stats;
         fprintf(stderr, ", \"reroot\": %d, \"reroot_merges\": %d, \"reroot_candidates\": %d, \"reroot_heights\": %d, \"reroot_batches\": %d, "
@@ -435,7 +436,7 @@ int main(int argc, char **argv) {
     }
     try {
         bool iters_set = false, stats = false, indel_set = false, edgehl_set = false, maxdist_set = false, cutdist_set = false;
-        std::string dump, dist_dump, batch_list;
+        std::string dump, dist_dump, joins_dump, batch_list;
         double batch_cells = 2e9;
         for (int i = 1; i < argc; ++i) {
             std::string s = argv[i];
@@ -473,6 +474,7 @@ int main(int argc, char **argv) {
             else if (s == "-R" || s == "--repeats") cmdlineopts.repeats_flag = true;
             else if (s == "--dump_jobs") dump = val();
             else if (s == "--dump_dist") dist_dump = val();
+            else if (s == "--dump_joins") joins_dump = val();
             else if (s == "--stats") stats = true;
             else if (s == "--batch") batch_list = val();
             else if (s == "--batch_cells") batch_cells = atof(val().c_str());
@@ -490,7 +492,7 @@ int main(int argc, char **argv) {
                                   : !cmdlineopts.tree_file.empty() ? "-t (a guide tree is the third field of a family's line)"
                                   : cmdlineopts.reroot_flag ? "-r" : cmdlineopts.wlsrefine_flag ? "-W"
                                   : cmdlineopts.repeats_flag ? "-R" : !cmdlineopts.readreps_file.empty() ? "--read_repeats"
-                                  : !cmdlineopts.profile_file.empty() ? "--profile_out" : !dump.empty() ? "--dump_jobs" : !dist_dump.empty() ? "--dump_dist" : nullptr;
+                                  : !cmdlineopts.profile_file.empty() ? "--profile_out" : !dump.empty() ? "--dump_jobs" : !dist_dump.empty() ? "--dump_dist" : !joins_dump.empty() ? "--dump_joins" : nullptr;
             if (refused) { std::cerr << "ERROR:--batch cannot be combined with " << refused << std::endl; return 2; }
         }
         if (cmdlineopts.sequence_file.empty() && batch_list.empty()) { usage(); return 1; }
@@ -512,6 +514,7 @@ int main(int argc, char **argv) {
         if (!iters_set && !cmdlineopts.tree_file.empty()) cmdlineopts.iters = 0;   // do not iterate when a guide tree is provided (main.cpp:243-246)
         if (!dump.empty()) set_job_dump(dump);
         if (!dist_dump.empty()) set_dist_dump(dist_dump);
+        if (!joins_dump.empty()) set_joins_dump(joins_dump);
         if (!batch_list.empty()) {
             Alphabet a(cmdlineopts.codon_flag ? ALPHA_CODON : cmdlineopts.dna_flag ? ALPHA_DNA : ALPHA_AA);
             if (!cmdlineopts.fasta_flag && !cmdlineopts.onlytree_flag) std::cerr << "note: Stockholm output is not built here; writing FASTA" << std::endl;

@@ -256,6 +256,8 @@ struct HostSwitches {
     bool no_resident = false;    // PGM_NO_RESIDENT: merged profiles travel through the host between the levels
     bool host_counts = false;    // PGM_HOST_COUNTS: pair counts of an alignment on the host instead of pgm_prealigned_counts (same integers)
     bool device_mldist = false;  // PGM_DEVICE_MLDIST: ML distances by pgm_mldist_batch (last-bit differences to the host's estimator)
+    bool device_bionj = false;   // PGM_DEVICE_BIONJ: the joins of every guide tree of 4 taxa and more by pgm_bionj_multi (same bits)
+    bool host_bionj = false;     // PGM_HOST_BIONJ: the joins of every guide tree by the host loop
     std::string describe() const;   // the switches that are on, comma separated ("" = the product's defaults)
 };
 const HostSwitches &host_switches();
@@ -314,6 +316,11 @@ struct Backend {
     // calls the host code made of the align-batch entry and of the distance entries (all-pairs tiles, pair counts, cosine, ML
     // distances): `pgmsa --batch --stats` shows with them that a stage was shared by the families of a chunk
     std::atomic<uint64_t> calls_align{0}, calls_dist{0};
+    // the joins of BioNJ for many families in one call (include/pgm_hip.h: pgm_bionj_multi; every n[f] >= 4, every entry finite):
+    // the join records and final_d of bionj_joins_host, bit for bit.  false = this backend has no such kernel (the host loop runs)
+    virtual bool bionj_multi(uint32_t, const uint32_t *, const double *, const double *, pgm_bionj_join *, double *, int = 0) { return false; }
+    double seconds_bionj = 0;                                // host wall of the joins of all guide trees, either path (--stats)
+    uint64_t bionj_device_calls = 0, bionj_launches = 0;     // bionj_multi calls that ran on the device, the kernels they launched
     // node profiles of a batch of merged graphs on the device (numeric part); false = host arithmetic
     virtual bool merge_profiles_batch(uint32_t, const pgm_merge_job *, int = 0) { return false; }
     double seconds_merge_profiles = 0;
@@ -354,6 +361,7 @@ void farm_run(const std::vector<std::vector<uint32_t>> &shards, const std::funct
 void set_job_dump(const std::string &path);  // if set, every alignGraphs job is appended to this file
 bool job_dump_active();
 void set_dist_dump(const std::string &path); // if set, every distance matrix TreeNJ estimates is appended (dim, D, V as raw doubles)
+void set_joins_dump(const std::string &path); // if set, the join record of every guide tree is appended (n, n - 3 joins, the 9 doubles of final_d)
 
 // alignGraphs (GraphAlign.h:200-534): one job; and the batched form the scheduler uses.
 AlignmentResult alignGraphs(const Graph &g1, const Graph &g2, const Model &model);
@@ -527,6 +535,13 @@ private:
     std::vector<int32_t> scoring_matrix_;   // (DIM+1)^2 column-major
 };
 PhyTree *buildNJTree(std::vector<std::string> seqs_order, DistanceMatrix dist);   // TreeNJ.cpp:132-281 (no topology plan)
+// buildNJTree in two parts: the joins (the O(n^3) loop; pgm_bionj_multi computes the same record on the device) and the tree of
+// a join record.  final_d: the 3 x 3 row-major D of the clusters left (of all min(n, 3) clusters when n < 4)
+void bionj_joins_host(DistanceMatrix dist, std::vector<pgm_bionj_join> &joins, double *final_d);
+PhyTree *bionj_tree(std::vector<std::string> seqs_order, const std::vector<pgm_bionj_join> &joins, const double *final_d);
+// families of this many taxa and more go to the device by default: the smallest measured size from which the device's joins
+// took less time than the host's at every larger size
+const uint32_t kBionjDeviceMin = 256;
 // LeastSquares::refineTree (LeastSquares.cpp:661-710; TreeNJ.h:52-54 when -W is given): nearest-neighbour interchanges by weighted
 // least squares on the unrooted tree, quartets (and with -WW quintets) swept until the fit stops falling, then every edge's support
 struct WlsStats {
