@@ -409,6 +409,19 @@ int pgm_bionj_multi(pgm_ctx *ctx, uint32_t nfam, const uint32_t *n, const double
 uint32_t pgm_bionj_last_launches(pgm_ctx *ctx);   /* kernels of the last call */
 float pgm_bionj_last_kernel_ms(pgm_ctx *ctx);     /* device time from its first kernel to its last */
 
+/* The same joins when the pair of every join is known beforehand (--topology: branch lengths on a fixed topology; reference
+ * src/TreeNJ.cpp:31-130, :158-179).  plan: n[f]-3 pairs per family back to back like joins, in reduced indices; join s of a
+ * family joins plan[s] and evaluates no criterion, so it needs two column sums and costs O(n).  One preparation kernel, then one
+ * kernel in which a workgroup per family runs all of the family's joins: the number of launches does not depend on n.  joins and
+ * final_d as above; the values are those of bionj_joins_host with the same plan, bit for bit.
+ * PGM_ERR_INVALID, before anything is launched: whatever pgm_bionj_multi rejects, a NULL plan, a pair with index1 >= index2 or
+ * index2 >= n[f]-s at join s. */
+typedef struct pgm_bionj_pair { uint32_t index1, index2; } pgm_bionj_pair;
+int pgm_bionj_plan(pgm_ctx *ctx, uint32_t n, const double *D, const double *V, const pgm_bionj_pair *plan,
+                   pgm_bionj_join *joins, double *final_d);
+int pgm_bionj_plan_multi(pgm_ctx *ctx, uint32_t nfam, const uint32_t *n, const double *D, const double *V,
+                         const pgm_bionj_pair *plan, pgm_bionj_join *joins, double *final_d);
+
 #ifdef __cplusplus
 }
 #endif

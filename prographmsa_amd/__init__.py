@@ -69,6 +69,10 @@ class pgm_bionj_join(C.Structure):
     _fields_ = [("index1", C.c_uint32), ("index2", C.c_uint32), ("dist1", C.c_double), ("dist2", C.c_double)]
 
 
+class pgm_bionj_pair(C.Structure):
+    _fields_ = [("index1", C.c_uint32), ("index2", C.c_uint32)]
+
+
 class pgm_align_out(C.Structure):
     _fields_ = [("score", C.c_float), ("n_tr_indels", C.c_uint32), ("len", C.c_uint32), ("status", C.c_int32),
                 ("map1", C.POINTER(C.c_uint32)), ("map2", C.POINTER(C.c_uint32))]
@@ -86,6 +90,7 @@ EXPORTS = [
     "pgm_gapmask_extend_batch", "pgm_gap_parsimony_batch", "pgm_parsimony_last_kernel_ms",
     "pgm_wls_load", "pgm_wls_pair_sums_batch", "pgm_wls_last_kernel_ms", "pgm_wls_last_launches",
     "pgm_bionj", "pgm_bionj_multi", "pgm_bionj_last_launches", "pgm_bionj_last_kernel_ms",
+    "pgm_bionj_plan", "pgm_bionj_plan_multi",
 ]
 
 
@@ -157,6 +162,8 @@ def _load():
         "pgm_bionj_multi": (C.c_int, [vp, u32, C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(pgm_bionj_join), C.POINTER(C.c_double)]),
         "pgm_bionj_last_launches": (C.c_uint32, [vp]),
         "pgm_bionj_last_kernel_ms": (C.c_float, [vp]),
+        "pgm_bionj_plan": (C.c_int, [vp, u32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(pgm_bionj_pair), C.POINTER(pgm_bionj_join), C.POINTER(C.c_double)]),
+        "pgm_bionj_plan_multi": (C.c_int, [vp, u32, C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(pgm_bionj_pair), C.POINTER(pgm_bionj_join), C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = the library does not export a declared symbol

@@ -1,7 +1,8 @@
 // pgm_bionj_capi.inc — C ABI of the BioNJ joins (included by pgm_capi.hip).  A call uploads the families' matrices, the family
 // descriptors and the identity index lists, runs the three kernels of pgm_bionj_kernels.h once per join of the largest family
 // (plain launches on the context's stream: stream order is the only dependency), and copies the join log and final_d back in
-// one copy behind one synchronisation.
+// one copy behind one synchronisation.  With a plan of joins (pgm_bionj_plan_multi) the kernels are two launches in all: the
+// preparation, then every join of every family.
 namespace {
 // scratch slots (see scratch_dev): 28 = D, T, V; 29 = sums, column minima, descriptors, index lists; 30 = join log + final_d
 enum { SC_BIONJ_MAT = 28, SC_BIONJ_VEC = 29, SC_BIONJ_OUT = 30 };
@@ -10,8 +11,10 @@ enum { SC_BIONJ_MAT = 28, SC_BIONJ_VEC = 29, SC_BIONJ_OUT = 30 };
 extern "C" float pgm_bionj_last_kernel_ms(pgm_ctx *ctx) { return ctx ? ctx->bionj_ms : 0.0f; }
 extern "C" uint32_t pgm_bionj_last_launches(pgm_ctx *ctx) { return ctx ? ctx->bionj_launches : 0u; }
 
-extern "C" int pgm_bionj_multi(pgm_ctx *ctx, uint32_t nfam, const uint32_t *n, const double *D, const double *V,
-                               pgm_bionj_join *joins, double *final_d) {
+namespace {
+// plan == nullptr: every join's pair is the criterion's first minimum (three kernels per join); else the pairs of `plan`
+int bionj_run(pgm_ctx *ctx, uint32_t nfam, const uint32_t *n, const double *D, const double *V, const pgm_bionj_pair *plan,
+              pgm_bionj_join *joins, double *final_d) {
     if (ctx) { ctx->bionj_ms = 0; ctx->bionj_launches = 0; }
     if (!ctx || !n || !D || !V || !joins || !final_d) return fail(PGM_ERR_INVALID, "null argument");
     if (nfam == 0) return fail(PGM_ERR_INVALID, "bionj: no family");
@@ -36,9 +39,18 @@ extern "C" int pgm_bionj_multi(pgm_ctx *ctx, uint32_t nfam, const uint32_t *n, c
         });
         if (bad.load()) return fail(PGM_ERR_INVALID, "bionj: a distance or variance is not finite");
     }
+    if (plan)   // the kernel indexes the matrices with these
+        for (uint32_t f = 0; f < nfam; ++f)
+            for (uint32_t s = 0; s + 3u < n[f]; ++s) {
+                const pgm_bionj_pair &p = plan[fam[f].joff + s];
+                if (p.index1 >= p.index2 || p.index2 >= n[f] - s)
+                    return fail(PGM_ERR_INVALID, "bionj: family " + std::to_string(f) + ": pair (" + std::to_string(p.index1) + ", " + std::to_string(p.index2) + ") of join " +
+                                                     std::to_string(s) + " is not index1 < index2 < " + std::to_string(n[f] - s));
+            }
     // the vector buffer: sums, best_q (doubles), the descriptors, act[0], act[1], best_row; descriptors and act[0] are uploaded
     const size_t o_sums = 0, o_bq = o_sums + 8 * sum_n, o_fam = o_bq + 8 * sum_n, o_act0 = o_fam + sizeof(PgmBionjFam) * nfam,
-                 o_act1 = o_act0 + 4 * sum_n, o_brow = o_act1 + 4 * sum_n, vec_bytes = o_brow + 4 * sum_n;
+                 o_act1 = o_act0 + 4 * sum_n, o_brow = o_act1 + 4 * sum_n, o_plan = o_brow + 4 * sum_n,
+                 vec_bytes = o_plan + (plan ? sizeof(pgm_bionj_pair) * sum_j : 0);   // (the plan behind the rest: uploaded)
     const size_t out_joins = sizeof(pgm_bionj_join) * sum_j, out_bytes = out_joins + 8 * 9 * (size_t)nfam;
     std::vector<uint8_t> img(o_act0 - o_fam + 4 * sum_n);
     memcpy(img.data(), fam.data(), sizeof(PgmBionjFam) * nfam);
@@ -64,16 +76,25 @@ extern "C" int pgm_bionj_multi(pgm_ctx *ctx, uint32_t nfam, const uint32_t *n, c
     HIPCHK(hipMemcpyAsync(S.D, D, 8 * (size_t)sum_nn, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(S.V, V, 8 * (size_t)sum_nn, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_vec + o_fam, img.data(), img.size(), hipMemcpyHostToDevice, s));
+    if (plan) HIPCHK(hipMemcpyAsync(d_vec + o_plan, plan, sizeof(pgm_bionj_pair) * sum_j, hipMemcpyHostToDevice, s));
     HIPCHK(hipEventRecord(ctx->sc_ev[0], s));
     const uint32_t gy = std::min(nfam, 65535u), gz = (nfam + gy - 1) / gy;
     uint32_t launches = 0;
-    for (uint32_t step = 0; step + 3u < nmax; ++step) {
-        const dim3 cols((nmax - step + PGM_BIONJ_COLS - 1) / PGM_BIONJ_COLS, gy, gz);
-        hipLaunchKernelGGL(pgm_bionj_sums_kernel, cols, dim3(64 * PGM_BIONJ_COLS), 0, s, S, step);
-        hipLaunchKernelGGL(pgm_bionj_scan_kernel, cols, dim3(64 * PGM_BIONJ_COLS), 0, s, S, step);
-        hipLaunchKernelGGL(pgm_bionj_join_kernel, dim3(1, gy, gz), dim3(256), 0, s, S, step);
+    if (plan) {   // the clamp of every matrix, then one workgroup per family for all of its joins
+        const uint32_t gx = (uint32_t)std::min<uint64_t>(((uint64_t)nmax * nmax + 255u) / 256u, 1024u);
+        hipLaunchKernelGGL(pgm_bionj_prepare_kernel, dim3(gx, gy, gz), dim3(256), 0, s, S);
+        hipLaunchKernelGGL(pgm_bionj_plan_kernel, dim3(1, gy, gz), dim3(256), 0, s, S, (const pgm_bionj_pair *)(d_vec + o_plan));
         HIPCHK(hipGetLastError());
-        launches += 3;
+        launches = 2;
+    } else {
+        for (uint32_t step = 0; step + 3u < nmax; ++step) {
+            const dim3 cols((nmax - step + PGM_BIONJ_COLS - 1) / PGM_BIONJ_COLS, gy, gz);
+            hipLaunchKernelGGL(pgm_bionj_sums_kernel, cols, dim3(64 * PGM_BIONJ_COLS), 0, s, S, step);
+            hipLaunchKernelGGL(pgm_bionj_scan_kernel, cols, dim3(64 * PGM_BIONJ_COLS), 0, s, S, step);
+            hipLaunchKernelGGL(pgm_bionj_join_kernel, dim3(1, gy, gz), dim3(256), 0, s, S, step);
+            HIPCHK(hipGetLastError());
+            launches += 3;
+        }
     }
     HIPCHK(hipEventRecord(ctx->sc_ev[1], s));
     std::vector<uint8_t> back(out_bytes);
@@ -84,6 +105,26 @@ extern "C" int pgm_bionj_multi(pgm_ctx *ctx, uint32_t nfam, const uint32_t *n, c
     memcpy(final_d, back.data() + out_joins, out_bytes - out_joins);
     ctx->bionj_launches = launches;
     return PGM_OK;
+}
+}  // namespace
+
+extern "C" int pgm_bionj_multi(pgm_ctx *ctx, uint32_t nfam, const uint32_t *n, const double *D, const double *V,
+                               pgm_bionj_join *joins, double *final_d) {
+    return bionj_run(ctx, nfam, n, D, V, nullptr, joins, final_d);
+}
+
+extern "C" int pgm_bionj_plan_multi(pgm_ctx *ctx, uint32_t nfam, const uint32_t *n, const double *D, const double *V,
+                                    const pgm_bionj_pair *plan, pgm_bionj_join *joins, double *final_d) {
+    if (!plan) {
+        if (ctx) { ctx->bionj_ms = 0; ctx->bionj_launches = 0; }
+        return fail(PGM_ERR_INVALID, "null argument");
+    }
+    return bionj_run(ctx, nfam, n, D, V, plan, joins, final_d);
+}
+
+extern "C" int pgm_bionj_plan(pgm_ctx *ctx, uint32_t n, const double *D, const double *V, const pgm_bionj_pair *plan,
+                              pgm_bionj_join *joins, double *final_d) {
+    return pgm_bionj_plan_multi(ctx, 1, &n, D, V, plan, joins, final_d);
 }
 
 extern "C" int pgm_bionj(pgm_ctx *ctx, uint32_t n, const double *D, const double *V, pgm_bionj_join *joins, double *final_d) {

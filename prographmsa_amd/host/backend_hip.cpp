@@ -129,6 +129,15 @@ struct HipBackend : Backend {
         bionj_launches += pgm_bionj_last_launches(c);
         return true;
     }
+    bool bionj_plan_multi(uint32_t nfam, const uint32_t *n, const double *D, const double *V, const pgm_bionj_pair *plan, pgm_bionj_join *joins, double *final_d,
+                          int worker) override {
+        pgm_ctx *c = ctx_of(worker);
+        int rc = pgm_bionj_plan_multi(c, nfam, n, D, V, plan, joins, final_d);
+        if (rc != PGM_OK) error("pgm_bionj_plan_multi failed (%d): %s", rc, pgm_last_error());
+        ++bionj_device_calls;
+        bionj_launches += pgm_bionj_last_launches(c);
+        return true;
+    }
     bool gapmask_extend_batch(uint32_t njobs, const pgm_gapmask_job *jobs, int worker) override {
         int rc = pgm_gapmask_extend_batch(ctx_of(worker), njobs, jobs);
         if (rc != PGM_OK) error("pgm_gapmask_extend_batch failed (%d): %s", rc, pgm_last_error());

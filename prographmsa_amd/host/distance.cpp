@@ -2,7 +2,7 @@
 // (reference src/DistanceFactoryAlign.{h,cpp}, DistanceFactoryML.{h,cpp}, TreeNJ.{h,cpp}).
 // The O(L^2) Needleman-Wunsch of every pair (alignPair), the pair counts of an alignment and the k-mer cosine matrix run behind the
 // C ABI, and so does ML distance estimation when PGM_DEVICE_MLDIST is set (pgm_mldist_batch; on the host threads otherwise);
-// the joins of neighbour joining run on the host threads or, from kBionjDeviceMin taxa on, behind pgm_bionj_multi.  TreeNJ (one family) and TreeNJ_multi (--batch) are one implementation: the last section.
+// the joins of neighbour joining run on the host threads or, from kBionjDeviceMin taxa on, behind pgm_bionj_multi; with a fixed topology (--topology) the pairs come from a plan.  TreeNJ (one family) and TreeNJ_multi (--batch) are one implementation: the last section.
 #include "pgm_host.h"
 #include "nnls.h"
 #include <quadmath.h>
@@ -12,6 +12,7 @@
 #include <chrono>
 #include <cmath>
 #include <fstream>
+#include <functional>
 #include <thread>
 
 namespace pgm {
@@ -167,7 +168,7 @@ DistanceFactoryAlign::DistanceFactoryAlign(const Alphabet &a, const ModelFactory
     gap_extend = -2;
 }
 
-// ---- BioNJ (TreeNJ.cpp:22-29, 132-281; no fixed-topology plan) --------------------------------------
+// ---- BioNJ (TreeNJ.cpp:22-29, 132-281; the plan of a fixed topology: TreeNJ.cpp:31-130) -------------
 static double support(double d) {
     double s = 1.0 - std::exp(-std::log(2.0) * d / cmdlineopts.edge_halflife);
     s = std::min(1.0, std::max(0.0, s));
@@ -209,6 +210,72 @@ static double eigen_column_sum(const std::vector<double> &tr, size_t ld, const s
     return res;
 }
 
+// The joins a fixed topology prescribes (TreeNJ.cpp:31-130), in reduced indices with index1 < index2: a node of `topo` is
+// visited when all its children have been (a leaf needs no visit), first in, first out; the visit joins the clusters of its
+// two children, the joined cluster keeps the smaller index and every index above the larger one moves down by one.  The order
+// of the visits shows in the branch lengths, so it has to be the reference's: its work list starts with the nodes all of
+// whose children are leaves in the order of a std::map keyed by node address, and its parser allocates a node before its
+// children, which makes that the pre-order of the file (tests/golden/topology.json pins it).  A leaf that is no sequence of
+// the family has no cluster: a node with one such child passes the other child's cluster up, without a join.  One pair per
+// internal node with sequences below both children: seqs_order.size() - 1 pairs, of which the join loop uses all but the
+// last two (it stops at three clusters).
+// Errors: a sequence that no leaf names (the reference's message, its missing blank included); a sequence that two leaves
+// name; a node whose number of children is not two (the reference asserts, and its release build goes on undefined).
+std::vector<pgm_bionj_pair> build_topo_plan(const std::vector<std::string> &seqs_order, const PhyTree *topo) {
+    const uint32_t NONE = 0xFFFFFFFFu;
+    struct Node { const PhyTree *tree; int parent, kid[2]; uint32_t cluster, ready; };   // cluster: reduced index, NONE: no sequence below
+    std::vector<Node> nodes;   // in pre-order
+    struct Todo { const PhyTree *tree; int parent; index_t slot; };
+    std::vector<Todo> todo{Todo{topo, -1, 0}};   // (an explicit stack: a ladder is as deep as it has leaves)
+    while (!todo.empty()) {
+        const Todo t = todo.back();
+        todo.pop_back();
+        const int me = (int)nodes.size();
+        nodes.push_back(Node{t.tree, t.parent, {-1, -1}, NONE, 0});
+        if (t.parent >= 0) {
+            if (t.slot < 2) nodes[(size_t)t.parent].kid[t.slot] = me;
+            if (t.tree->isLeaf()) ++nodes[(size_t)t.parent].ready;
+        }
+        for (index_t c = t.tree->n_children(); c-- > 0;) todo.push_back(Todo{&(*t.tree)[(int)c], me, c});   // (the first child on top)
+    }
+    std::map<std::string, uint32_t> orig_leaf_index;
+    for (size_t i = 0; i < seqs_order.size(); ++i) orig_leaf_index[seqs_order[i]] = (uint32_t)i;
+    std::vector<int> at(seqs_order.size(), -1);   // reduced index -> the node that holds the cluster
+    for (size_t k = 0; k < nodes.size(); ++k) {
+        if (!nodes[k].tree->isLeaf()) continue;
+        auto pos = orig_leaf_index.find(nodes[k].tree->getName());
+        if (pos == orig_leaf_index.end()) continue;
+        if (at[pos->second] >= 0) error("sequence \"%s\" appears more than once in given topology", pos->first.c_str());
+        at[pos->second] = (int)k;
+        nodes[k].cluster = pos->second;
+    }
+    for (size_t i = 0; i < at.size(); ++i)
+        if (at[i] < 0) error("sequence \"%s\"is missing in given topology", seqs_order[i].c_str());
+    for (const Node &nd : nodes)
+        if (!nd.tree->isLeaf() && nd.tree->n_children() != 2)
+            error("--topology: a node with %d children (every node of the topology must have two)", (int)nd.tree->n_children());
+    std::vector<int> worklist;   // (a queue: `head` is its front)
+    for (size_t k = 0; k < nodes.size(); ++k)
+        if (!nodes[k].tree->isLeaf() && nodes[k].ready == 2) worklist.push_back((int)k);
+    std::vector<pgm_bionj_pair> plan;
+    for (size_t head = 0; head < worklist.size(); ++head) {
+        Node &node = nodes[(size_t)worklist[head]];
+        uint32_t index1 = nodes[(size_t)node.kid[0]].cluster, index2 = nodes[(size_t)node.kid[1]].cluster;
+        if (index1 == NONE || index2 == NONE) {
+            node.cluster = index1 == NONE ? index2 : index1;
+        } else {
+            if (index1 > index2) std::swap(index1, index2);
+            plan.push_back(pgm_bionj_pair{index1, index2});
+            node.cluster = index1;
+            at.erase(at.begin() + (std::ptrdiff_t)index2);
+            for (size_t i = index2; i < at.size(); ++i) nodes[(size_t)at[i]].cluster = (uint32_t)i;
+        }
+        if (node.cluster != NONE) at[node.cluster] = worklist[head];
+        if (node.parent >= 0 && ++nodes[(size_t)node.parent].ready == 2) worklist.push_back(node.parent);
+    }
+    return plan;
+}
+
 // O(N^2) per join, N - 3 joins.  What the reference does per join — clamp every entry, column sums, the scan of the criterion, a
 // copy of the matrix without the joined column — is here: the clamp of the entries the previous join wrote (the others were
 // clamped when they were written, and nothing reads an entry between its join and the next clamp), sums and scan on the host
@@ -217,7 +284,10 @@ static double eigen_column_sum(const std::vector<double> &tr, size_t ld, const s
 // The loop records its joins (reduced indices, index1 < index2, and the two branch lengths) and, when it ends, the D of the
 // clusters left (final_d: 3 x 3 row-major; for n0 < 4 the matrix as it came, nothing clamped): all bionj_tree needs to assemble
 // the tree, and what pgm_bionj_multi computes on the device (same bits: DESIGN.md 3.11).
-void bionj_joins_host(DistanceMatrix dist, std::vector<pgm_bionj_join> &joins, double *final_d) {
+// With a plan (build_topo_plan; TreeNJ.cpp:158-179) a join takes its pair from it while it has entries: the two column sums of
+// that pair, no scan, O(N) per join; everything after the choice of the pair is the same lines (pgm_bionj_plan_multi on the
+// device: DESIGN.md 3.12).
+void bionj_joins_host(DistanceMatrix dist, std::vector<pgm_bionj_join> &joins, double *final_d, const std::vector<pgm_bionj_pair> *plan) {
     const double MIN_DIST = 1e-4, MIN_VAR = 1e-5;
     const int n0 = dist.dim;
     joins.clear();
@@ -245,34 +315,42 @@ void bionj_joins_host(DistanceMatrix dist, std::vector<pgm_bionj_join> &joins, d
             }
         }
         sums.assign((size_t)dim, 0.0);  // colwise sums
-        const bool threads = dim >= 512;   // (a section of half a millisecond and more; tests/test_oracle_golden.py: the 1024-taxon tree)
-        const size_t nranges = threads ? 16 : 1;
-        auto range = [&](size_t r, int &c0, int &c1) { c0 = (int)((size_t)dim * r / nranges); c1 = (int)((size_t)dim * (r + 1) / nranges); };
-        auto sum_range = [&](size_t r) { int c0, c1; range(r, c0, c1); for (int j = c0; j < c1; ++j) sums[(size_t)j] = eigen_column_sum(tr, ld, act, dim, j); };
-        if (threads) parallel_for(nranges, sum_range); else sum_range(0);
-        // Q = 0.5 d - 0.5/(dim-2) (S + S^T); minCoeff scans column-major (row index fastest) and keeps the first minimum
-        struct Best { double min; int row, col; };
-        std::vector<Best> best(nranges, Best{INFINITY, 0, 0});
-        auto scan_range = [&](size_t r) {
-            int c0, c1; range(r, c0, c1);
-            Best bq{INFINITY, 0, 0};
-            const double f = 0.5 / (dim - 2.0);
-            for (int col = c0; col < c1; ++col) {
-                const double *colp = &tr[(size_t)act[(size_t)col] * ld];   // column col of the distances
-                const double sc = sums[(size_t)col];
-                for (int row = 0; row < dim; ++row) {
-                    if (row == col) continue;
-                    const double q = 0.5 * colp[(size_t)act[(size_t)row]] - f * (sc + sums[(size_t)row]);
-                    if (q < bq.min) { bq.min = q; bq.row = row; bq.col = col; }
-                }
-            }
-            best[r] = bq;
-        };
-        if (threads) parallel_for(nranges, scan_range); else scan_range(0);
         int index1 = 0, index2 = 0;
-        double min = INFINITY;
-        for (size_t r = 0; r < nranges; ++r) if (best[r].min < min) { min = best[r].min; index2 = best[r].row; index1 = best[r].col; }
-        if (index2 < index1) std::swap(index1, index2);
+        const size_t step = (size_t)(n0 - dim);
+        if (plan && step < plan->size()) {   // the pair is given: its two sums, the bits of the full loop's
+            index1 = (int)(*plan)[step].index1; index2 = (int)(*plan)[step].index2;
+            if (index1 < 0 || index1 >= index2 || index2 >= dim) error("BioNJ: join %zu of the topology's plan is out of range", step);
+            sums[(size_t)index1] = eigen_column_sum(tr, ld, act, dim, index1);
+            sums[(size_t)index2] = eigen_column_sum(tr, ld, act, dim, index2);
+        } else {
+            const bool threads = dim >= 512;   // (a section of half a millisecond and more; tests/test_oracle_golden.py: the 1024-taxon tree)
+            const size_t nranges = threads ? 16 : 1;
+            auto range = [&](size_t r, int &c0, int &c1) { c0 = (int)((size_t)dim * r / nranges); c1 = (int)((size_t)dim * (r + 1) / nranges); };
+            auto sum_range = [&](size_t r) { int c0, c1; range(r, c0, c1); for (int j = c0; j < c1; ++j) sums[(size_t)j] = eigen_column_sum(tr, ld, act, dim, j); };
+            if (threads) parallel_for(nranges, sum_range); else sum_range(0);
+            // Q = 0.5 d - 0.5/(dim-2) (S + S^T); minCoeff scans column-major (row index fastest) and keeps the first minimum
+            struct Best { double min; int row, col; };
+            std::vector<Best> best(nranges, Best{INFINITY, 0, 0});
+            auto scan_range = [&](size_t r) {
+                int c0, c1; range(r, c0, c1);
+                Best bq{INFINITY, 0, 0};
+                const double f = 0.5 / (dim - 2.0);
+                for (int col = c0; col < c1; ++col) {
+                    const double *colp = &tr[(size_t)act[(size_t)col] * ld];   // column col of the distances
+                    const double sc = sums[(size_t)col];
+                    for (int row = 0; row < dim; ++row) {
+                        if (row == col) continue;
+                        const double q = 0.5 * colp[(size_t)act[(size_t)row]] - f * (sc + sums[(size_t)row]);
+                        if (q < bq.min) { bq.min = q; bq.row = row; bq.col = col; }
+                    }
+                }
+                best[r] = bq;
+            };
+            if (threads) parallel_for(nranges, scan_range); else scan_range(0);
+            double min = INFINITY;
+            for (size_t r = 0; r < nranges; ++r) if (best[r].min < min) { min = best[r].min; index2 = best[r].row; index1 = best[r].col; }
+            if (index2 < index1) std::swap(index1, index2);
+        }
         double dist1 = (D(index1, index2) + (sums[index1] - sums[index2]) / (dim - 2.0)) / 2.0;
         dist1 = std::min(std::max(dist1, MIN_DIST), D(index1, index2));
         double dist2 = std::max(D(index2, index1) - dist1, MIN_DIST);
@@ -338,10 +416,12 @@ PhyTree *bionj_tree(std::vector<std::string> seqs_order, const std::vector<pgm_b
     return tree;
 }
 
-PhyTree *buildNJTree(std::vector<std::string> seqs_order, DistanceMatrix dist) {
+PhyTree *buildNJTree(std::vector<std::string> seqs_order, DistanceMatrix dist, const PhyTree *topo) {
     std::vector<pgm_bionj_join> joins;
     double final_d[9];
-    bionj_joins_host(std::move(dist), joins, final_d);
+    std::vector<pgm_bionj_pair> plan;
+    if (topo) plan = build_topo_plan(seqs_order, topo);
+    bionj_joins_host(std::move(dist), joins, final_d, topo ? &plan : nullptr);
     return bionj_tree(std::move(seqs_order), joins, final_d);
 }
 
@@ -1296,6 +1376,22 @@ void tree_nj(const Alphabet &a, std::vector<TreeJob> &jobs, bool prealigned, boo
         }
         act.push_back(j);
     }
+    // the plans of the families with a fixed topology (std::map key order is the order of the matrix: TreeNJ.h:34-39); a family
+    // whose topology does not fit leaves with the message before any distance is estimated
+    std::vector<std::vector<pgm_bionj_pair>> plans(jobs.size());
+    {
+        std::vector<size_t> fits;
+        for (size_t j : act) {
+            if (jobs[j].topo) {
+                std::vector<std::string> order;
+                for (const auto &kv : *jobs[j].seqs) order.push_back(kv.first);
+                try { plans[j] = build_topo_plan(order, jobs[j].topo); }
+                catch (std::exception &e) { jobs[j].error = e.what(); continue; }
+            }
+            fits.push_back(j);
+        }
+        act.swap(fits);
+    }
     if (act.empty()) return;
     Families F;
     const uint32_t nfam = F.nfam = (uint32_t)act.size();
@@ -1319,18 +1415,21 @@ void tree_nj(const Alphabet &a, std::vector<TreeJob> &jobs, bool prealigned, boo
     // the largest family has kBionjDeviceMin taxa and every entry is finite: the device entry takes no NaN or infinity), or the
     // host loop per family (one family: on this thread, the loop's sections on the host threads; several: the families on the
     // host threads).  Either way the same join records, and so the same trees.
+    // The families with a fixed topology are a call of their own, bionj_plan_multi, with PGM_DEVICE_BIONJ only: their host loop
+    // is O(n) per join as well, so it is the default.
     std::vector<std::vector<pgm_bionj_join>> joins(nfam);
     std::vector<double> final_d((size_t)9 * nfam, 0.0);
     for (DistanceMatrix &d : F.dist)
         for (int i = 0; i < d.dim; ++i) { d.D(i, i) = 0; d.V(i, i) = 0; }
-    bool on_device = false;
-    {
+    auto plan_of = [&](uint32_t f) -> const std::vector<pgm_bionj_pair> * { return jobs[act[f]].topo ? &plans[act[f]] : nullptr; };
+    std::vector<char> on_device(nfam, 0);
+    for (int planned = 0; planned < 2; ++planned) {
         std::vector<uint32_t> dev;   // the families of the device call
         uint32_t nmax = 0;
         for (uint32_t f = 0; f < nfam; ++f)
-            if (F.nseq[f] >= 4 && F.nseq[f] <= PGM_BIONJ_MAX_N) { dev.push_back(f); nmax = std::max(nmax, F.nseq[f]); }
+            if ((plan_of(f) != nullptr) == (planned != 0) && F.nseq[f] >= 4 && F.nseq[f] <= PGM_BIONJ_MAX_N) { dev.push_back(f); nmax = std::max(nmax, F.nseq[f]); }
         const HostSwitches &sw = host_switches();
-        if (!dev.empty() && !sw.host_bionj && (sw.device_bionj || nmax >= kBionjDeviceMin)) {
+        if (!dev.empty() && !sw.host_bionj && (sw.device_bionj || (!planned && nmax >= kBionjDeviceMin))) {
             std::vector<char> finite(dev.size(), 1);
             parallel_for(dev.size(), [&](size_t k) {
                 const DistanceMatrix &d = F.dist[dev[k]];
@@ -1358,12 +1457,20 @@ void tree_nj(const Alphabet &a, std::vector<TreeJob> &jobs, bool prealigned, boo
                     });
                 }
                 const DistanceMatrix &d0 = F.dist[dev[0]];
+                const double *Dp = dev.size() > 1 ? Dcat.data() : d0.distances.data(), *Vp = dev.size() > 1 ? Vcat.data() : d0.variances.data();
                 std::vector<pgm_bionj_join> jcat(j0[dev.size()]);
                 std::vector<double> fcat((size_t)9 * dev.size());
-                on_device = be_bionj.bionj_multi((uint32_t)dev.size(), ns.data(), dev.size() > 1 ? Dcat.data() : d0.distances.data(),
-                                                 dev.size() > 1 ? Vcat.data() : d0.variances.data(), jcat.data(), fcat.data(), 0);
-                if (on_device)
+                bool ran;
+                if (planned) {
+                    std::vector<pgm_bionj_pair> pcat(j0[dev.size()]);   // (a plan has n - 1 pairs: the joins use the first n - 3)
+                    for (size_t k = 0; k < dev.size(); ++k) std::copy(plan_of(dev[k])->begin(), plan_of(dev[k])->begin() + (std::ptrdiff_t)(ns[k] - 3), pcat.begin() + (std::ptrdiff_t)j0[k]);
+                    ran = be_bionj.bionj_plan_multi((uint32_t)dev.size(), ns.data(), Dp, Vp, pcat.data(), jcat.data(), fcat.data(), 0);
+                } else {
+                    ran = be_bionj.bionj_multi((uint32_t)dev.size(), ns.data(), Dp, Vp, jcat.data(), fcat.data(), 0);
+                }
+                if (ran)
                     for (size_t k = 0; k < dev.size(); ++k) {
+                        on_device[dev[k]] = 1;
                         joins[dev[k]].assign(jcat.begin() + (std::ptrdiff_t)j0[k], jcat.begin() + (std::ptrdiff_t)j0[k + 1]);
                         std::copy(fcat.begin() + (std::ptrdiff_t)(9 * k), fcat.begin() + (std::ptrdiff_t)(9 * k + 9), final_d.begin() + (std::ptrdiff_t)(9 * (size_t)dev[k]));
                     }
@@ -1372,8 +1479,8 @@ void tree_nj(const Alphabet &a, std::vector<TreeJob> &jobs, bool prealigned, boo
     }
     std::vector<std::string> join_error(nfam);
     parallel_for(nfam, [&](size_t f) {
-        if (on_device && F.nseq[f] >= 4 && F.nseq[f] <= PGM_BIONJ_MAX_N) return;
-        try { bionj_joins_host(F.dist[f], joins[f], &final_d[9 * f]); }
+        if (on_device[f]) return;
+        try { bionj_joins_host(F.dist[f], joins[f], &final_d[9 * f], plan_of((uint32_t)f)); }
         catch (std::exception &e) { join_error[f] = e.what(); }
     });
     be_bionj.seconds_bionj += std::chrono::duration<double>(std::chrono::steady_clock::now() - tq1).count();
@@ -1396,10 +1503,11 @@ void tree_nj(const Alphabet &a, std::vector<TreeJob> &jobs, bool prealigned, boo
 }
 }  // namespace
 
-PhyTree *TreeNJ(const Alphabet &a, const std::map<std::string, sequence_t> &seqs, const ModelFactory *mf, bool prealigned) {
+PhyTree *TreeNJ(const Alphabet &a, const std::map<std::string, sequence_t> &seqs, const ModelFactory *mf, bool prealigned, const PhyTree *topo) {
     std::vector<TreeJob> job(1);
     job[0].seqs = &seqs;
     job[0].model_factory = mf;
+    job[0].topo = topo;
     tree_nj(a, job, prealigned, true);
     if (!job[0].error.empty()) throw pgm_exception(job[0].error);
     return job[0].tree;

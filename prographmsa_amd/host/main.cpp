@@ -18,16 +18,21 @@
 using namespace pgm;
 
 static void usage() {
-    std::cerr << "USAGE: pgmsa [-f|--fasta] [-t|--tree <newick>] [-o <file>] [-T] [-I] [-a] [-m] [-M]\n"
+    std::cerr << "USAGE: pgmsa [-f|--fasta] [-t|--tree <newick>] [--topology <newick>] [-o <file>] [-T] [-I] [-a] [-m] [-M]\n"
                  "             [--codon] [-c|--cs_profile <lib>] [-i <iters>] [-g rate] [-e prob] [-E prob]\n"
                  "             [-s prob] [-A] [--early_refinement] [--ancestral_seqs] [--profile_out <file>] [-R] [--read_repeats <file>]\n"
                  "             [-r|--reroot [-r]] [-W|--wls_refine [-W]] [--dna] [--custom_model <file>] [-F|--estimate_aafreqs]\n"
                  "             [-C|--aafreqs_pseudocount <count>] [--dump_jobs <file>] [--dump_dist <file>] [--dump_joins <file>] [--stats] <fasta file>\n"
                  "       pgmsa --batch <list> [--batch_cells <cells>] [options]\n"
-                 "  --batch <list>  align many families in one run: every line of <list> is input.fa<TAB>output[<TAB>guide_tree.nwk] (blank\n"
-                 "                lines and lines starting with # are skipped); the other options apply to every family and every output is\n"
-                 "                what the same options write for that family alone.  Not with a positional file, -o, -t, -r, -W, -R,\n"
-                 "                --read_repeats, --profile_out, --dump_jobs, --dump_dist, --dump_joins\n"
+                 "  --batch <list>  align many families in one run: every line of <list> is input.fa<TAB>output[<TAB>guide_tree.nwk[<TAB>topology.nwk]]\n"
+                 "                (an empty third field: no guide tree; blank lines and lines starting with # are skipped); the other options\n"
+                 "                apply to every family and every output is what the same options write for that family alone.  Not with a\n"
+                 "                positional file, -o, -t, --topology, -r, -W, -R, --read_repeats, --profile_out, --dump_jobs, --dump_dist,\n"
+                 "                --dump_joins\n"
+                 "  --topology <newick>  every guide tree the run estimates (the initial one unless -t is given, and the one after every\n"
+                 "                pass) keeps the topology of this tree; only its branch lengths are estimated.  The file needs a branch\n"
+                 "                length on every edge (the values are ignored) and two children at every node; every sequence must be a\n"
+                 "                leaf, leaves that are no sequence are pruned\n"
                  "  --batch_cells <cells>  families share the device stages in chunks of at most this many estimated DP cells per pass\n"
                  "                (default 2e9); a larger family is a chunk of its own\n"
                  "  --dna         align DNA sequences (T C A G; U reads as T; N, X and the IUPAC ambiguity codes as unknown); needs\n"
@@ -90,7 +95,7 @@ static std::string value_name(const Alphabet &a, int j) {   // ALPHABET(j).asStr
 // a chunk of families through the same stages together.
 namespace {
 struct Family {
-    std::string input, output, tree_file;   // (--batch: the fields of the family's line of the list)
+    std::string input, output, tree_file, topo_file;   // (--batch: the fields of the family's line of the list)
     int iters = 0;
     std::vector<std::string> input_order;
     std::map<std::string, std::string> seqs;   // as read
@@ -99,13 +104,14 @@ struct Family {
     std::map<std::string, sequence_t> seqs2;   // start / stop stripped
     std::unique_ptr<ModelFactory> model_factory;   // (per family: -F estimates the frequencies from the family's sequences)
     PhyTree *tree = nullptr;
+    PhyTree *topo = nullptr;   // --topology: every estimated tree keeps this topology
     ProgressiveAlignmentResult result, old_result;
     bool done = false;   // converged: takes no further part in the iterations
     std::string failure;   // --batch: the message the solo run would have ended with
     double cells = 0;    // --batch: estimated DP cells of one pass
     int worker = 0;
     std::map<std::string, std::string> aligned;
-    ~Family() { delete tree; }
+    ~Family() { delete tree; delete topo; }
 
     // strip start/stop (main.cpp:332-353) and set the models up
     void prepare(const Alphabet &a) {
@@ -125,6 +131,11 @@ struct Family {
         std::ifstream ts(tree_file.c_str());
         if (!ts) error("cannot open tree file %s", tree_file.c_str());
         tree = parse_newick(ts);
+    }
+    void read_topology() {   // (main.cpp:384-387)
+        std::ifstream ts(topo_file.c_str());
+        if (!ts) error("cannot open topology file %s", topo_file.c_str());
+        topo = parse_newick(ts);
     }
     void drop_ancestral_rows() {
         for (auto it = result.aligned_sequences.begin(); it != result.aligned_sequences.end();)   // ancestral sequences
@@ -211,8 +222,9 @@ static int doAlign(const Alphabet &a, Family &fam, bool stats) {
     std::map<std::string, std::vector<repeat_t>> reps;   // main.cpp:367-370 (detection by T-REKS itself is not built here: --read_repeats only)
     if (!cmdlineopts.readreps_file.empty()) reps = read_repeats(a, cmdlineopts.readreps_file, fam.seqs2);
     auto t0 = std::chrono::steady_clock::now();
+    if (!fam.topo_file.empty()) fam.read_topology();
     if (!fam.tree_file.empty()) fam.read_tree();
-    else fam.tree = TreeNJ(a, fam.seqs2, fam.model_factory.get());
+    else fam.tree = TreeNJ(a, fam.seqs2, fam.model_factory.get(), false, fam.topo);
     double t_tree = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     ProgressiveAlignmentResult &result = fam.result;
     t0 = std::chrono::steady_clock::now();
@@ -225,7 +237,7 @@ static int doAlign(const Alphabet &a, Family &fam, bool stats) {
         delete fam.tree;
         fam.tree = nullptr;
         const auto tt0 = std::chrono::steady_clock::now();
-        fam.tree = TreeNJ(a, result.aligned_sequences, fam.model_factory.get(), true);
+        fam.tree = TreeNJ(a, result.aligned_sequences, fam.model_factory.get(), true, fam.topo);
         if (host_switches().profile) fprintf(stderr, "guide tree from the alignment: %.1f ms\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tt0).count());
         fam.old_result = result;
     }
@@ -292,6 +304,7 @@ static void trees_for(const Alphabet &a, const std::vector<Family *> &act, bool 
     for (size_t k = 0; k < act.size(); ++k) {
         jobs[k].seqs = prealigned ? &act[k]->result.aligned_sequences : &act[k]->seqs2;
         jobs[k].model_factory = act[k]->model_factory.get();
+        jobs[k].topo = act[k]->topo;
     }
     TreeNJ_multi(a, jobs, prealigned);
     for (size_t k = 0; k < act.size(); ++k) {
@@ -355,11 +368,12 @@ static int doBatch(const Alphabet &a, const std::string &list_file, bool iters_s
             bool blank = true;
             for (char c : line) blank = blank && (c == '\t' || c == ' ');
             if (blank) continue;
-            if (field.size() < 2 || field.size() > 3 || field[0].empty() || field[1].empty())
-                error("--batch: line %d of %s: expected input<TAB>output[<TAB>tree], found %zu field(s)", lineno, list_file.c_str(), field.size());
+            if (field.size() < 2 || field.size() > 4 || field[0].empty() || field[1].empty())
+                error("--batch: line %d of %s: expected input<TAB>output[<TAB>tree[<TAB>topology]], found %zu field(s)", lineno, list_file.c_str(), field.size());
             std::unique_ptr<Family> f(new Family);
             f->input = field[0]; f->output = field[1];
-            if (field.size() == 3) f->tree_file = field[2];
+            if (field.size() >= 3) f->tree_file = field[2];
+            if (field.size() == 4) f->topo_file = field[3];
             f->iters = (!iters_set && !f->tree_file.empty()) ? 0 : cmdlineopts.iters;   // no iterations with a guide tree (main.cpp:243-246)
             fams.push_back(std::move(f));
         }
@@ -376,6 +390,7 @@ static int doBatch(const Alphabet &a, const std::string &list_file, bool iters_s
             f.seqs = read_fasta(f.input, f.input_order);
             f.prepare(a);
             if (!f.tree_file.empty()) f.read_tree();
+            if (!f.topo_file.empty()) f.read_topology();
             f.cells = estimate_cells(f);
         } catch (std::exception &e) { f.failure = e.what(); }
     });
@@ -416,6 +431,7 @@ static int doBatch(const Alphabet &a, const std::string &list_file, bool iters_s
             f->seqs.clear(); f->seqs2.clear(); f->aligned.clear();
             f->result = ProgressiveAlignmentResult(); f->old_result = ProgressiveAlignmentResult();
             delete f->tree; f->tree = nullptr;
+            delete f->topo; f->topo = nullptr;
             f->model_factory.reset();
         }
     }
@@ -436,13 +452,14 @@ int main(int argc, char **argv) {
     }
     try {
         bool iters_set = false, stats = false, indel_set = false, edgehl_set = false, maxdist_set = false, cutdist_set = false;
-        std::string dump, dist_dump, joins_dump, batch_list;
+        std::string dump, dist_dump, joins_dump, batch_list, topo_file;
         double batch_cells = 2e9;
         for (int i = 1; i < argc; ++i) {
             std::string s = argv[i];
             auto val = [&]() -> std::string { if (i + 1 >= argc) { usage(); exit(1); } return argv[++i]; };
             if (s == "-f" || s == "--fasta") cmdlineopts.fasta_flag = true;
             else if (s == "-t" || s == "--tree") cmdlineopts.tree_file = val();
+            else if (s == "--topology") topo_file = val();
             else if (s == "-o" || s == "--output") cmdlineopts.output_file = val();
             else if (s == "-T" || s == "--only_tree") cmdlineopts.onlytree_flag = true;
             else if (s == "-I" || s == "--input_order") cmdlineopts.inputorder_flag = true;
@@ -490,6 +507,7 @@ int main(int argc, char **argv) {
             const char *refused = !cmdlineopts.sequence_file.empty() ? "a positional sequence file (the families come from the list)"
                                   : !cmdlineopts.output_file.empty() ? "-o (every line of the list names its output)"
                                   : !cmdlineopts.tree_file.empty() ? "-t (a guide tree is the third field of a family's line)"
+                                  : !topo_file.empty() ? "--topology (a topology is the fourth field of a family's line)"
                                   : cmdlineopts.reroot_flag ? "-r" : cmdlineopts.wlsrefine_flag ? "-W"
                                   : cmdlineopts.repeats_flag ? "-R" : !cmdlineopts.readreps_file.empty() ? "--read_repeats"
                                   : !cmdlineopts.profile_file.empty() ? "--profile_out" : !dump.empty() ? "--dump_jobs" : !dist_dump.empty() ? "--dump_dist" : !joins_dump.empty() ? "--dump_joins" : nullptr;
@@ -529,7 +547,7 @@ int main(int argc, char **argv) {
         g_startup.start();
         parallel_for(64, [](size_t) {});   // (the driver's host threads start while the device runtime does)
         Family fam;
-        fam.input = cmdlineopts.sequence_file; fam.tree_file = cmdlineopts.tree_file; fam.iters = cmdlineopts.iters;
+        fam.input = cmdlineopts.sequence_file; fam.tree_file = cmdlineopts.tree_file; fam.topo_file = topo_file; fam.iters = cmdlineopts.iters;
         fam.seqs = read_fasta(cmdlineopts.sequence_file, fam.input_order);
         std::ofstream custom_out;
         std::ostream *out = &std::cout;

@@ -319,8 +319,10 @@ struct Backend {
     // the joins of BioNJ for many families in one call (include/pgm_hip.h: pgm_bionj_multi; every n[f] >= 4, every entry finite):
     // the join records and final_d of bionj_joins_host, bit for bit.  false = this backend has no such kernel (the host loop runs)
     virtual bool bionj_multi(uint32_t, const uint32_t *, const double *, const double *, pgm_bionj_join *, double *, int = 0) { return false; }
+    // the same with the pair of every join given (pgm_bionj_plan_multi: n[f] - 3 pairs per family): bionj_joins_host with that plan
+    virtual bool bionj_plan_multi(uint32_t, const uint32_t *, const double *, const double *, const pgm_bionj_pair *, pgm_bionj_join *, double *, int = 0) { return false; }
     double seconds_bionj = 0;                                // host wall of the joins of all guide trees, either path (--stats)
-    uint64_t bionj_device_calls = 0, bionj_launches = 0;     // bionj_multi calls that ran on the device, the kernels they launched
+    uint64_t bionj_device_calls = 0, bionj_launches = 0;     // bionj_multi / bionj_plan_multi calls that ran on the device, the kernels they launched
     // node profiles of a batch of merged graphs on the device (numeric part); false = host arithmetic
     virtual bool merge_profiles_batch(uint32_t, const pgm_merge_job *, int = 0) { return false; }
     double seconds_merge_profiles = 0;
@@ -534,10 +536,16 @@ public:
 private:
     std::vector<int32_t> scoring_matrix_;   // (DIM+1)^2 column-major
 };
-PhyTree *buildNJTree(std::vector<std::string> seqs_order, DistanceMatrix dist);   // TreeNJ.cpp:132-281 (no topology plan)
+// TreeNJ.cpp:132-281; topo: the tree keeps this topology (--topology) and only its branch lengths are estimated
+PhyTree *buildNJTree(std::vector<std::string> seqs_order, DistanceMatrix dist, const PhyTree *topo = nullptr);
 // buildNJTree in two parts: the joins (the O(n^3) loop; pgm_bionj_multi computes the same record on the device) and the tree of
-// a join record.  final_d: the 3 x 3 row-major D of the clusters left (of all min(n, 3) clusters when n < 4)
-void bionj_joins_host(DistanceMatrix dist, std::vector<pgm_bionj_join> &joins, double *final_d);
+// a join record.  final_d: the 3 x 3 row-major D of the clusters left (of all min(n, 3) clusters when n < 4).
+// plan: the pairs to join, one per join while it has entries (build_topo_plan; a join is then O(n): two column sums, no scan;
+// pgm_bionj_plan_multi on the device); nullptr: every pair is the criterion's minimum
+void bionj_joins_host(DistanceMatrix dist, std::vector<pgm_bionj_join> &joins, double *final_d, const std::vector<pgm_bionj_pair> *plan = nullptr);
+// TreeNJ.cpp:31-130: the joins that give the tree over seqs_order the topology `topo`, in the reference's order; leaves of topo
+// that are no sequence are pruned; throws for a sequence topo does not hold and for a node that has not two children
+std::vector<pgm_bionj_pair> build_topo_plan(const std::vector<std::string> &seqs_order, const PhyTree *topo);
 PhyTree *bionj_tree(std::vector<std::string> seqs_order, const std::vector<pgm_bionj_join> &joins, const double *final_d);
 // families of this many taxa and more go to the device by default: the smallest measured size from which the device's joins
 // took less time than the host's at every larger size
@@ -557,7 +565,8 @@ void wls_pair_sums_host(uint32_t n, const double *D, const double *W, uint32_t n
 // (-a; both prealigned == false) or induced by an existing alignment (prealigned == true, the guide-tree re-estimation of
 // main.cpp:404-430), the estimate of every pair on the host threads or, with PGM_DEVICE_MLDIST, on the device for the models the
 // backend's kernels take; then BioNJ, with -W the least-squares refinement, and the midpoint rooting.
-PhyTree *TreeNJ(const Alphabet &a, const std::map<std::string, sequence_t> &seqs, const ModelFactory *mf, bool prealigned = false);
+// topo (--topology): BioNJ joins the pairs this topology prescribes and estimates the branch lengths only.
+PhyTree *TreeNJ(const Alphabet &a, const std::map<std::string, sequence_t> &seqs, const ModelFactory *mf, bool prealigned = false, const PhyTree *topo = nullptr);
 
 // TreeNJ for the families of a --batch chunk.  Both are one implementation over a list of families (TreeNJ: a list of one), so every
 // family's tree is the one TreeNJ gives it alone; the distance stage runs once for all families (one farm of all-pairs tiles over the
@@ -566,6 +575,7 @@ PhyTree *TreeNJ(const Alphabet &a, const std::map<std::string, sequence_t> &seqs
 struct TreeJob {
     const std::map<std::string, sequence_t> *seqs = nullptr;
     const ModelFactory *model_factory = nullptr;
+    const PhyTree *topo = nullptr;   // the family's fixed topology, if it has one
     PhyTree *tree = nullptr;
     std::string error;
 };
