@@ -295,7 +295,16 @@ int pgm_kmer_cosine_multi(pgm_ctx *ctx, uint32_t nfam, const uint32_t *nseq, uin
 int pgm_prealigned_counts_multi(pgm_ctx *ctx, uint32_t dim, uint32_t nfam, const uint32_t *nrows, const uint32_t *ncols,
                                 const int8_t *rows, uint32_t npairs, const uint32_t *fam, const uint32_t *pi, const uint32_t *pj,
                                 int32_t *counts, uint32_t *gaps);
-/* Device time of the kernel of the last pgm_mldist_batch / pgm_prealigned_counts_batch / pgm_kmer_cosine call on this context (ms). */
+/* ---- (f3) for nrep resamplings of the columns of one alignment in one launch (pgmsa --bootstrap).  Replicate r is the alignment
+ * whose column k is column cols[r * ncols + k] of rows; counts[(r * npairs + p) * dim * dim + s1 + dim * s2] and gaps[r * npairs + p]
+ * are what pgm_prealigned_counts_batch gives pair p on that gathered matrix (its gap openings are the gathered matrix's), the rows
+ * uploaded once (1 <= dim <= 64; a result matrix smaller than 20 x 20 keeps that corner of the counts).  PGM_ERR_INVALID, before
+ * anything is launched: a null pointer, nrep == 0, nrows < 2, ncols == 0, dim outside 1..64, a pair index >= nrows, a cols entry
+ * >= ncols. */
+int pgm_prealigned_counts_resampled(pgm_ctx *ctx, uint32_t dim, uint32_t nrows, uint32_t ncols, const int8_t *rows, uint32_t nrep,
+                                    const uint32_t *cols, uint32_t npairs, const uint32_t *pi, const uint32_t *pj, int32_t *counts,
+                                    uint32_t *gaps);
+/* Device time of the kernel of the last pgm_mldist_batch / pgm_prealigned_counts_* / pgm_kmer_cosine call on this context (ms). */
 float pgm_dist_last_kernel_ms(pgm_ctx *ctx);
 
 /* ---- (f1, numeric part) mergeGraphs' node profiles — replaces the P*g products and the L2 normalisation of reference

@@ -85,7 +85,7 @@ EXPORTS = [
     "pgm_align_batch_destroy", "pgm_align_batch_cells", "pgm_align_batch_test_stall", "pgm_test_cu_shares", "pgm_test_batch_plan", "pgm_align_batch_stage_times", "pgm_align_batch_job_times", "pgm_align_batch_time", "pgm_align_batch_read_matrices",
     "pgm_nw_pairs_batch", "pgm_nw_pairs_submit", "pgm_nw_pairs_wait", "pgm_nw_last_kernel_ms", "pgm_host_alloc", "pgm_host_free", "pgm_csprofile_load", "pgm_csprofile_create_batch", "pgm_csprofile_create_batch_res",
     "pgm_csprofile_last_kernel_ms", "pgm_mldist_batch", "pgm_prealigned_counts_batch", "pgm_kmer_cosine", "pgm_dist_last_kernel_ms",
-    "pgm_kmer_cosine_multi", "pgm_prealigned_counts_multi",
+    "pgm_kmer_cosine_multi", "pgm_prealigned_counts_multi", "pgm_prealigned_counts_resampled",
     "pgm_merge_profiles_batch", "pgm_merge_profiles_batch_ex", "pgm_resident_reset", "pgm_resident_onehot", "pgm_resident_import", "pgm_merge_last_kernel_ms",
     "pgm_gapmask_extend_batch", "pgm_gap_parsimony_batch", "pgm_parsimony_last_kernel_ms",
     "pgm_wls_load", "pgm_wls_pair_sums_batch", "pgm_wls_last_kernel_ms", "pgm_wls_last_launches",
@@ -145,6 +145,8 @@ def _load():
         "pgm_kmer_cosine_multi": (C.c_int, [vp, u32, C.POINTER(u32), u32, C.POINTER(i32), C.POINTER(C.c_double)]),
         "pgm_prealigned_counts_multi": (C.c_int, [vp, u32, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_int8), u32, C.POINTER(u32), C.POINTER(u32),
                                                   C.POINTER(u32), C.POINTER(i32), C.POINTER(u32)]),
+        "pgm_prealigned_counts_resampled": (C.c_int, [vp, u32, u32, u32, C.POINTER(C.c_int8), u32, C.POINTER(u32), u32, C.POINTER(u32), C.POINTER(u32),
+                                                      C.POINTER(i32), C.POINTER(u32)]),
         "pgm_merge_profiles_batch": (C.c_int, [vp, u32, C.POINTER(pgm_merge_job)]),
         "pgm_merge_profiles_batch_ex": (C.c_int, [vp, u32, C.POINTER(pgm_merge_job), u32, C.POINTER(C.POINTER(C.c_double))]),
         "pgm_resident_reset": (C.c_int, [vp]),
@@ -196,6 +198,22 @@ class Context:
         cu = C.c_int()
         check(lib.pgm_ctx_device_info(self.handle, buf, 256, C.byref(cu)))
         return buf.value.decode(), cu.value
+
+    def prealigned_counts_resampled(self, dim, rows, cols, pi, pj):
+        """pgm_prealigned_counts_resampled: rows (nrows x ncols int8), cols (nrep x ncols source columns), the pairs (pi, pj) ->
+        counts (nrep x npairs x dim * dim int32) and gaps (nrep x npairs uint32)."""
+        import numpy as np
+        rows = np.ascontiguousarray(rows, np.int8)
+        cols = np.ascontiguousarray(cols, np.uint32)
+        pi = np.ascontiguousarray(pi, np.uint32)
+        pj = np.ascontiguousarray(pj, np.uint32)
+        nrep, npairs = cols.shape[0], len(pi)
+        counts = np.zeros((nrep, npairs, dim * dim), np.int32)
+        gaps = np.zeros((nrep, npairs), np.uint32)
+        P = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+        check(lib.pgm_prealigned_counts_resampled(self.handle, dim, rows.shape[0], rows.shape[1], P(rows, C.c_int8), nrep, P(cols, C.c_uint32), npairs,
+                                                  P(pi, C.c_uint32), P(pj, C.c_uint32), P(counts, C.c_int32), P(gaps, C.c_uint32)), "pgm_prealigned_counts_resampled")
+        return counts, gaps
 
     def close(self):
         if self.handle:

@@ -226,3 +226,49 @@ extern "C" int pgm_prealigned_counts_multi(pgm_ctx *ctx, uint32_t dim, uint32_t 
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("prealigned (multi): ") + hipGetErrorString(e));
     return PGM_OK;
 }
+
+// ---- resampled columns of one alignment (pgmsa --bootstrap) ----
+extern "C" int pgm_prealigned_counts_resampled(pgm_ctx *ctx, uint32_t dim, uint32_t nrows, uint32_t ncols, const int8_t *rows, uint32_t nrep,
+                                               const uint32_t *cols, uint32_t npairs, const uint32_t *pi, const uint32_t *pj, int32_t *counts, uint32_t *gaps) {
+    if (!ctx || !rows || !cols || !pi || !pj || !counts || !gaps || nrep == 0 || nrows < 2 || ncols == 0 || dim == 0 || dim > 64) return fail(PGM_ERR_INVALID, "bad argument");
+    ctx->ml_ms = 0;
+    for (uint32_t p = 0; p < npairs; ++p)
+        if (pi[p] >= nrows || pj[p] >= nrows) return fail(PGM_ERR_INVALID, "pair index out of range");
+    const size_t ncells = (size_t)nrep * ncols;
+    for (size_t k = 0; k < ncells; ++k)
+        if (cols[k] >= ncols) return fail(PGM_ERR_INVALID, "column index out of range");
+    if (npairs == 0) return PGM_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    int8_t *d_rows = nullptr;
+    uint32_t *d_pi = nullptr, *d_pj = nullptr, *d_gaps = nullptr, *d_cols = nullptr;
+    int32_t *d_counts = nullptr;
+    const size_t nout = (size_t)nrep * npairs, cbytes = 4 * nout * dim * dim;
+    struct Buf { void **p; size_t bytes; const void *src; };
+    Buf bufs[] = {{(void **)&d_rows, (size_t)nrows * ncols, rows}, {(void **)&d_pi, 4 * (size_t)npairs, pi}, {(void **)&d_pj, 4 * (size_t)npairs, pj},
+                  {(void **)&d_counts, cbytes, nullptr}, {(void **)&d_gaps, 4 * nout, nullptr}, {(void **)&d_cols, 4 * ncells, cols}};
+    hipError_t e = hipSuccess;
+    hipStream_t s = ctx->stream;
+    int slot_ix = 0;
+    for (auto &b : bufs) {
+        if (e == hipSuccess) e = scratch_dev(ctx, slot_ix++, b.bytes, b.p);
+        if (e == hipSuccess && b.src) e = hipMemcpyAsync(*b.p, b.src, b.bytes, hipMemcpyHostToDevice, s);
+    }
+    if (e == hipSuccess) e = scratch_events(ctx);
+    if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, cbytes, s);
+    if (e == hipSuccess) {
+        PgmPaResampledArgs A;
+        A.dim = dim; A.ncols = ncols; A.npairs = npairs; A.nrep = nrep; A.rows = d_rows; A.cols = d_cols; A.pi = d_pi; A.pj = d_pj; A.counts = d_counts; A.gaps = d_gaps;
+        const uint32_t blocks = std::min<uint32_t>((npairs + 3) / 4, (uint32_t)ctx->prop.multiProcessorCount * 8u);
+        e = hipEventRecord(ctx->sc_ev[0], s);
+        hipLaunchKernelGGL(pgm_prealigned_resampled_kernel, dim3(blocks, std::min<uint32_t>(nrep, 65535u)), dim3(256), 0, s, A);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = hipEventRecord(ctx->sc_ev[1], s);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, cbytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(gaps, d_gaps, 4 * nout, hipMemcpyDeviceToHost, s);
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = es;
+    if (e == hipSuccess) (void)hipEventElapsedTime(&ctx->ml_ms, ctx->sc_ev[0], ctx->sc_ev[1]);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("prealigned (resampled): ") + hipGetErrorString(e));
+    return PGM_OK;
+}

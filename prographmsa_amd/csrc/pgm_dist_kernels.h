@@ -348,9 +348,18 @@ struct PgmPaArgs {
     uint32_t *gaps;      // npairs
 };
 
+// Which column of the stored rows column k of the scanned alignment is: itself, or cols[k] (a bootstrap replicate: the alignment
+// with its columns gathered in that order; pgm_prealigned_resampled_kernel)
+struct PgmPaColSelf { __device__ __forceinline__ uint32_t operator()(uint32_t k) const { return k; } };
+struct PgmPaColGather {
+    const uint32_t *__restrict__ cols;
+    __device__ __forceinline__ uint32_t operator()(uint32_t k) const { return cols[k]; }
+};
+
 // one pair on one wavefront: rows r1, r2 of L columns; cnt: the wavefront's 400 LDS counters
+template <class Col>
 __device__ __forceinline__ void pgm_prealigned_pair(const int8_t *__restrict__ r1, const int8_t *__restrict__ r2, uint32_t L, uint32_t D, int *cnt,
-                                                    int32_t *__restrict__ out, uint32_t *__restrict__ gaps_out, int lane) {
+                                                    int32_t *__restrict__ out, uint32_t *__restrict__ gaps_out, int lane, Col col) {
     const uint32_t chunk = (L + 63u) / 64u;
     for (int i = lane; i < 400; i += 64) cnt[i] = 0;
     __builtin_amdgcn_wave_barrier();
@@ -359,7 +368,8 @@ __device__ __forceinline__ void pgm_prealigned_pair(const int8_t *__restrict__ r
     uint32_t g = 0;
     const uint32_t k0 = min(L, (uint32_t)lane * chunk), k1 = min(L, k0 + chunk);
     for (uint32_t k = k0; k < k1; ++k) {
-        const int c1 = r1[k], c2 = r2[k];
+        const uint32_t src = col(k);
+        const int c1 = r1[src], c2 = r2[src];
         const bool g1 = c1 == -1, g2 = c2 == -1;
         const int ty = (!g1 && !g2) ? 0 : ((g1 && g2) ? 3 : (!g1 ? 1 : 2));
         if (ty == 3) continue;
@@ -394,7 +404,7 @@ __global__ void __launch_bounds__(256) pgm_prealigned_kernel(PgmPaArgs A) {
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t D = A.dim, L = A.ncols;
     for (uint32_t pair = blockIdx.x * 4 + w; pair < A.npairs; pair += gridDim.x * 4)
-        pgm_prealigned_pair(A.rows + (size_t)A.pi[pair] * L, A.rows + (size_t)A.pj[pair] * L, L, D, cnt[w], A.counts + (size_t)pair * D * D, A.gaps + pair, lane);
+        pgm_prealigned_pair(A.rows + (size_t)A.pi[pair] * L, A.rows + (size_t)A.pj[pair] * L, L, D, cnt[w], A.counts + (size_t)pair * D * D, A.gaps + pair, lane, PgmPaColSelf());
 }
 
 // The same for the alignments of many families in one launch (pgm_prealigned_counts_multi): pair p compares rows pi[p], pj[p] of
@@ -416,7 +426,35 @@ __global__ void __launch_bounds__(256) pgm_prealigned_multi_kernel(PgmPaMultiArg
     for (uint32_t pair = blockIdx.x * 4 + w; pair < A.npairs; pair += gridDim.x * 4) {
         const uint32_t f = A.fam[pair], L = A.ncols[f];
         const int8_t *m = A.rows + A.base[f];
-        pgm_prealigned_pair(m + (size_t)A.pi[pair] * L, m + (size_t)A.pj[pair] * L, L, D, cnt[w], A.counts + (size_t)pair * D * D, A.gaps + pair, lane);
+        pgm_prealigned_pair(m + (size_t)A.pi[pair] * L, m + (size_t)A.pj[pair] * L, L, D, cnt[w], A.counts + (size_t)pair * D * D, A.gaps + pair, lane, PgmPaColSelf());
+    }
+}
+
+// The same for nrep resamplings of the columns of one alignment (pgm_prealigned_counts_resampled): replicate r is the alignment whose
+// column k is the stored column cols[r * ncols + k], and its pair p writes counts[r * npairs + p] and gaps[r * npairs + p].  The grid
+// is (blocks of 4 pairs, replicates); the per-pair code is the one above with the column read through cols, so the gap openings are
+// those of the gathered matrix.  The rows are stored once and read in place: a wavefront's two rows (ncols bytes each, any ncols)
+// have no fixed place in the 4 x 400 counters' LDS layout, and its reads of them, in the order cols gives, stay within those
+// 2 ncols bytes, which the caches hold.
+struct PgmPaResampledArgs {
+    uint32_t dim, ncols, npairs, nrep;
+    const int8_t *rows;
+    const uint32_t *cols;     // nrep x ncols, every entry < ncols
+    const uint32_t *pi, *pj;
+    int32_t *counts;          // nrep x npairs x dim x dim, zero-initialised
+    uint32_t *gaps;           // nrep x npairs
+};
+
+__global__ void __launch_bounds__(256) pgm_prealigned_resampled_kernel(PgmPaResampledArgs A) {
+    __shared__ int cnt[4][400];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t D = A.dim, L = A.ncols;
+    for (uint32_t rep = blockIdx.y; rep < A.nrep; rep += gridDim.y) {
+        const PgmPaColGather col{A.cols + (size_t)rep * L};
+        for (uint32_t pair = blockIdx.x * 4 + w; pair < A.npairs; pair += gridDim.x * 4) {
+            const size_t o = (size_t)rep * A.npairs + pair;
+            pgm_prealigned_pair(A.rows + (size_t)A.pi[pair] * L, A.rows + (size_t)A.pj[pair] * L, L, D, cnt[w], A.counts + o * D * D, A.gaps + o, lane, col);
+        }
     }
 }
 

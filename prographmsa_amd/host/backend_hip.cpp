@@ -121,6 +121,12 @@ struct HipBackend : Backend {
         if (rc != PGM_OK) error("pgm_prealigned_counts_multi failed (%d): %s", rc, pgm_last_error());
         return true;
     }
+    bool prealigned_counts_resampled(uint32_t dim, uint32_t nrows, uint32_t ncols, const int8_t *rows, uint32_t nrep, const uint32_t *cols, uint32_t npairs,
+                                     const uint32_t *pi, const uint32_t *pj, int32_t *counts, uint32_t *gaps, int worker) override {
+        int rc = pgm_prealigned_counts_resampled(ctx_of(worker), dim, nrows, ncols, rows, nrep, cols, npairs, pi, pj, counts, gaps);
+        if (rc != PGM_OK) error("pgm_prealigned_counts_resampled failed (%d): %s", rc, pgm_last_error());
+        return true;
+    }
     bool bionj_multi(uint32_t nfam, const uint32_t *n, const double *D, const double *V, pgm_bionj_join *joins, double *final_d, int worker) override {
         pgm_ctx *c = ctx_of(worker);
         int rc = pgm_bionj_multi(c, nfam, n, D, V, joins, final_d);

@@ -1356,6 +1356,89 @@ void angle_distances(const Alphabet &a, Families &F, bool per_family_calls) {
     });
 }
 
+// BioNJ's joins of the families whose matrices are `dist` (nseq[f] taxa each; plan_of(f): the pairs a fixed topology prescribes, or
+// nullptr): the join record and final_d of every family, and the message of a family whose joins failed.  The route is described
+// inside; tree_nj and the bootstrap replicates share it.
+void bionj_joins_families(std::vector<DistanceMatrix> &dist, const std::vector<uint32_t> &nseq,
+                          const std::function<const std::vector<pgm_bionj_pair> *(uint32_t)> &plan_of, std::vector<std::vector<pgm_bionj_join>> &joins,
+                          std::vector<double> &final_d, std::vector<std::string> &join_error) {
+    const auto tq1 = std::chrono::steady_clock::now();
+    Backend &be_bionj = default_backend();
+    const uint32_t nfam = (uint32_t)dist.size();
+    // BioNJ's joins: one bionj_multi call over the families of 4 taxa and more on worker 0 (PGM_DEVICE_BIONJ, or by default when
+    // the largest family has kBionjDeviceMin taxa and every entry is finite: the device entry takes no NaN or infinity), or the
+    // host loop per family (one family: on this thread, the loop's sections on the host threads; several: the families on the
+    // host threads).  Either way the same join records, and so the same trees.
+    // The families with a fixed topology are a call of their own, bionj_plan_multi, with PGM_DEVICE_BIONJ only: their host loop
+    // is O(n) per join as well, so it is the default (DESIGN.md 3.12).
+    joins.assign(nfam, std::vector<pgm_bionj_join>());
+    final_d.assign((size_t)9 * nfam, 0.0);
+    for (DistanceMatrix &d : dist)
+        for (int i = 0; i < d.dim; ++i) { d.D(i, i) = 0; d.V(i, i) = 0; }
+    std::vector<char> on_device(nfam, 0);
+    for (int planned = 0; planned < 2; ++planned) {
+        std::vector<uint32_t> dev;   // the families of the device call
+        uint32_t nmax = 0;
+        for (uint32_t f = 0; f < nfam; ++f)
+            if ((plan_of(f) != nullptr) == (planned != 0) && nseq[f] >= 4 && nseq[f] <= PGM_BIONJ_MAX_N) { dev.push_back(f); nmax = std::max(nmax, nseq[f]); }
+        const HostSwitches &sw = host_switches();
+        if (!dev.empty() && !sw.host_bionj && (sw.device_bionj || (!planned && nmax >= kBionjDeviceMin))) {
+            std::vector<char> finite(dev.size(), 1);
+            parallel_for(dev.size(), [&](size_t k) {
+                const DistanceMatrix &d = dist[dev[k]];
+                bool ok = true;
+                for (size_t e = 0; e < d.distances.size(); ++e) ok = ok && std::isfinite(d.distances[e]) && std::isfinite(d.variances[e]);
+                finite[k] = ok ? 1 : 0;
+            });
+            bool all_finite = true;
+            for (char c : finite) all_finite = all_finite && c;
+            if (all_finite) {
+                std::vector<uint32_t> ns(dev.size());
+                std::vector<size_t> m0(dev.size() + 1, 0), j0(dev.size() + 1, 0);
+                for (size_t k = 0; k < dev.size(); ++k) {
+                    ns[k] = nseq[dev[k]];
+                    m0[k + 1] = m0[k] + (size_t)ns[k] * ns[k];
+                    j0[k + 1] = j0[k] + ns[k] - 3;
+                }
+                std::vector<double> Dcat, Vcat;   // (one family: its own matrices)
+                if (dev.size() > 1) {
+                    Dcat.resize(m0[dev.size()]); Vcat.resize(m0[dev.size()]);
+                    parallel_for(dev.size(), [&](size_t k) {
+                        const DistanceMatrix &d = dist[dev[k]];
+                        std::copy(d.distances.begin(), d.distances.end(), Dcat.begin() + (std::ptrdiff_t)m0[k]);
+                        std::copy(d.variances.begin(), d.variances.end(), Vcat.begin() + (std::ptrdiff_t)m0[k]);
+                    });
+                }
+                const DistanceMatrix &d0 = dist[dev[0]];
+                const double *Dp = dev.size() > 1 ? Dcat.data() : d0.distances.data(), *Vp = dev.size() > 1 ? Vcat.data() : d0.variances.data();
+                std::vector<pgm_bionj_join> jcat(j0[dev.size()]);
+                std::vector<double> fcat((size_t)9 * dev.size());
+                bool ran;
+                if (planned) {
+                    std::vector<pgm_bionj_pair> pcat(j0[dev.size()]);   // (a plan has n - 1 pairs: the joins use the first n - 3)
+                    for (size_t k = 0; k < dev.size(); ++k) std::copy(plan_of(dev[k])->begin(), plan_of(dev[k])->begin() + (std::ptrdiff_t)(ns[k] - 3), pcat.begin() + (std::ptrdiff_t)j0[k]);
+                    ran = be_bionj.bionj_plan_multi((uint32_t)dev.size(), ns.data(), Dp, Vp, pcat.data(), jcat.data(), fcat.data(), 0);
+                } else {
+                    ran = be_bionj.bionj_multi((uint32_t)dev.size(), ns.data(), Dp, Vp, jcat.data(), fcat.data(), 0);
+                }
+                if (ran)
+                    for (size_t k = 0; k < dev.size(); ++k) {
+                        on_device[dev[k]] = 1;
+                        joins[dev[k]].assign(jcat.begin() + (std::ptrdiff_t)j0[k], jcat.begin() + (std::ptrdiff_t)j0[k + 1]);
+                        std::copy(fcat.begin() + (std::ptrdiff_t)(9 * k), fcat.begin() + (std::ptrdiff_t)(9 * k + 9), final_d.begin() + (std::ptrdiff_t)(9 * (size_t)dev[k]));
+                    }
+            }
+        }
+    }
+    join_error.assign(nfam, std::string());
+    parallel_for(nfam, [&](size_t f) {
+        if (on_device[f]) return;
+        try { bionj_joins_host(dist[f], joins[f], &final_d[9 * f], plan_of((uint32_t)f)); }
+        catch (std::exception &e) { join_error[f] = e.what(); }
+    });
+    be_bionj.seconds_bionj += std::chrono::duration<double>(std::chrono::steady_clock::now() - tq1).count();
+}
+
 // TreeNJ.h:27-59 for a list of families: one of the three distance stages over the pairs of all of them, then BioNJ, the -W
 // refinement (TreeNJ.h:52-54) and the rooting per family.  per_family_calls is all that tells the two entry points apart: the
 // cosine matrix and the pair counts of an alignment through the per-family entries of the backend (TreeNJ: kmer_cosine, and
@@ -1410,80 +1493,11 @@ void tree_nj(const Alphabet &a, std::vector<TreeJob> &jobs, bool prealigned, boo
     else nw_distances(a, F);
     for (const DistanceMatrix &d : F.dist) dump_distances(d);   // (--dump_dist: refused with --batch, so one matrix per call)
     const auto tq1 = std::chrono::steady_clock::now();
-    Backend &be_bionj = default_backend();
-    // BioNJ's joins: one bionj_multi call over the families of 4 taxa and more on worker 0 (PGM_DEVICE_BIONJ, or by default when
-    // the largest family has kBionjDeviceMin taxa and every entry is finite: the device entry takes no NaN or infinity), or the
-    // host loop per family (one family: on this thread, the loop's sections on the host threads; several: the families on the
-    // host threads).  Either way the same join records, and so the same trees.
-    // The families with a fixed topology are a call of their own, bionj_plan_multi, with PGM_DEVICE_BIONJ only: their host loop
-    // is O(n) per join as well, so it is the default (DESIGN.md 3.12).
-    std::vector<std::vector<pgm_bionj_join>> joins(nfam);
-    std::vector<double> final_d((size_t)9 * nfam, 0.0);
-    for (DistanceMatrix &d : F.dist)
-        for (int i = 0; i < d.dim; ++i) { d.D(i, i) = 0; d.V(i, i) = 0; }
+    std::vector<std::vector<pgm_bionj_join>> joins;
+    std::vector<double> final_d;
+    std::vector<std::string> join_error;
     auto plan_of = [&](uint32_t f) -> const std::vector<pgm_bionj_pair> * { return jobs[act[f]].topo ? &plans[act[f]] : nullptr; };
-    std::vector<char> on_device(nfam, 0);
-    for (int planned = 0; planned < 2; ++planned) {
-        std::vector<uint32_t> dev;   // the families of the device call
-        uint32_t nmax = 0;
-        for (uint32_t f = 0; f < nfam; ++f)
-            if ((plan_of(f) != nullptr) == (planned != 0) && F.nseq[f] >= 4 && F.nseq[f] <= PGM_BIONJ_MAX_N) { dev.push_back(f); nmax = std::max(nmax, F.nseq[f]); }
-        const HostSwitches &sw = host_switches();
-        if (!dev.empty() && !sw.host_bionj && (sw.device_bionj || (!planned && nmax >= kBionjDeviceMin))) {
-            std::vector<char> finite(dev.size(), 1);
-            parallel_for(dev.size(), [&](size_t k) {
-                const DistanceMatrix &d = F.dist[dev[k]];
-                bool ok = true;
-                for (size_t e = 0; e < d.distances.size(); ++e) ok = ok && std::isfinite(d.distances[e]) && std::isfinite(d.variances[e]);
-                finite[k] = ok ? 1 : 0;
-            });
-            bool all_finite = true;
-            for (char c : finite) all_finite = all_finite && c;
-            if (all_finite) {
-                std::vector<uint32_t> ns(dev.size());
-                std::vector<size_t> m0(dev.size() + 1, 0), j0(dev.size() + 1, 0);
-                for (size_t k = 0; k < dev.size(); ++k) {
-                    ns[k] = F.nseq[dev[k]];
-                    m0[k + 1] = m0[k] + (size_t)ns[k] * ns[k];
-                    j0[k + 1] = j0[k] + ns[k] - 3;
-                }
-                std::vector<double> Dcat, Vcat;   // (one family: its own matrices)
-                if (dev.size() > 1) {
-                    Dcat.resize(m0[dev.size()]); Vcat.resize(m0[dev.size()]);
-                    parallel_for(dev.size(), [&](size_t k) {
-                        const DistanceMatrix &d = F.dist[dev[k]];
-                        std::copy(d.distances.begin(), d.distances.end(), Dcat.begin() + (std::ptrdiff_t)m0[k]);
-                        std::copy(d.variances.begin(), d.variances.end(), Vcat.begin() + (std::ptrdiff_t)m0[k]);
-                    });
-                }
-                const DistanceMatrix &d0 = F.dist[dev[0]];
-                const double *Dp = dev.size() > 1 ? Dcat.data() : d0.distances.data(), *Vp = dev.size() > 1 ? Vcat.data() : d0.variances.data();
-                std::vector<pgm_bionj_join> jcat(j0[dev.size()]);
-                std::vector<double> fcat((size_t)9 * dev.size());
-                bool ran;
-                if (planned) {
-                    std::vector<pgm_bionj_pair> pcat(j0[dev.size()]);   // (a plan has n - 1 pairs: the joins use the first n - 3)
-                    for (size_t k = 0; k < dev.size(); ++k) std::copy(plan_of(dev[k])->begin(), plan_of(dev[k])->begin() + (std::ptrdiff_t)(ns[k] - 3), pcat.begin() + (std::ptrdiff_t)j0[k]);
-                    ran = be_bionj.bionj_plan_multi((uint32_t)dev.size(), ns.data(), Dp, Vp, pcat.data(), jcat.data(), fcat.data(), 0);
-                } else {
-                    ran = be_bionj.bionj_multi((uint32_t)dev.size(), ns.data(), Dp, Vp, jcat.data(), fcat.data(), 0);
-                }
-                if (ran)
-                    for (size_t k = 0; k < dev.size(); ++k) {
-                        on_device[dev[k]] = 1;
-                        joins[dev[k]].assign(jcat.begin() + (std::ptrdiff_t)j0[k], jcat.begin() + (std::ptrdiff_t)j0[k + 1]);
-                        std::copy(fcat.begin() + (std::ptrdiff_t)(9 * k), fcat.begin() + (std::ptrdiff_t)(9 * k + 9), final_d.begin() + (std::ptrdiff_t)(9 * (size_t)dev[k]));
-                    }
-            }
-        }
-    }
-    std::vector<std::string> join_error(nfam);
-    parallel_for(nfam, [&](size_t f) {
-        if (on_device[f]) return;
-        try { bionj_joins_host(F.dist[f], joins[f], &final_d[9 * f], plan_of((uint32_t)f)); }
-        catch (std::exception &e) { join_error[f] = e.what(); }
-    });
-    be_bionj.seconds_bionj += std::chrono::duration<double>(std::chrono::steady_clock::now() - tq1).count();
+    bionj_joins_families(F.dist, F.nseq, plan_of, joins, final_d, join_error);
     for (uint32_t f = 0; f < nfam; ++f) dump_joins((int32_t)F.nseq[f], joins[f], &final_d[9 * (size_t)f]);   // (--dump_joins: refused with --batch)
     // the trees, -W and the rooting per family on the host threads (-W is refused with --batch: refineTree loads one tree's
     // matrices into the backend)
@@ -1515,4 +1529,118 @@ PhyTree *TreeNJ(const Alphabet &a, const std::map<std::string, sequence_t> &seqs
 
 void TreeNJ_multi(const Alphabet &a, std::vector<TreeJob> &jobs, bool prealigned) { tree_nj(a, jobs, prealigned, false); }
 
+// ==== --bootstrap: the trees of resampled columns of one alignment =====================================================
+BootstrapStats bootstrap_stats;
+
+uint64_t splitmix64(uint64_t &state) {
+    uint64_t z = (state += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+bool Backend::prealigned_counts_resampled(uint32_t dim, uint32_t nrows, uint32_t ncols, const int8_t *rows, uint32_t nrep, const uint32_t *cols,
+                                          uint32_t npairs, const uint32_t *pi, const uint32_t *pj, int32_t *counts, uint32_t *gaps, int worker) {
+    std::vector<int8_t> gathered((size_t)nrows * ncols);
+    for (uint32_t r = 0; r < nrep; ++r) {
+        const uint32_t *c = cols + (size_t)r * ncols;
+        for (uint32_t i = 0; i < nrows; ++i)
+            for (uint32_t k = 0; k < ncols; ++k) gathered[(size_t)i * ncols + k] = rows[(size_t)i * ncols + c[k]];
+        if (!prealigned_counts_batch(dim, nrows, ncols, gathered.data(), npairs, pi, pj, counts + (size_t)r * npairs * dim * dim, gaps + (size_t)r * npairs, worker))
+            return false;
+    }
+    return true;
+}
+
+std::vector<PhyTree *> bootstrap_trees(const Alphabet &a, const std::map<std::string, sequence_t> &rows, const ModelFactory *mf, uint32_t nrep, uint64_t seed) {
+    const uint32_t n = (uint32_t)rows.size(), D = (uint32_t)a.DIM;
+    if (n < 4) error("bootstrap: fewer than 4 sequences");
+    const size_t L = rows.begin()->second.size();
+    std::vector<std::string> order;   // (std::map key order: the order of the matrices, TreeNJ.h:34-39)
+    std::vector<const sequence_t *> seq;
+    for (const auto &kv : rows) {
+        if (kv.second.size() != L) error("bootstrap: rows of different length");
+        order.push_back(kv.first);
+        seq.push_back(&kv.second);
+    }
+    if (L == 0 || L > 0xffffffffull) error("bootstrap: an alignment of %zu columns", L);
+    const uint32_t ncols = (uint32_t)L;
+    Backend &be = default_backend();
+    std::vector<int8_t> mat((size_t)n * ncols);
+    parallel_for(n, [&](size_t i) { prealigned_row(a, *seq[i], mat.data() + i * ncols); });
+    std::vector<uint32_t> cols((size_t)nrep * ncols);
+    uint64_t state = seed;
+    for (size_t k = 0; k < cols.size(); ++k) cols[k] = (uint32_t)(splitmix64(state) % ncols);
+    std::vector<uint32_t> pi, pj;
+    for (uint32_t i = 0; i < n; ++i)
+        for (uint32_t j = i + 1; j < n; ++j) { pi.push_back(i); pj.push_back(j); }
+    const uint32_t np = (uint32_t)pi.size();
+    // The entry points count 20 to 64 states (prealigned_distances): DNA keeps the 4 x 4 corner of each 20 x 20 matrix
+    const uint32_t Dk = std::max<uint32_t>(D, 20u);
+    const size_t dd = (size_t)D * D, ddk = (size_t)Dk * Dk;
+    const uint32_t group = (uint32_t)std::max<size_t>(1, std::min<size_t>(nrep, kBootstrapCountBytes / (sizeof(int32_t) * ddk * np)));
+    std::vector<PhyTree *> trees(nrep, nullptr);
+    try {
+        std::vector<int32_t> wide, counts;
+        std::vector<uint32_t> gaps;
+        std::vector<int8_t> gathered;
+        for (uint32_t r0 = 0; r0 < nrep; r0 += group) {
+            const uint32_t g = std::min(group, nrep - r0);
+            const size_t gp = (size_t)g * np;
+            const uint32_t *gcols = cols.data() + (size_t)r0 * ncols;
+            counts.assign(gp * dd, 0);
+            gaps.assign(gp, 0);
+            bool done = false;
+            if (!host_switches().host_counts) {
+                const auto t0 = std::chrono::steady_clock::now();
+                if (Dk != D) wide.assign(gp * ddk, 0);
+                int32_t *const cdst = Dk != D ? wide.data() : counts.data();
+                ++bootstrap_stats.counts_calls;
+                ++be.calls_dist;
+                done = be.prealigned_counts_resampled(Dk, n, ncols, mat.data(), g, gcols, np, pi.data(), pj.data(), cdst, gaps.data());
+                if (done && Dk != D)
+                    for (size_t p = 0; p < gp; ++p)
+                        for (uint32_t b = 0; b < D; ++b)
+                            for (uint32_t c = 0; c < D; ++c) counts[p * dd + c + (size_t)D * b] = wide[p * ddk + c + (size_t)Dk * b];
+                be.seconds_mldist += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            }
+            if (!done) {   // (PGM_HOST_COUNTS, or a backend without the kernel: the host's scan of the gathered rows)
+                const auto t1 = std::chrono::steady_clock::now();
+                std::fill(counts.begin(), counts.end(), 0);
+                for (uint32_t r = 0; r < g; ++r) {
+                    std::vector<sequence_t> grow(n, sequence_t(ncols, 0));
+                    parallel_for(n, [&](size_t i) { for (uint32_t k = 0; k < ncols; ++k) grow[i][k] = (*seq[i])[gcols[(size_t)r * ncols + k]]; });
+                    parallel_for(np, [&](size_t p) { gaps[(size_t)r * np + p] = prealigned_count_pair(a, grow[pi[p]], grow[pj[p]], counts.data() + ((size_t)r * np + p) * dd); });
+                }
+                be.seconds_mldist += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+            }
+            // the replicates of the group as families of one call: the estimator and the joins of tree_nj
+            Families F;
+            F.nfam = g;
+            F.nseq.assign(g, n);
+            F.blocks.resize(g);
+            for (uint32_t f = 0; f < g; ++f) {
+                F.df.emplace_back(a, mf);
+                F.dist.emplace_back((int)n);
+                F.blocks[f] = PairBlock{mf, (size_t)f * np, np};
+                for (uint32_t p = 0; p < np; ++p) { F.pfam.push_back(f); F.pi.push_back(pi[p]); F.pj.push_back(pj[p]); }
+            }
+            const std::vector<double> seqlen(gp, ((double)ncols + (double)ncols) / 2.0);
+            estimate_distances(a, F, counts.data(), gaps.data(), seqlen.data());
+            std::vector<std::vector<pgm_bionj_join>> joins;
+            std::vector<double> final_d;
+            std::vector<std::string> join_error;
+            bionj_joins_families(F.dist, F.nseq, [](uint32_t) -> const std::vector<pgm_bionj_pair> * { return nullptr; }, joins, final_d, join_error);
+            for (uint32_t f = 0; f < g; ++f) {
+                if (!join_error[f].empty()) throw pgm_exception(join_error[f]);
+                trees[r0 + f] = bionj_tree(order, joins[f], &final_d[9 * (size_t)f]);
+            }
+        }
+    } catch (...) {
+        for (PhyTree *t : trees) delete t;
+        throw;
+    }
+    bootstrap_stats.replicates += (int)nrep;
+    return trees;
+}
 }  // namespace pgm

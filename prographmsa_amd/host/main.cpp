@@ -22,7 +22,8 @@ static void usage() {
                  "             [--codon] [-c|--cs_profile <lib>] [-i <iters>] [-g rate] [-e prob] [-E prob]\n"
                  "             [-s prob] [-A] [--early_refinement] [--ancestral_seqs] [--profile_out <file>] [-R] [--read_repeats <file>]\n"
                  "             [-r|--reroot [-r]] [-W|--wls_refine [-W]] [--dna] [--custom_model <file>] [-F|--estimate_aafreqs]\n"
-                 "             [-C|--aafreqs_pseudocount <count>] [--dump_jobs <file>] [--dump_dist <file>] [--dump_joins <file>] [--stats] <fasta file>\n"
+                 "             [-C|--aafreqs_pseudocount <count>] [--dump_jobs <file>] [--dump_dist <file>] [--dump_joins <file>] [--stats]\n"
+                 "             [--bootstrap <N> --bootstrap_out <file> [--bootstrap_seed <S>]] <fasta file>\n"
                  "       pgmsa --batch <list> [--batch_cells <cells>] [options]\n"
                  "  --batch <list>  align many families in one run: every line of <list> is input.fa<TAB>output[<TAB>guide_tree.nwk[<TAB>topology.nwk]]\n"
                  "                (an empty third field: no guide tree; blank lines and lines starting with # are skipped); the other options\n"
@@ -50,6 +51,11 @@ static void usage() {
                  "                and a model without an eigen form included (last-bit differences to the host's values)\n"
                  "  -r, --reroot  realign with the guide tree rooted on every branch and keep the alignment of the lowest gap\n"
                  "                parsimony score; given twice (-rr), a hill climb over neighbouring branches instead\n"
+                 "  --bootstrap <N>  bootstrap support (1 <= N <= 1000) for the tree estimated from the final alignment (the tree -T prints\n"
+                 "                after a further round): N resamplings of the alignment's columns, a BioNJ tree of each, and for every internal\n"
+                 "                edge the number of replicate trees with the same split of the sequences.  --bootstrap_out <file> (required)\n"
+                 "                gets that tree with the counts as node labels; --bootstrap_seed <S> (default 1) seeds the resampling.  Needs\n"
+                 "                at least 4 sequences; not with --batch, -W, -r, --topology\n"
                  "  -W, --wls_refine  refine every guide tree estimated from distances by weighted least squares (nearest-neighbour\n"
                  "                interchanges of quartets); given twice (-WW), quintet moves as well\n";
 }
@@ -162,7 +168,38 @@ struct Family {
 };
 
 struct BatchRun { int families = 0, failed = 0, chunks = 0; };
+
+struct BootstrapOpts {   // --bootstrap N --bootstrap_out FILE --bootstrap_seed S
+    bool given = false, out_given = false;
+    long long n = 0;
+    std::string out;
+    uint64_t seed = 1;
+} g_bootstrap;
 }  // namespace
+
+// --bootstrap: the tree TreeNJ estimates from the final alignment without its ancestral rows (the re-estimation step of the
+// iterations: main.cpp:404-430, DistanceFactoryPrealigned.h:34-90, TreeNJ.h:27-59), the support of its internal edges among the
+// trees of N column resamplings, and the file: formatNewick()'s text with the counts as node labels
+static void doBootstrap(const Alphabet &a, const Family &fam, const std::map<std::string, sequence_t> &alignment) {
+    const auto t0 = std::chrono::steady_clock::now();
+    std::map<std::string, sequence_t> rows;
+    for (const auto &kv : alignment)
+        if (kv.first.empty() || kv.first[0] != '(') rows.insert(kv);   // (ancestral sequences dropped)
+    std::unique_ptr<PhyTree> tree(TreeNJ(a, rows, fam.model_factory.get(), true));
+    std::vector<PhyTree *> reps = bootstrap_trees(a, rows, fam.model_factory.get(), (uint32_t)g_bootstrap.n, g_bootstrap.seed);
+    std::string text;
+    try {
+        text = tree->formatNewick(bipartition_support(*tree, std::vector<const PhyTree *>(reps.begin(), reps.end())));
+    } catch (...) {
+        for (PhyTree *t : reps) delete t;
+        throw;
+    }
+    for (PhyTree *t : reps) delete t;
+    std::ofstream out(g_bootstrap.out.c_str());
+    if (!out) error("error opening the bootstrap output file %s", g_bootstrap.out.c_str());
+    out << text << std::endl;
+    bootstrap_stats.seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
 
 static void print_stats(double t_init, double t_tree, double t_prog, const BatchRun *batch) {
     Backend &be = default_backend();
@@ -187,6 +224,9 @@ static void print_stats(double t_init, double t_tree, double t_prog, const Batch
     }
     if (host_switches().device_mldist)   // (keys of PGM_DEVICE_MLDIST only: pairs estimated by the device kernel, its time)
         fprintf(stderr, ", \"mldist_device_pairs\": %llu, \"mldist_kernel_ms\": %.3f", (unsigned long long)be.mldist_device_pairs, be.mldist_kernel_ms);
+    if (g_bootstrap.given)   // (keys of --bootstrap only)
+        fprintf(stderr, ", \"bootstrap_replicates\": %d, \"bootstrap_s\": %.6f, \"bootstrap_counts_calls\": %llu", bootstrap_stats.replicates, bootstrap_stats.seconds,
+                (unsigned long long)bootstrap_stats.counts_calls);
     if (batch)   // (keys of --batch only)
         fprintf(stderr, ", \"batch_families\": %d, \"batch_failed\": %d, \"batch_chunks\": %d, \"batch_passes\": %llu, \"batch_levels\": %llu, "
                         "\"batch_align_calls\": %llu, \"batch_dist_calls\": %llu",
@@ -247,6 +287,10 @@ static int doAlign(const Alphabet &a, Family &fam, bool stats) {
                                          : progressive_alignment(a, fam.seqs2, *fam.tree, csprofile.get(), *fam.model_factory, &reps);
     if (host_switches().profile) fprintf(stderr, "[%.1f ms] back in main\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     double t_prog = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (g_bootstrap.given) {   // (with -T the final alignment is computed for it alone: what is printed stays the tree)
+        if (cmdlineopts.onlytree_flag) doBootstrap(a, fam, progressive_alignment(a, fam.seqs2, *fam.tree, csprofile.get(), *fam.model_factory, &reps).aligned_sequences);
+        else doBootstrap(a, fam, result.aligned_sequences);
+    }
 
     fam.finish(a);
     if (cmdlineopts.repeats_flag) {
@@ -495,6 +539,9 @@ int main(int argc, char **argv) {
             else if (s == "--stats") stats = true;
             else if (s == "--batch") batch_list = val();
             else if (s == "--batch_cells") batch_cells = atof(val().c_str());
+            else if (s == "--bootstrap") { g_bootstrap.given = true; g_bootstrap.n = atoll(val().c_str()); }
+            else if (s == "--bootstrap_out") { g_bootstrap.out_given = true; g_bootstrap.out = val(); }
+            else if (s == "--bootstrap_seed") g_bootstrap.seed = strtoull(val().c_str(), nullptr, 10);
             else if (s == "--reroot") ++cmdlineopts.reroot_flag;
             else if (s == "--wls_refine") ++cmdlineopts.wlsrefine_flag;
             else if (s.size() >= 2 && s[0] == '-' && s.find_first_not_of('W', 1) == std::string::npos) cmdlineopts.wlsrefine_flag += (int)s.size() - 1;   // -W, -WW
@@ -510,10 +557,19 @@ int main(int argc, char **argv) {
                                   : !topo_file.empty() ? "--topology (a topology is the fourth field of a family's line)"
                                   : cmdlineopts.reroot_flag ? "-r" : cmdlineopts.wlsrefine_flag ? "-W"
                                   : cmdlineopts.repeats_flag ? "-R" : !cmdlineopts.readreps_file.empty() ? "--read_repeats"
-                                  : !cmdlineopts.profile_file.empty() ? "--profile_out" : !dump.empty() ? "--dump_jobs" : !dist_dump.empty() ? "--dump_dist" : !joins_dump.empty() ? "--dump_joins" : nullptr;
+                                  : !cmdlineopts.profile_file.empty() ? "--profile_out" : !dump.empty() ? "--dump_jobs" : !dist_dump.empty() ? "--dump_dist" : !joins_dump.empty() ? "--dump_joins"
+                                  : (g_bootstrap.given || g_bootstrap.out_given) ? "--bootstrap" : nullptr;
             if (refused) { std::cerr << "ERROR:--batch cannot be combined with " << refused << std::endl; return 2; }
         }
         if (cmdlineopts.sequence_file.empty() && batch_list.empty()) { usage(); return 1; }
+        if (g_bootstrap.given || g_bootstrap.out_given) {
+            const char *why = g_bootstrap.given != g_bootstrap.out_given ? "--bootstrap and --bootstrap_out need each other"
+                              : (g_bootstrap.n < 1 || g_bootstrap.n > 1000) ? "--bootstrap takes a number of replicates from 1 to 1000"
+                              : cmdlineopts.wlsrefine_flag ? "--bootstrap cannot be combined with -W"
+                              : cmdlineopts.reroot_flag ? "--bootstrap cannot be combined with -r"
+                              : !topo_file.empty() ? "--bootstrap cannot be combined with --topology" : nullptr;
+            if (why) { std::cerr << "ERROR:" << why << std::endl; return 2; }
+        }
         if (cmdlineopts.reroot_flag && (cmdlineopts.ancestral_flag || !cmdlineopts.profile_file.empty())) {
             std::cerr << "ERROR:--ancestral_seqs and --profile_out cannot be combined with -r (the root search keeps no ancestral profiles)" << std::endl;
             return 2;
@@ -549,6 +605,7 @@ int main(int argc, char **argv) {
         Family fam;
         fam.input = cmdlineopts.sequence_file; fam.tree_file = cmdlineopts.tree_file; fam.topo_file = topo_file; fam.iters = cmdlineopts.iters;
         fam.seqs = read_fasta(cmdlineopts.sequence_file, fam.input_order);
+        if (g_bootstrap.given && fam.seqs.size() < 4) error("--bootstrap needs at least 4 sequences");
         std::ofstream custom_out;
         std::ostream *out = &std::cout;
         if (!cmdlineopts.output_file.empty()) {

@@ -313,6 +313,13 @@ struct Backend {
     virtual void kmer_cosine_multi(uint32_t nfam, const uint32_t *nseq, uint32_t ncols, const int32_t *counts, double *cosine, int worker = 0);
     virtual bool prealigned_counts_multi(uint32_t dim, uint32_t nfam, const uint32_t *nrows, const uint32_t *ncols, const int8_t *rows, uint32_t npairs,
                                          const uint32_t *fam, const uint32_t *pi, const uint32_t *pj, int32_t *counts, uint32_t *gaps, int worker = 0);
+    // The pair counts of nrep resamplings of the columns of one alignment in one call (--bootstrap; include/pgm_hip.h:
+    // pgm_prealigned_counts_resampled): replicate r is the matrix whose column k is column cols[r * ncols + k] of rows; counts and gaps
+    // hold the replicates' results back to back, each laid out as prealigned_counts_batch lays them out.  The default gathers every
+    // replicate's matrix on the host and hands it to prealigned_counts_batch: a backend without a kernel of its own computes the same
+    // integers one replicate at a time (false where it has no pair-count entry at all).
+    virtual bool prealigned_counts_resampled(uint32_t dim, uint32_t nrows, uint32_t ncols, const int8_t *rows, uint32_t nrep, const uint32_t *cols,
+                                             uint32_t npairs, const uint32_t *pi, const uint32_t *pj, int32_t *counts, uint32_t *gaps, int worker = 0);
     // calls the host code made of the align-batch entry and of the distance entries (all-pairs tiles, pair counts, cosine, ML
     // distances): `pgmsa --batch --stats` shows with them that a stage was shared by the families of a chunk
     std::atomic<uint64_t> calls_align{0}, calls_dist{0};
@@ -418,7 +425,10 @@ public:
     index_t n_children() const { return (index_t)children_.size(); }
     bool isLeaf() const { return children_.empty(); }
     std::string formatNewick() const;
+    // the same text with labels[node] printed between ')' and ':' for every internal node that has one (--bootstrap_out)
+    std::string formatNewick(const std::map<const PhyTree *, uint32_t> &labels) const;
 private:
+    std::string formatNewickR(const std::map<const PhyTree *, uint32_t> *labels) const;
     std::string formatNewickR() const;
     std::vector<PhyTree *> children_;
     PhyTree *parent_;
@@ -426,6 +436,12 @@ private:
     std::string name_;
 };
 PhyTree *midpointRoot(PhyTree *root);                      // PhyTree.cpp:60-116
+// Bootstrap support (--bootstrap): for every internal edge of `tree`, the number of `replicates` whose unrooted tree has the same
+// bipartition of the leaves.  A bipartition is a bit set over the leaves in sorted-name order, the side without leaf 0.  The key
+// is the node below the edge; the two edges below a bifurcating root are one bipartition and get the same number; an edge that
+// cuts off a single leaf (a trivial bipartition: every tree has it) gets no entry.  Every replicate must have the leaves of `tree`;
+// where it is rooted, and how many children its root has, does not matter.
+std::map<const PhyTree *, uint32_t> bipartition_support(const PhyTree &tree, const std::vector<const PhyTree *> &replicates);
 std::vector<std::string> get_tree_order(const PhyTree *tree);  // PhyTree.cpp:164-182
 PhyTree *parse_newick(std::istream &in);                   // newick.cpp:127-147
 
@@ -580,6 +596,21 @@ struct TreeJob {
     std::string error;
 };
 void TreeNJ_multi(const Alphabet &a, std::vector<TreeJob> &jobs, bool prealigned = false);
+
+// --bootstrap: nrep resamplings of the columns of an alignment (rows: its sequences, all of one length, at least 4) and the
+// unrooted BioNJ tree of each.  Replicate r draws ncols source columns cols[r][c] = splitmix64() % ncols, c ascending, replicates
+// in order, from one stream seeded with `seed`.  The pair counts of every replicate come from Backend::prealigned_counts_resampled,
+// in groups of replicates whose counts stay within kBootstrapCountBytes per call; the estimator and the joins are those of TreeNJ
+// (prealigned == true) without -W and without rooting.  The caller owns the trees.
+uint64_t splitmix64(uint64_t &state);
+const size_t kBootstrapCountBytes = (size_t)1 << 30;   // count output of one prealigned_counts_resampled call
+struct BootstrapStats {   // `pgmsa --bootstrap --stats`
+    int replicates = 0;
+    double seconds = 0;
+    uint64_t counts_calls = 0;
+};
+extern BootstrapStats bootstrap_stats;
+std::vector<PhyTree *> bootstrap_trees(const Alphabet &a, const std::map<std::string, sequence_t> &rows, const ModelFactory *mf, uint32_t nrep, uint64_t seed);
 
 std::string data_dir();   // directory holding wag.qmat etc.
 

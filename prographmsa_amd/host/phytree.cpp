@@ -54,18 +54,103 @@ PhyTree *PhyTree::pluckChild(index_t index) {  // PhyTree.h:125-135
     return child;
 }
 
-std::string PhyTree::formatNewickR() const {  // PhyTree.h:41-55 (default ostream precision: 6 s.f.)
+std::string PhyTree::formatNewickR(const std::map<const PhyTree *, uint32_t> *labels) const {  // PhyTree.h:41-55 (default ostream precision: 6 s.f.)
     if (isLeaf()) return name_;
     std::stringstream ss;
     ss << "(";
     for (size_t i = 0; i < children_.size(); ++i) {
         if (i) ss << ",";
-        ss << children_[i]->formatNewickR() << ":" << children_[i]->branch_length_;
+        ss << children_[i]->formatNewickR(labels);
+        if (labels && !children_[i]->isLeaf()) {
+            const auto it = labels->find(children_[i]);
+            if (it != labels->end()) ss << it->second;
+        }
+        ss << ":" << children_[i]->branch_length_;
     }
     ss << ")";
     return ss.str();
 }
+std::string PhyTree::formatNewickR() const { return formatNewickR(nullptr); }
 std::string PhyTree::formatNewick() const { return formatNewickR() + ";"; }
+std::string PhyTree::formatNewick(const std::map<const PhyTree *, uint32_t> &labels) const { return formatNewickR(&labels) + ";"; }
+
+// ---- bootstrap support ------------------------------------------------------------------------------------------------
+namespace {
+typedef std::vector<uint64_t> LeafSet;   // one bit per leaf, leaves in sorted-name order
+
+void collect_leaves(const PhyTree &t, std::vector<std::string> &names) {
+    if (t.isLeaf()) { names.push_back(t.getName()); return; }
+    for (index_t c = 0; c < t.n_children(); ++c) collect_leaves(t[(int)c], names);
+}
+
+// The canonical side (the one without leaf 0) of the bipartition of every non-root node of a tree over `index`'s leaves, in
+// post-order into `out` (node, set); a trivial bipartition, one side a single leaf, is left out.  Returns the leaves below `t`.
+struct Bipartitions {
+    const std::map<std::string, size_t> &index;
+    size_t nleaves, words;
+    std::vector<std::pair<const PhyTree *, LeafSet>> out;
+    LeafSet below(const PhyTree &t, bool is_root) {
+        LeafSet s(words, 0);
+        if (t.isLeaf()) {
+            const auto it = index.find(t.getName());
+            if (it == index.end()) error("bootstrap support: leaf \"%s\" is not in the tree", t.getName().c_str());
+            if ((s[it->second / 64] >> (it->second % 64)) & 1) error("bootstrap support: leaf \"%s\" twice", t.getName().c_str());
+            s[it->second / 64] |= (uint64_t)1 << (it->second % 64);
+            return s;
+        }
+        for (index_t c = 0; c < t.n_children(); ++c) {
+            const LeafSet sub = below(t[(int)c], false);
+            for (size_t w = 0; w < words; ++w) {
+                if (s[w] & sub[w]) error("bootstrap support: a leaf name twice in one tree");
+                s[w] |= sub[w];
+            }
+        }
+        if (!is_root) {
+            LeafSet side = s;
+            if (side[0] & 1)   // leaf 0 is below the node: the other side
+                for (size_t k = 0; k < nleaves; ++k) side[k / 64] ^= (uint64_t)1 << (k % 64);
+            size_t size = 0;
+            for (uint64_t w : side) size += (size_t)__builtin_popcountll(w);
+            if (size >= 2 && size + 2 <= nleaves) out.emplace_back(&t, std::move(side));
+        }
+        return s;
+    }
+};
+}  // namespace
+
+std::map<const PhyTree *, uint32_t> bipartition_support(const PhyTree &tree, const std::vector<const PhyTree *> &replicates) {
+    std::vector<std::string> names;
+    collect_leaves(tree, names);
+    std::sort(names.begin(), names.end());
+    std::map<std::string, size_t> index;
+    for (size_t k = 0; k < names.size(); ++k)
+        if (!index.emplace(names[k], k).second) error("bootstrap support: leaf \"%s\" twice", names[k].c_str());
+    const size_t n = names.size(), words = (n + 63) / 64;
+    auto bipartitions_of = [&](const PhyTree &t) {
+        Bipartitions b{index, n, words, {}};
+        const LeafSet all = b.below(t, true);
+        size_t size = 0;
+        for (uint64_t w : all) size += (size_t)__builtin_popcountll(w);
+        if (size != n) error("bootstrap support: a replicate has %zu of the tree's %zu leaves", size, n);
+        return std::move(b.out);
+    };
+    const std::vector<std::pair<const PhyTree *, LeafSet>> edges = bipartitions_of(tree);
+    std::map<LeafSet, uint32_t> count;
+    for (const auto &e : edges) count[e.second] = 0;
+    for (const PhyTree *rep : replicates) {
+        std::vector<std::pair<const PhyTree *, LeafSet>> theirs = bipartitions_of(*rep);
+        // (the two edges below a bifurcating root are one bipartition: a replicate counts once)
+        std::sort(theirs.begin(), theirs.end(), [](const std::pair<const PhyTree *, LeafSet> &x, const std::pair<const PhyTree *, LeafSet> &y) { return x.second < y.second; });
+        for (size_t k = 0; k < theirs.size(); ++k) {
+            if (k && theirs[k].second == theirs[k - 1].second) continue;
+            const auto it = count.find(theirs[k].second);
+            if (it != count.end()) ++it->second;
+        }
+    }
+    std::map<const PhyTree *, uint32_t> support;
+    for (const auto &e : edges) support[e.first] = count[e.second];
+    return support;
+}
 
 // ---- midpoint rooting (behaviour of PhyTree.cpp:11-116: the newick of the re-rooted tree must come out byte for byte) ----
 // Own formulation.  The leaves are numbered in depth-first order, so the leaves of a subtree are one contiguous range of the
