@@ -401,7 +401,7 @@ float pgm_wls_last_kernel_ms(pgm_ctx *ctx);       /* device time of the last pai
 uint32_t pgm_wls_last_launches(pgm_ctx *ctx);     /* kernels it launched */
 
 /* ---- BioNJ guide trees (reference src/TreeNJ.cpp:132-281) ------------------------------------------------------------ */
-/* The joins of BioNJ on the device: every value is the expression of the host loop (bionj_joins_host, host/distance.cpp), the
+/* The joins of BioNJ on the device: every value is the expression of the host loop (bionj_joins_host, host/bionj.cpp), the
  * column sums in Eigen's association, the joined pair the first strict minimum of the criterion in column-major order, so the
  * join record and final_d equal the host's bit for bit.  Three kernels per join of the largest family.
  * PGM_ERR_INVALID, before anything is launched: a NULL pointer, nfam == 0, a family with n < 4 or n > PGM_BIONJ_MAX_N, an

@@ -715,7 +715,7 @@ int pgmo_prealigned_counts(uint32_t dim, uint32_t nrows, uint32_t ncols, const i
  * handed over in the eigen form ModelFactory builds (ModelFactory.h:48-67): getModel(d) = parseDistance (with -m / -M: the
  * distance itself, NaN -> 5.2, clamped to [min_dist, max_dist], :104-127), P = V diag(exp(sigma d)) V^-1.  Every matrix
  * product accumulates k = 0..n-1 from zero (one multiply, one add per term), f and f' add the n^2 entries in storage
- * order: the order of the host mirror (host/distance.cpp, host/model_factory.cpp), whose distances agree with the
+ * order: the order of the host mirror (host/mldist.cpp, host/model_factory.cpp), whose distances agree with the
  * reference binary's to the 6 significant digits its newick output prints (tests/golden: nw_pairs.json, *.nw_ml.tree). */
 static void pgmo_matmul(const double *A, const double *B, uint32_t n, double *C) {
     for (size_t i = 0; i < (size_t)n * n; ++i) C[i] = 0.0;

@@ -1,5 +1,5 @@
 // pgm_bionj_kernels.h — the joins of BioNJ (reference src/TreeNJ.cpp:132-281; the host statement is bionj_joins_host in
-// host/distance.cpp) for many families at once, three kernels per join, the families lock-stepped over the join number.
+// host/bionj.cpp) for many families at once, three kernels per join, the families lock-stepped over the join number.
 //
 // fp64 contract: every value is the host's expression, operation by operation (IEEE add, sub, mul, div and strict comparisons;
 // the library is built with -ffp-contract=off -fno-fast-math), and every order-sensitive sum is the host's order:

@@ -1,4 +1,41 @@
-// pgm_dist_capi.inc — C ABI of the distance-estimation stages (included by pgm_capi.hip).
+// pgm_dist_capi.inc — C ABI of the distance-estimation stages (included by pgm_capi.hip).  Every entry is its argument checks, its
+// list of device buffers, the argument struct of its kernel and the launch; dist_run is the call path they share.
+namespace {
+// A device buffer of a call.  Its place in the call's list is its scratch slot (the slots are shared with the all-pairs call: the
+// calls of one context are serial).  src: uploaded before the launch; dst: copied back behind it; zero: cleared before it.
+struct Buf { void **p; size_t bytes; const void *src; void *dst; bool zero; };
+
+// Stages the buffers, runs `launch` between the two events of ctx->ml_ms and copies the results back behind one synchronisation.
+// The stream is synchronised after a failure too: the queued copies read and write host memory of the call.
+template <class Launch>
+int dist_run(pgm_ctx *ctx, const char *what, std::initializer_list<Buf> bufs, const Launch &launch) {
+    HIPCHK(hipSetDevice(ctx->device));
+    hipError_t e = hipSuccess;
+    hipStream_t s = ctx->stream;
+    int slot_ix = 0;
+    for (const Buf &b : bufs) {
+        if (e == hipSuccess) e = scratch_dev(ctx, slot_ix++, b.bytes, b.p);
+        if (e == hipSuccess && b.src && b.bytes) e = hipMemcpyAsync(*b.p, b.src, b.bytes, hipMemcpyHostToDevice, s);
+    }
+    if (e == hipSuccess) e = scratch_events(ctx);
+    for (const Buf &b : bufs)
+        if (e == hipSuccess && b.zero) e = hipMemsetAsync(*b.p, 0, b.bytes, s);
+    if (e == hipSuccess) {
+        e = hipEventRecord(ctx->sc_ev[0], s);
+        launch(s);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = hipEventRecord(ctx->sc_ev[1], s);
+    }
+    for (const Buf &b : bufs)
+        if (e == hipSuccess && b.dst && b.bytes) e = hipMemcpyAsync(b.dst, *b.p, b.bytes, hipMemcpyDeviceToHost, s);
+    const hipError_t es = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = es;
+    if (e == hipSuccess) (void)hipEventElapsedTime(&ctx->ml_ms, ctx->sc_ev[0], ctx->sc_ev[1]);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+    return PGM_OK;
+}
+}  // namespace
+
 extern "C" int pgm_mldist_batch(pgm_ctx *ctx, const pgm_mldist_model *m, uint32_t npairs, const int32_t *counts, const uint32_t *gaps,
                                 const double *seqlen, double *dist, double *var) {
     // two forms of the model: the eigen form (V, Vi, sigma all given, dim <= 20) and the general form (none of them given, dim <= 64)
@@ -8,24 +45,16 @@ extern "C" int pgm_mldist_batch(pgm_ctx *ctx, const pgm_mldist_model *m, uint32_
     if (npairs && (!counts || !gaps || !seqlen || !dist || !var)) return fail(PGM_ERR_INVALID, "null argument");
     ctx->ml_ms = 0;
     if (npairs == 0) return PGM_OK;
-    HIPCHK(hipSetDevice(ctx->device));
     const size_t nn = (size_t)m->dim * m->dim;
     double *d_Q = nullptr, *d_V = nullptr, *d_Vi = nullptr, *d_sig = nullptr, *d_len = nullptr, *d_dist = nullptr, *d_var = nullptr;
     int32_t *d_counts = nullptr;
     uint32_t *d_gaps = nullptr;
-    struct Buf { void **p; size_t bytes; const void *src; };
-    Buf bufs[] = {{(void **)&d_Q, 8 * nn, m->Q}, {(void **)&d_V, eigen ? 8 * nn : 0, m->V}, {(void **)&d_Vi, eigen ? 8 * nn : 0, m->Vi}, {(void **)&d_sig, eigen ? 8 * (size_t)m->dim : 0, m->sigma},
-                  {(void **)&d_counts, 4 * nn * npairs, counts}, {(void **)&d_gaps, 4 * (size_t)npairs, gaps}, {(void **)&d_len, 8 * (size_t)npairs, seqlen},
-                  {(void **)&d_dist, 8 * (size_t)npairs, nullptr}, {(void **)&d_var, 8 * (size_t)npairs, nullptr}};
-    hipError_t e = hipSuccess;
-    hipStream_t s = ctx->stream;
-    int slot_ix = 0;   // shares the scratch slots of the all-pairs call (the calls of one context are serial)
-    for (auto &b : bufs) {
-        if (e == hipSuccess) e = scratch_dev(ctx, slot_ix++, b.bytes, b.p);
-        if (e == hipSuccess && b.src) e = hipMemcpyAsync(*b.p, b.src, b.bytes, hipMemcpyHostToDevice, s);
-    }
-    if (e == hipSuccess) e = scratch_events(ctx);
-    if (e == hipSuccess) {
+    return dist_run(ctx, "mldist",
+                    {{(void **)&d_Q, 8 * nn, m->Q}, {(void **)&d_V, eigen ? 8 * nn : 0, m->V}, {(void **)&d_Vi, eigen ? 8 * nn : 0, m->Vi},
+                     {(void **)&d_sig, eigen ? 8 * (size_t)m->dim : 0, m->sigma}, {(void **)&d_counts, 4 * nn * npairs, counts},
+                     {(void **)&d_gaps, 4 * (size_t)npairs, gaps}, {(void **)&d_len, 8 * (size_t)npairs, seqlen},
+                     {(void **)&d_dist, 8 * (size_t)npairs, nullptr, dist}, {(void **)&d_var, 8 * (size_t)npairs, nullptr, var}},
+                    [&](hipStream_t s) {
         PgmMlArgs A;
         A.dim = m->dim; A.npairs = npairs; A.Q = d_Q; A.V = d_V; A.Vi = d_Vi; A.sigma = d_sig;
         A.counts = d_counts; A.gaps = d_gaps; A.seqlen = d_len;
@@ -33,18 +62,9 @@ extern "C" int pgm_mldist_batch(pgm_ctx *ctx, const pgm_mldist_model *m, uint32_
         A.min_dist = m->min_dist; A.max_dist = m->max_dist; A.indel_rate = m->indel_rate; A.mldist = m->mldist; A.mldist_gap = m->mldist_gap;
         A.dist = d_dist; A.var = d_var;
         const uint32_t blocks = std::min<uint32_t>((npairs + PGM_ML_WAVES - 1) / PGM_ML_WAVES, (uint32_t)ctx->prop.multiProcessorCount * 2u);
-        e = hipEventRecord(ctx->sc_ev[0], s);
         if (eigen) hipLaunchKernelGGL(pgm_mldist_kernel, dim3(blocks), dim3(PGM_ML_WAVES * 64), 0, s, A);
         else hipLaunchKernelGGL(pgm_mldist_general_kernel, dim3(npairs), dim3(PGM_MLG_THREADS), 0, s, A);   // one workgroup per pair
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(ctx->sc_ev[1], s);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(dist, d_dist, 8 * (size_t)npairs, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(var, d_var, 8 * (size_t)npairs, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) (void)hipEventElapsedTime(&ctx->ml_ms, ctx->sc_ev[0], ctx->sc_ev[1]);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("mldist: ") + hipGetErrorString(e));
-    return PGM_OK;
+    });
 }
 
 extern "C" int pgm_prealigned_counts_batch(pgm_ctx *ctx, uint32_t dim, uint32_t nrows, uint32_t ncols, const int8_t *rows, uint32_t npairs,
@@ -54,38 +74,18 @@ extern "C" int pgm_prealigned_counts_batch(pgm_ctx *ctx, uint32_t dim, uint32_t 
     if (npairs == 0) return PGM_OK;
     for (uint32_t p = 0; p < npairs; ++p)
         if (pi[p] >= nrows || pj[p] >= nrows) return fail(PGM_ERR_INVALID, "pair index out of range");
-    HIPCHK(hipSetDevice(ctx->device));
     int8_t *d_rows = nullptr;
     uint32_t *d_pi = nullptr, *d_pj = nullptr, *d_gaps = nullptr;
     int32_t *d_counts = nullptr;
-    const size_t cbytes = 4 * (size_t)npairs * dim * dim;
-    struct Buf { void **p; size_t bytes; const void *src; };
-    Buf bufs[] = {{(void **)&d_rows, (size_t)nrows * ncols, rows}, {(void **)&d_pi, 4 * (size_t)npairs, pi}, {(void **)&d_pj, 4 * (size_t)npairs, pj},
-                  {(void **)&d_counts, cbytes, nullptr}, {(void **)&d_gaps, 4 * (size_t)npairs, nullptr}};
-    hipError_t e = hipSuccess;
-    hipStream_t s = ctx->stream;
-    int slot_ix = 0;
-    for (auto &b : bufs) {
-        if (e == hipSuccess) e = scratch_dev(ctx, slot_ix++, b.bytes, b.p);
-        if (e == hipSuccess && b.src) e = hipMemcpyAsync(*b.p, b.src, b.bytes, hipMemcpyHostToDevice, s);
-    }
-    if (e == hipSuccess) e = scratch_events(ctx);
-    if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, cbytes, s);
-    if (e == hipSuccess) {
+    return dist_run(ctx, "prealigned",
+                    {{(void **)&d_rows, (size_t)nrows * ncols, rows}, {(void **)&d_pi, 4 * (size_t)npairs, pi}, {(void **)&d_pj, 4 * (size_t)npairs, pj},
+                     {(void **)&d_counts, 4 * (size_t)npairs * dim * dim, nullptr, counts, true}, {(void **)&d_gaps, 4 * (size_t)npairs, nullptr, gaps}},
+                    [&](hipStream_t s) {
         PgmPaArgs A;
         A.dim = dim; A.nrows = nrows; A.ncols = ncols; A.npairs = npairs; A.rows = d_rows; A.pi = d_pi; A.pj = d_pj; A.counts = d_counts; A.gaps = d_gaps;
         const uint32_t blocks = std::min<uint32_t>((npairs + 3) / 4, (uint32_t)ctx->prop.multiProcessorCount * 8u);
-        e = hipEventRecord(ctx->sc_ev[0], s);
         hipLaunchKernelGGL(pgm_prealigned_kernel, dim3(blocks), dim3(256), 0, s, A);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(ctx->sc_ev[1], s);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, cbytes, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(gaps, d_gaps, 4 * (size_t)npairs, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) (void)hipEventElapsedTime(&ctx->ml_ms, ctx->sc_ev[0], ctx->sc_ev[1]);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("prealigned: ") + hipGetErrorString(e));
-    return PGM_OK;
+    });
 }
 
 extern "C" float pgm_dist_last_kernel_ms(pgm_ctx *ctx) { return ctx ? ctx->ml_ms : 0.f; }
@@ -102,30 +102,16 @@ extern "C" int pgm_kmer_cosine(pgm_ctx *ctx, uint32_t nseq, uint32_t ncols, cons
     if (!ctx || (nseq && (!counts || !cosine)) || ncols == 0) return fail(PGM_ERR_INVALID, "bad argument");
     ctx->ml_ms = 0;
     if (nseq == 0) return PGM_OK;
-    HIPCHK(hipSetDevice(ctx->device));
     int32_t *d_counts = nullptr;
     double *d_inv = nullptr, *d_out = nullptr;
-    hipError_t e = hipSuccess;
-    hipStream_t s = ctx->stream;
-    e = scratch_dev(ctx, 0, 4 * (size_t)nseq * ncols, (void **)&d_counts);
-    if (e == hipSuccess) e = scratch_dev(ctx, 1, 8 * (size_t)nseq, (void **)&d_inv);
-    if (e == hipSuccess) e = scratch_dev(ctx, 2, 8 * (size_t)nseq * nseq, (void **)&d_out);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_counts, counts, 4 * (size_t)nseq * ncols, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = scratch_events(ctx);
-    if (e == hipSuccess) {
-        e = hipEventRecord(ctx->sc_ev[0], s);
+    return dist_run(ctx, "kmer cosine",
+                    {{(void **)&d_counts, 4 * (size_t)nseq * ncols, counts}, {(void **)&d_inv, 8 * (size_t)nseq}, {(void **)&d_out, 8 * (size_t)nseq * nseq, nullptr, cosine}},
+                    [&](hipStream_t s) {
         hipLaunchKernelGGL(pgm_kmer_norm_kernel, dim3((nseq + 255) / 256), dim3(256), 0, s, nseq, ncols, d_counts, d_inv);
         const uint32_t tiles = (nseq + PGM_KC_TILE - 1) / PGM_KC_TILE;
         const uint32_t kc = kmer_depth_block();
         hipLaunchKernelGGL(pgm_kmer_cosine_kernel, dim3(tiles, tiles), dim3(PGM_KC_TILE * PGM_KC_TILE), 0, s, nseq, ncols, d_counts, d_inv, d_out, kc);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(ctx->sc_ev[1], s);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(cosine, d_out, 8 * (size_t)nseq * nseq, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) (void)hipEventElapsedTime(&ctx->ml_ms, ctx->sc_ev[0], ctx->sc_ev[1]);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("kmer cosine: ") + hipGetErrorString(e));
-    return PGM_OK;
+    });
 }
 
 // ---- many families per launch (pgmsa --batch) ----
@@ -143,37 +129,19 @@ extern "C" int pgm_kmer_cosine_multi(pgm_ctx *ctx, uint32_t nfam, const uint32_t
         out0[f + 1] = out0[f] + (uint64_t)nseq[f] * nseq[f];
     }
     const uint32_t nrows = row0[nfam];
-    HIPCHK(hipSetDevice(ctx->device));
     int32_t *d_counts = nullptr;
     double *d_inv = nullptr, *d_out = nullptr;
     uint32_t *d_tile0 = nullptr, *d_row0 = nullptr;
     uint64_t *d_out0 = nullptr;
-    hipStream_t s = ctx->stream;
-    hipError_t e = scratch_dev(ctx, 0, 4 * (size_t)nrows * ncols, (void **)&d_counts);
-    if (e == hipSuccess) e = scratch_dev(ctx, 1, 8 * (size_t)nrows, (void **)&d_inv);
-    if (e == hipSuccess) e = scratch_dev(ctx, 2, 8 * (size_t)out0[nfam], (void **)&d_out);
-    if (e == hipSuccess) e = scratch_dev(ctx, 3, 4 * (size_t)(nfam + 1), (void **)&d_tile0);
-    if (e == hipSuccess) e = scratch_dev(ctx, 4, 4 * (size_t)(nfam + 1), (void **)&d_row0);
-    if (e == hipSuccess) e = scratch_dev(ctx, 5, 8 * (size_t)(nfam + 1), (void **)&d_out0);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_counts, counts, 4 * (size_t)nrows * ncols, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tile0, tile0.data(), 4 * (size_t)(nfam + 1), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_row0, row0.data(), 4 * (size_t)(nfam + 1), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_out0, out0.data(), 8 * (size_t)(nfam + 1), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = scratch_events(ctx);
-    if (e == hipSuccess) {
-        e = hipEventRecord(ctx->sc_ev[0], s);
+    return dist_run(ctx, "kmer cosine (multi)",
+                    {{(void **)&d_counts, 4 * (size_t)nrows * ncols, counts}, {(void **)&d_inv, 8 * (size_t)nrows}, {(void **)&d_out, 8 * (size_t)out0[nfam], nullptr, cosine},
+                     {(void **)&d_tile0, 4 * (size_t)(nfam + 1), tile0.data()}, {(void **)&d_row0, 4 * (size_t)(nfam + 1), row0.data()},
+                     {(void **)&d_out0, 8 * (size_t)(nfam + 1), out0.data()}},
+                    [&](hipStream_t s) {
         hipLaunchKernelGGL(pgm_kmer_norm_kernel, dim3((nrows + 255) / 256), dim3(256), 0, s, nrows, ncols, d_counts, d_inv);   // (every row has ncols counts)
         hipLaunchKernelGGL(pgm_kmer_cosine_multi_kernel, dim3(tile0[nfam]), dim3(PGM_KC_TILE * PGM_KC_TILE), 0, s, nfam, d_tile0, d_row0, d_out0, ncols, d_counts,
                            d_inv, d_out, kmer_depth_block());
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(ctx->sc_ev[1], s);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(cosine, d_out, 8 * (size_t)out0[nfam], hipMemcpyDeviceToHost, s);
-    const hipError_t es = hipStreamSynchronize(s);   // (also after a failure: the copies read this call's vectors)
-    if (e == hipSuccess) e = es;
-    if (e == hipSuccess) (void)hipEventElapsedTime(&ctx->ml_ms, ctx->sc_ev[0], ctx->sc_ev[1]);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("kmer cosine (multi): ") + hipGetErrorString(e));
-    return PGM_OK;
+    });
 }
 
 extern "C" int pgm_prealigned_counts_multi(pgm_ctx *ctx, uint32_t dim, uint32_t nfam, const uint32_t *nrows, const uint32_t *ncols, const int8_t *rows,
@@ -190,41 +158,20 @@ extern "C" int pgm_prealigned_counts_multi(pgm_ctx *ctx, uint32_t dim, uint32_t 
         if (pi[p] >= nrows[fam[p]] || pj[p] >= nrows[fam[p]]) return fail(PGM_ERR_INVALID, "pair index out of range");
     }
     if (npairs == 0) return PGM_OK;
-    HIPCHK(hipSetDevice(ctx->device));
     int8_t *d_rows = nullptr;
     uint64_t *d_base = nullptr;
     uint32_t *d_ncols = nullptr, *d_fam = nullptr, *d_pi = nullptr, *d_pj = nullptr, *d_gaps = nullptr;
     int32_t *d_counts = nullptr;
-    const size_t cbytes = 4 * (size_t)npairs * dim * dim;
-    struct Buf { void **p; size_t bytes; const void *src; };
-    Buf bufs[] = {{(void **)&d_rows, (size_t)base[nfam], rows}, {(void **)&d_pi, 4 * (size_t)npairs, pi}, {(void **)&d_pj, 4 * (size_t)npairs, pj},
-                  {(void **)&d_counts, cbytes, nullptr}, {(void **)&d_gaps, 4 * (size_t)npairs, nullptr}, {(void **)&d_fam, 4 * (size_t)npairs, fam},
-                  {(void **)&d_base, 8 * (size_t)nfam, base.data()}, {(void **)&d_ncols, 4 * (size_t)nfam, ncols}};
-    hipError_t e = hipSuccess;
-    hipStream_t s = ctx->stream;
-    int slot_ix = 0;
-    for (auto &b : bufs) {
-        if (e == hipSuccess) e = scratch_dev(ctx, slot_ix++, b.bytes, b.p);
-        if (e == hipSuccess && b.src && b.bytes) e = hipMemcpyAsync(*b.p, b.src, b.bytes, hipMemcpyHostToDevice, s);
-    }
-    if (e == hipSuccess) e = scratch_events(ctx);
-    if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, cbytes, s);
-    if (e == hipSuccess) {
+    return dist_run(ctx, "prealigned (multi)",
+                    {{(void **)&d_rows, (size_t)base[nfam], rows}, {(void **)&d_pi, 4 * (size_t)npairs, pi}, {(void **)&d_pj, 4 * (size_t)npairs, pj},
+                     {(void **)&d_counts, 4 * (size_t)npairs * dim * dim, nullptr, counts, true}, {(void **)&d_gaps, 4 * (size_t)npairs, nullptr, gaps},
+                     {(void **)&d_fam, 4 * (size_t)npairs, fam}, {(void **)&d_base, 8 * (size_t)nfam, base.data()}, {(void **)&d_ncols, 4 * (size_t)nfam, ncols}},
+                    [&](hipStream_t s) {
         PgmPaMultiArgs A;
         A.dim = dim; A.npairs = npairs; A.rows = d_rows; A.base = d_base; A.ncols = d_ncols; A.fam = d_fam; A.pi = d_pi; A.pj = d_pj; A.counts = d_counts; A.gaps = d_gaps;
         const uint32_t blocks = std::min<uint32_t>((npairs + 3) / 4, (uint32_t)ctx->prop.multiProcessorCount * 8u);
-        e = hipEventRecord(ctx->sc_ev[0], s);
         hipLaunchKernelGGL(pgm_prealigned_multi_kernel, dim3(blocks), dim3(256), 0, s, A);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(ctx->sc_ev[1], s);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, cbytes, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(gaps, d_gaps, 4 * (size_t)npairs, hipMemcpyDeviceToHost, s);
-    const hipError_t es = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = es;
-    if (e == hipSuccess) (void)hipEventElapsedTime(&ctx->ml_ms, ctx->sc_ev[0], ctx->sc_ev[1]);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("prealigned (multi): ") + hipGetErrorString(e));
-    return PGM_OK;
+    });
 }
 
 // ---- resampled columns of one alignment (pgmsa --bootstrap) ----
@@ -238,37 +185,17 @@ extern "C" int pgm_prealigned_counts_resampled(pgm_ctx *ctx, uint32_t dim, uint3
     for (size_t k = 0; k < ncells; ++k)
         if (cols[k] >= ncols) return fail(PGM_ERR_INVALID, "column index out of range");
     if (npairs == 0) return PGM_OK;
-    HIPCHK(hipSetDevice(ctx->device));
     int8_t *d_rows = nullptr;
     uint32_t *d_pi = nullptr, *d_pj = nullptr, *d_gaps = nullptr, *d_cols = nullptr;
     int32_t *d_counts = nullptr;
-    const size_t nout = (size_t)nrep * npairs, cbytes = 4 * nout * dim * dim;
-    struct Buf { void **p; size_t bytes; const void *src; };
-    Buf bufs[] = {{(void **)&d_rows, (size_t)nrows * ncols, rows}, {(void **)&d_pi, 4 * (size_t)npairs, pi}, {(void **)&d_pj, 4 * (size_t)npairs, pj},
-                  {(void **)&d_counts, cbytes, nullptr}, {(void **)&d_gaps, 4 * nout, nullptr}, {(void **)&d_cols, 4 * ncells, cols}};
-    hipError_t e = hipSuccess;
-    hipStream_t s = ctx->stream;
-    int slot_ix = 0;
-    for (auto &b : bufs) {
-        if (e == hipSuccess) e = scratch_dev(ctx, slot_ix++, b.bytes, b.p);
-        if (e == hipSuccess && b.src) e = hipMemcpyAsync(*b.p, b.src, b.bytes, hipMemcpyHostToDevice, s);
-    }
-    if (e == hipSuccess) e = scratch_events(ctx);
-    if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, cbytes, s);
-    if (e == hipSuccess) {
+    const size_t nout = (size_t)nrep * npairs;
+    return dist_run(ctx, "prealigned (resampled)",
+                    {{(void **)&d_rows, (size_t)nrows * ncols, rows}, {(void **)&d_pi, 4 * (size_t)npairs, pi}, {(void **)&d_pj, 4 * (size_t)npairs, pj},
+                     {(void **)&d_counts, 4 * nout * dim * dim, nullptr, counts, true}, {(void **)&d_gaps, 4 * nout, nullptr, gaps}, {(void **)&d_cols, 4 * ncells, cols}},
+                    [&](hipStream_t s) {
         PgmPaResampledArgs A;
         A.dim = dim; A.ncols = ncols; A.npairs = npairs; A.nrep = nrep; A.rows = d_rows; A.cols = d_cols; A.pi = d_pi; A.pj = d_pj; A.counts = d_counts; A.gaps = d_gaps;
         const uint32_t blocks = std::min<uint32_t>((npairs + 3) / 4, (uint32_t)ctx->prop.multiProcessorCount * 8u);
-        e = hipEventRecord(ctx->sc_ev[0], s);
         hipLaunchKernelGGL(pgm_prealigned_resampled_kernel, dim3(blocks, std::min<uint32_t>(nrep, 65535u)), dim3(256), 0, s, A);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(ctx->sc_ev[1], s);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, cbytes, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(gaps, d_gaps, 4 * nout, hipMemcpyDeviceToHost, s);
-    const hipError_t es = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = es;
-    if (e == hipSuccess) (void)hipEventElapsedTime(&ctx->ml_ms, ctx->sc_ev[0], ctx->sc_ev[1]);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("prealigned (resampled): ") + hipGetErrorString(e));
-    return PGM_OK;
+    });
 }

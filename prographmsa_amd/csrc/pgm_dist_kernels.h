@@ -6,7 +6,7 @@
 //                          codon model): one workgroup per pair, P(d) = exp(Q d) by the host's scaling-and-squaring expm
 //   pgm_prealigned_kernel  DistanceFactoryPrealigned::computePwDistances' pair counts (src/DistanceFactoryPrealigned.h:34-90):
 //                          residue-pair counts and gap openings of every pair of rows of an alignment
-// fp64 throughout.  Every sum keeps the host mirror's order (host/distance.cpp, host/model_factory.cpp): matrix
+// fp64 throughout.  Every sum keeps the host mirror's order (host/mldist.cpp, host/model_factory.cpp): matrix
 // products accumulate k = 0..n-1 from zero with one multiply and one add per term (no FMA), the two sums over the
 // count matrix run over the entries in storage order.  What is NOT bit-identical to the host is exp() (and one log()):
 // the device library's results can differ from glibc's in the last bit, so distances agree to ~1e-15 relative, not

@@ -3,7 +3,7 @@
 //
 // fp64 contract: every term is the reference's W(k,l) * ((D(k,l) - a_k) - b_l), each operation rounded to nearest
 // (__dsub_rn / __dmul_rn / __dadd_rn, and -ffp-contract=off for the rest), added in this fixed order (DESIGN.md "WLS
-// refinement"; the host statement is wls_pair_sums_host in host/distance.cpp):
+// refinement"; the host statement is wls_pair_sums_host in host/wls.cpp):
 //   1. row k of subtree p (one wavefront): lane t adds the terms of the columns l = t, t + 64, ... (ascending) whose subtree q
 //      is above p, one accumulator per q; the 64 lanes are combined by the xor butterfly 32, 16, 8, 4, 2, 1 (v += v^m)
 //   2. a workgroup holds PGM_WLS_ROWS consecutive rows; wave v takes the rows v, v + 4, v + 8, v + 12 of them and adds each

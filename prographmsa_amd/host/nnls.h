@@ -1,4 +1,4 @@
-// nnls.h — NNLS (reference src/NNLS.h) for the weighted least-squares refinement of the guide tree (distance.cpp).
+// nnls.h — NNLS (reference src/NNLS.h) for the weighted least-squares refinement of the guide tree (wls.cpp).
 //
 // The reference's active-set loop (TOL 1e-6, MAX_ITER 100) restated literally over small row-major matrices.  Its inner
 // least-squares solves use Eigen's JacobiSVD (`Zp.jacobiSvd(ComputeThinU | ComputeThinV).solve(x)`), which is not available

@@ -534,6 +534,8 @@ struct DistanceMatrix {   // DistanceFactory.h:12-18
     double &V(int i, int j) { return variances[(size_t)i * dim + j]; }
 };
 struct distvar_t { distance_t dist, var; };
+// the limits of an estimate per alphabet (DistanceFactoryML.cpp:5-32): what computeDistance clamps to, and pgm_mldist_batch with it
+void mldist_limits(const Alphabet &a, double &DIST_MAX, double &VAR_MAX, double &VAR_MIN);
 class DistanceFactoryML {   // DistanceFactoryML.h
 public:
     DistanceFactoryML(const Alphabet &a, const ModelFactory *mf) : alphabet(a), model_factory(mf) {}
@@ -563,6 +565,13 @@ void bionj_joins_host(DistanceMatrix dist, std::vector<pgm_bionj_join> &joins, d
 // that are no sequence are pruned; throws for a sequence topo does not hold and for a node that has not two children
 std::vector<pgm_bionj_pair> build_topo_plan(const std::vector<std::string> &seqs_order, const PhyTree *topo);
 PhyTree *bionj_tree(std::vector<std::string> seqs_order, const std::vector<pgm_bionj_join> &joins, const double *final_d);
+// the support of an edge of length d, 1 - 2^(-d / edge_halflife) within [0, 1] (TreeNJ.cpp:22-29, LeastSquares.cpp:16-23)
+double edge_support(double d);
+// The joins of the families whose matrices are `dist` (nseq[f] taxa each; plan_of(f): the pairs a fixed topology prescribes, or
+// nullptr) in one device call or by bionj_joins_host per family: joins[f], final_d[9 f ..] and the message of a family that failed
+void bionj_joins_families(std::vector<DistanceMatrix> &dist, const std::vector<uint32_t> &nseq,
+                          const std::function<const std::vector<pgm_bionj_pair> *(uint32_t)> &plan_of, std::vector<std::vector<pgm_bionj_join>> &joins,
+                          std::vector<double> &final_d, std::vector<std::string> &join_error);
 // families of this many taxa and more go to the device by default: the smallest measured size from which the device's joins
 // took less time than the host's at every larger size
 const uint32_t kBionjDeviceMin = 256;

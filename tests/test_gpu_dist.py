@@ -1,7 +1,7 @@
 """GPU parity of the guide-tree tail: batched ML distances and the pair counts of an alignment.
 
 pgm_prealigned_counts_batch is integer work: bit-exact against the oracle's pgmo_prealigned_counts
-(src/DistanceFactoryPrealigned.h:34-90).  pgm_mldist_batch against the oracle's pgmo_mldist on synthetic reversible models.  pgm_mldist_batch keeps the host estimator's operation order (host/distance.cpp,
+(src/DistanceFactoryPrealigned.h:34-90).  pgm_mldist_batch against the oracle's pgmo_mldist on synthetic reversible models.  pgm_mldist_batch keeps the host estimator's operation order (host/mldist.cpp,
 the mirror of src/DistanceFactoryML.h:66-190) but uses the device library's exp / log: tolerance 1e-12 relative, checked
 through the product driver (`pgmsa --dump_dist`, host estimator vs PGM_DEVICE_MLDIST=1) on the committed families."""
 import ctypes as C

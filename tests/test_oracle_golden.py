@@ -74,7 +74,7 @@ def test_ancestral_sequences_and_profiles(oracle_build, tmp_path):
 
 @pytest.mark.parametrize("case,flags", [
     # 8 taxa: the last BioNJ join is the exact 4-cluster tie Q(0,1) == Q(2,3), decided by the last bit of Eigen's vectorised
-    # column sums (TreeNJ.cpp:157), which the host restates (distance.cpp eigen_column_sum)
+    # column sums (TreeNJ.cpp:157), which the host restates (bionj.cpp eigen_column_sum)
     ("c1.nw_ml.tree", ["-a", "-m"]),
     ("c1.nw_p.tree", ["-a"])])
 def test_nw_guide_tree_c1(oracle_build, case, flags):

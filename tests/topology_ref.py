@@ -1,5 +1,5 @@
 """The independent statement of --topology in python / numpy float64: the plan of joins a fixed topology gives (reference
-src/TreeNJ.cpp:31-130 as build_topo_plan in host/distance.cpp restates it) and BioNJ's join record when the pairs come from such a
+src/TreeNJ.cpp:31-130 as build_topo_plan in host/bionj.cpp restates it) and BioNJ's join record when the pairs come from such a
 plan (TreeNJ.cpp:158-179: the pair is taken from the plan, the criterion is not evaluated).  tests/test_cpu_topology.py pins both
 to the host loop and to the goldens of the reference binary (tests/golden/topology.json); tests/test_gpu_topology.py holds
 pgm_bionj_plan to them.
