@@ -431,6 +431,18 @@ int pgm_bionj_plan(pgm_ctx *ctx, uint32_t n, const double *D, const double *V, c
 int pgm_bionj_plan_multi(pgm_ctx *ctx, uint32_t nfam, const uint32_t *n, const double *D, const double *V,
                          const pgm_bionj_pair *plan, pgm_bionj_join *joins, double *final_d);
 
+/* ---- residue-pair agreement between a base alignment and nrep replicate alignments of the same sequences (pgmsa --guidance).
+ * where[(r * nrows + i) * ncols + c]: the column of replicate r that holds the residue row i has in base column c, negative where
+ * row i has a gap there.  With hit(r,i,j,c) = where[r][i][c] >= 0 && where[r][i][c] == where[r][j][c]:
+ *   res_hits[i * ncols + c]  = sum over r and j != i of hit     (how often the residue's column-mates were recovered)
+ *   pair_hits[i * nrows + j] = sum over r and c of hit, i != j  (symmetric, zero diagonal)
+ * Both outputs are overwritten.  Two gaps never hit.  All sums are integers, so the results do not depend on the launch.
+ * PGM_ERR_INVALID, before anything is launched or any buffer is touched: nrows, ncols or nrep zero, nrep * (nrows - 1) or
+ * nrep * ncols beyond 32 bits (the range of the sums), more than 2^31 - 1 tiles of 64 x 64; then a null pointer. */
+int pgm_msa_agreement(pgm_ctx *ctx, uint32_t nrows, uint32_t ncols, uint32_t nrep, const int32_t *where,
+                      uint32_t *res_hits /* nrows x ncols */, uint32_t *pair_hits /* nrows x nrows */);
+float pgm_agreement_last_kernel_ms(pgm_ctx *ctx);   /* device time of the two kernels of the last call */
+
 #ifdef __cplusplus
 }
 #endif

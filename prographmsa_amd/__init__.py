@@ -91,6 +91,7 @@ EXPORTS = [
     "pgm_wls_load", "pgm_wls_pair_sums_batch", "pgm_wls_last_kernel_ms", "pgm_wls_last_launches",
     "pgm_bionj", "pgm_bionj_multi", "pgm_bionj_last_launches", "pgm_bionj_last_kernel_ms",
     "pgm_bionj_plan", "pgm_bionj_plan_multi",
+    "pgm_msa_agreement", "pgm_agreement_last_kernel_ms",
 ]
 
 
@@ -166,6 +167,8 @@ def _load():
         "pgm_bionj_last_kernel_ms": (C.c_float, [vp]),
         "pgm_bionj_plan": (C.c_int, [vp, u32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(pgm_bionj_pair), C.POINTER(pgm_bionj_join), C.POINTER(C.c_double)]),
         "pgm_bionj_plan_multi": (C.c_int, [vp, u32, C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(pgm_bionj_pair), C.POINTER(pgm_bionj_join), C.POINTER(C.c_double)]),
+        "pgm_msa_agreement": (C.c_int, [vp, u32, u32, u32, C.POINTER(i32), C.POINTER(u32), C.POINTER(u32)]),
+        "pgm_agreement_last_kernel_ms": (C.c_float, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = the library does not export a declared symbol
@@ -214,6 +217,20 @@ class Context:
         check(lib.pgm_prealigned_counts_resampled(self.handle, dim, rows.shape[0], rows.shape[1], P(rows, C.c_int8), nrep, P(cols, C.c_uint32), npairs,
                                                   P(pi, C.c_uint32), P(pj, C.c_uint32), P(counts, C.c_int32), P(gaps, C.c_uint32)), "pgm_prealigned_counts_resampled")
         return counts, gaps
+
+    def msa_agreement(self, where, res_hits=None, pair_hits=None):
+        """pgm_msa_agreement: where (nrep x nrows x ncols int32, negative = gap) -> res_hits (nrows x ncols uint32) and pair_hits
+        (nrows x nrows uint32).  Given output arrays (C-contiguous uint32 of those shapes) are overwritten in place."""
+        import numpy as np
+        where = np.ascontiguousarray(where, np.int32)
+        nrep, nrows, ncols = where.shape
+        if res_hits is None: res_hits = np.zeros((nrows, ncols), np.uint32)
+        if pair_hits is None: pair_hits = np.zeros((nrows, nrows), np.uint32)
+        for o, shape in ((res_hits, (nrows, ncols)), (pair_hits, (nrows, nrows))):
+            if o.dtype != np.uint32 or o.shape != shape or not o.flags.c_contiguous: raise ValueError("msa_agreement: output array of the wrong kind")
+        P = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+        check(lib.pgm_msa_agreement(self.handle, nrows, ncols, nrep, P(where, C.c_int32), P(res_hits, C.c_uint32), P(pair_hits, C.c_uint32)), "pgm_msa_agreement")
+        return res_hits, pair_hits
 
     def close(self):
         if self.handle:

@@ -127,6 +127,10 @@ struct HipBackend : Backend {
         if (rc != PGM_OK) error("pgm_prealigned_counts_resampled failed (%d): %s", rc, pgm_last_error());
         return true;
     }
+    void msa_agreement(uint32_t nrows, uint32_t ncols, uint32_t nrep, const int32_t *where, uint32_t *res_hits, uint32_t *pair_hits, int worker) override {
+        int rc = pgm_msa_agreement(ctx_of(worker), nrows, ncols, nrep, where, res_hits, pair_hits);
+        if (rc != PGM_OK) error("pgm_msa_agreement failed (%d): %s", rc, pgm_last_error());
+    }
     bool bionj_multi(uint32_t nfam, const uint32_t *n, const double *D, const double *V, pgm_bionj_join *joins, double *final_d, int worker) override {
         pgm_ctx *c = ctx_of(worker);
         int rc = pgm_bionj_multi(c, nfam, n, D, V, joins, final_d);

@@ -11,6 +11,7 @@
 #include <fstream>
 #include <iostream>
 #include <malloc.h>
+#include <sstream>
 #include <unistd.h>
 #include <string>
 #include <thread>
@@ -23,7 +24,9 @@ static void usage() {
                  "             [-s prob] [-A] [--early_refinement] [--ancestral_seqs] [--profile_out <file>] [-R] [--read_repeats <file>]\n"
                  "             [-r|--reroot [-r]] [-W|--wls_refine [-W]] [--dna] [--custom_model <file>] [-F|--estimate_aafreqs]\n"
                  "             [-C|--aafreqs_pseudocount <count>] [--dump_jobs <file>] [--dump_dist <file>] [--dump_joins <file>] [--stats]\n"
-                 "             [--bootstrap <N> --bootstrap_out <file> [--bootstrap_seed <S>]] <fasta file>\n"
+                 "             [--bootstrap <N> --bootstrap_out <file> [--bootstrap_seed <S>]]\n"
+                 "             [--guidance <N> --guidance_out <file> [--guidance_seed <S>] [--guidance_residues <file>] [--guidance_dump <prefix>]]\n"
+                 "             <fasta file>\n"
                  "       pgmsa --batch <list> [--batch_cells <cells>] [options]\n"
                  "  --batch <list>  align many families in one run: every line of <list> is input.fa<TAB>output[<TAB>guide_tree.nwk[<TAB>topology.nwk]]\n"
                  "                (an empty third field: no guide tree; blank lines and lines starting with # are skipped); the other options\n"
@@ -56,6 +59,15 @@ static void usage() {
                  "                edge the number of replicate trees with the same split of the sequences.  --bootstrap_out <file> (required)\n"
                  "                gets that tree with the counts as node labels; --bootstrap_seed <S> (default 1) seeds the resampling.  Needs\n"
                  "                at least 4 sequences; not with --batch, -W, -r, --topology\n"
+                 "  --guidance <N>  confidence of the alignment under perturbed guide trees (1 <= N <= 1000): the BioNJ trees of N resamplings of\n"
+                 "                the final alignment's columns (those of --bootstrap for the same N and seed), midpoint rooted, are each used as\n"
+                 "                the guide tree of a realignment, and every residue pair, column and sequence of the alignment written is scored\n"
+                 "                by how often the replicate alignments put the same residues in one column.  --guidance_out <file> (required)\n"
+                 "                gets the alignment, column, sequence and sequence-pair lines (tab separated: hits, pairs, hits / pairs);\n"
+                 "                --guidance_residues <file> a line per residue; --guidance_seed <S> (default 1) seeds the resampling;\n"
+                 "                --guidance_dump <prefix> writes every replicate's guide tree and alignment to <prefix>.<r>.nwk / .fa.  The\n"
+                 "                replicates share the device stages in groups of at most --batch_cells estimated DP cells.  Needs at least 4\n"
+                 "                sequences; not with --batch, -T, -r, -W, --topology\n"
                  "  -W, --wls_refine  refine every guide tree estimated from distances by weighted least squares (nearest-neighbour\n"
                  "                interchanges of quartets); given twice (-WW), quintet moves as well\n";
 }
@@ -147,15 +159,20 @@ struct Family {
         for (auto it = result.aligned_sequences.begin(); it != result.aligned_sequences.end();)   // ancestral sequences
             if (!it->first.empty() && it->first[0] == '(') it = result.aligned_sequences.erase(it); else ++it;
     }
-    // re-insert start/stop (main.cpp:459-482)
-    void finish(const Alphabet &a) {
-        for (auto &kv : result.aligned_sequences) {
-            sequence_t aseq = kv.second;
-            if (any_start) aseq.insert(aseq.begin(), startStripped[kv.first] ? a.unknown() : a.gap());
-            if (any_end) aseq.insert(aseq.end(), endStripped[kv.first] ? a.unknown() : a.gap());
-            aligned[kv.first] = seqs.count(kv.first) ? stringFromSequence(a, aseq, seqs.at(kv.first)) : stringFromSequence(a, aseq);   // (ancestral rows have no original)
+    // re-insert start/stop (main.cpp:459-482): a row as it is written, one symbol a column (ancestral rows were never stripped)
+    sequence_t written_row(const Alphabet &a, const std::string &name, sequence_t aseq) const {
+        const auto st = startStripped.find(name), en = endStripped.find(name);
+        if (any_start) aseq.insert(aseq.begin(), st != startStripped.end() && st->second ? a.unknown() : a.gap());
+        if (any_end) aseq.insert(aseq.end(), en != endStripped.end() && en->second ? a.unknown() : a.gap());
+        return aseq;
+    }
+    void finish_rows(const Alphabet &a, const std::map<std::string, sequence_t> &rows, std::map<std::string, std::string> &out) const {
+        for (const auto &kv : rows) {
+            const sequence_t aseq = written_row(a, kv.first, kv.second);
+            out[kv.first] = seqs.count(kv.first) ? stringFromSequence(a, aseq, seqs.at(kv.first)) : stringFromSequence(a, aseq);   // (ancestral rows have no original)
         }
     }
+    void finish(const Alphabet &a) { finish_rows(a, result.aligned_sequences, aligned); }
     void write(std::ostream &out) const {
         if (!cmdlineopts.onlytree_flag) {
             std::vector<std::string> order = input_order;
@@ -175,7 +192,17 @@ struct BootstrapOpts {   // --bootstrap N --bootstrap_out FILE --bootstrap_seed 
     std::string out;
     uint64_t seed = 1;
 } g_bootstrap;
+
+struct GuidanceOpts {   // --guidance N --guidance_out FILE --guidance_seed S --guidance_residues FILE --guidance_dump PREFIX
+    bool given = false, out_given = false;
+    long long n = 0;
+    std::string out, residues, dump;
+    uint64_t seed = 1;
+    double cells = 2e9;   // --batch_cells: estimated DP cells of one group of replicates
+} g_guidance;
 }  // namespace
+
+static void doGuidance(const Alphabet &a, const Family &fam, const CSProfile *csprofile, const std::map<std::string, std::vector<repeat_t>> &reps);
 
 // --bootstrap: the tree TreeNJ estimates from the final alignment without its ancestral rows (the re-estimation step of the
 // iterations: main.cpp:404-430, DistanceFactoryPrealigned.h:34-90, TreeNJ.h:27-59), the support of its internal edges among the
@@ -227,6 +254,11 @@ static void print_stats(double t_init, double t_tree, double t_prog, const Batch
     if (g_bootstrap.given)   // (keys of --bootstrap only)
         fprintf(stderr, ", \"bootstrap_replicates\": %d, \"bootstrap_s\": %.6f, \"bootstrap_counts_calls\": %llu", bootstrap_stats.replicates, bootstrap_stats.seconds,
                 (unsigned long long)bootstrap_stats.counts_calls);
+    if (g_guidance.given)   // (keys of --guidance only)
+        fprintf(stderr, ", \"guidance_replicates\": %d, \"guidance_s\": %.6f, \"guidance_align_s\": %.6f, \"guidance_agreement_s\": %.6f, "
+                        "\"guidance_passes\": %llu, \"guidance_agreement_calls\": %llu",
+                guidance_stats.replicates, guidance_stats.seconds, guidance_stats.align_s, guidance_stats.agreement_s, (unsigned long long)guidance_stats.passes,
+                (unsigned long long)guidance_stats.agreement_calls);
     if (batch)   // (keys of --batch only)
         fprintf(stderr, ", \"batch_families\": %d, \"batch_failed\": %d, \"batch_chunks\": %d, \"batch_passes\": %llu, \"batch_levels\": %llu, "
                         "\"batch_align_calls\": %llu, \"batch_dist_calls\": %llu",
@@ -291,6 +323,7 @@ static int doAlign(const Alphabet &a, Family &fam, bool stats) {
         if (cmdlineopts.onlytree_flag) doBootstrap(a, fam, progressive_alignment(a, fam.seqs2, *fam.tree, csprofile.get(), *fam.model_factory, &reps).aligned_sequences);
         else doBootstrap(a, fam, result.aligned_sequences);
     }
+    if (g_guidance.given) doGuidance(a, fam, csprofile.get(), reps);
 
     fam.finish(a);
     if (cmdlineopts.repeats_flag) {
@@ -360,6 +393,128 @@ static std::vector<Family *> alive(const std::vector<Family *> &v) {
     std::vector<Family *> out;
     for (Family *f : v) if (f->failure.empty()) out.push_back(f);
     return out;
+}
+
+// --guidance (Penn et al. 2010, GUIDANCE: the guide tree as the source of alignment uncertainty): the final alignment's columns are
+// resampled N times as --bootstrap resamples them, every replicate's BioNJ tree, midpoint rooted and written with exact branch
+// lengths, is read back as `-t` reads a tree and used as the guide tree of a realignment of the family's sequences (forest passes
+// over groups of replicates within --batch_cells), and Backend::msa_agreement counts per group how often the residue pairs of the
+// alignment as written (start / stop columns re-inserted, ancestral rows left out) share a column in the replicates' alignments.
+static void doGuidance(const Alphabet &a, const Family &fam, const CSProfile *csprofile, const std::map<std::string, std::vector<repeat_t>> &reps) {
+    typedef std::chrono::steady_clock clk;
+    const auto t0 = clk::now();
+    Backend &be = default_backend();
+    const uint32_t N = (uint32_t)g_guidance.n;
+    std::map<std::string, sequence_t> rows;
+    for (const auto &kv : fam.result.aligned_sequences)
+        if (kv.first.empty() || kv.first[0] != '(') rows.insert(kv);   // (ancestral sequences dropped)
+    if (rows.size() < 4) error("--guidance needs at least 4 sequences");
+    std::vector<std::string> names;
+    std::vector<sequence_t> base;
+    for (const auto &kv : rows) { names.push_back(kv.first); base.push_back(fam.written_row(a, kv.first, kv.second)); }
+    const size_t n = names.size(), L = base[0].size();
+    if (L == 0 || L > 0x7fffffffull) error("guidance: an alignment of %zu columns", L);
+
+    // the replicates' guide trees
+    std::vector<std::unique_ptr<PhyTree>> trees(N);
+    {
+        const BootstrapStats kept = bootstrap_stats;   // (the keys of --bootstrap count its own replicates only)
+        std::vector<PhyTree *> unrooted = bootstrap_trees(a, rows, fam.model_factory.get(), N, g_guidance.seed);
+        bootstrap_stats = kept;
+        for (uint32_t r = 0; r < N; ++r) trees[r].reset(unrooted[r]);
+        for (uint32_t r = 0; r < N; ++r) {
+            trees[r].reset(midpointRoot(trees[r].release()));
+            const std::string text = format_newick_exact(*trees[r]);
+            if (!g_guidance.dump.empty()) {
+                const std::string path = g_guidance.dump + "." + std::to_string(r) + ".nwk";
+                std::ofstream out(path.c_str());
+                if (!out) error("error opening the guidance dump file %s", path.c_str());
+                out << text << std::endl;
+            }
+            std::istringstream in(text);
+            trees[r].reset(parse_newick(in));   // (as -t reads it: every branch support 1)
+        }
+    }
+    // groups of replicates in order while the estimated cells of a pass stay within the bound; a larger replicate alone
+    std::vector<double> cells(N, 0.0);
+    std::vector<std::pair<uint32_t, uint32_t>> groups;
+    {
+        double sum = 0;
+        for (uint32_t r = 0; r < N; ++r) {
+            subtree_cells(*trees[r], fam.seqs2, cells[r]);
+            if (groups.empty() || sum + cells[r] > g_guidance.cells) { groups.emplace_back(r, r); sum = 0; }
+            ++groups.back().second;
+            sum += cells[r];
+        }
+    }
+    GuidanceCounts G;
+    G.nrows = (uint32_t)n; G.ncols = (uint32_t)L; G.nrep = N;
+    G.res_hits.assign(n * L, 0); G.pair_hits.assign(n * n, 0);
+    const uint32_t per_call = guidance_call_replicates(G.nrows, G.ncols);
+    std::vector<int32_t> where;
+    std::vector<uint32_t> res32(n * L), pair32(n * n);
+    for (const auto &grp : groups) {
+        const uint32_t g = grp.second - grp.first;
+        const auto ta = clk::now();
+        std::vector<ProgressiveAlignmentResult> res(g);
+        {
+            std::vector<ForestFamily> ff(g);
+            std::vector<uint64_t> cost(g);
+            for (uint32_t k = 0; k < g; ++k) {
+                ff[k].sequences = &fam.seqs2; ff[k].tree = trees[grp.first + k].get(); ff[k].model_factory = fam.model_factory.get();
+                ff[k].repeats = &reps; ff[k].result = &res[k];
+                cost[k] = (uint64_t)cells[grp.first + k] + 1u;
+            }
+            const std::vector<std::vector<uint32_t>> shards = farm_shards(cost, be.workers());   // (as run_chunk deals families)
+            for (size_t w = 0; w < shards.size(); ++w) for (uint32_t k : shards[w]) ff[k].worker = (int)w;
+            progressive_alignment_forest(a, ff, csprofile);
+            ++guidance_stats.passes;
+            for (uint32_t k = 0; k < g; ++k) if (!ff[k].error.empty()) throw pgm_exception(ff[k].error);
+        }
+        guidance_stats.align_s += std::chrono::duration<double>(clk::now() - ta).count();
+        std::vector<std::vector<sequence_t>> written(g);
+        parallel_for(g, [&](size_t k) {
+            for (const std::string &name : names) {
+                const auto it = res[k].aligned_sequences.find(name);
+                if (it == res[k].aligned_sequences.end()) error("guidance: a replicate alignment without sequence %s", name.c_str());
+                written[k].push_back(fam.written_row(a, name, it->second));
+            }
+            if (!g_guidance.dump.empty()) {   // the replicate's alignment as `-t <its tree>` writes it
+                const uint32_t r = grp.first + (uint32_t)k;
+                std::map<std::string, std::string> aligned;
+                fam.finish_rows(a, res[k].aligned_sequences, aligned);
+                const std::string path = g_guidance.dump + "." + std::to_string(r) + ".fa";
+                std::ofstream out(path.c_str());
+                if (!out) error("error opening the guidance dump file %s", path.c_str());
+                write_fasta(aligned, cmdlineopts.inputorder_flag ? fam.input_order : get_tree_order(trees[r].get()), out);
+            }
+            res[k] = ProgressiveAlignmentResult();
+        });
+        for (uint32_t k0 = 0; k0 < g; k0 += per_call) {
+            const uint32_t m = std::min(per_call, g - k0);
+            where.resize((size_t)m * n * L);
+            parallel_for(m, [&](size_t k) { guidance_where(a, base, written[k0 + k], where.data() + k * n * L); });
+            const auto tg = clk::now();
+            be.msa_agreement(G.nrows, G.ncols, m, where.data(), res32.data(), pair32.data());
+            guidance_stats.agreement_s += std::chrono::duration<double>(clk::now() - tg).count();
+            ++guidance_stats.agreement_calls;
+            for (size_t k = 0; k < res32.size(); ++k) G.res_hits[k] += res32[k];
+            for (size_t k = 0; k < pair32.size(); ++k) G.pair_hits[k] += pair32[k];
+        }
+    }
+    std::vector<int32_t> where0(n * L);   // (the gaps of the base alignment)
+    for (size_t i = 0; i < n; ++i)
+        for (size_t c = 0; c < L; ++c) where0[i * L + c] = a.isGap(base[i][c]) ? -1 : 0;
+    std::ofstream out(g_guidance.out.c_str());
+    if (!out) error("error opening the guidance output file %s", g_guidance.out.c_str());
+    std::ofstream rout;
+    if (!g_guidance.residues.empty()) {
+        rout.open(g_guidance.residues.c_str());
+        if (!rout) error("error opening the guidance residue file %s", g_guidance.residues.c_str());
+    }
+    guidance_write(G, names, where0.data(), g_guidance.seed, out, g_guidance.residues.empty() ? nullptr : &rout);
+    guidance_stats.replicates += (int)N;
+    guidance_stats.seconds += std::chrono::duration<double>(clk::now() - t0).count();
 }
 
 // The families of a chunk through the stages of doAlign in lock-step: every device stage once for all of them.
@@ -542,6 +697,11 @@ int main(int argc, char **argv) {
             else if (s == "--bootstrap") { g_bootstrap.given = true; g_bootstrap.n = atoll(val().c_str()); }
             else if (s == "--bootstrap_out") { g_bootstrap.out_given = true; g_bootstrap.out = val(); }
             else if (s == "--bootstrap_seed") g_bootstrap.seed = strtoull(val().c_str(), nullptr, 10);
+            else if (s == "--guidance") { g_guidance.given = true; g_guidance.n = atoll(val().c_str()); }
+            else if (s == "--guidance_out") { g_guidance.out_given = true; g_guidance.out = val(); }
+            else if (s == "--guidance_seed") g_guidance.seed = strtoull(val().c_str(), nullptr, 10);
+            else if (s == "--guidance_residues") g_guidance.residues = val();
+            else if (s == "--guidance_dump") g_guidance.dump = val();
             else if (s == "--reroot") ++cmdlineopts.reroot_flag;
             else if (s == "--wls_refine") ++cmdlineopts.wlsrefine_flag;
             else if (s.size() >= 2 && s[0] == '-' && s.find_first_not_of('W', 1) == std::string::npos) cmdlineopts.wlsrefine_flag += (int)s.size() - 1;   // -W, -WW
@@ -558,7 +718,8 @@ int main(int argc, char **argv) {
                                   : cmdlineopts.reroot_flag ? "-r" : cmdlineopts.wlsrefine_flag ? "-W"
                                   : cmdlineopts.repeats_flag ? "-R" : !cmdlineopts.readreps_file.empty() ? "--read_repeats"
                                   : !cmdlineopts.profile_file.empty() ? "--profile_out" : !dump.empty() ? "--dump_jobs" : !dist_dump.empty() ? "--dump_dist" : !joins_dump.empty() ? "--dump_joins"
-                                  : (g_bootstrap.given || g_bootstrap.out_given) ? "--bootstrap" : nullptr;
+                                  : (g_bootstrap.given || g_bootstrap.out_given) ? "--bootstrap"
+                                  : (g_guidance.given || g_guidance.out_given || !g_guidance.residues.empty() || !g_guidance.dump.empty()) ? "--guidance" : nullptr;
             if (refused) { std::cerr << "ERROR:--batch cannot be combined with " << refused << std::endl; return 2; }
         }
         if (cmdlineopts.sequence_file.empty() && batch_list.empty()) { usage(); return 1; }
@@ -569,6 +730,17 @@ int main(int argc, char **argv) {
                               : cmdlineopts.reroot_flag ? "--bootstrap cannot be combined with -r"
                               : !topo_file.empty() ? "--bootstrap cannot be combined with --topology" : nullptr;
             if (why) { std::cerr << "ERROR:" << why << std::endl; return 2; }
+        }
+        if (g_guidance.given || g_guidance.out_given || !g_guidance.residues.empty() || !g_guidance.dump.empty()) {
+            const char *why = g_guidance.given != g_guidance.out_given ? "--guidance and --guidance_out need each other"
+                              : !g_guidance.given ? "--guidance_residues and --guidance_dump need --guidance"
+                              : (g_guidance.n < 1 || g_guidance.n > 1000) ? "--guidance takes a number of replicates from 1 to 1000"
+                              : cmdlineopts.onlytree_flag ? "--guidance cannot be combined with -T (there is no alignment to score)"
+                              : cmdlineopts.wlsrefine_flag ? "--guidance cannot be combined with -W"
+                              : cmdlineopts.reroot_flag ? "--guidance cannot be combined with -r"
+                              : !topo_file.empty() ? "--guidance cannot be combined with --topology (every replicate would have the same topology)" : nullptr;
+            if (why) { std::cerr << "ERROR:" << why << std::endl; return 2; }
+            g_guidance.cells = batch_cells;
         }
         if (cmdlineopts.reroot_flag && (cmdlineopts.ancestral_flag || !cmdlineopts.profile_file.empty())) {
             std::cerr << "ERROR:--ancestral_seqs and --profile_out cannot be combined with -r (the root search keeps no ancestral profiles)" << std::endl;
@@ -606,6 +778,7 @@ int main(int argc, char **argv) {
         fam.input = cmdlineopts.sequence_file; fam.tree_file = cmdlineopts.tree_file; fam.topo_file = topo_file; fam.iters = cmdlineopts.iters;
         fam.seqs = read_fasta(cmdlineopts.sequence_file, fam.input_order);
         if (g_bootstrap.given && fam.seqs.size() < 4) error("--bootstrap needs at least 4 sequences");
+        if (g_guidance.given && fam.seqs.size() < 4) error("--guidance needs at least 4 sequences");
         std::ofstream custom_out;
         std::ostream *out = &std::cout;
         if (!cmdlineopts.output_file.empty()) {

@@ -320,6 +320,9 @@ struct Backend {
     // integers one replicate at a time (false where it has no pair-count entry at all).
     virtual bool prealigned_counts_resampled(uint32_t dim, uint32_t nrows, uint32_t ncols, const int8_t *rows, uint32_t nrep, const uint32_t *cols,
                                              uint32_t npairs, const uint32_t *pi, const uint32_t *pj, int32_t *counts, uint32_t *gaps, int worker = 0);
+    // The residue-pair agreement counts of --guidance (include/pgm_hip.h: pgm_msa_agreement): where is nrep x nrows x ncols, res_hits
+    // nrows x ncols and pair_hits nrows x nrows are overwritten.  The default is the host statement, msa_agreement_host.
+    virtual void msa_agreement(uint32_t nrows, uint32_t ncols, uint32_t nrep, const int32_t *where, uint32_t *res_hits, uint32_t *pair_hits, int worker = 0);
     // calls the host code made of the align-batch entry and of the distance entries (all-pairs tiles, pair counts, cosine, ML
     // distances): `pgmsa --batch --stats` shows with them that a stage was shared by the families of a chunk
     std::atomic<uint64_t> calls_align{0}, calls_dist{0};
@@ -620,6 +623,32 @@ struct BootstrapStats {   // `pgmsa --bootstrap --stats`
 };
 extern BootstrapStats bootstrap_stats;
 std::vector<PhyTree *> bootstrap_trees(const Alphabet &a, const std::map<std::string, sequence_t> &rows, const ModelFactory *mf, uint32_t nrep, uint64_t seed);
+
+// --guidance: how often the residue pairs of the base alignment stand in one column again in the alignments of N bootstrap guide
+// trees (host/guidance.inc; the flow is doGuidance in main.cpp).
+// guidance_where: one replicate's residue map, where[i * ncols + c] = the column of `rep` that holds the residue row i of `base`
+//   has in column c, -1 for a gap (rows as written, one symbol a column; both alignments hold the same residues in the same order).
+// msa_agreement_host: the counts of pgm_msa_agreement by plain loops on the host threads (Backend::msa_agreement's default).
+// guidance_call_replicates: the most replicates one agreement call takes for `where` to stay within where_bytes and for the sums
+//   to fit 32 bits (nrep * (nrows - 1), nrep * ncols), at least 1.
+// format_newick_exact: formatNewick()'s text with every branch length printed with %.17g (reading it back gives the same doubles).
+// guidance_write: the two score files from the summed counts; where0 is any replicate's map (only its gaps are read).
+const size_t kGuidanceWhereBytes = (size_t)1 << 30;   // `where` of one msa_agreement call
+struct GuidanceStats {   // `pgmsa --guidance --stats`
+    int replicates = 0;
+    double seconds = 0, align_s = 0, agreement_s = 0;
+    uint64_t passes = 0, agreement_calls = 0;
+};
+extern GuidanceStats guidance_stats;
+struct GuidanceCounts {
+    uint32_t nrows = 0, ncols = 0, nrep = 0;
+    std::vector<uint64_t> res_hits, pair_hits;   // nrows x ncols, nrows x nrows
+};
+void guidance_where(const Alphabet &a, const std::vector<sequence_t> &base, const std::vector<sequence_t> &rep, int32_t *where);
+void msa_agreement_host(uint32_t nrows, uint32_t ncols, uint32_t nrep, const int32_t *where, uint32_t *res_hits, uint32_t *pair_hits);
+uint32_t guidance_call_replicates(uint32_t nrows, uint32_t ncols, size_t where_bytes = kGuidanceWhereBytes);
+std::string format_newick_exact(const PhyTree &tree);
+void guidance_write(const GuidanceCounts &g, const std::vector<std::string> &names, const int32_t *where0, uint64_t seed, std::ostream &out, std::ostream *residues);
 
 std::string data_dir();   // directory holding wag.qmat etc.
 

@@ -1307,5 +1307,7 @@ ProgressiveAlignmentResult progressive_alignment_find_root(const Alphabet &a, co
     return result;
 }
 
+// ==== --guidance: residue map, agreement counts on the host, score files ===============================================
+#include "guidance.inc"
 
 }  // namespace pgm
