@@ -443,6 +443,22 @@ int pgm_msa_agreement(pgm_ctx *ctx, uint32_t nrows, uint32_t ncols, uint32_t nre
                       uint32_t *res_hits /* nrows x ncols */, uint32_t *pair_hits /* nrows x nrows */);
 float pgm_agreement_last_kernel_ms(pgm_ctx *ctx);   /* device time of the two kernels of the last call */
 
+/* ---- transfer indices of the bipartitions of a tree against those of nrep replicate trees (pgmsa --bootstrap_tbe; Lemoine et al.,
+ * Nature 2018).  A bipartition of nleaves leaves is a bit set of words = (nleaves + 63) / 64 little-endian uint64 words, either of its
+ * sides, bits at or above nleaves zero.  With |A| = popcount, p(A) = min(|A|, nleaves - |A|) and the transfer distance
+ * d(A, B) = min(h, nleaves - h), h = popcount(A xor B):
+ *   phi[e * nrep + r] = min(p(A_e) - 1, min over rep_off[r] <= s < rep_off[r + 1] of d(A_e, B_s))
+ * for reference set e (ref + e * words) and the sets B_s (rep + s * words) of replicate r.  p(A_e) - 1 is what the single-leaf
+ * bipartitions of any tree give, so rep holds a replicate's other bipartitions only and may hold none.  phi is overwritten.
+ * All values are integers, so the result does not depend on the launch.
+ * PGM_ERR_INVALID, before anything is launched or phi is touched: nleaves < 4, nref == 0, nrep == 0, nref * nrep beyond 32 bits, a
+ * null pointer (rep may be null when rep_off[nrep] == 0), rep_off not ascending from 0, a set with a bit at or above nleaves, a
+ * reference set that is empty or full. */
+int pgm_transfer_min(pgm_ctx *ctx, uint32_t nleaves, uint32_t nref, const uint64_t *ref /* nref x words */,
+                     uint32_t nrep, const uint32_t *rep_off /* nrep + 1, ascending, rep_off[0] == 0 */,
+                     const uint64_t *rep /* rep_off[nrep] x words */, uint32_t *phi /* nref x nrep, overwritten */);
+float pgm_transfer_last_kernel_ms(pgm_ctx *ctx);   /* device time of the kernel of the last call */
+
 #ifdef __cplusplus
 }
 #endif

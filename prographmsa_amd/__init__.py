@@ -92,6 +92,7 @@ EXPORTS = [
     "pgm_bionj", "pgm_bionj_multi", "pgm_bionj_last_launches", "pgm_bionj_last_kernel_ms",
     "pgm_bionj_plan", "pgm_bionj_plan_multi",
     "pgm_msa_agreement", "pgm_agreement_last_kernel_ms",
+    "pgm_transfer_min", "pgm_transfer_last_kernel_ms",
 ]
 
 
@@ -169,6 +170,8 @@ def _load():
         "pgm_bionj_plan_multi": (C.c_int, [vp, u32, C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(pgm_bionj_pair), C.POINTER(pgm_bionj_join), C.POINTER(C.c_double)]),
         "pgm_msa_agreement": (C.c_int, [vp, u32, u32, u32, C.POINTER(i32), C.POINTER(u32), C.POINTER(u32)]),
         "pgm_agreement_last_kernel_ms": (C.c_float, [vp]),
+        "pgm_transfer_min": (C.c_int, [vp, u32, u32, C.POINTER(C.c_uint64), u32, C.POINTER(u32), C.POINTER(C.c_uint64), C.POINTER(u32)]),
+        "pgm_transfer_last_kernel_ms": (C.c_float, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = the library does not export a declared symbol
@@ -231,6 +234,24 @@ class Context:
         P = lambda a, t: a.ctypes.data_as(C.POINTER(t))
         check(lib.pgm_msa_agreement(self.handle, nrows, ncols, nrep, P(where, C.c_int32), P(res_hits, C.c_uint32), P(pair_hits, C.c_uint32)), "pgm_msa_agreement")
         return res_hits, pair_hits
+
+    def transfer_min(self, nleaves, ref, rep_off, rep, phi=None):
+        """pgm_transfer_min: ref (nref x words uint64, words = (nleaves + 63) // 64), rep_off (nrep + 1 uint32), rep (rep_off[-1] x words
+        uint64) -> phi (nref x nrep uint32).  A given output array (C-contiguous uint32 of that shape) is overwritten in place."""
+        import numpy as np
+        words = (nleaves + 63) // 64
+        ref = np.ascontiguousarray(ref, np.uint64)
+        rep_off = np.ascontiguousarray(rep_off, np.uint32)
+        rep = np.ascontiguousarray(rep, np.uint64).reshape(-1, words)
+        if ref.ndim != 2 or ref.shape[1] != words or rep_off.ndim != 1 or len(rep_off) < 1 or rep.shape[0] != int(rep_off[-1]):
+            raise ValueError("transfer_min: input array of the wrong shape")
+        nref, nrep = ref.shape[0], len(rep_off) - 1
+        if phi is None: phi = np.zeros((nref, nrep), np.uint32)
+        if phi.dtype != np.uint32 or phi.shape != (nref, nrep) or not phi.flags.c_contiguous: raise ValueError("transfer_min: output array of the wrong kind")
+        P = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+        check(lib.pgm_transfer_min(self.handle, nleaves, nref, P(ref, C.c_uint64), nrep, P(rep_off, C.c_uint32), P(rep, C.c_uint64) if rep.size else None,
+                                   P(phi, C.c_uint32)), "pgm_transfer_min")
+        return phi
 
     def close(self):
         if self.handle:

@@ -131,6 +131,13 @@ struct HipBackend : Backend {
         int rc = pgm_msa_agreement(ctx_of(worker), nrows, ncols, nrep, where, res_hits, pair_hits);
         if (rc != PGM_OK) error("pgm_msa_agreement failed (%d): %s", rc, pgm_last_error());
     }
+    void transfer_min(uint32_t nleaves, uint32_t nref, const uint64_t *ref, uint32_t nrep, const uint32_t *rep_off, const uint64_t *rep, uint32_t *phi,
+                      int worker) override {
+        pgm_ctx *c = ctx_of(worker);
+        int rc = pgm_transfer_min(c, nleaves, nref, ref, nrep, rep_off, rep, phi);
+        if (rc != PGM_OK) error("pgm_transfer_min failed (%d): %s", rc, pgm_last_error());
+        transfer_stats.kernel_ms += pgm_transfer_last_kernel_ms(c);
+    }
     bool bionj_multi(uint32_t nfam, const uint32_t *n, const double *D, const double *V, pgm_bionj_join *joins, double *final_d, int worker) override {
         pgm_ctx *c = ctx_of(worker);
         int rc = pgm_bionj_multi(c, nfam, n, D, V, joins, final_d);

@@ -86,6 +86,8 @@ const HostSwitches &host_switches() {
         h.device_mldist = getenv("PGM_DEVICE_MLDIST") != nullptr;
         h.device_bionj = getenv("PGM_DEVICE_BIONJ") != nullptr;
         h.host_bionj = getenv("PGM_HOST_BIONJ") != nullptr;
+        h.host_transfer = getenv("PGM_HOST_TRANSFER") != nullptr;
+        h.device_transfer = getenv("PGM_DEVICE_TRANSFER") != nullptr;
         return h;
     }();
     return sw;
@@ -95,6 +97,7 @@ std::string HostSwitches::describe() const {
     auto add = [&](bool on, const char *name) { if (on) { if (!s.empty()) s += ","; s += name; } };
     add(host_merge, "PGM_HOST_MERGE"); add(no_resident, "PGM_NO_RESIDENT"); add(host_counts, "PGM_HOST_COUNTS"); add(device_mldist, "PGM_DEVICE_MLDIST");
     add(device_bionj, "PGM_DEVICE_BIONJ"); add(host_bionj, "PGM_HOST_BIONJ");
+    add(host_transfer, "PGM_HOST_TRANSFER"); add(device_transfer, "PGM_DEVICE_TRANSFER");
     return s;
 }
 

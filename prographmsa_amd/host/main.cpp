@@ -24,7 +24,7 @@ static void usage() {
                  "             [-s prob] [-A] [--early_refinement] [--ancestral_seqs] [--profile_out <file>] [-R] [--read_repeats <file>]\n"
                  "             [-r|--reroot [-r]] [-W|--wls_refine [-W]] [--dna] [--custom_model <file>] [-F|--estimate_aafreqs]\n"
                  "             [-C|--aafreqs_pseudocount <count>] [--dump_jobs <file>] [--dump_dist <file>] [--dump_joins <file>] [--stats]\n"
-                 "             [--bootstrap <N> --bootstrap_out <file> [--bootstrap_seed <S>]]\n"
+                 "             [--bootstrap <N> --bootstrap_out <file> [--bootstrap_seed <S>] [--bootstrap_tbe <file>] [--bootstrap_trees <file>]]\n"
                  "             [--guidance <N> --guidance_out <file> [--guidance_seed <S>] [--guidance_residues <file>] [--guidance_dump <prefix>]]\n"
                  "             <fasta file>\n"
                  "       pgmsa --batch <list> [--batch_cells <cells>] [options]\n"
@@ -59,6 +59,10 @@ static void usage() {
                  "                edge the number of replicate trees with the same split of the sequences.  --bootstrap_out <file> (required)\n"
                  "                gets that tree with the counts as node labels; --bootstrap_seed <S> (default 1) seeds the resampling.  Needs\n"
                  "                at least 4 sequences; not with --batch, -W, -r, --topology\n"
+                 "  --bootstrap_tbe <file>  with --bootstrap: the same tree with the transfer bootstrap expectation (TBE, Lemoine et al. 2018) of\n"
+                 "                every internal edge as node labels (%.6f): 1 - the mean over the replicates of the fewest leaves to move for the\n"
+                 "                replicate to have the edge, over the size of the edge's smaller side - 1\n"
+                 "  --bootstrap_trees <file>  with --bootstrap: the N replicate trees, one newick line each, in replicate order\n"
                  "  --guidance <N>  confidence of the alignment under perturbed guide trees (1 <= N <= 1000): the BioNJ trees of N resamplings of\n"
                  "                the final alignment's columns (those of --bootstrap for the same N and seed), midpoint rooted, are each used as\n"
                  "                the guide tree of a realignment, and every residue pair, column and sequence of the alignment written is scored\n"
@@ -189,8 +193,9 @@ struct BatchRun { int families = 0, failed = 0, chunks = 0; };
 struct BootstrapOpts {   // --bootstrap N --bootstrap_out FILE --bootstrap_seed S
     bool given = false, out_given = false;
     long long n = 0;
-    std::string out;
+    std::string out, tbe, trees;   // --bootstrap_tbe FILE, --bootstrap_trees FILE
     uint64_t seed = 1;
+    bool any() const { return given || out_given || !tbe.empty() || !trees.empty(); }
 } g_bootstrap;
 
 struct GuidanceOpts {   // --guidance N --guidance_out FILE --guidance_seed S --guidance_residues FILE --guidance_dump PREFIX
@@ -206,7 +211,9 @@ static void doGuidance(const Alphabet &a, const Family &fam, const CSProfile *cs
 
 // --bootstrap: the tree TreeNJ estimates from the final alignment without its ancestral rows (the re-estimation step of the
 // iterations: main.cpp:404-430, DistanceFactoryPrealigned.h:34-90, TreeNJ.h:27-59), the support of its internal edges among the
-// trees of N column resamplings, and the file: formatNewick()'s text with the counts as node labels
+// trees of N column resamplings, and the file: formatNewick()'s text with the counts as node labels.  --bootstrap_tbe: the same
+// text with the transfer bootstrap expectation of every labelled node (transfer_support; the device from kTransferDeviceMin taxa
+// or with PGM_DEVICE_TRANSFER, the host loop with PGM_HOST_TRANSFER); --bootstrap_trees: formatNewick() of every replicate's tree
 static void doBootstrap(const Alphabet &a, const Family &fam, const std::map<std::string, sequence_t> &alignment) {
     const auto t0 = std::chrono::steady_clock::now();
     std::map<std::string, sequence_t> rows;
@@ -214,9 +221,17 @@ static void doBootstrap(const Alphabet &a, const Family &fam, const std::map<std
         if (kv.first.empty() || kv.first[0] != '(') rows.insert(kv);   // (ancestral sequences dropped)
     std::unique_ptr<PhyTree> tree(TreeNJ(a, rows, fam.model_factory.get(), true));
     std::vector<PhyTree *> reps = bootstrap_trees(a, rows, fam.model_factory.get(), (uint32_t)g_bootstrap.n, g_bootstrap.seed);
-    std::string text;
+    std::string text, tbe_text, trees_text;
     try {
-        text = tree->formatNewick(bipartition_support(*tree, std::vector<const PhyTree *>(reps.begin(), reps.end())));
+        const std::vector<const PhyTree *> replicates(reps.begin(), reps.end());
+        text = tree->formatNewick(bipartition_support(*tree, replicates));
+        if (!g_bootstrap.tbe.empty()) {
+            const HostSwitches &sw = host_switches();
+            const bool device = !sw.host_transfer && (sw.device_transfer || rows.size() >= kTransferDeviceMin);
+            tbe_text = tree->formatNewick(transfer_labels(transfer_support(*tree, replicates, device ? &default_backend() : nullptr), (uint32_t)replicates.size()));
+        }
+        if (!g_bootstrap.trees.empty())
+            for (const PhyTree *t : replicates) trees_text += t->formatNewick() + "\n";
     } catch (...) {
         for (PhyTree *t : reps) delete t;
         throw;
@@ -225,6 +240,16 @@ static void doBootstrap(const Alphabet &a, const Family &fam, const std::map<std
     std::ofstream out(g_bootstrap.out.c_str());
     if (!out) error("error opening the bootstrap output file %s", g_bootstrap.out.c_str());
     out << text << std::endl;
+    if (!g_bootstrap.tbe.empty()) {
+        std::ofstream tbe(g_bootstrap.tbe.c_str());
+        if (!tbe) error("error opening the bootstrap output file %s", g_bootstrap.tbe.c_str());
+        tbe << tbe_text << std::endl;
+    }
+    if (!g_bootstrap.trees.empty()) {
+        std::ofstream trees(g_bootstrap.trees.c_str());
+        if (!trees) error("error opening the bootstrap output file %s", g_bootstrap.trees.c_str());
+        trees << trees_text << std::flush;
+    }
     bootstrap_stats.seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
@@ -254,6 +279,9 @@ static void print_stats(double t_init, double t_tree, double t_prog, const Batch
     if (g_bootstrap.given)   // (keys of --bootstrap only)
         fprintf(stderr, ", \"bootstrap_replicates\": %d, \"bootstrap_s\": %.6f, \"bootstrap_counts_calls\": %llu", bootstrap_stats.replicates, bootstrap_stats.seconds,
                 (unsigned long long)bootstrap_stats.counts_calls);
+    if (!g_bootstrap.tbe.empty())   // (keys of --bootstrap_tbe only)
+        fprintf(stderr, ", \"bootstrap_tbe_s\": %.6f, \"bootstrap_transfer_calls\": %llu, \"bootstrap_transfer_kernel_ms\": %.3f", transfer_stats.seconds,
+                (unsigned long long)transfer_stats.calls, transfer_stats.kernel_ms);
     if (g_guidance.given)   // (keys of --guidance only)
         fprintf(stderr, ", \"guidance_replicates\": %d, \"guidance_s\": %.6f, \"guidance_align_s\": %.6f, \"guidance_agreement_s\": %.6f, "
                         "\"guidance_passes\": %llu, \"guidance_agreement_calls\": %llu",
@@ -697,6 +725,8 @@ int main(int argc, char **argv) {
             else if (s == "--bootstrap") { g_bootstrap.given = true; g_bootstrap.n = atoll(val().c_str()); }
             else if (s == "--bootstrap_out") { g_bootstrap.out_given = true; g_bootstrap.out = val(); }
             else if (s == "--bootstrap_seed") g_bootstrap.seed = strtoull(val().c_str(), nullptr, 10);
+            else if (s == "--bootstrap_tbe") g_bootstrap.tbe = val();
+            else if (s == "--bootstrap_trees") g_bootstrap.trees = val();
             else if (s == "--guidance") { g_guidance.given = true; g_guidance.n = atoll(val().c_str()); }
             else if (s == "--guidance_out") { g_guidance.out_given = true; g_guidance.out = val(); }
             else if (s == "--guidance_seed") g_guidance.seed = strtoull(val().c_str(), nullptr, 10);
@@ -718,13 +748,14 @@ int main(int argc, char **argv) {
                                   : cmdlineopts.reroot_flag ? "-r" : cmdlineopts.wlsrefine_flag ? "-W"
                                   : cmdlineopts.repeats_flag ? "-R" : !cmdlineopts.readreps_file.empty() ? "--read_repeats"
                                   : !cmdlineopts.profile_file.empty() ? "--profile_out" : !dump.empty() ? "--dump_jobs" : !dist_dump.empty() ? "--dump_dist" : !joins_dump.empty() ? "--dump_joins"
-                                  : (g_bootstrap.given || g_bootstrap.out_given) ? "--bootstrap"
+                                  : g_bootstrap.any() ? "--bootstrap"
                                   : (g_guidance.given || g_guidance.out_given || !g_guidance.residues.empty() || !g_guidance.dump.empty()) ? "--guidance" : nullptr;
             if (refused) { std::cerr << "ERROR:--batch cannot be combined with " << refused << std::endl; return 2; }
         }
         if (cmdlineopts.sequence_file.empty() && batch_list.empty()) { usage(); return 1; }
-        if (g_bootstrap.given || g_bootstrap.out_given) {
-            const char *why = g_bootstrap.given != g_bootstrap.out_given ? "--bootstrap and --bootstrap_out need each other"
+        if (g_bootstrap.any()) {
+            const char *why = !g_bootstrap.given && !g_bootstrap.out_given ? "--bootstrap_tbe and --bootstrap_trees need --bootstrap and --bootstrap_out"
+                              : g_bootstrap.given != g_bootstrap.out_given ? "--bootstrap and --bootstrap_out need each other"
                               : (g_bootstrap.n < 1 || g_bootstrap.n > 1000) ? "--bootstrap takes a number of replicates from 1 to 1000"
                               : cmdlineopts.wlsrefine_flag ? "--bootstrap cannot be combined with -W"
                               : cmdlineopts.reroot_flag ? "--bootstrap cannot be combined with -r"

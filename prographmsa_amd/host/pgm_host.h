@@ -258,6 +258,8 @@ struct HostSwitches {
     bool device_mldist = false;  // PGM_DEVICE_MLDIST: ML distances by pgm_mldist_batch (last-bit differences to the host's estimator)
     bool device_bionj = false;   // PGM_DEVICE_BIONJ: the joins of every guide tree of 4 taxa and more by pgm_bionj_multi (same bits)
     bool host_bionj = false;     // PGM_HOST_BIONJ: the joins of every guide tree by the host loop
+    bool host_transfer = false;    // PGM_HOST_TRANSFER: the transfer indices of --bootstrap_tbe by the host loop (same integers)
+    bool device_transfer = false;  // PGM_DEVICE_TRANSFER: ... by pgm_transfer_min at every size
     std::string describe() const;   // the switches that are on, comma separated ("" = the product's defaults)
 };
 const HostSwitches &host_switches();
@@ -323,6 +325,10 @@ struct Backend {
     // The residue-pair agreement counts of --guidance (include/pgm_hip.h: pgm_msa_agreement): where is nrep x nrows x ncols, res_hits
     // nrows x ncols and pair_hits nrows x nrows are overwritten.  The default is the host statement, msa_agreement_host.
     virtual void msa_agreement(uint32_t nrows, uint32_t ncols, uint32_t nrep, const int32_t *where, uint32_t *res_hits, uint32_t *pair_hits, int worker = 0);
+    // The transfer indices of --bootstrap_tbe (include/pgm_hip.h: pgm_transfer_min): phi[e * nrep + r] of reference set e against the
+    // sets of replicate r, overwritten.  The default is the host statement, transfer_min_host.
+    virtual void transfer_min(uint32_t nleaves, uint32_t nref, const uint64_t *ref, uint32_t nrep, const uint32_t *rep_off, const uint64_t *rep, uint32_t *phi,
+                              int worker = 0);
     // calls the host code made of the align-batch entry and of the distance entries (all-pairs tiles, pair counts, cosine, ML
     // distances): `pgmsa --batch --stats` shows with them that a stage was shared by the families of a chunk
     std::atomic<uint64_t> calls_align{0}, calls_dist{0};
@@ -430,8 +436,9 @@ public:
     std::string formatNewick() const;
     // the same text with labels[node] printed between ')' and ':' for every internal node that has one (--bootstrap_out)
     std::string formatNewick(const std::map<const PhyTree *, uint32_t> &labels) const;
+    std::string formatNewick(const std::map<const PhyTree *, std::string> &labels) const;   // (--bootstrap_tbe: labels as text)
 private:
-    std::string formatNewickR(const std::map<const PhyTree *, uint32_t> *labels) const;
+    std::string formatNewickR(const std::map<const PhyTree *, std::string> *labels) const;
     std::string formatNewickR() const;
     std::vector<PhyTree *> children_;
     PhyTree *parent_;
@@ -445,6 +452,14 @@ PhyTree *midpointRoot(PhyTree *root);                      // PhyTree.cpp:60-116
 // cuts off a single leaf (a trivial bipartition: every tree has it) gets no entry.  Every replicate must have the leaves of `tree`;
 // where it is rooted, and how many children its root has, does not matter.
 std::map<const PhyTree *, uint32_t> bipartition_support(const PhyTree &tree, const std::vector<const PhyTree *> &replicates);
+// The walk both support measures share: the leaves of `tree` numbered in sorted-name order, and the non-trivial bipartitions of a
+// tree over those leaves in post-order, (node below the edge, canonical side as (nleaves + 63) / 64 little-endian words).
+struct LeafNumbering {
+    std::map<std::string, size_t> index;
+    size_t nleaves = 0, words = 0;
+};
+LeafNumbering leaf_numbering(const PhyTree &tree);
+std::vector<std::pair<const PhyTree *, std::vector<uint64_t>>> bipartitions_of(const LeafNumbering &num, const PhyTree &t);
 std::vector<std::string> get_tree_order(const PhyTree *tree);  // PhyTree.cpp:164-182
 PhyTree *parse_newick(std::istream &in);                   // newick.cpp:127-147
 
@@ -649,6 +664,28 @@ void msa_agreement_host(uint32_t nrows, uint32_t ncols, uint32_t nrep, const int
 uint32_t guidance_call_replicates(uint32_t nrows, uint32_t ncols, size_t where_bytes = kGuidanceWhereBytes);
 std::string format_newick_exact(const PhyTree &tree);
 void guidance_write(const GuidanceCounts &g, const std::vector<std::string> &names, const int32_t *where0, uint64_t seed, std::ostream &out, std::ostream *residues);
+
+// --bootstrap_tbe: the transfer bootstrap expectation (Lemoine et al. 2018) of every internal edge (host/transfer.inc).
+// transfer_min_host: pgm_transfer_min (include/pgm_hip.h) by plain loops on the host threads, the same contract; what it rejects is
+//   an error().  Backend::transfer_min's default.
+// transfer_call_replicates: the most replicates of at most max_sets sets each that one call takes for `rep` to stay within
+//   rep_bytes and nref * nrep within 32 bits, at least 1.
+// transfer_support: per labelled node of `tree` (the nodes bipartition_support labels) S = the sum of its transfer indices over
+//   the replicates and p = the smaller side of its bipartition.  be: the backend whose transfer_min runs, nullptr for the host loop.
+// transfer_labels: "%.6f" of 1.0 - (double)S / ((double)nrep * (double)(p - 1)) per node.
+const size_t kTransferRepBytes = (size_t)1 << 30;   // `rep` of one transfer_min call
+// families of this many taxa and more go to the device by default (the smallest measured size at which it is faster)
+const uint32_t kTransferDeviceMin = 256;
+struct TransferStats {   // `pgmsa --bootstrap_tbe --stats`
+    double seconds = 0, kernel_ms = 0;
+    uint64_t calls = 0;
+};
+extern TransferStats transfer_stats;
+struct TransferEdge { uint64_t S = 0; uint32_t p = 0; };
+void transfer_min_host(uint32_t nleaves, uint32_t nref, const uint64_t *ref, uint32_t nrep, const uint32_t *rep_off, const uint64_t *rep, uint32_t *phi);
+uint32_t transfer_call_replicates(uint32_t nleaves, uint32_t nref, size_t max_sets, size_t rep_bytes = kTransferRepBytes);
+std::map<const PhyTree *, TransferEdge> transfer_support(const PhyTree &tree, const std::vector<const PhyTree *> &replicates, Backend *be = nullptr);
+std::map<const PhyTree *, std::string> transfer_labels(const std::map<const PhyTree *, TransferEdge> &support, uint32_t nrep);
 
 std::string data_dir();   // directory holding wag.qmat etc.
 

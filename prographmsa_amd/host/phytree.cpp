@@ -54,7 +54,7 @@ PhyTree *PhyTree::pluckChild(index_t index) {  // PhyTree.h:125-135
     return child;
 }
 
-std::string PhyTree::formatNewickR(const std::map<const PhyTree *, uint32_t> *labels) const {  // PhyTree.h:41-55 (default ostream precision: 6 s.f.)
+std::string PhyTree::formatNewickR(const std::map<const PhyTree *, std::string> *labels) const {  // PhyTree.h:41-55 (default ostream precision: 6 s.f.)
     if (isLeaf()) return name_;
     std::stringstream ss;
     ss << "(";
@@ -72,7 +72,12 @@ std::string PhyTree::formatNewickR(const std::map<const PhyTree *, uint32_t> *la
 }
 std::string PhyTree::formatNewickR() const { return formatNewickR(nullptr); }
 std::string PhyTree::formatNewick() const { return formatNewickR() + ";"; }
-std::string PhyTree::formatNewick(const std::map<const PhyTree *, uint32_t> &labels) const { return formatNewickR(&labels) + ";"; }
+std::string PhyTree::formatNewick(const std::map<const PhyTree *, std::string> &labels) const { return formatNewickR(&labels) + ";"; }
+std::string PhyTree::formatNewick(const std::map<const PhyTree *, uint32_t> &labels) const {   // (the decimal digits a stream prints)
+    std::map<const PhyTree *, std::string> text;
+    for (const auto &kv : labels) text[kv.first] = std::to_string(kv.second);
+    return formatNewick(text);
+}
 
 // ---- bootstrap support ------------------------------------------------------------------------------------------------
 namespace {
@@ -118,27 +123,34 @@ struct Bipartitions {
 };
 }  // namespace
 
-std::map<const PhyTree *, uint32_t> bipartition_support(const PhyTree &tree, const std::vector<const PhyTree *> &replicates) {
+LeafNumbering leaf_numbering(const PhyTree &tree) {
     std::vector<std::string> names;
     collect_leaves(tree, names);
     std::sort(names.begin(), names.end());
-    std::map<std::string, size_t> index;
+    LeafNumbering num;
     for (size_t k = 0; k < names.size(); ++k)
-        if (!index.emplace(names[k], k).second) error("bootstrap support: leaf \"%s\" twice", names[k].c_str());
-    const size_t n = names.size(), words = (n + 63) / 64;
-    auto bipartitions_of = [&](const PhyTree &t) {
-        Bipartitions b{index, n, words, {}};
-        const LeafSet all = b.below(t, true);
-        size_t size = 0;
-        for (uint64_t w : all) size += (size_t)__builtin_popcountll(w);
-        if (size != n) error("bootstrap support: a replicate has %zu of the tree's %zu leaves", size, n);
-        return std::move(b.out);
-    };
-    const std::vector<std::pair<const PhyTree *, LeafSet>> edges = bipartitions_of(tree);
+        if (!num.index.emplace(names[k], k).second) error("bootstrap support: leaf \"%s\" twice", names[k].c_str());
+    num.nleaves = names.size();
+    num.words = (names.size() + 63) / 64;
+    return num;
+}
+
+std::vector<std::pair<const PhyTree *, std::vector<uint64_t>>> bipartitions_of(const LeafNumbering &num, const PhyTree &t) {
+    Bipartitions b{num.index, num.nleaves, num.words, {}};
+    const LeafSet all = b.below(t, true);
+    size_t size = 0;
+    for (uint64_t w : all) size += (size_t)__builtin_popcountll(w);
+    if (size != num.nleaves) error("bootstrap support: a replicate has %zu of the tree's %zu leaves", size, num.nleaves);
+    return std::move(b.out);
+}
+
+std::map<const PhyTree *, uint32_t> bipartition_support(const PhyTree &tree, const std::vector<const PhyTree *> &replicates) {
+    const LeafNumbering num = leaf_numbering(tree);
+    const std::vector<std::pair<const PhyTree *, LeafSet>> edges = bipartitions_of(num, tree);
     std::map<LeafSet, uint32_t> count;
     for (const auto &e : edges) count[e.second] = 0;
     for (const PhyTree *rep : replicates) {
-        std::vector<std::pair<const PhyTree *, LeafSet>> theirs = bipartitions_of(*rep);
+        std::vector<std::pair<const PhyTree *, LeafSet>> theirs = bipartitions_of(num, *rep);
         // (the two edges below a bifurcating root are one bipartition: a replicate counts once)
         std::sort(theirs.begin(), theirs.end(), [](const std::pair<const PhyTree *, LeafSet> &x, const std::pair<const PhyTree *, LeafSet> &y) { return x.second < y.second; });
         for (size_t k = 0; k < theirs.size(); ++k) {

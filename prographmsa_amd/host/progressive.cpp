@@ -1310,4 +1310,7 @@ ProgressiveAlignmentResult progressive_alignment_find_root(const Alphabet &a, co
 // ==== --guidance: residue map, agreement counts on the host, score files ===============================================
 #include "guidance.inc"
 
+// ==== --bootstrap_tbe: transfer indices on the host, the support of every edge ========================================
+#include "transfer.inc"
+
 }  // namespace pgm
