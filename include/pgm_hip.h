@@ -457,7 +457,23 @@ float pgm_agreement_last_kernel_ms(pgm_ctx *ctx);   /* device time of the two ke
 int pgm_transfer_min(pgm_ctx *ctx, uint32_t nleaves, uint32_t nref, const uint64_t *ref /* nref x words */,
                      uint32_t nrep, const uint32_t *rep_off /* nrep + 1, ascending, rep_off[0] == 0 */,
                      const uint64_t *rep /* rep_off[nrep] x words */, uint32_t *phi /* nref x nrep, overwritten */);
-float pgm_transfer_last_kernel_ms(pgm_ctx *ctx);   /* device time of the kernel of the last call */
+float pgm_transfer_last_kernel_ms(pgm_ctx *ctx);   /* device time of the kernel(s) of the last pgm_transfer_min / pgm_transfer_taxa call */
+
+/* ---- which taxa the transfer indices move (pgmsa --bootstrap_taxa: the taxon side of the transfer bootstrap).  Sets, p, h and
+ * phi as for pgm_transfer_min.  The moved set T(A, B) is A xor B if h <= nleaves - h and else its complement within the nleaves
+ * leaves: the leaves on the wrong side, |T| = d(A, B).
+ *   arg[e * nrep + r]   = the lowest s in rep_off[r] <= s < rep_off[r + 1] with d(A_e, B_s) == phi[e * nrep + r], or
+ *                         PGM_TRANSFER_NONE when no set of the replicate is that near (only the clamp p - 1 gave phi);
+ *   (e, r) is counted   iff arg != PGM_TRANSFER_NONE and phi[e * nrep + r] <= thr[e];
+ *   moved[e * nleaves + t] = the number of counted r whose T(A_e, B_arg) holds leaf t;  counted[e] = the number of counted r.
+ * All four outputs are overwritten; all values are integers, so the result does not depend on the launch.
+ * PGM_ERR_INVALID, before anything is launched or an output is touched: what pgm_transfer_min refuses, a null thr or output,
+ * nleaves beyond 2^31 - 1, nref * nleaves beyond 32 bits.  thr is otherwise free (0xffffffff counts every pair with a set). */
+#define PGM_TRANSFER_NONE 0xffffffffu
+int pgm_transfer_taxa(pgm_ctx *ctx, uint32_t nleaves, uint32_t nref, const uint64_t *ref /* nref x words */, const uint32_t *thr /* nref */,
+                      uint32_t nrep, const uint32_t *rep_off /* nrep + 1 */, const uint64_t *rep /* rep_off[nrep] x words */,
+                      uint32_t *phi /* nref x nrep */, uint32_t *arg /* nref x nrep */, uint32_t *moved /* nref x nleaves */,
+                      uint32_t *counted /* nref */);
 
 #ifdef __cplusplus
 }

@@ -92,7 +92,7 @@ EXPORTS = [
     "pgm_bionj", "pgm_bionj_multi", "pgm_bionj_last_launches", "pgm_bionj_last_kernel_ms",
     "pgm_bionj_plan", "pgm_bionj_plan_multi",
     "pgm_msa_agreement", "pgm_agreement_last_kernel_ms",
-    "pgm_transfer_min", "pgm_transfer_last_kernel_ms",
+    "pgm_transfer_min", "pgm_transfer_last_kernel_ms", "pgm_transfer_taxa",
 ]
 
 
@@ -172,6 +172,8 @@ def _load():
         "pgm_agreement_last_kernel_ms": (C.c_float, [vp]),
         "pgm_transfer_min": (C.c_int, [vp, u32, u32, C.POINTER(C.c_uint64), u32, C.POINTER(u32), C.POINTER(C.c_uint64), C.POINTER(u32)]),
         "pgm_transfer_last_kernel_ms": (C.c_float, [vp]),
+        "pgm_transfer_taxa": (C.c_int, [vp, u32, u32, C.POINTER(C.c_uint64), C.POINTER(u32), u32, C.POINTER(u32), C.POINTER(C.c_uint64),
+                                        C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = the library does not export a declared symbol
@@ -252,6 +254,27 @@ class Context:
         check(lib.pgm_transfer_min(self.handle, nleaves, nref, P(ref, C.c_uint64), nrep, P(rep_off, C.c_uint32), P(rep, C.c_uint64) if rep.size else None,
                                    P(phi, C.c_uint32)), "pgm_transfer_min")
         return phi
+
+    def transfer_taxa(self, nleaves, ref, thr, rep_off, rep, out=None):
+        """pgm_transfer_taxa: inputs as transfer_min plus thr (nref uint32) -> (phi, arg (nref x nrep), moved (nref x nleaves),
+        counted (nref)), all uint32.  Given output arrays (a tuple of four, C-contiguous uint32 of those shapes) are overwritten."""
+        import numpy as np
+        words = (nleaves + 63) // 64
+        ref = np.ascontiguousarray(ref, np.uint64)
+        thr = np.ascontiguousarray(thr, np.uint32)
+        rep_off = np.ascontiguousarray(rep_off, np.uint32)
+        rep = np.ascontiguousarray(rep, np.uint64).reshape(-1, words)
+        if ref.ndim != 2 or ref.shape[1] != words or thr.shape != (ref.shape[0],) or rep_off.ndim != 1 or len(rep_off) < 1 or rep.shape[0] != int(rep_off[-1]):
+            raise ValueError("transfer_taxa: input array of the wrong shape")
+        nref, nrep = ref.shape[0], len(rep_off) - 1
+        shapes = [(nref, nrep), (nref, nrep), (nref, nleaves), (nref,)]
+        if out is None: out = tuple(np.zeros(s, np.uint32) for s in shapes)
+        if len(out) != 4 or any(a.dtype != np.uint32 or a.shape != s or not a.flags.c_contiguous for a, s in zip(out, shapes)):
+            raise ValueError("transfer_taxa: output array of the wrong kind")
+        P = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+        check(lib.pgm_transfer_taxa(self.handle, nleaves, nref, P(ref, C.c_uint64), P(thr, C.c_uint32), nrep, P(rep_off, C.c_uint32),
+                                    P(rep, C.c_uint64) if rep.size else None, *[P(a, C.c_uint32) for a in out]), "pgm_transfer_taxa")
+        return tuple(out)
 
     def close(self):
         if self.handle:

@@ -68,7 +68,7 @@ struct pgm_ctx {
     uint32_t wls_n = 0, wls_launches = 0;   // the WLS refinement: size of the loaded matrices (0 = none), kernels of the last call
     float bionj_ms = 0;
     float agree_ms = 0;                     // --guidance agreement counts: device time of the last call
-    float transfer_ms = 0;                  // --bootstrap_tbe transfer indices: device time of the last call
+    float transfer_ms = 0;                  // --bootstrap_tbe / --bootstrap_taxa transfer entries: device time of the last call
     uint32_t bionj_launches = 0;            // BioNJ: device time and kernels of the last call
     // grow-only scratch buffers of the all-pairs / context-profile calls (slot = position in the call's buffer list): a
     // guide-tree stage issues many calls (one per pair tile), hipMalloc / hipFree of up to 2 GB per call would dominate them
@@ -949,3 +949,4 @@ int pgm_align_batch_read_matrices(pgm_ctx *ctx, pgm_align_batch *b, uint32_t job
 #include "pgm_bionj_capi.inc"
 #include "pgm_agreement_capi.inc"
 #include "pgm_transfer_capi.inc"
+#include "pgm_transfer_taxa_capi.inc"

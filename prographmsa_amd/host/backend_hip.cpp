@@ -138,6 +138,13 @@ struct HipBackend : Backend {
         if (rc != PGM_OK) error("pgm_transfer_min failed (%d): %s", rc, pgm_last_error());
         transfer_stats.kernel_ms += pgm_transfer_last_kernel_ms(c);
     }
+    void transfer_taxa(uint32_t nleaves, uint32_t nref, const uint64_t *ref, const uint32_t *thr, uint32_t nrep, const uint32_t *rep_off, const uint64_t *rep,
+                       uint32_t *phi, uint32_t *arg, uint32_t *moved, uint32_t *counted, int worker) override {
+        pgm_ctx *c = ctx_of(worker);
+        int rc = pgm_transfer_taxa(c, nleaves, nref, ref, thr, nrep, rep_off, rep, phi, arg, moved, counted);
+        if (rc != PGM_OK) error("pgm_transfer_taxa failed (%d): %s", rc, pgm_last_error());
+        taxa_stats.kernel_ms += pgm_transfer_last_kernel_ms(c);
+    }
     bool bionj_multi(uint32_t nfam, const uint32_t *n, const double *D, const double *V, pgm_bionj_join *joins, double *final_d, int worker) override {
         pgm_ctx *c = ctx_of(worker);
         int rc = pgm_bionj_multi(c, nfam, n, D, V, joins, final_d);

@@ -24,7 +24,8 @@ static void usage() {
                  "             [-s prob] [-A] [--early_refinement] [--ancestral_seqs] [--profile_out <file>] [-R] [--read_repeats <file>]\n"
                  "             [-r|--reroot [-r]] [-W|--wls_refine [-W]] [--dna] [--custom_model <file>] [-F|--estimate_aafreqs]\n"
                  "             [-C|--aafreqs_pseudocount <count>] [--dump_jobs <file>] [--dump_dist <file>] [--dump_joins <file>] [--stats]\n"
-                 "             [--bootstrap <N> --bootstrap_out <file> [--bootstrap_seed <S>] [--bootstrap_tbe <file>] [--bootstrap_trees <file>]]\n"
+                 "             [--bootstrap <N> --bootstrap_out <file> [--bootstrap_seed <S>] [--bootstrap_tbe <file>] [--bootstrap_trees <file>]\n"
+                 "              [--bootstrap_taxa <file> [--bootstrap_taxa_cutoff <X>] [--bootstrap_taxa_edges <file>]]]\n"
                  "             [--guidance <N> --guidance_out <file> [--guidance_seed <S>] [--guidance_residues <file>] [--guidance_dump <prefix>]]\n"
                  "             <fasta file>\n"
                  "       pgmsa --batch <list> [--batch_cells <cells>] [options]\n"
@@ -63,6 +64,12 @@ static void usage() {
                  "                every internal edge as node labels (%.6f): 1 - the mean over the replicates of the fewest leaves to move for the\n"
                  "                replicate to have the edge, over the size of the edge's smaller side - 1\n"
                  "  --bootstrap_trees <file>  with --bootstrap: the N replicate trees, one newick line each, in replicate order\n"
+                 "  --bootstrap_taxa <file>  with --bootstrap: per sequence how often it is among the fewest leaves to move for a replicate to\n"
+                 "                have an edge (the taxon side of the transfer bootstrap: unstable, \"rogue\" sequences score high).  Counted are\n"
+                 "                the (edge, replicate) pairs whose transfer index is at most X times the size of the edge's smaller side - 1,\n"
+                 "                --bootstrap_taxa_cutoff <X> (0 <= X < 1, default 0.3); among equally near replicate edges the first in sorted\n"
+                 "                order is taken.  One line per sequence in sorted-name order: name, times moved, that over the counted pairs.\n"
+                 "                --bootstrap_taxa_edges <file>: the same counts per labelled node of the --bootstrap_out tree\n"
                  "  --guidance <N>  confidence of the alignment under perturbed guide trees (1 <= N <= 1000): the BioNJ trees of N resamplings of\n"
                  "                the final alignment's columns (those of --bootstrap for the same N and seed), midpoint rooted, are each used as\n"
                  "                the guide tree of a realignment, and every residue pair, column and sequence of the alignment written is scored\n"
@@ -194,8 +201,12 @@ struct BootstrapOpts {   // --bootstrap N --bootstrap_out FILE --bootstrap_seed 
     bool given = false, out_given = false;
     long long n = 0;
     std::string out, tbe, trees;   // --bootstrap_tbe FILE, --bootstrap_trees FILE
+    std::string taxa, taxa_edges, cutoff_text;   // --bootstrap_taxa FILE, --bootstrap_taxa_edges FILE, --bootstrap_taxa_cutoff X
+    bool cutoff_given = false;
+    double cutoff = 0.3;
     uint64_t seed = 1;
-    bool any() const { return given || out_given || !tbe.empty() || !trees.empty(); }
+    bool any_taxa() const { return !taxa.empty() || !taxa_edges.empty() || cutoff_given; }
+    bool any() const { return given || out_given || !tbe.empty() || !trees.empty() || any_taxa(); }
 } g_bootstrap;
 
 struct GuidanceOpts {   // --guidance N --guidance_out FILE --guidance_seed S --guidance_residues FILE --guidance_dump PREFIX
@@ -213,7 +224,8 @@ static void doGuidance(const Alphabet &a, const Family &fam, const CSProfile *cs
 // iterations: main.cpp:404-430, DistanceFactoryPrealigned.h:34-90, TreeNJ.h:27-59), the support of its internal edges among the
 // trees of N column resamplings, and the file: formatNewick()'s text with the counts as node labels.  --bootstrap_tbe: the same
 // text with the transfer bootstrap expectation of every labelled node (transfer_support; the device from kTransferDeviceMin taxa
-// or with PGM_DEVICE_TRANSFER, the host loop with PGM_HOST_TRANSFER); --bootstrap_trees: formatNewick() of every replicate's tree
+// or with PGM_DEVICE_TRANSFER, the host loop with PGM_HOST_TRANSFER); --bootstrap_trees: formatNewick() of every replicate's tree;
+// --bootstrap_taxa / --bootstrap_taxa_edges: taxa_support by the same route, taxa_text and taxa_edges_text
 static void doBootstrap(const Alphabet &a, const Family &fam, const std::map<std::string, sequence_t> &alignment) {
     const auto t0 = std::chrono::steady_clock::now();
     std::map<std::string, sequence_t> rows;
@@ -221,14 +233,18 @@ static void doBootstrap(const Alphabet &a, const Family &fam, const std::map<std
         if (kv.first.empty() || kv.first[0] != '(') rows.insert(kv);   // (ancestral sequences dropped)
     std::unique_ptr<PhyTree> tree(TreeNJ(a, rows, fam.model_factory.get(), true));
     std::vector<PhyTree *> reps = bootstrap_trees(a, rows, fam.model_factory.get(), (uint32_t)g_bootstrap.n, g_bootstrap.seed);
-    std::string text, tbe_text, trees_text;
+    std::string text, tbe_text, trees_text, taxa_file_text, taxa_edges_file_text;
     try {
         const std::vector<const PhyTree *> replicates(reps.begin(), reps.end());
         text = tree->formatNewick(bipartition_support(*tree, replicates));
-        if (!g_bootstrap.tbe.empty()) {
-            const HostSwitches &sw = host_switches();
-            const bool device = !sw.host_transfer && (sw.device_transfer || rows.size() >= kTransferDeviceMin);
+        const HostSwitches &sw = host_switches();
+        const bool device = !sw.host_transfer && (sw.device_transfer || rows.size() >= kTransferDeviceMin);
+        if (!g_bootstrap.tbe.empty())
             tbe_text = tree->formatNewick(transfer_labels(transfer_support(*tree, replicates, device ? &default_backend() : nullptr), (uint32_t)replicates.size()));
+        if (!g_bootstrap.taxa.empty()) {
+            const TaxaSupport taxa = taxa_support(*tree, replicates, g_bootstrap.cutoff, device ? &default_backend() : nullptr);
+            taxa_file_text = taxa_text(taxa, g_bootstrap.cutoff);
+            if (!g_bootstrap.taxa_edges.empty()) taxa_edges_file_text = taxa_edges_text(taxa);
         }
         if (!g_bootstrap.trees.empty())
             for (const PhyTree *t : replicates) trees_text += t->formatNewick() + "\n";
@@ -249,6 +265,16 @@ static void doBootstrap(const Alphabet &a, const Family &fam, const std::map<std
         std::ofstream trees(g_bootstrap.trees.c_str());
         if (!trees) error("error opening the bootstrap output file %s", g_bootstrap.trees.c_str());
         trees << trees_text << std::flush;
+    }
+    if (!g_bootstrap.taxa.empty()) {
+        std::ofstream taxa(g_bootstrap.taxa.c_str());
+        if (!taxa) error("error opening the bootstrap output file %s", g_bootstrap.taxa.c_str());
+        taxa << taxa_file_text << std::flush;
+    }
+    if (!g_bootstrap.taxa_edges.empty()) {
+        std::ofstream edges(g_bootstrap.taxa_edges.c_str());
+        if (!edges) error("error opening the bootstrap output file %s", g_bootstrap.taxa_edges.c_str());
+        edges << taxa_edges_file_text << std::flush;
     }
     bootstrap_stats.seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
@@ -282,6 +308,9 @@ static void print_stats(double t_init, double t_tree, double t_prog, const Batch
     if (!g_bootstrap.tbe.empty())   // (keys of --bootstrap_tbe only)
         fprintf(stderr, ", \"bootstrap_tbe_s\": %.6f, \"bootstrap_transfer_calls\": %llu, \"bootstrap_transfer_kernel_ms\": %.3f", transfer_stats.seconds,
                 (unsigned long long)transfer_stats.calls, transfer_stats.kernel_ms);
+    if (!g_bootstrap.taxa.empty())   // (keys of --bootstrap_taxa only)
+        fprintf(stderr, ", \"bootstrap_taxa_s\": %.6f, \"bootstrap_taxa_calls\": %llu, \"bootstrap_taxa_kernel_ms\": %.3f", taxa_stats.seconds,
+                (unsigned long long)taxa_stats.calls, taxa_stats.kernel_ms);
     if (g_guidance.given)   // (keys of --guidance only)
         fprintf(stderr, ", \"guidance_replicates\": %d, \"guidance_s\": %.6f, \"guidance_align_s\": %.6f, \"guidance_agreement_s\": %.6f, "
                         "\"guidance_passes\": %llu, \"guidance_agreement_calls\": %llu",
@@ -727,6 +756,9 @@ int main(int argc, char **argv) {
             else if (s == "--bootstrap_seed") g_bootstrap.seed = strtoull(val().c_str(), nullptr, 10);
             else if (s == "--bootstrap_tbe") g_bootstrap.tbe = val();
             else if (s == "--bootstrap_trees") g_bootstrap.trees = val();
+            else if (s == "--bootstrap_taxa") g_bootstrap.taxa = val();
+            else if (s == "--bootstrap_taxa_edges") g_bootstrap.taxa_edges = val();
+            else if (s == "--bootstrap_taxa_cutoff") { g_bootstrap.cutoff_given = true; g_bootstrap.cutoff_text = val(); g_bootstrap.cutoff = atof(g_bootstrap.cutoff_text.c_str()); }
             else if (s == "--guidance") { g_guidance.given = true; g_guidance.n = atoll(val().c_str()); }
             else if (s == "--guidance_out") { g_guidance.out_given = true; g_guidance.out = val(); }
             else if (s == "--guidance_seed") g_guidance.seed = strtoull(val().c_str(), nullptr, 10);
@@ -754,9 +786,17 @@ int main(int argc, char **argv) {
         }
         if (cmdlineopts.sequence_file.empty() && batch_list.empty()) { usage(); return 1; }
         if (g_bootstrap.any()) {
-            const char *why = !g_bootstrap.given && !g_bootstrap.out_given ? "--bootstrap_tbe and --bootstrap_trees need --bootstrap and --bootstrap_out"
+            // (the cutoff is a number in [0, 1): text that is no number, a NaN and everything outside are refused)
+            char *cutoff_end = nullptr;
+            if (g_bootstrap.cutoff_given) (void)strtod(g_bootstrap.cutoff_text.c_str(), &cutoff_end);
+            const bool cutoff_ok = !g_bootstrap.cutoff_given || (!g_bootstrap.cutoff_text.empty() && *cutoff_end == '\0' && g_bootstrap.cutoff >= 0.0 && g_bootstrap.cutoff < 1.0);
+            const char *why = !g_bootstrap.given && !g_bootstrap.out_given
+                                  ? (g_bootstrap.any_taxa() ? "--bootstrap_taxa, --bootstrap_taxa_cutoff and --bootstrap_taxa_edges need --bootstrap and --bootstrap_out"
+                                                            : "--bootstrap_tbe and --bootstrap_trees need --bootstrap and --bootstrap_out")
                               : g_bootstrap.given != g_bootstrap.out_given ? "--bootstrap and --bootstrap_out need each other"
                               : (g_bootstrap.n < 1 || g_bootstrap.n > 1000) ? "--bootstrap takes a number of replicates from 1 to 1000"
+                              : (g_bootstrap.any_taxa() && g_bootstrap.taxa.empty()) ? "--bootstrap_taxa_cutoff and --bootstrap_taxa_edges need --bootstrap_taxa"
+                              : !cutoff_ok ? "--bootstrap_taxa_cutoff takes a number X with 0 <= X < 1"
                               : cmdlineopts.wlsrefine_flag ? "--bootstrap cannot be combined with -W"
                               : cmdlineopts.reroot_flag ? "--bootstrap cannot be combined with -r"
                               : !topo_file.empty() ? "--bootstrap cannot be combined with --topology" : nullptr;

@@ -258,8 +258,8 @@ struct HostSwitches {
     bool device_mldist = false;  // PGM_DEVICE_MLDIST: ML distances by pgm_mldist_batch (last-bit differences to the host's estimator)
     bool device_bionj = false;   // PGM_DEVICE_BIONJ: the joins of every guide tree of 4 taxa and more by pgm_bionj_multi (same bits)
     bool host_bionj = false;     // PGM_HOST_BIONJ: the joins of every guide tree by the host loop
-    bool host_transfer = false;    // PGM_HOST_TRANSFER: the transfer indices of --bootstrap_tbe by the host loop (same integers)
-    bool device_transfer = false;  // PGM_DEVICE_TRANSFER: ... by pgm_transfer_min at every size
+    bool host_transfer = false;    // PGM_HOST_TRANSFER: the transfer indices of --bootstrap_tbe and the counts of --bootstrap_taxa by the host loop (same integers)
+    bool device_transfer = false;  // PGM_DEVICE_TRANSFER: ... by pgm_transfer_min / pgm_transfer_taxa at every size
     std::string describe() const;   // the switches that are on, comma separated ("" = the product's defaults)
 };
 const HostSwitches &host_switches();
@@ -329,6 +329,10 @@ struct Backend {
     // sets of replicate r, overwritten.  The default is the host statement, transfer_min_host.
     virtual void transfer_min(uint32_t nleaves, uint32_t nref, const uint64_t *ref, uint32_t nrep, const uint32_t *rep_off, const uint64_t *rep, uint32_t *phi,
                               int worker = 0);
+    // The moved-taxon counts of --bootstrap_taxa (include/pgm_hip.h: pgm_transfer_taxa): phi, arg (nref x nrep), moved (nref x nleaves)
+    // and counted (nref), overwritten.  The default is the host statement, transfer_taxa_host.
+    virtual void transfer_taxa(uint32_t nleaves, uint32_t nref, const uint64_t *ref, const uint32_t *thr, uint32_t nrep, const uint32_t *rep_off,
+                               const uint64_t *rep, uint32_t *phi, uint32_t *arg, uint32_t *moved, uint32_t *counted, int worker = 0);
     // calls the host code made of the align-batch entry and of the distance entries (all-pairs tiles, pair counts, cosine, ML
     // distances): `pgmsa --batch --stats` shows with them that a stage was shared by the families of a chunk
     std::atomic<uint64_t> calls_align{0}, calls_dist{0};
@@ -686,6 +690,29 @@ void transfer_min_host(uint32_t nleaves, uint32_t nref, const uint64_t *ref, uin
 uint32_t transfer_call_replicates(uint32_t nleaves, uint32_t nref, size_t max_sets, size_t rep_bytes = kTransferRepBytes);
 std::map<const PhyTree *, TransferEdge> transfer_support(const PhyTree &tree, const std::vector<const PhyTree *> &replicates, Backend *be = nullptr);
 std::map<const PhyTree *, std::string> transfer_labels(const std::map<const PhyTree *, TransferEdge> &support, uint32_t nrep);
+
+// --bootstrap_taxa: the taxon side of the transfer bootstrap, which leaves the transfer indices move (host/transfer.inc).
+// transfer_taxa_host: pgm_transfer_taxa (include/pgm_hip.h) by plain loops on the host threads, the same contract; what it rejects
+//   is an error().  Backend::transfer_taxa's default.
+// taxa_support: the replicates' sets sorted (as vectors of words) and equal ones dropped, the reference edges that share a
+//   bipartition as one row, thr = floor(cutoff * (p - 1)), the replicates in calls of transfer_call_replicates, sums in 64 bits.
+//   be: the backend whose transfer_taxa runs, nullptr for the host loop.
+// taxa_text, taxa_edges_text: the files of --bootstrap_taxa and --bootstrap_taxa_edges.
+const uint32_t kTransferNone = 0xffffffffu;   // PGM_TRANSFER_NONE
+extern TransferStats taxa_stats;              // `pgmsa --bootstrap_taxa --stats`
+struct TaxaEdge { uint32_t p = 0; uint64_t counted = 0; std::vector<uint64_t> moved; };   // moved: per leaf
+struct TaxaSupport {
+    std::vector<std::string> names;   // the leaves in sorted-name order
+    std::vector<uint64_t> moved;      // per leaf, summed over the distinct bipartitions
+    uint64_t counted = 0;             // K: the counted (edge, replicate) pairs of the distinct bipartitions
+    size_t edges = 0, replicates = 0; // E: the distinct non-trivial bipartitions of the tree; N
+    std::vector<TaxaEdge> nodes;      // per labelled node, in the order of the labels in formatNewick's text
+};
+void transfer_taxa_host(uint32_t nleaves, uint32_t nref, const uint64_t *ref, const uint32_t *thr, uint32_t nrep, const uint32_t *rep_off, const uint64_t *rep,
+                        uint32_t *phi, uint32_t *arg, uint32_t *moved, uint32_t *counted);
+TaxaSupport taxa_support(const PhyTree &tree, const std::vector<const PhyTree *> &replicates, double cutoff, Backend *be = nullptr);
+std::string taxa_text(const TaxaSupport &t, double cutoff);
+std::string taxa_edges_text(const TaxaSupport &t);
 
 std::string data_dir();   // directory holding wag.qmat etc.
 
