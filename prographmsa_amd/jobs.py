@@ -243,10 +243,111 @@ def sequence_job(seed, L1, L2, dim=20, unknown_frac=0.05):
     return job
 
 
-def random_job(seed, n1, n2, dim=20, **kw):
+def _stored(cost):
+    """the stored value of a regular edge of that cost (random_graph: cost - 10000; a stored 0 is an edge of infinite cost)"""
+    return np.float32(np.float32(cost) - np.float32(1e4))
+
+
+def edit_graph(g, rng, kill_frac=0.0, kill_at=(), kill_band_edges=False, inf_frac=0.0, inf_chain_frac=0.0, dup_frac=0.0, dup_span=12,
+               hub_frac=0.0, hub_k=(13, 16), hub_span=16, hubs=(), broken_chain=()):
+    """A post-pass over a graph of random_graph for the edges it never draws (every option off: nothing changes, nothing is drawn):
+      hubs      [first, last, k, dlo, dhi]: every node first..last gets k more regular edges of finite cost, their distances cycling
+                through dlo..dhi (k > dhi - dlo + 1: several edges from one predecessor)
+      hub_frac  that share of the nodes gets hub_k[0]..hub_k[1] distinct predecessors within hub_span nodes
+      dup_frac  that share of the nodes gets a repeat edge from the node of one of its regular edges, at distance 1, 2, 3 and farther
+                (up to dup_span) in turn; the regular edge is added where the node has none from there
+      inf_frac  that share of the edges not from node - 1 gets infinite cost (a stored value of 0, 0 repeat units)
+      inf_chain_frac  that share of the nodes has its regular edge from node - 1 made infinite and followed by a finite edge from
+                node - 1, a repeat edge and a second regular entry in turn
+      broken_chain  nodes whose edge from node - 1 is made infinite and bridged by a finite edge from node - 2
+      kill_at / kill_band_edges / kill_frac  interior nodes that lose every edge (negative: counted from the end); their successor gets
+                an edge from the node before them.  kill_band_edges: the last row of band 0, 4, ..., the first row of band 2, 6, ...
+                and the node before END.  Kill nodes are never adjacent.
+    Last, every node but the kill nodes that is left without a finite edge from a node that is no kill node gets one from the nearest
+    such node: by induction every such node, END among them, is reachable from START over finite edges."""
+    n = g.n
+    rows = [[[int(g.e_col[e]), np.float32(g.e_val[e])] for e in range(g.e_rowptr[v], g.e_rowptr[v + 1])] for v in range(n)]
+    rep = [[] for _ in range(n)]
+    if g.r_rowptr is not None:
+        rep = [[[int(g.r_col[e]), int(g.r_units[e])] for e in range(g.r_rowptr[v], g.r_rowptr[v + 1])] for v in range(n)]
+    cost = lambda: _stored(rng.choice([0.0, 0.80369, 1.60738, 2.5]))
+    for first, last, k, dlo, dhi in hubs:
+        for v in range(first, last + 1):
+            assert 0 < v < n and v - dhi >= 0 and 1 <= dlo <= dhi
+            for i in range(k):
+                rows[v].append([v - dlo - i % (dhi - dlo + 1), cost()])
+    if hub_frac:
+        for v in range(hub_span + 2, n - 1):
+            if rng.random() < hub_frac:
+                have = {p for p, _ in rows[v]}
+                for p in rng.choice(np.arange(v - hub_span, v), size=int(rng.integers(hub_k[0], hub_k[1] + 1)), replace=False):
+                    if int(p) not in have:
+                        rows[v].append([int(p), cost()])
+    if dup_frac:
+        turn = 0
+        for v in range(dup_span + 1, n - 1):
+            if rng.random() < dup_frac:
+                d = (1, 2, 3, int(rng.integers(4, dup_span + 1)))[turn % 4]
+                turn += 1
+                if not any(p == v - d for p, _ in rows[v]):
+                    rows[v].append([v - d, cost()])
+                rep[v].append([v - d, int(rng.integers(1, 4))])
+    if inf_frac:
+        for v in range(2, n):
+            for e in rows[v]:
+                if e[0] != v - 1 and rng.random() < inf_frac:
+                    e[1] = np.float32(0.0)
+            for e in rep[v]:
+                if e[0] != v - 1 and rng.random() < inf_frac:
+                    e[1] = 0
+    if inf_chain_frac:
+        turn = 0
+        for v in range(2, n):
+            chain = [e for e in rows[v] if e[0] == v - 1 and e[1] != 0]
+            if len(chain) == 1 and rng.random() < inf_chain_frac:
+                chain[0][1] = np.float32(0.0)
+                if turn % 2 == 0: rep[v].append([v - 1, int(rng.integers(1, 4))])
+                else: rows[v].append([v - 1, cost()])   # (sorted stably below: after the infinite entry)
+                turn += 1
+    for v in broken_chain:
+        assert 2 <= v < n
+        for e in rows[v]:
+            if e[0] == v - 1: e[1] = np.float32(0.0)
+        rows[v].append([v - 2, _stored(0.80369)])
+    killed = set()
+    want = [v if v >= 0 else n + v for v in kill_at]
+    if kill_band_edges:
+        want += [64 * b + 63 for b in range(0, n // 64 + 1, 4)] + [64 * b for b in range(2, n // 64 + 1, 4)] + [n - 2]
+    want += [v for v in range(1, n - 1) if kill_frac and rng.random() < kill_frac]
+    for v in want:
+        if 1 <= v <= n - 2 and not ({v - 1, v, v + 1} & killed):
+            killed.add(v)
+            rows[v], rep[v] = [], []
+            rows[v + 1].append([v - 1, _stored(0.80369)])
+    for v in range(1, n):
+        if v not in killed and not any(val != 0 and p not in killed for p, val in rows[v]) and not any(u != 0 and p not in killed for p, u in rep[v]):
+            rows[v].append([v - 1 if v - 1 not in killed else v - 2, _stored(0.80369)])
+    rp, col, val, rrp, rcol, ru = [0], [], [], [0], [], []
+    for v in range(n):
+        for p, c in sorted(rows[v], key=lambda e: e[0]):
+            col.append(p); val.append(c)
+        rp.append(len(col))
+        for p, u in rep[v]:
+            rcol.append(p); ru.append(u)
+        rrp.append(len(rcol))
+    return Graph(n, g.dim, g.sites, rp, col, val, rrp, rcol, ru)
+
+
+def random_job(seed, n1, n2, dim=20, edit=None, edit1=None, edit2=None, **kw):
+    """edit / edit1 / edit2: edit_graph's options for both graphs / graph 1 / graph 2, drawn from a stream of their own (the job of the
+    same seed without them is the job these edges are added to)."""
     rng = np.random.default_rng(seed)
     g1 = random_graph(rng, n1, dim, **kw)
     g2 = random_graph(rng, n2, dim, **kw)
+    if edit or edit1 or edit2:
+        rng2 = np.random.default_rng([seed, 0x45444954])
+        g1 = edit_graph(g1, rng2, **dict(edit or {}, **(edit1 or {})))
+        g2 = edit_graph(g2, rng2, **dict(edit or {}, **(edit2 or {})))
     # a plausible joint matrix M = diag(pi) P with P row-stochastic, pi uniform (the reference's quirk)
     P = rng.gamma(0.3, 1.0, (dim, dim)) + 0.02
     P += np.eye(dim) * dim * 0.3

@@ -2,11 +2,23 @@
 import numpy as np
 import pytest
 
+import align_cases as A
+from align_cases import FAMILIES   # (test_gpu_dims.py takes them from here)
+
 pytestmark = pytest.mark.gpu
+
+
+def _jobs(ctx, name, recipe, claims=(), named=None):
+    """The jobs of a case of align_cases.py, held to what the case claims by the plan of this batch at the device's CU count: on a
+    device where the plan sends them elsewhere the test fails with the label's name instead of testing another kernel."""
+    js = A.build(recipe)
+    A.check_claims(name, js, list(claims), named or {}, ctx.device_info()[1])
+    return js
 
 
 def _cmp_job(batch, idx, job, res):
     import oracle_lib
+    assert A.end_is_reachable(job.g1) and A.end_is_reachable(job.g2)   # (the oracle is undefined on a job without an alignment)
     ref = oracle_lib.align_graphs(job, want_matrices=True)
     mats = batch.read_matrices(idx)
     n1, n2 = job.g1.n, job.g2.n
@@ -25,36 +37,12 @@ def _cmp_job(batch, idx, job, res):
     assert np.array_equal(res["map1"], ref["map1"]) and np.array_equal(res["map2"], ref["map2"])
 
 
-FAMILIES = [
-    dict(skip_frac=0.0, drop_chain_frac=0.0),                 # pure chains (leaf vs leaf)
-    dict(skip_frac=0.0, drop_chain_frac=0.0, onehot_frac=1.0),   # ... with one-hot rows throughout: the emission kernel's score table per (symbol, column)
-    dict(skip_frac=0.0, drop_chain_frac=0.0, chain_cost_frac=0.2),   # chain-only with costs on some chain edges (lean sweep, R rows per lane)
-    dict(skip_frac=0.1, onehot_frac=0.97),                    # almost one-hot: workgroups with and without other rows
-    dict(skip_frac=0.2),                                      # merged-graph like skip edges: near window + LDS history
-    dict(skip_frac=0.3, repeat_frac=0.05),                    # + tandem-repeat edges
-    dict(skip_frac=0.4, skip_span=3, skip_max=2),             # only near predecessors (distance 2 and 3): the register window alone
-    dict(skip_frac=0.95, skip_max=9, drop_chain_frac=0.0),    # dense extras: more far edges per node than the history serves (generic path)
-    dict(skip_frac=0.1, skip_span=70, repeat_frac=0.03, repeat_span=90),   # far edges: beyond the LDS history and the traceback tile
-    dict(skip_frac=0.25, skip_span=27, skip_max=2),           # distances up to the on-chip limit: deepest history (64 steps), virtual lanes
-    # heavy-tailed graphs (MODE 2 with the long / remote entries of the far helpers):
-    dict(skip_frac=0.3, skip_span=150, skip_max=5),           # several long edges per node: long slots 7, 6, 5, remote rows, > 3 long: generic
-    dict(skip_frac=0.5, skip_span=27, skip_max=14),           # 9-14 on-chip entries per node: overflow table (and its 48-record limit), row CSR
-    dict(skip_frac=0.4, skip_span=60, skip_max=10, repeat_frac=0.05, repeat_span=120),   # everything mixed
-]
-
-
 @pytest.mark.parametrize("dim", [20, 61])
 @pytest.mark.parametrize("kw", FAMILIES)
 def test_random_jobs_bit_exact(ctx, kw, dim):
     from prographmsa_amd import jobs as J
-    sizes = [(2, 2), (3, 2), (2, 5), (3, 3), (7, 4), (40, 33), (64, 64), (65, 66), (66, 65), (130, 97), (200, 310), (517, 129)]
-    if kw.get("skip_frac", 1) == 0.0:   # chain-only: more than eight bands of 128 / 256 rows (the worker's wavefronts take a second band), ring wrap-around
-        sizes = sizes + [(129, 130), (257, 70), (1100, 700), (2500, 90), (90, 2300)]
-    if dim == 61:   # the 61-state alphabet (codons): fewer sizes, same families incl. skip and repeat edges
-        sizes = [(3, 2), (7, 4), (65, 66), (130, 97), (200, 310)]
-    if kw.get("skip_span", 0) >= 60 or kw.get("skip_max", 0) >= 10:   # several bands with remote rows and long columns in flight
-        sizes = sizes + [(700, 650)]
-    js = [J.random_job(1000 + i, n1, n2, dim=dim, **kw) for i, (n1, n2) in enumerate(sizes)]
+    fi = next(i for i, f in enumerate(FAMILIES) if f is kw)
+    js = _jobs(ctx, "family %d D%d" % (fi, dim), A.family_recipe(fi, dim), A.FAMILY_CLAIMS[fi] + A.FAMILY_CLAIMS_AT.get((fi, dim), []))
     b = J.Batch(ctx, js, keep_matrices=True)
     b.run()
     res = b.fetch()
@@ -78,11 +66,10 @@ def test_random_jobs_bit_exact(ctx, kw, dim):
 
 def test_large_heavy_tailed_jobs_bit_exact(ctx):
     """Jobs of the size of the roots of configs 3-5 with heavy-tailed edge lengths: dozens of MODE 2 bands with long column
-    entries, remote row entries and overflow columns in flight at once (tools/probe_big.py goes to 6000 x 5000)."""
+    entries, remote row entries and overflow columns in flight at once (tools/probe_big.py goes to 6000 x 5000).  Every job has nodes
+    of the generic path (a column with more than three long entries, or past the overflow table's 128 records: the plan does not say which)."""
     from prographmsa_amd import jobs as J
-    js = [J.random_job(77, 2300, 2200, skip_frac=0.3, skip_span=150, skip_max=5),
-          J.random_job(78, 1500, 2600, skip_frac=0.5, skip_span=27, skip_max=14),
-          J.random_job(79, 2600, 1400, skip_frac=0.25, skip_span=90, skip_max=6, repeat_frac=0.03, repeat_span=120)]
+    js = _jobs(ctx, "large_heavy", A.LARGE_HEAVY, (), A.LARGE_HEAVY_CLAIMS)
     b = J.Batch(ctx, js, keep_matrices=True)
     b.run()
     res = b.fetch()
@@ -92,20 +79,15 @@ def test_large_heavy_tailed_jobs_bit_exact(ctx):
 
 
 def test_critical_path_kernel_and_wide_bands_bit_exact(ctx):
-    """Jobs of pgm_crit_kernel (20 and more bands, every predecessor near or within the on-chip history: the chain terms on one wavefront,
-    everything else on fifteen others) and of pgm_band_kernel's wide workers (a 32-step history, fewer than 20 bands), 20 and 61 states:
-    all four DP matrices, scores and mappings against the oracle; in one batch, so that workers take several bands one after another."""
+    """A batch that does not fill a device of 256 CUs, 20 and 61 states (align_cases.crit_wide_recipe says what the plan makes of every
+    job): two MODE 2 jobs with remote row entries, the longer one in the launch of the longest chains; five crit3 jobs of 7 to 21 bands
+    that share the main launch with the other one, so that pgm_fill_kernel sweeps them (pgm_crit_kernel sweeps a launch of crit3 jobs
+    only: the families 3-7 above, test_job_modes_of_small_and_large_batches, the long job of the wide cases below); and one job of 5 bands
+    with a 32-step history on a wide worker of pgm_band_kernel.  All four DP matrices, scores and mappings against the oracle; in one
+    batch, so that workers take several bands one after another."""
     from prographmsa_amd import jobs as J
     for dim in (20, 61):
-        js = [J.random_job(7100 + dim, 1500, 1400, dim=dim, skip_frac=0.25, skip_span=27, skip_max=2, drop_chain_frac=0.0),   # remote rows: the helper sweep of the fill kernel
-              J.random_job(7200 + dim, 1300, 700, dim=dim, skip_frac=0.1, skip_span=9, skip_max=3, drop_chain_frac=0.0),    # near and a few far edges, 21 bands: pgm_crit_kernel
-              J.random_job(7300 + dim, 1000, 1100, dim=dim, skip_frac=0.2, skip_span=20, skip_max=2, drop_chain_frac=0.0),
-              J.random_job(7400 + dim, 1290, 90, dim=dim, skip_frac=0.5, skip_span=5, skip_max=3, drop_chain_frac=0.0),     # short columns: the sweep is mostly ramp (pgm_crit_kernel)
-              J.random_job(7500 + dim, 400, 380, dim=dim, skip_frac=0.2),                                                   # (pgm_crit_kernel)
-              # few far edges, a 32-step history, chains well below the longest job's: the wide workers of pgm_band_kernel
-              J.random_job(7600 + dim, 450, 400, dim=dim, skip_frac=0.03, skip_span=9, skip_max=2, drop_chain_frac=0.0),
-              J.random_job(7700 + dim, 600, 300, dim=dim, skip_frac=0.02, skip_span=12, skip_max=2, drop_chain_frac=0.0),
-              J.random_job(7800 + dim, 300, 500, dim=dim, skip_frac=0.04, skip_span=10, skip_max=3, drop_chain_frac=0.0)]
+        js = _jobs(ctx, "crit_wide D%d" % dim, A.crit_wide_recipe(dim), *A.CRIT_WIDE_CLAIMS)
         b = J.Batch(ctx, js, keep_matrices=True)
         b.run()
         res = b.fetch()
@@ -115,17 +97,20 @@ def test_critical_path_kernel_and_wide_bands_bit_exact(ctx):
 
 
 def test_job_modes_of_small_and_large_batches_bit_exact(ctx):
-    """A batch that would not fill the device as MODE 2 sweeps sends every job of 8 bands or more to the critical-path kernel
-    (pgm_align_batch_create: a guide-tree level on its own); the same jobs among enough others stay on the band kernel's wavefronts.
-    Both ways: all four DP matrices, scores and mappings of those jobs against the oracle, and the fillers' mappings."""
+    """Four probes of 5 to 15 bands alone, among 22 fillers of 2000 x 2000 and among 64 fillers of 900 x 900 (at 256 CUs; asserted from
+    the plan, here and in test_cpu_align_reach.py).  Alone the batch does not fill the device and every job of 8 bands or more is promoted
+    to MODE 2 (pgm_align_batch_create: a guide-tree level on its own): probe 0, with remote row entries, is the launch of the longest
+    chains on pgm_fill_kernel, probes 1-3 are crit3 jobs and the main launch is pgm_crit_kernel's.  Among the big fillers nothing is
+    promoted and the longest chain is long: probe 3 becomes a self-contained sweep on a wide worker of pgm_band_kernel, probes 1 and 2
+    stay crit3 jobs (their histories do not fit a wide worker's slot) but share the main launch with probe 0, so pgm_fill_kernel sweeps
+    them, and the fillers are pgm_crit_kernel's.  Among the 64 fillers of old every probe keeps the kernel it has alone — what differs
+    is the order of the lists and the workers — and the fillers, in one launch with probe 0, are swept by pgm_fill_kernel.
+    Every way: all four DP matrices, scores and mappings of the probes against the oracle, and the mappings of every ninth filler."""
     from prographmsa_amd import jobs as J
     import oracle_lib
-    probes = [J.random_job(8100, 700, 650, skip_frac=0.2, skip_span=20, skip_max=2, drop_chain_frac=0.0),
-              J.random_job(8101, 640, 720, skip_frac=0.1, skip_span=9, skip_max=3, drop_chain_frac=0.0),
-              J.random_job(8102, 580, 600, skip_frac=0.3, repeat_frac=0.05),
-              J.random_job(8103, 900, 300, skip_frac=0.03, skip_span=9, skip_max=2, drop_chain_frac=0.0)]
-    fillers = [J.random_job(8200 + k, 900, 900, skip_frac=0.15, skip_span=12, skip_max=2, drop_chain_frac=0.0) for k in range(64)]
-    for js in (probes, probes + fillers):
+    probes = A.PROBES
+    for name, fill in (("alone", []), ("big fillers", A.BIG_FILLERS), ("fillers", A.FILLERS)):
+        js = _jobs(ctx, "modes " + name, probes + fill, *A.MODES_CLAIMS[name])
         b = J.Batch(ctx, js, keep_matrices=True)
         b.run()
         res = b.fetch()
@@ -282,3 +267,26 @@ def test_sequence_graph_jobs_score_table_after_other_batches(ctx):
                     ref = oracle_lib.align_graphs(j)
                     assert np.float32(res[i]["score"]).view(np.uint32) == np.float32(ref["score"]).view(np.uint32), (D, rnd, i)
                     assert np.array_equal(res[i]["map1"], ref["map1"]) and np.array_equal(res[i]["map2"], ref["map2"]), (D, rnd, i)
+
+
+@pytest.mark.parametrize("dim", [20, 61])
+@pytest.mark.parametrize("case", A.NEW_CASES)
+def test_unreached_paths_bit_exact(ctx, case, dim):
+    """The paths no random_graph job takes (align_cases.new_recipes: generic nodes of self-contained sweeps, more than one wide job, kill
+    nodes, edges of infinite cost, a broken chain, two edges from one predecessor): M, X, Y, W, S, score and mappings of every job
+    against the oracle, with the matrices kept and in the product's form."""
+    from test_gpu_dims import _kept_and_product
+    recipe, claims, named = A.new_recipes(dim)[case]
+    _kept_and_product(ctx, _jobs(ctx, "%s D%d" % (case, dim), recipe, claims, named))
+
+
+@pytest.mark.parametrize("dim", [20, 61])
+def test_mode2_refusals_bit_exact(ctx, dim):
+    """Each rule by which a node of a MODE 2 job goes to the generic path (align_cases.refusal_recipes), the hub one entry past the limit
+    and, in the control, at it: every job against the oracle."""
+    from test_gpu_dims import _kept_and_product
+    recipe, claims, named = A.refusal_case(dim)
+    js = _jobs(ctx, "refusals D%d" % dim, recipe, claims, named)
+    gen = A.generic_nodes(js, ctx.device_info()[1])
+    assert all(gen[k] > gen[k + 1] for k in range(0, len(js), 2)), gen
+    _kept_and_product(ctx, js)

@@ -10,20 +10,18 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_gpu_align import FAMILIES, _cmp_job
+import align_cases as A
+from test_gpu_align import FAMILIES, _cmp_job, _jobs
 
 pytestmark = pytest.mark.gpu
 
-DIMS = [1, 2, 3, 4, 5, 19, 21, 22, 23, 32, 33, 60, 62, 63, 64]
-SIZES = [(2, 2), (3, 2), (2, 5), (7, 4), (40, 33), (65, 66), (130, 97), (200, 310), (517, 129), (700, 650)]
+DIMS, SIZES = A.DIMS, A.DIM_SIZES
 # pure chains, one-hot rows (in the product form: two sequence graphs, the lean kernel's score table), chains with edge costs,
-# skip edges, dense extras (generic path), far edges, heavy-tailed edges (MODE 2 long entries)
-SWEEP_FAMILIES = {"chain": FAMILIES[0], "onehot": FAMILIES[1], "chaincost": FAMILIES[2], "skip": FAMILIES[4], "dense": FAMILIES[7],
-                  "far": FAMILIES[8], "heavy": FAMILIES[10]}
+# skip edges (wide workers and crit3 jobs), dense extras (crit3 jobs: no node of them is generic), far edges, heavy-tailed edges
+# (MODE 2 long entries, generic columns); align_cases.DIMS_CLAIMS holds each to it
+SWEEP_FAMILIES = {name: FAMILIES[fi] for name, fi in A.SWEEP_FAMILIES.items()}
 # the critical-path kernel's shape: 21 bands, every predecessor near or in the on-chip history (a small batch: pgm_crit_kernel)
-CRIT = [(1300, 700, dict(skip_frac=0.1, skip_span=9, skip_max=3, drop_chain_frac=0.0)),
-        (1290, 90, dict(skip_frac=0.5, skip_span=5, skip_max=3, drop_chain_frac=0.0)),
-        (400, 380, dict(skip_frac=0.2))]
+CRIT = A.DIM_CRIT
 P = lambda a, t: a.ctypes.data_as(C.POINTER(t))
 
 
@@ -83,13 +81,16 @@ def _kept_and_product(ctx, js):
 @pytest.mark.parametrize("dim", DIMS)
 @pytest.mark.parametrize("family", sorted(SWEEP_FAMILIES) + ["crit"])
 def test_align_graphs_every_dim_bit_exact(ctx, family, dim):
-    from prographmsa_amd import jobs as J
-    if family == "crit":
-        js = [J.random_job(31000 + 100 * dim + i, n1, n2, dim=dim, **kw) for i, (n1, n2, kw) in enumerate(CRIT)]
-    else:
-        kw = SWEEP_FAMILIES[family]
-        js = [J.random_job(30000 + 100 * dim + i, n1, n2, dim=dim, **kw) for i, (n1, n2) in enumerate(SIZES)]
-    _kept_and_product(ctx, js)
+    _kept_and_product(ctx, _jobs(ctx, "dims %s D%d" % (family, dim), A.dims_recipe(family, dim), *A.DIMS_CLAIMS[family]))
+
+
+@pytest.mark.parametrize("dim", [4, 64])
+@pytest.mark.parametrize("case", A.NEW_CASES + ["refusals"])
+def test_unreached_paths_smallest_and_largest_dim_bit_exact(ctx, case, dim):
+    """test_gpu_align.py's cases for the paths no random_graph job takes (generic nodes of self-contained sweeps, wide workers, kill
+    nodes, edges of infinite cost, two edges from one predecessor, the refusals of a MODE 2 sweep) at 4 and 64 states."""
+    recipe, claims, named = A.refusal_case(dim) if case == "refusals" else A.new_recipes(dim)[case]
+    _kept_and_product(ctx, _jobs(ctx, "%s D%d" % (case, dim), recipe, claims, named))
 
 
 @pytest.mark.parametrize("dim", DIMS + [20, 61])
