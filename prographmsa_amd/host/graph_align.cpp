@@ -10,7 +10,6 @@
 
 #include <algorithm>
 #include <chrono>
-#include <thread>
 #include <cmath>
 #include <cstdio>
 
@@ -132,31 +131,6 @@ static void dump_job(const pgm_graph &g1, const pgm_graph &g2, const pgm_model &
     fclose(f);
 }
 
-std::vector<std::vector<uint32_t>> farm_shards(const std::vector<uint64_t> &cost, int nw) {
-    const uint32_t n = (uint32_t)cost.size();
-    nw = std::max(1, std::min<int>(nw, (int)std::max(1u, n)));
-    std::vector<std::vector<uint32_t>> sh((size_t)nw);
-    std::vector<uint32_t> order(n);
-    for (uint32_t i = 0; i < n; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
-    std::vector<uint64_t> load((size_t)nw, 0);
-    for (uint32_t i : order) {
-        size_t w = 0;
-        for (size_t k = 1; k < load.size(); ++k) if (load[k] < load[w]) w = k;
-        sh[w].push_back(i);
-        load[w] += std::max<uint64_t>(cost[i], 1);
-    }
-    while (sh.size() > 1 && sh.back().empty()) sh.pop_back();
-    return sh;
-}
-
-void farm_run(const std::vector<std::vector<uint32_t>> &shards, const std::function<void(int)> &fn) {
-    std::vector<std::thread> th;
-    for (size_t w = 1; w < shards.size(); ++w) if (!shards[w].empty()) th.emplace_back(fn, (int)w);
-    if (!shards.empty() && !shards[0].empty()) fn(0);
-    for (auto &t : th) t.join();
-}
-
 std::vector<AlignmentResult> alignGraphsBatch(const std::vector<const Graph *> &g1, const std::vector<const Graph *> &g2,
                                               const std::vector<const Model *> &model, const std::vector<pgm_site_ref> &res1,
                                               const std::vector<pgm_site_ref> &res2, const std::vector<int> *worker_of) {
@@ -209,37 +183,18 @@ std::vector<AlignmentResult> alignGraphsBatch(const std::vector<const Graph *> &
     if (shards.size() <= 1) {
         ++be.calls_align;
         be.align_graphs_batch(n, p1.data(), p2.data(), pm.data(), sc.data(), out.data(), 0, res1.empty() ? nullptr : res1.data(), res2.empty() ? nullptr : res2.data());
-    } else if (worker_of) {
-        farm_run(shards, [&](int w) {
-            const std::vector<uint32_t> &sh = shards[(size_t)w];
-            const uint32_t m = (uint32_t)sh.size();
-            std::vector<const pgm_graph *> q1(m), q2(m);
-            std::vector<const pgm_model *> qm(m);
-            std::vector<pgm_scores> qs(m);
-            std::vector<pgm_align_out> qo(m);
-            std::vector<pgm_site_ref> r1(res1.empty() ? 0 : m), r2(res2.empty() ? 0 : m);
-            for (uint32_t k = 0; k < m; ++k) {
-                q1[k] = p1[sh[k]]; q2[k] = p2[sh[k]]; qm[k] = pm[sh[k]]; qs[k] = sc[sh[k]]; qo[k] = out[sh[k]];
-                if (!res1.empty()) r1[k] = res1[sh[k]];
-                if (!res2.empty()) r2[k] = res2[sh[k]];
-            }
-            ++be.calls_align;
-            be.align_graphs_batch(m, q1.data(), q2.data(), qm.data(), qs.data(), qo.data(), w, r1.empty() ? nullptr : r1.data(), r2.empty() ? nullptr : r2.data());
-            for (uint32_t k = 0; k < m; ++k) out[sh[k]] = qo[k];
-        });
     } else {
-        if (!res1.empty() || !res2.empty()) error("alignGraphsBatch: resident profiles need the jobs' workers (worker_of)");
+        if (!worker_of && (!res1.empty() || !res2.empty())) error("alignGraphsBatch: resident profiles need the jobs' workers (worker_of)");
         farm_run(shards, [&](int w) {
             const std::vector<uint32_t> &sh = shards[(size_t)w];
-            const uint32_t m = (uint32_t)sh.size();
-            std::vector<const pgm_graph *> q1(m), q2(m);
-            std::vector<const pgm_model *> qm(m);
-            std::vector<pgm_scores> qs(m);
-            std::vector<pgm_align_out> qo(m);
-            for (uint32_t k = 0; k < m; ++k) { q1[k] = p1[sh[k]]; q2[k] = p2[sh[k]]; qm[k] = pm[sh[k]]; qs[k] = sc[sh[k]]; qo[k] = out[sh[k]]; }
+            const std::vector<const pgm_graph *> q1 = shard_pick(p1, sh), q2 = shard_pick(p2, sh);
+            const std::vector<const pgm_model *> qm = shard_pick(pm, sh);
+            const std::vector<pgm_scores> qs = shard_pick(sc, sh);
+            std::vector<pgm_align_out> qo = shard_pick(out, sh);
+            const std::vector<pgm_site_ref> r1 = res1.empty() ? res1 : shard_pick(res1, sh), r2 = res2.empty() ? res2 : shard_pick(res2, sh);
             ++be.calls_align;
-            be.align_graphs_batch(m, q1.data(), q2.data(), qm.data(), qs.data(), qo.data(), w);
-            for (uint32_t k = 0; k < m; ++k) out[sh[k]] = qo[k];
+            be.align_graphs_batch((uint32_t)sh.size(), q1.data(), q2.data(), qm.data(), qs.data(), qo.data(), w, r1.empty() ? nullptr : r1.data(), r2.empty() ? nullptr : r2.data());
+            for (size_t k = 0; k < sh.size(); ++k) out[sh[k]] = qo[k];
         });
     }
     be.farm_level_workers = std::max(be.farm_level_workers, (int)std::max<size_t>(used, 1));

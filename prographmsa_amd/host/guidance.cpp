@@ -1,7 +1,14 @@
-// guidance.inc — the host parts of `pgmsa --guidance` that need no driver state (included by progressive.cpp): the residue map
+// guidance.cpp — the host parts of `pgmsa --guidance` that need no driver state: the residue map
 // between the base alignment and a replicate alignment, the host statement of the agreement counts (Backend::msa_agreement's
 // default, what pgmsa_oracle runs), the bounds of one agreement call, the exact newick text of a replicate's guide tree and the
 // two score files.  The flow that joins them (bootstrap trees, forest passes, groups) is doGuidance in main.cpp.
+#include "pgm_host.h"
+
+#include <algorithm>
+#include <cstdio>
+#include <ostream>
+
+namespace pgm {
 
 GuidanceStats guidance_stats;
 
@@ -129,3 +136,5 @@ void guidance_write(const GuidanceCounts &g, const std::vector<std::string> &nam
             for (size_t c = 0; c < L; ++c)
                 if (where0[i * L + c] >= 0) { *residues << names[i] << "\t" << (c + 1) << "\t"; guidance_line(*residues, g.res_hits[i * L + c], N * (occ[c] - 1)); }
 }
+
+}  // namespace pgm

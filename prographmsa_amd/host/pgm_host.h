@@ -380,6 +380,12 @@ Backend &default_backend();            // defined by exactly one backend_*.cpp l
 std::vector<std::vector<uint32_t>> farm_shards(const std::vector<uint64_t> &cost, int nw);
 // runs fn(w) for every non-empty shard, worker 0 on the calling thread, the others on threads of their own
 void farm_run(const std::vector<std::vector<uint32_t>> &shards, const std::function<void(int)> &fn);
+// the entries of a batch's array that belong to shard `sh`, in the shard's order
+template <class T> std::vector<T> shard_pick(const std::vector<T> &v, const std::vector<uint32_t> &sh) {
+    std::vector<T> q(sh.size());
+    for (size_t k = 0; k < sh.size(); ++k) q[k] = v[sh[k]];
+    return q;
+}
 void set_job_dump(const std::string &path);  // if set, every alignGraphs job is appended to this file
 bool job_dump_active();
 void set_dist_dump(const std::string &path); // if set, every distance matrix TreeNJ estimates is appended (dim, D, V as raw doubles)
@@ -490,7 +496,7 @@ private:
 // ProgressiveAlignment.{h,cpp}
 struct Profile { int dim = 0; index_t cols = 0; std::vector<double> data; };   // Model<A>::Profile: dim x cols, column-major
 struct repeat_t { index_t len = 0, start = 0; std::vector<int> tr_hom; };        // Repeat.h
-// --read_repeats: T-REKS output (RepeatDetectionTReks.cpp:62-157) against the (start / stop stripped) sequences
+// --read_repeats: T-REKS output (RepeatDetectionTReks.cpp:62-157; repeats.cpp) against the (start / stop stripped) sequences
 std::map<std::string, std::vector<repeat_t>> read_repeats(const Alphabet &a, const std::string &filename, const std::map<std::string, sequence_t> &seqs);
 struct ProgressiveAlignmentResult {   // ProgressiveAlignment.h:27-37
     std::map<std::string, sequence_t> aligned_sequences;
@@ -502,12 +508,12 @@ struct ProgressiveAlignmentResult {   // ProgressiveAlignment.h:27-37
     index_t n_tr_indels = 0;
     bool is_csprofile = false;
 };
-// align_progressive_results (ProgressiveAlignment.h:413-476) for a whole guide-tree level at once.
-// fn(0..n-1) on the host threads (PGM_HOST_THREADS, at most 16); exceptions are rethrown on the caller
+// fn(0..n-1) on the host threads (PGM_HOST_THREADS, at most 16); exceptions are rethrown on the caller (host_threads.cpp)
 void parallel_for(size_t n, const std::function<void(size_t)> &fn);
 
 // progressive_alignment (ProgressiveAlignment.cpp:12-71): same post-order results as the reference's
-// recursion; internal nodes whose children are finished are aligned together in one batch.
+// recursion; internal nodes whose children are finished are aligned together in one batch:
+// align_progressive_results (ProgressiveAlignment.h:413-476) for a whole guide-tree level at once.
 ProgressiveAlignmentResult progressive_alignment(const Alphabet &a, const std::map<std::string, sequence_t> &sequences,
                                                  const PhyTree &tree, const CSProfile *csprofile,
                                                  const ModelFactory &model_factory,
@@ -644,7 +650,7 @@ extern BootstrapStats bootstrap_stats;
 std::vector<PhyTree *> bootstrap_trees(const Alphabet &a, const std::map<std::string, sequence_t> &rows, const ModelFactory *mf, uint32_t nrep, uint64_t seed);
 
 // --guidance: how often the residue pairs of the base alignment stand in one column again in the alignments of N bootstrap guide
-// trees (host/guidance.inc; the flow is doGuidance in main.cpp).
+// trees (host/guidance.cpp; the flow is doGuidance in main.cpp).
 // guidance_where: one replicate's residue map, where[i * ncols + c] = the column of `rep` that holds the residue row i of `base`
 //   has in column c, -1 for a gap (rows as written, one symbol a column; both alignments hold the same residues in the same order).
 // msa_agreement_host: the counts of pgm_msa_agreement by plain loops on the host threads (Backend::msa_agreement's default).
@@ -669,7 +675,7 @@ uint32_t guidance_call_replicates(uint32_t nrows, uint32_t ncols, size_t where_b
 std::string format_newick_exact(const PhyTree &tree);
 void guidance_write(const GuidanceCounts &g, const std::vector<std::string> &names, const int32_t *where0, uint64_t seed, std::ostream &out, std::ostream *residues);
 
-// --bootstrap_tbe: the transfer bootstrap expectation (Lemoine et al. 2018) of every internal edge (host/transfer.inc).
+// --bootstrap_tbe: the transfer bootstrap expectation (Lemoine et al. 2018) of every internal edge (host/transfer.cpp).
 // transfer_min_host: pgm_transfer_min (include/pgm_hip.h) by plain loops on the host threads, the same contract; what it rejects is
 //   an error().  Backend::transfer_min's default.
 // transfer_call_replicates: the most replicates of at most max_sets sets each that one call takes for `rep` to stay within
@@ -691,7 +697,7 @@ uint32_t transfer_call_replicates(uint32_t nleaves, uint32_t nref, size_t max_se
 std::map<const PhyTree *, TransferEdge> transfer_support(const PhyTree &tree, const std::vector<const PhyTree *> &replicates, Backend *be = nullptr);
 std::map<const PhyTree *, std::string> transfer_labels(const std::map<const PhyTree *, TransferEdge> &support, uint32_t nrep);
 
-// --bootstrap_taxa: the taxon side of the transfer bootstrap, which leaves the transfer indices move (host/transfer.inc).
+// --bootstrap_taxa: the taxon side of the transfer bootstrap, which leaves the transfer indices move (host/transfer.cpp).
 // transfer_taxa_host: pgm_transfer_taxa (include/pgm_hip.h) by plain loops on the host threads, the same contract; what it rejects
 //   is an error().  Backend::transfer_taxa's default.
 // taxa_support: the replicates' sets sorted (as vectors of words) and equal ones dropped, the reference edges that share a

@@ -1,9 +1,16 @@
-// transfer.inc — the host parts of `pgmsa --bootstrap_tbe` and `--bootstrap_taxa` (included by progressive.cpp, like guidance.inc: they need parallel_for,
-// and the source lists of the drivers are fixed): the host statement of the transfer indices (Backend::transfer_min's default, what
-// pgmsa_oracle runs), the bounds of one call, and the support of every internal edge of a tree.  The leaf numbering and the
-// bipartition walk are those of bipartition_support (phytree.cpp); the flow that writes the files is doBootstrap in main.cpp.
+// transfer.cpp — the host parts of `pgmsa --bootstrap_tbe` and `--bootstrap_taxa`: the host statement of the transfer indices
+// (Backend::transfer_min's default, what pgmsa_oracle runs), the bounds of one call, and the support of every internal edge of a
+// tree.  The leaf numbering and the bipartition walk are those of bipartition_support (phytree.cpp); the flow that writes the
+// files is doBootstrap in main.cpp.
 // --bootstrap_taxa (below the TBE part): the host statement of the moved-taxon counts (Backend::transfer_taxa's default), the
 // per-taxon sums over the distinct bipartitions of a tree, and the two file texts.
+#include "pgm_host.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+
+namespace pgm {
 
 TransferStats transfer_stats;
 
@@ -273,3 +280,5 @@ std::string taxa_edges_text(const TaxaSupport &t) {
     }
     return s;
 }
+
+}  // namespace pgm

@@ -1,25 +1,15 @@
-// guidance_test.cpp — the host residue map (guidance_where) and the host agreement counts (msa_agreement_host) of host/guidance.inc
+// guidance_test.cpp — the host residue map (guidance_where) and the host agreement counts (msa_agreement_host) of host/guidance.cpp
 // on hand-made alignments: all gaps, one residue per column, identical replicates (the maximum N * (occ - 1)), disjoint replicates
 // (zero), a shifted replicate, rows that do not hold the same residues (refused), the bounds of one call and the exact newick text.
-// guidance.inc is compiled into this program with a parallel_for of its own (threads, so that a sanitizer sees the rows being
-// counted concurrently); built by tests/test_cpu_guidance.py with -fsanitize=address,undefined from this file and alphabet.cpp.
+// Linked with guidance.cpp and the driver's own parallel_for (host_threads.cpp: the pooled threads, so that a sanitizer sees the rows
+// being counted concurrently); built by tests/test_cpu_guidance.py with -fsanitize=address,undefined from this file, those two,
+// phytree.cpp and alphabet.cpp.
 // Prints "ok <checks>" and exits 0, or says what differs.
 #include "pgm_host.h"
 
 #include <algorithm>
 #include <cstdio>
 #include <sstream>
-#include <thread>
-
-namespace pgm {
-void parallel_for(size_t n, const std::function<void(size_t)> &fn) {
-    std::vector<std::thread> pool;
-    for (size_t t = 0; t < 4; ++t)
-        pool.emplace_back([&, t]() { for (size_t i = t; i < n; i += 4) fn(i); });
-    for (std::thread &th : pool) th.join();
-}
-#include "guidance.inc"
-}  // namespace pgm
 
 using namespace pgm;
 

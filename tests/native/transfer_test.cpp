@@ -1,7 +1,7 @@
-// transfer_test.cpp — transfer_min_host and transfer_support (host/transfer.inc) on hand-written trees of 5 to 8 leaves and on
+// transfer_test.cpp — transfer_min_host and transfer_support (host/transfer.cpp) on hand-written trees of 5 to 8 leaves and on
 // hand-made sets: exact transfer indices, printed the way --bootstrap_tbe prints them.  Leaf 0 is "a" (sorted-name order).
-// transfer.inc is compiled into this program with a parallel_for of its own (threads); built by tests/test_cpu_transfer.py with
-// -fsanitize=address,undefined from this file, phytree.cpp and alphabet.cpp.  Prints "ok <checks>" and exits 0, or says what differs.
+// Linked with transfer.cpp and the driver's own parallel_for (host_threads.cpp); built by tests/test_cpu_transfer.py with
+// -fsanitize=address,undefined from this file, those two, phytree.cpp and alphabet.cpp.  Prints "ok <checks>" and exits 0, or says what differs.
 #include "pgm_host.h"
 
 #include <algorithm>
@@ -9,23 +9,6 @@
 #include <cstdio>
 #include <memory>
 #include <sstream>
-#include <thread>
-
-namespace pgm {
-void parallel_for(size_t n, const std::function<void(size_t)> &fn) {
-    std::vector<std::thread> pool;
-    std::exception_ptr failed[4];   // (as the driver's: an exception is rethrown on the caller)
-    for (size_t t = 0; t < 4; ++t)
-        pool.emplace_back([&, t]() {
-            try { for (size_t i = t; i < n; i += 4) fn(i); }
-            catch (...) { failed[t] = std::current_exception(); }
-        });
-    for (std::thread &th : pool) th.join();
-    for (const std::exception_ptr &e : failed)
-        if (e) std::rethrow_exception(e);
-}
-#include "transfer.inc"
-}  // namespace pgm
 
 using namespace pgm;
 

@@ -193,7 +193,7 @@ def test_guidance_native_sanitized(tmp_path):
     exe = str(tmp_path / "guidance_test")
     host = os.path.join(ROOT, "prographmsa_amd", "host")
     subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-Wall", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-I", host, "-o", exe, os.path.join(ROOT, "tests", "native", "guidance_test.cpp"), os.path.join(host, "phytree.cpp"),
+                    "-I", host, "-o", exe, os.path.join(ROOT, "tests", "native", "guidance_test.cpp"), os.path.join(host, "host_threads.cpp"), os.path.join(host, "guidance.cpp"), os.path.join(host, "phytree.cpp"),
                     os.path.join(host, "alphabet.cpp")], check=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout + r.stderr

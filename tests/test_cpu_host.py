@@ -136,8 +136,8 @@ def test_all_pairs_farm_one_vs_k_workers(oracle_build, case, flags, gold):
                                              ("c1.fa", ["--fasta", "-a"], "c1.a_iter.out.fa")])
 def test_level_and_leaf_farm_one_vs_k_workers(oracle_build, case, flags, gold):
     """The jobs of a guide-tree level (alignGraphsBatch), the leaves' context profiles and the merges of a level are dealt to
-    the device contexts (farm_shards: by cost, longest first; one host thread per context, host/graph_align.cpp,
-    host/progressive.cpp).  1, 2, 3 and 5 workers over the oracle backend: identical FASTA, identical to the reference's."""
+    the device contexts (farm_shards: by cost, longest first; one host thread per context: host/host_threads.cpp; the
+    callers are host/graph_align.cpp and host/progressive.cpp).  1, 2, 3 and 5 workers over the oracle backend: identical FASTA, identical to the reference's."""
     exe = os.path.join(oracle_build, "pgmsa_oracle")
     outs = {}
     for workers in (1, 2, 3, 5):

@@ -303,3 +303,37 @@ def test_root_search_with_repeats_and_codons_runs(oracle_build, tmp_path):
     assert any(ln.startswith("TR indels: ") for ln in err.splitlines())
     out, err = run(exe, ["-f", "-rr", "--codon", "-t", os.path.join(GOLD, "cd1.tree"), os.path.join(GOLD, "cd1.fa")])
     assert out.count(">") == open(os.path.join(GOLD, "cd1.fa")).read().count(">")
+
+
+def _reroot_family(which, tmp_path):
+    if which == "c1":
+        return ["-t", os.path.join(GOLD, "c1.tree"), os.path.join(GOLD, "c1.fa")]
+    seqs, trd = gen.gen_repeat_family(6, 90, 3)
+    (tmp_path / "r.fa").write_text(gen.fasta(seqs)); (tmp_path / "r.trd").write_text(trd)
+    return ["-R", "--read_repeats", str(tmp_path / "r.trd"), str(tmp_path / "r.fa")]
+
+
+@pytest.mark.parametrize("flag", ["-r", "-rr"])
+@pytest.mark.parametrize("which", ["c1", "repeats"])
+def test_root_search_with_resident_profiles(oracle_build, tmp_path, which, flag):
+    """The root search with the profiles kept behind the backend (PGM_ORACLE_RESIDENT=1: leaves without host profiles, built by
+    the one-hot upload, repeats attached to them) gives the FASTA, the score line and the TR indels lines of the host-profile run."""
+    exe = os.path.join(oracle_build, "pgmsa_oracle")
+    args = ["-f", flag, "--stats"] + _reroot_family(which, tmp_path)
+    res = {}
+    for resident in (False, True):
+        env = {k: v for k, v in os.environ.items() if k != "PGM_ORACLE_RESIDENT"}
+        if resident:
+            env["PGM_ORACLE_RESIDENT"] = "1"
+        r = subprocess.run([exe] + args, capture_output=True, text=True, env=env)
+        assert r.returncode == 0, r.stderr
+        lines = r.stderr.splitlines()
+        stats = [ln for ln in lines if ln.startswith("{")]
+        assert len(stats) == 1 and ('"resident": true' in stats[0]) == resident, stats
+        score = [ln for ln in lines if ln.startswith("best gap parsimony score: ")]
+        assert len(score) == 1
+        res[resident] = (r.stdout, score, [ln for ln in lines if ln.startswith("TR indels")])
+    assert res[True][0].count(">") == (8 if which == "c1" else 6)
+    assert res[True] == res[False]
+    if which == "repeats":
+        assert res[True][2]

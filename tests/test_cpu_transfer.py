@@ -160,7 +160,7 @@ def test_transfer_native_sanitized(tmp_path):
     # (-fno-sanitize=vptr: transfer_support calls Backend::transfer_min through a pointer, and the check wants Backend's type
     #  information, which lives with the drivers' backends)
     subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-Wall", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize=vptr",
-                    "-fno-sanitize-recover=undefined", "-I", host, "-o", exe, os.path.join(ROOT, "tests", "native", "transfer_test.cpp"),
+                    "-fno-sanitize-recover=undefined", "-I", host, "-o", exe, os.path.join(ROOT, "tests", "native", "transfer_test.cpp"), os.path.join(host, "host_threads.cpp"), os.path.join(host, "transfer.cpp"),
                     os.path.join(host, "phytree.cpp"), os.path.join(host, "alphabet.cpp")], check=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout + r.stderr
