@@ -475,6 +475,38 @@ int pgm_transfer_taxa(pgm_ctx *ctx, uint32_t nleaves, uint32_t nref, const uint6
                       uint32_t *phi /* nref x nrep */, uint32_t *arg /* nref x nrep */, uint32_t *moved /* nref x nleaves */,
                       uint32_t *counted /* nref */);
 
+/* ---- likelihood of an alignment on a rooted tree, with the first and second derivative of its logarithm by every branch length
+ * (pgmsa --ml_tree; Felsenstein pruning).
+ * The tree: nnodes nodes, children before parents (parent[v] > v), the leaves are nodes 0 .. nleaves-1, the root is the one node
+ * whose parent is UINT32_MAX; a node's children are taken in ascending node order and an inner node has at least two.  Edge e is
+ * the edge above node e (e < nnodes-1: the root is the last node).
+ * rows[l * ncols + s]: leaf l at site s, 0 .. dim-1 a state, -1 a gap, -2 a residue without a value (both: missing data).
+ * P: per edge e one dim x dim matrix (derivs == 0) or three back to back (P, P' = Q P, P'' = Q Q P), column-major, X(i, j) at
+ * i + dim * j = parent state i -> child state j.  All matrices are the caller's: no transcendental function runs on the device.
+ *   up     U_l(j) = 1 if rows == j or rows < 0, else 0;  U_v(i) = prod over the children c of S_c(i), S_c(i) = sum_j P_c(i, j) U_c(j)
+ *   scale  after a node's product: if the largest of its dim entries is below 2^-256 and above 0, every entry * 2^256, site_k += 1
+ *   site   site_l[s] = sum_i pi[i] U_root(i); the likelihood of the site is site_l[s] * 2^(-256 site_k[s])
+ *   down   O_c(i) = B_v(i) * prod over the siblings c' of c of S_c'(i), v the parent of c, B_root = pi,
+ *          B_v(i) = sum_h O_v(h) P_v(h, i); then the scaling rule (no count: only ratios are taken)
+ *   edge   A^X = sum_i O_e(i) * (sum_j X_e(i, j) U_e(j)) for X = P, P', P'';  g = A^P' / A^P,  h = A^P'' / A^P - g * g
+ *   d1[e] = sum_s g, d2[e] = sum_s h: sites ascending within consecutive chunks of PGM_TREELIK_CHUNK sites, then the chunk sums
+ *          ascending.
+ * Every sum runs over its index ascending and starts from 0.0 with one multiply and one add per term; every product starts with its
+ * first factor.  Only + - * / occur and nothing is contracted, so the values do not depend on the launch and equal the host
+ * statement's (tree_likelihood_host) bit for bit.  site_l and site_k are overwritten; d1 and d2 (nnodes-1 each) only when derivs.
+ * Stateless: everything is uploaded per call.  Device memory: 8 * (nnodes - nleaves) * ncols * dim bytes for the partials, as much
+ * again and 16 * (nnodes - 1) * ncols for the per-site ratios with derivs (below the round figure 2 * nnodes * ncols * dim * 8);
+ * memory that cannot be had is PGM_ERR_NOMEM.
+ * PGM_ERR_INVALID, before anything is launched or an output is touched: a null pointer (d1, d2 only when derivs), dim outside
+ * 1 .. 64, nleaves < 2, ncols == 0, nnodes <= nleaves, a parent index <= its child or >= nnodes, a leaf that is a parent, an inner
+ * node with fewer than 2 children, not exactly one root, a row value outside -2 .. dim-1. */
+#define PGM_TREELIK_CHUNK 16
+int pgm_tree_likelihood(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent /* nnodes, root: UINT32_MAX */,
+                        uint32_t ncols, const int8_t *rows /* nleaves x ncols */, const double *pi /* dim */,
+                        const double *P /* (nnodes-1) x {1 or 3} x dim x dim */, int derivs,
+                        double *site_l /* ncols */, int32_t *site_k /* ncols */, double *d1, double *d2 /* nnodes-1, derivs only */);
+float pgm_treelik_last_kernel_ms(pgm_ctx *ctx);   /* device time of the kernels of the last pgm_tree_likelihood call */
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,7 @@ EXPORTS = [
     "pgm_bionj_plan", "pgm_bionj_plan_multi",
     "pgm_msa_agreement", "pgm_agreement_last_kernel_ms",
     "pgm_transfer_min", "pgm_transfer_last_kernel_ms", "pgm_transfer_taxa",
+    "pgm_tree_likelihood", "pgm_treelik_last_kernel_ms",
 ]
 
 
@@ -174,6 +175,9 @@ def _load():
         "pgm_transfer_last_kernel_ms": (C.c_float, [vp]),
         "pgm_transfer_taxa": (C.c_int, [vp, u32, u32, C.POINTER(C.c_uint64), C.POINTER(u32), u32, C.POINTER(u32), C.POINTER(C.c_uint64),
                                         C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]),
+        "pgm_tree_likelihood": (C.c_int, [vp, u32, u32, u32, C.POINTER(u32), u32, C.POINTER(C.c_int8), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int,
+                                          C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "pgm_treelik_last_kernel_ms": (C.c_float, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = the library does not export a declared symbol
@@ -274,6 +278,29 @@ class Context:
         P = lambda a, t: a.ctypes.data_as(C.POINTER(t))
         check(lib.pgm_transfer_taxa(self.handle, nleaves, nref, P(ref, C.c_uint64), P(thr, C.c_uint32), nrep, P(rep_off, C.c_uint32),
                                     P(rep, C.c_uint64) if rep.size else None, *[P(a, C.c_uint32) for a in out]), "pgm_transfer_taxa")
+        return tuple(out)
+
+    def tree_likelihood(self, dim, parent, rows, pi, P, derivs=True, out=None):
+        """pgm_tree_likelihood: parent (nnodes uint32, the root's 0xffffffff), rows (nleaves x ncols int8), pi (dim), P ((nnodes - 1) x
+        {3 with derivs, else 1} x dim x dim float64, every matrix column-major) -> (site_l (ncols float64), site_k (ncols int32),
+        d1, d2 (nnodes - 1 float64; left as given without derivs)).  Given output arrays (a tuple of four, C-contiguous of those
+        kinds) are overwritten."""
+        import numpy as np
+        parent = np.ascontiguousarray(parent, np.uint32)
+        rows = np.ascontiguousarray(rows, np.int8)
+        pi = np.ascontiguousarray(pi, np.float64)
+        P = np.ascontiguousarray(P, np.float64)
+        if parent.ndim != 1 or rows.ndim != 2 or pi.shape != (dim,) or P.size != (len(parent) - 1) * (3 if derivs else 1) * dim * dim:
+            raise ValueError("tree_likelihood: input array of the wrong shape")
+        nnodes, (nleaves, ncols) = len(parent), rows.shape
+        kinds = [((ncols,), np.float64), ((ncols,), np.int32), ((nnodes - 1,), np.float64), ((nnodes - 1,), np.float64)]
+        if out is None: out = tuple(np.zeros(s, t) for s, t in kinds)
+        if len(out) != 4 or any(a.dtype != t or a.shape != s or not a.flags.c_contiguous for a, (s, t) in zip(out, kinds)):
+            raise ValueError("tree_likelihood: output array of the wrong kind")
+        P_ = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+        check(lib.pgm_tree_likelihood(self.handle, dim, nleaves, nnodes, P_(parent, C.c_uint32), ncols, P_(rows, C.c_int8), P_(pi, C.c_double), P_(P, C.c_double),
+                                      1 if derivs else 0, P_(out[0], C.c_double), P_(out[1], C.c_int32), P_(out[2], C.c_double), P_(out[3], C.c_double)),
+              "pgm_tree_likelihood")
         return tuple(out)
 
     def close(self):

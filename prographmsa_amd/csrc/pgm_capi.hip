@@ -31,6 +31,7 @@
 #include "pgm_bionj_kernels.h"
 #include "pgm_agreement_kernels.h"
 #include "pgm_transfer_kernels.h"
+#include "pgm_treelik_kernels.h"
 #include "pgm_pool.h"
 #include "pgm_plan.h"
 static_assert(kC3Bytes == PGM_C3_BYTES, "pgm_plan.h plans the LDS of a crit3 sweep with PGM_C3_BYTES");
@@ -69,10 +70,11 @@ struct pgm_ctx {
     float bionj_ms = 0;
     float agree_ms = 0;                     // --guidance agreement counts: device time of the last call
     float transfer_ms = 0;                  // --bootstrap_tbe / --bootstrap_taxa transfer entries: device time of the last call
+    float treelik_ms = 0;                   // --ml_tree likelihood evaluations: device time of the last call
     uint32_t bionj_launches = 0;            // BioNJ: device time and kernels of the last call
     // grow-only scratch buffers of the all-pairs / context-profile calls (slot = position in the call's buffer list): a
     // guide-tree stage issues many calls (one per pair tile), hipMalloc / hipFree of up to 2 GB per call would dominate them
-    enum { SC_DEV = 36, SC_HOST = 4 };
+    enum { SC_DEV = 41, SC_HOST = 4 };
     void *sc_dev[SC_DEV] = {};
     size_t sc_dev_bytes[SC_DEV] = {};
     void *sc_host[SC_HOST] = {};      // pinned
@@ -950,3 +952,4 @@ int pgm_align_batch_read_matrices(pgm_ctx *ctx, pgm_align_batch *b, uint32_t job
 #include "pgm_agreement_capi.inc"
 #include "pgm_transfer_capi.inc"
 #include "pgm_transfer_taxa_capi.inc"
+#include "pgm_treelik_capi.inc"

@@ -1,0 +1,249 @@
+// pgm_treelik_kernels.h — Felsenstein pruning for pgm_tree_likelihood (include/pgm_hip.h), plain form.
+//
+// Columns are independent: a workgroup of one wavefront owns 64 / dim consecutive sites and walks the whole tree itself, one thread
+// per (site, state).  The up pass goes over the inner nodes in ascending order (children come before parents), the down pass and
+// the per-edge ratios over them in descending order; the partials and the outside vectors of the inner nodes live in global memory,
+// written and read by the same workgroup only (__syncthreads between a node and its parent).  No workgroup waits for another,
+// nothing spins, there are no atomics.  The matrices of the edge in hand are read from global memory by every thread (lanes of one
+// site read consecutive entries of a column; the 3.2 KB to 98 KB of an edge stay in the vector L1 / L2 while the workgroups pass it).
+// pgm_treelik_sums_kernel adds the per-site ratios of an edge in the fixed order of the interface.
+//
+// Every sum over states runs ascending from 0.0 with one multiply and one add per term (-ffp-contract=off): the bits are those of
+// tree_likelihood_host.  The walk is a chain of dependent steps on one wavefront, so what a step costs is the latency of its loads:
+// the sums fetch eight terms' operands ahead of the eight adds (the adds keep their order), the three sums of an edge (P, P', P'')
+// share one pass over the child's partial, and a leaf with a state reads its one column.
+#ifndef PGM_TREELIK_KERNELS_H_
+#define PGM_TREELIK_KERNELS_H_
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#define PGM_TREELIK_THREADS 64
+
+struct PgmTreelikArgs {
+    uint32_t dim, nleaves, nnodes, ncols, spb;   // spb: sites per workgroup = 64 / dim
+    int derivs;
+    const uint32_t *child_off, *child;           // CSR: the children of every node, ascending
+    const int8_t *rows;
+    const double *pi, *P;
+    double *U, *O;                               // (nnodes - nleaves) x ncols x dim each; O only with derivs
+    double *g, *h;                               // (nnodes - 1) x ncols each, derivs only
+    double *site_l;
+    int32_t *site_k;
+};
+
+// acc[x] = sum over j ascending of X_x(i, j) u_c(j) for this thread's state i and site s, X_x the NX matrices of edge c back to back
+// (`mat` doubles apart): u_c the stored partial of an inner node, the indicator of the row value for a leaf.  A leaf with a state r:
+// 0.0 + X_x(i, r), what the sum gives when every other term is a zero; a leaf without one: the terms are the entries themselves.
+template <int NX>
+__device__ __forceinline__ void pgm_treelik_apply(const PgmTreelikArgs &a, const double *X, size_t mat, uint32_t c, uint32_t s, uint32_t i, double (&acc)[NX]) {
+    const uint32_t dim = a.dim;
+    const double *col = X + i;
+#pragma unroll
+    for (int x = 0; x < NX; ++x) acc[x] = 0.0;
+    if (c < a.nleaves) {
+        const int r = a.rows[(size_t)c * a.ncols + s];
+        if (r >= 0) {
+#pragma unroll
+            for (int x = 0; x < NX; ++x) acc[x] = 0.0 + col[mat * x + (size_t)dim * (uint32_t)r];
+            return;
+        }
+        uint32_t j = 0;
+        for (; j + 8 <= dim; j += 8) {
+            double xv[NX][8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+#pragma unroll
+                for (int x = 0; x < NX; ++x) xv[x][q] = col[mat * x + (size_t)dim * (j + q)];
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+#pragma unroll
+                for (int x = 0; x < NX; ++x) acc[x] = acc[x] + xv[x][q];
+        }
+        for (; j < dim; ++j)
+#pragma unroll
+            for (int x = 0; x < NX; ++x) acc[x] = acc[x] + col[mat * x + (size_t)dim * j];
+        return;
+    }
+    const double *u = a.U + ((size_t)(c - a.nleaves) * a.ncols + s) * dim;
+    uint32_t j = 0;
+    for (; j + 8 <= dim; j += 8) {
+        double xv[NX][8], uv[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            uv[q] = u[j + q];
+#pragma unroll
+            for (int x = 0; x < NX; ++x) xv[x][q] = col[mat * x + (size_t)dim * (j + q)];
+        }
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+#pragma unroll
+            for (int x = 0; x < NX; ++x) acc[x] = acc[x] + xv[x][q] * uv[q];
+    }
+    for (; j < dim; ++j) {
+        const double uj = u[j];
+#pragma unroll
+        for (int x = 0; x < NX; ++x) acc[x] = acc[x] + col[mat * x + (size_t)dim * j] * uj;
+    }
+}
+
+// the scaling rule on the dim values of a site, one per thread: true when the values were multiplied by 2^256.
+// sh: this site's dim doubles of shared memory.  Every thread of the workgroup calls it (two barriers).
+__device__ __forceinline__ bool pgm_treelik_rescale(double &v, double *sh, uint32_t dim, uint32_t i, bool active) {
+    __syncthreads();
+    if (active) sh[i] = v;
+    __syncthreads();
+    bool scaled = false;
+    if (active) {
+        double m = sh[0];
+#pragma unroll 8
+        for (uint32_t k = 1; k < dim; ++k) m = sh[k] > m ? sh[k] : m;
+        scaled = m < 0x1p-256 && m > 0.0;
+        if (scaled) v = v * 0x1p256;
+    }
+    return scaled;
+}
+
+// One edge of the down pass, for the dim threads of a site: the outside vector o (before its scaling) and T[x] = sum_j X_x(i, j) U_c(j)
+// of this thread's state.  Scales o, stores it for an inner child, and the thread of state 0 adds the three sums over the states
+// ascending and writes the two ratios.  Every thread of the workgroup calls it (barriers).
+__device__ __forceinline__ void pgm_treelik_edge(const PgmTreelikArgs &a, double (*sh)[PGM_TREELIK_THREADS], double *shs, uint32_t c, uint32_t s, uint32_t i,
+                                                 bool active, double o, const double (&T)[3]) {
+    const uint32_t dim = a.dim;
+    (void)pgm_treelik_rescale(o, shs, dim, i, active);
+    if (active && c >= a.nleaves) a.O[((size_t)(c - a.nleaves) * a.ncols + s) * dim + i] = o;
+    __syncthreads();   // (the maximum's reads of sh[0] are done)
+    if (active) {
+        sh[0][threadIdx.x] = o * T[0];
+        sh[1][threadIdx.x] = o * T[1];
+        sh[2][threadIdx.x] = o * T[2];
+    }
+    __syncthreads();
+    if (active && i == 0) {
+        double A0 = 0.0, A1 = 0.0, A2 = 0.0;
+#pragma unroll 8
+        for (uint32_t j = 0; j < dim; ++j) {
+            A0 = A0 + sh[0][threadIdx.x + j];
+            A1 = A1 + sh[1][threadIdx.x + j];
+            A2 = A2 + sh[2][threadIdx.x + j];
+        }
+        const double g = A1 / A0;
+        a.g[(size_t)c * a.ncols + s] = g;
+        a.h[(size_t)c * a.ncols + s] = A2 / A0 - g * g;
+    }
+}
+
+__global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_kernel(PgmTreelikArgs a) {
+    __shared__ double sh[3][PGM_TREELIK_THREADS];
+    const uint32_t dim = a.dim, nleaves = a.nleaves, root = a.nnodes - 1;
+    const uint32_t local = threadIdx.x / dim, i = threadIdx.x - local * dim;
+    const uint64_t s64 = (uint64_t)blockIdx.x * a.spb + local;
+    const bool active = local < a.spb && s64 < a.ncols;
+    const uint32_t s = (uint32_t)s64;
+    const size_t mat = (size_t)dim * dim, estride = a.derivs ? 3 * mat : mat;
+    double *shs = &sh[0][local * dim];   // (local * dim + i == threadIdx.x < 64)
+
+    // up pass
+    int32_t k = 0;
+    for (uint32_t v = nleaves; v <= root; ++v) {
+        double prod = 0.0;
+        if (active) {
+            const uint32_t q0 = a.child_off[v], q1 = a.child_off[v + 1];
+            for (uint32_t q = q0; q < q1; ++q) {
+                const uint32_t c = a.child[q];
+                double S[1];
+                pgm_treelik_apply<1>(a, a.P + estride * c, mat, c, s, i, S);
+                prod = q == q0 ? S[0] : prod * S[0];
+            }
+        }
+        if (pgm_treelik_rescale(prod, shs, dim, i, active)) ++k;
+        if (active) a.U[((size_t)(v - nleaves) * a.ncols + s) * dim + i] = prod;
+        __syncthreads();   // the node's partial is in memory before its parent reads it
+    }
+    {   // the site likelihood: sum over the states ascending
+        const double *u = a.U + ((size_t)(root - nleaves) * a.ncols + s) * dim;
+        if (active && i == 0) {
+            double L = 0.0;
+#pragma unroll 8
+            for (uint32_t j = 0; j < dim; ++j) L = L + a.pi[j] * u[j];
+            a.site_l[s] = L;
+            a.site_k[s] = k;
+        }
+    }
+    if (!a.derivs) return;
+
+    // down pass, parents before children: the outside vector of every edge below v, then the edge's three sums
+    for (uint32_t v = root; v >= nleaves; --v) {
+        double base = 0.0;
+        const uint32_t q0 = a.child_off[v], q1 = a.child_off[v + 1];   // (uniform over the workgroup: the barriers below)
+        if (active) {
+            if (v == root) base = a.pi[i];
+            else {
+                const double *o = a.O + ((size_t)(v - nleaves) * a.ncols + s) * dim, *Pv = a.P + estride * v + (size_t)dim * i;
+                uint32_t h = 0;
+                for (; h + 8 <= dim; h += 8) {
+                    double ov[8], pv[8];
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) { ov[q] = o[h + q]; pv[q] = Pv[h + q]; }
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) base = base + ov[q] * pv[q];
+                }
+                for (; h < dim; ++h) base = base + o[h] * Pv[h];
+            }
+        }
+        if (q1 - q0 == 2) {   // two children: the sibling's S is the other child's own first sum
+            const uint32_t c0 = a.child[q0], c1 = a.child[q0 + 1];
+            double T0[3] = {0.0, 0.0, 0.0}, T1[3] = {0.0, 0.0, 0.0};
+            if (active) {
+                pgm_treelik_apply<3>(a, a.P + estride * c0, mat, c0, s, i, T0);
+                pgm_treelik_apply<3>(a, a.P + estride * c1, mat, c1, s, i, T1);
+            }
+            pgm_treelik_edge(a, sh, shs, c0, s, i, active, base * T1[0], T0);
+            pgm_treelik_edge(a, sh, shs, c1, s, i, active, base * T0[0], T1);
+        } else {
+            for (uint32_t q = q0; q < q1; ++q) {
+                const uint32_t c = a.child[q];
+                double o = base, T[3] = {0.0, 0.0, 0.0};
+                if (active) {
+                    for (uint32_t r = q0; r < q1; ++r) {
+                        const uint32_t sib = a.child[r];
+                        if (r == q) pgm_treelik_apply<3>(a, a.P + estride * sib, mat, sib, s, i, T);
+                        else {
+                            double S[1];
+                            pgm_treelik_apply<1>(a, a.P + estride * sib, mat, sib, s, i, S);
+                            o = o * S[0];
+                        }
+                    }
+                }
+                pgm_treelik_edge(a, sh, shs, c, s, i, active, o, T);
+            }
+        }
+        __syncthreads();   // the children's outside vectors are in memory before they are parents themselves
+    }
+}
+
+// d1[e] = sum of g[e][.], d2[e] = sum of h[e][.]: sites ascending within chunks of PGM_TREELIK_CHUNK, then the chunk sums ascending.
+// A workgroup per edge; chunk sums into `part` (nedges x 2 x nchunks), then thread 0 adds those of g and thread 1 those of h.
+__global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_sums_kernel(const double *g, const double *h, uint32_t ncols, uint32_t nchunks, double *part,
+                                                                                double *d1, double *d2) {
+    const uint32_t e = blockIdx.x;
+    const double *ge = g + (size_t)e * ncols, *he = h + (size_t)e * ncols;
+    double *p1 = part + (size_t)e * 2 * nchunks, *p2 = p1 + nchunks;
+    for (uint32_t chunk = threadIdx.x; chunk < nchunks; chunk += blockDim.x) {
+        const uint32_t s0 = chunk * PGM_TREELIK_CHUNK, s1 = ncols - s0 < PGM_TREELIK_CHUNK ? ncols : s0 + PGM_TREELIK_CHUNK;
+        double a1 = 0.0, a2 = 0.0;
+        for (uint32_t s = s0; s < s1; ++s) { a1 = a1 + ge[s]; a2 = a2 + he[s]; }
+        p1[chunk] = a1;
+        p2[chunk] = a2;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const double *p = threadIdx.x == 0 ? p1 : p2;
+        double acc = 0.0;
+#pragma unroll 8
+        for (uint32_t chunk = 0; chunk < nchunks; ++chunk) acc = acc + p[chunk];
+        (threadIdx.x == 0 ? d1 : d2)[e] = acc;
+    }
+}
+
+#endif

@@ -87,6 +87,8 @@ const HostSwitches &host_switches() {
         h.host_bionj = getenv("PGM_HOST_BIONJ") != nullptr;
         h.host_transfer = getenv("PGM_HOST_TRANSFER") != nullptr;
         h.device_transfer = getenv("PGM_DEVICE_TRANSFER") != nullptr;
+        h.host_treelik = getenv("PGM_HOST_TREELIK") != nullptr;
+        h.device_treelik = getenv("PGM_DEVICE_TREELIK") != nullptr;
         return h;
     }();
     return sw;
@@ -97,6 +99,7 @@ std::string HostSwitches::describe() const {
     add(host_merge, "PGM_HOST_MERGE"); add(no_resident, "PGM_NO_RESIDENT"); add(host_counts, "PGM_HOST_COUNTS"); add(device_mldist, "PGM_DEVICE_MLDIST");
     add(device_bionj, "PGM_DEVICE_BIONJ"); add(host_bionj, "PGM_HOST_BIONJ");
     add(host_transfer, "PGM_HOST_TRANSFER"); add(device_transfer, "PGM_DEVICE_TRANSFER");
+    add(host_treelik, "PGM_HOST_TREELIK"); add(device_treelik, "PGM_DEVICE_TREELIK");
     return s;
 }
 

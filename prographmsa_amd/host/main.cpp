@@ -5,6 +5,7 @@
 #include "pgm_host.h"
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -27,6 +28,7 @@ static void usage() {
                  "             [--bootstrap <N> --bootstrap_out <file> [--bootstrap_seed <S>] [--bootstrap_tbe <file>] [--bootstrap_trees <file>]\n"
                  "              [--bootstrap_taxa <file> [--bootstrap_taxa_cutoff <X>] [--bootstrap_taxa_edges <file>]]]\n"
                  "             [--guidance <N> --guidance_out <file> [--guidance_seed <S>] [--guidance_residues <file>] [--guidance_dump <prefix>]]\n"
+                 "             [--ml_tree <file> [--ml_sites <file>] [--ml_rounds <N>] [--ml_epsilon <X>]]\n"
                  "             <fasta file>\n"
                  "       pgmsa --batch <list> [--batch_cells <cells>] [options]\n"
                  "  --batch <list>  align many families in one run: every line of <list> is input.fa<TAB>output[<TAB>guide_tree.nwk[<TAB>topology.nwk]]\n"
@@ -79,6 +81,13 @@ static void usage() {
                  "                --guidance_dump <prefix> writes every replicate's guide tree and alignment to <prefix>.<r>.nwk / .fa.  The\n"
                  "                replicates share the device stages in groups of at most --batch_cells estimated DP cells.  Needs at least 4\n"
                  "                sequences; not with --batch, -T, -r, -W, --topology\n"
+                 "  --ml_tree <file>  maximum-likelihood branch lengths for the tree estimated from the final alignment (the tree of --bootstrap):\n"
+                 "                the likelihood of the alignment as written under the run's substitution model, gaps and residues without a\n"
+                 "                value as missing data, is maximised over the branch lengths (each within 1e-6 .. 10) on the fixed topology and\n"
+                 "                root; <file> gets the tree with those lengths.  --ml_sites <file>: a line `lnL <value>`, then the\n"
+                 "                log-likelihood of every column (column<TAB>value, columns from 1).  --ml_rounds <N> (1 <= N <= 10000, default\n"
+                 "                100) bounds the rounds of the optimiser, --ml_epsilon <X> (X >= 0, default 1e-4) is the gain of lnL below\n"
+                 "                which it stops.  Needs at least 3 sequences; not with --batch, -W, -r, --topology\n"
                  "  -W, --wls_refine  refine every guide tree estimated from distances by weighted least squares (nearest-neighbour\n"
                  "                interchanges of quartets); given twice (-WW), quintet moves as well\n";
 }
@@ -216,6 +225,14 @@ struct GuidanceOpts {   // --guidance N --guidance_out FILE --guidance_seed S --
     uint64_t seed = 1;
     double cells = 2e9;   // --batch_cells: estimated DP cells of one group of replicates
 } g_guidance;
+
+struct MlTreeOpts {   // --ml_tree FILE --ml_sites FILE --ml_rounds N --ml_epsilon X
+    std::string tree, sites, rounds_text, eps_text;
+    bool tree_given = false, sites_given = false, rounds_given = false, eps_given = false;
+    long rounds = 100;
+    double eps = 1e-4;
+    bool any() const { return tree_given || sites_given || rounds_given || eps_given; }
+} g_mltree;
 }  // namespace
 
 static void doGuidance(const Alphabet &a, const Family &fam, const CSProfile *csprofile, const std::map<std::string, std::vector<repeat_t>> &reps);
@@ -279,6 +296,48 @@ static void doBootstrap(const Alphabet &a, const Family &fam, const std::map<std
     bootstrap_stats.seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
+// --ml_tree: the tree of --bootstrap (TreeNJ on the final alignment without its ancestral rows, midpoint rooted) with the branch
+// lengths that maximise the likelihood of the alignment as it is written (start / stop columns re-inserted, every residue the
+// character of the input: Family::finish_rows), and --ml_sites: the log-likelihood of every column (ml_branch_lengths, DESIGN.md
+// 3.17; the device from kTreelikDeviceMin taxa or with PGM_DEVICE_TREELIK, the host loop with PGM_HOST_TREELIK)
+static void doMlTree(const Alphabet &a, const Family &fam, const std::map<std::string, sequence_t> &alignment) {
+    std::map<std::string, sequence_t> rows;
+    for (const auto &kv : alignment)
+        if (kv.first.empty() || kv.first[0] != '(') rows.insert(kv);   // (ancestral sequences dropped)
+    std::unique_ptr<PhyTree> tree(TreeNJ(a, rows, fam.model_factory.get(), true));
+    std::vector<std::vector<int8_t>> values;   // the rows in sorted-name order: the leaves' order
+    for (const auto &kv : rows) {
+        const sequence_t written = fam.written_row(a, kv.first, kv.second), orig = sequenceFromString(a, fam.seqs.at(kv.first));
+        std::vector<int8_t> v(written.size());
+        size_t j = 0;
+        for (size_t k = 0; k < written.size(); ++k) {
+            if (a.isGap(written[k])) { v[k] = -1; continue; }
+            const int x = j < orig.size() ? a.value(orig[j]) : -1;
+            ++j;
+            v[k] = (int8_t)(x >= 0 && x < a.DIM ? x : -2);
+        }
+        values.push_back(std::move(v));
+    }
+    const HostSwitches &sw = host_switches();
+    const bool device = !sw.host_treelik && (sw.device_treelik || rows.size() >= kTreelikDeviceMin);
+    const MlTreeResult res = ml_branch_lengths(a, values, *fam.model_factory, *tree, (uint32_t)g_mltree.rounds, g_mltree.eps, device ? &default_backend() : nullptr);
+    std::unique_ptr<PhyTree> ml(ml_tree_with_lengths(ml_tree_topology(*tree), res.lengths));
+    std::ofstream out(g_mltree.tree.c_str());
+    if (!out) error("error opening the ml tree output file %s", g_mltree.tree.c_str());
+    out << ml->formatNewick() << std::endl;
+    if (g_mltree.sites_given) {
+        std::ofstream sites(g_mltree.sites.c_str());
+        if (!sites) error("error opening the ml tree output file %s", g_mltree.sites.c_str());
+        char buf[64];
+        snprintf(buf, sizeof buf, "lnL %.17g\n", res.lnl);
+        sites << buf;
+        for (size_t c = 0; c < res.site_lnl.size(); ++c) {
+            snprintf(buf, sizeof buf, "%zu\t%.17g\n", c + 1, res.site_lnl[c]);
+            sites << buf;
+        }
+    }
+}
+
 static void print_stats(double t_init, double t_tree, double t_prog, const BatchRun *batch) {
     Backend &be = default_backend();
     fprintf(stderr,
@@ -316,6 +375,10 @@ static void print_stats(double t_init, double t_tree, double t_prog, const Batch
                         "\"guidance_passes\": %llu, \"guidance_agreement_calls\": %llu",
                 guidance_stats.replicates, guidance_stats.seconds, guidance_stats.align_s, guidance_stats.agreement_s, (unsigned long long)guidance_stats.passes,
                 (unsigned long long)guidance_stats.agreement_calls);
+    if (g_mltree.tree_given)   // (keys of --ml_tree only)
+        fprintf(stderr, ", \"ml_tree_s\": %.6f, \"ml_rounds\": %llu, \"ml_evaluations\": %llu, \"ml_lnl_start\": %.17g, \"ml_lnl\": %.17g, \"ml_kernel_ms\": %.3f",
+                ml_tree_stats.seconds, (unsigned long long)ml_tree_stats.rounds, (unsigned long long)ml_tree_stats.evaluations, ml_tree_stats.lnl_start, ml_tree_stats.lnl,
+                ml_tree_stats.kernel_ms);
     if (batch)   // (keys of --batch only)
         fprintf(stderr, ", \"batch_families\": %d, \"batch_failed\": %d, \"batch_chunks\": %d, \"batch_passes\": %llu, \"batch_levels\": %llu, "
                         "\"batch_align_calls\": %llu, \"batch_dist_calls\": %llu",
@@ -379,6 +442,10 @@ static int doAlign(const Alphabet &a, Family &fam, bool stats) {
     if (g_bootstrap.given) {   // (with -T the final alignment is computed for it alone: what is printed stays the tree)
         if (cmdlineopts.onlytree_flag) doBootstrap(a, fam, progressive_alignment(a, fam.seqs2, *fam.tree, csprofile.get(), *fam.model_factory, &reps).aligned_sequences);
         else doBootstrap(a, fam, result.aligned_sequences);
+    }
+    if (g_mltree.tree_given) {   // (with -T the final alignment is computed for it alone, as for --bootstrap)
+        if (cmdlineopts.onlytree_flag) doMlTree(a, fam, progressive_alignment(a, fam.seqs2, *fam.tree, csprofile.get(), *fam.model_factory, &reps).aligned_sequences);
+        else doMlTree(a, fam, result.aligned_sequences);
     }
     if (g_guidance.given) doGuidance(a, fam, csprofile.get(), reps);
 
@@ -764,6 +831,10 @@ int main(int argc, char **argv) {
             else if (s == "--guidance_seed") g_guidance.seed = strtoull(val().c_str(), nullptr, 10);
             else if (s == "--guidance_residues") g_guidance.residues = val();
             else if (s == "--guidance_dump") g_guidance.dump = val();
+            else if (s == "--ml_tree") { g_mltree.tree_given = true; g_mltree.tree = val(); }
+            else if (s == "--ml_sites") { g_mltree.sites_given = true; g_mltree.sites = val(); }
+            else if (s == "--ml_rounds") { g_mltree.rounds_given = true; g_mltree.rounds_text = val(); }
+            else if (s == "--ml_epsilon") { g_mltree.eps_given = true; g_mltree.eps_text = val(); }
             else if (s == "--reroot") ++cmdlineopts.reroot_flag;
             else if (s == "--wls_refine") ++cmdlineopts.wlsrefine_flag;
             else if (s.size() >= 2 && s[0] == '-' && s.find_first_not_of('W', 1) == std::string::npos) cmdlineopts.wlsrefine_flag += (int)s.size() - 1;   // -W, -WW
@@ -781,7 +852,8 @@ int main(int argc, char **argv) {
                                   : cmdlineopts.repeats_flag ? "-R" : !cmdlineopts.readreps_file.empty() ? "--read_repeats"
                                   : !cmdlineopts.profile_file.empty() ? "--profile_out" : !dump.empty() ? "--dump_jobs" : !dist_dump.empty() ? "--dump_dist" : !joins_dump.empty() ? "--dump_joins"
                                   : g_bootstrap.any() ? "--bootstrap"
-                                  : (g_guidance.given || g_guidance.out_given || !g_guidance.residues.empty() || !g_guidance.dump.empty()) ? "--guidance" : nullptr;
+                                  : (g_guidance.given || g_guidance.out_given || !g_guidance.residues.empty() || !g_guidance.dump.empty()) ? "--guidance"
+                                  : g_mltree.any() ? "--ml_tree" : nullptr;
             if (refused) { std::cerr << "ERROR:--batch cannot be combined with " << refused << std::endl; return 2; }
         }
         if (cmdlineopts.sequence_file.empty() && batch_list.empty()) { usage(); return 1; }
@@ -812,6 +884,26 @@ int main(int argc, char **argv) {
                               : !topo_file.empty() ? "--guidance cannot be combined with --topology (every replicate would have the same topology)" : nullptr;
             if (why) { std::cerr << "ERROR:" << why << std::endl; return 2; }
             g_guidance.cells = batch_cells;
+        }
+        if (g_mltree.any()) {
+            // (the rounds are a whole number in 1 .. 10000, the gain a finite number >= 0: other text, a NaN and everything outside are refused)
+            char *end = nullptr;
+            bool rounds_ok = true, eps_ok = true;
+            if (g_mltree.rounds_given) {
+                g_mltree.rounds = strtol(g_mltree.rounds_text.c_str(), &end, 10);
+                rounds_ok = !g_mltree.rounds_text.empty() && *end == '\0' && g_mltree.rounds >= 1 && g_mltree.rounds <= 10000;
+            }
+            if (g_mltree.eps_given) {
+                g_mltree.eps = strtod(g_mltree.eps_text.c_str(), &end);
+                eps_ok = !g_mltree.eps_text.empty() && *end == '\0' && g_mltree.eps >= 0.0 && g_mltree.eps < INFINITY;
+            }
+            const char *why = !g_mltree.tree_given ? "--ml_sites, --ml_rounds and --ml_epsilon need --ml_tree"
+                              : !rounds_ok ? "--ml_rounds takes a number of rounds from 1 to 10000"
+                              : !eps_ok ? "--ml_epsilon takes a number X >= 0"
+                              : cmdlineopts.wlsrefine_flag ? "--ml_tree cannot be combined with -W"
+                              : cmdlineopts.reroot_flag ? "--ml_tree cannot be combined with -r"
+                              : !topo_file.empty() ? "--ml_tree cannot be combined with --topology" : nullptr;
+            if (why) { std::cerr << "ERROR:" << why << std::endl; return 2; }
         }
         if (cmdlineopts.reroot_flag && (cmdlineopts.ancestral_flag || !cmdlineopts.profile_file.empty())) {
             std::cerr << "ERROR:--ancestral_seqs and --profile_out cannot be combined with -r (the root search keeps no ancestral profiles)" << std::endl;
@@ -850,6 +942,7 @@ int main(int argc, char **argv) {
         fam.seqs = read_fasta(cmdlineopts.sequence_file, fam.input_order);
         if (g_bootstrap.given && fam.seqs.size() < 4) error("--bootstrap needs at least 4 sequences");
         if (g_guidance.given && fam.seqs.size() < 4) error("--guidance needs at least 4 sequences");
+        if (g_mltree.tree_given && fam.seqs.size() < 3) error("--ml_tree needs at least 3 sequences");
         std::ofstream custom_out;
         std::ostream *out = &std::cout;
         if (!cmdlineopts.output_file.empty()) {

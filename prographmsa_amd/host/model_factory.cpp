@@ -307,6 +307,13 @@ void ModelFactory::fillP(Model &model) const {
     model.Q = Q_;
 }
 
+std::vector<double> ModelFactory::transition(distance_t t) const {
+    Model model;
+    model.distance = t;
+    fillP(model);
+    return model.P;
+}
+
 Model ModelFactory::getModel(distance_t distance) const {
     Model model;
     parseDistance(distance, model);
@@ -327,3 +334,6 @@ Model ModelFactory::getModel(distance_t distance, distance_t gap_distance) const
 }
 
 }  // namespace pgm
+
+// --ml_tree: tree likelihood, its derivatives and the branch-length optimiser (kept in a file of their own, built with this unit)
+#include "treelik.inc"

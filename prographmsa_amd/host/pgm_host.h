@@ -113,6 +113,8 @@ public:
     static ModelFactory *getDefault(const Alphabet &a, const std::map<std::string, sequence_t> &seqs);
     Model getModel(distance_t distance) const;                   // ModelFactory.h:48-67
     Model getModel(distance_t distance, distance_t gap_distance) const;  // :70-90
+    // P(t) = exp(Q t) as getModel builds it, for the distance t itself (none of parseDistance's clamps): dim x dim column-major
+    std::vector<double> transition(distance_t t) const;
     double getEpsilon(distance_t) const { return cmdlineopts.gapext_prob; }
     double getDelta(distance_t distance) const;
     int dim() const { return dim_; }
@@ -260,6 +262,8 @@ struct HostSwitches {
     bool host_bionj = false;     // PGM_HOST_BIONJ: the joins of every guide tree by the host loop
     bool host_transfer = false;    // PGM_HOST_TRANSFER: the transfer indices of --bootstrap_tbe and the counts of --bootstrap_taxa by the host loop (same integers)
     bool device_transfer = false;  // PGM_DEVICE_TRANSFER: ... by pgm_transfer_min / pgm_transfer_taxa at every size
+    bool host_treelik = false;     // PGM_HOST_TREELIK: the likelihood evaluations of --ml_tree by the host loop (same bits)
+    bool device_treelik = false;   // PGM_DEVICE_TREELIK: ... by pgm_tree_likelihood at every size
     std::string describe() const;   // the switches that are on, comma separated ("" = the product's defaults)
 };
 const HostSwitches &host_switches();
@@ -333,6 +337,10 @@ struct Backend {
     // and counted (nref), overwritten.  The default is the host statement, transfer_taxa_host.
     virtual void transfer_taxa(uint32_t nleaves, uint32_t nref, const uint64_t *ref, const uint32_t *thr, uint32_t nrep, const uint32_t *rep_off,
                                const uint64_t *rep, uint32_t *phi, uint32_t *arg, uint32_t *moved, uint32_t *counted, int worker = 0);
+    // The site likelihoods of an alignment on a rooted tree and the derivatives of lnL by every branch length (--ml_tree;
+    // include/pgm_hip.h: pgm_tree_likelihood).  The default is the host statement, tree_likelihood_host: the same bits.
+    virtual void tree_likelihood(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
+                                 const double *P, int derivs, double *site_l, int32_t *site_k, double *d1, double *d2, int worker = 0);
     // calls the host code made of the align-batch entry and of the distance entries (all-pairs tiles, pair counts, cosine, ML
     // distances): `pgmsa --batch --stats` shows with them that a stage was shared by the families of a chunk
     std::atomic<uint64_t> calls_align{0}, calls_dist{0};
@@ -719,6 +727,47 @@ void transfer_taxa_host(uint32_t nleaves, uint32_t nref, const uint64_t *ref, co
 TaxaSupport taxa_support(const PhyTree &tree, const std::vector<const PhyTree *> &replicates, double cutoff, Backend *be = nullptr);
 std::string taxa_text(const TaxaSupport &t, double cutoff);
 std::string taxa_edges_text(const TaxaSupport &t);
+
+// --ml_tree: the likelihood of an alignment on a rooted tree and maximum-likelihood branch lengths on its fixed topology
+// (host/treelik.inc).
+// tree_likelihood_host: pgm_tree_likelihood (include/pgm_hip.h) by a loop over the sites on the host threads, the same contract and
+//   the same bits; what it rejects is an error().  Backend::tree_likelihood's default.
+// MlTreeTopology: the nodes of a tree numbered children before parents, the leaves first in sorted-name order, the inner nodes in
+//   post-order, the root last; edge e is the edge above node e.
+// treelik_matrices: P(t_e), Q P(t_e), Q Q P(t_e) of every edge back to back (derivs) or P(t_e) alone, as pgm_tree_likelihood reads them.
+// treelik_lnl: sum over the sites of log(site_l) - 256 ln 2 site_k, sites ascending; site_lnl (may be null) gets the terms.
+// ml_branch_lengths: the optimiser.  rows: the alignment's rows in sorted-name order as state values (0..dim-1, -1 a gap, -2 a residue
+//   without a value), all of one length.  be: the backend whose tree_likelihood runs, nullptr for the host loop.
+const double kMlMinLength = 1e-6, kMlMaxLength = 10.0;   // the interval every branch length stays in
+// alignments of this many taxa and more go to the device by default: the smallest size at which the two routes were timed, and the
+// device was faster there and at every larger one (measured once); below it the host loop runs, untimed
+const uint32_t kTreelikDeviceMin = 24;
+struct MlTreeStats {   // `pgmsa --ml_tree --stats`
+    double seconds = 0, kernel_ms = 0, lnl_start = 0, lnl = 0;
+    uint64_t rounds = 0, evaluations = 0;
+};
+extern MlTreeStats ml_tree_stats;
+struct MlTreeTopology {
+    uint32_t nleaves = 0, nnodes = 0;
+    std::vector<uint32_t> parent;           // nnodes, the root's: UINT32_MAX
+    std::vector<const PhyTree *> node;      // nnodes
+    std::vector<std::string> names;         // the leaves' names, sorted
+};
+MlTreeTopology ml_tree_topology(const PhyTree &tree);
+void tree_likelihood_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
+                          const double *P, int derivs, double *site_l, int32_t *site_k, double *d1, double *d2);
+void treelik_matrices(const ModelFactory &mf, const std::vector<double> &t /* nnodes - 1 */, bool derivs, std::vector<double> &P);
+double treelik_lnl(uint32_t ncols, const double *site_l, const int32_t *site_k, double *site_lnl);
+struct MlTreeResult {
+    std::vector<double> lengths;    // per edge (node below it)
+    std::vector<double> site_lnl;   // per column, at `lengths`
+    double lnl_start = 0, lnl = 0;
+    uint32_t rounds = 0, evaluations = 0;
+};
+MlTreeResult ml_branch_lengths(const Alphabet &a, const std::vector<std::vector<int8_t>> &rows, const ModelFactory &model_factory, const PhyTree &tree,
+                               uint32_t rounds, double eps, Backend *be = nullptr);
+// a copy of `tree` whose edge above topo.node[e] has length lengths[e]
+PhyTree *ml_tree_with_lengths(const MlTreeTopology &topo, const std::vector<double> &lengths);
 
 std::string data_dir();   // directory holding wag.qmat etc.
 
