@@ -1,10 +1,5 @@
 // pgm_agreement_capi.inc — C ABI of the residue-pair agreement counts of pgmsa --guidance (included by pgm_capi.hip).
 // One upload of `where`, the two kernels of pgm_agreement_kernels.h on the zeroed outputs, one copy back of each.
-namespace {
-// scratch slots (see scratch_dev): 31 = where, 32 = res_hits followed by pair_hits
-enum { SC_AGREE_IN = 31, SC_AGREE_OUT = 32 };
-}  // namespace
-
 extern "C" float pgm_agreement_last_kernel_ms(pgm_ctx *ctx) { return ctx ? ctx->agree_ms : 0.0f; }
 
 extern "C" int pgm_msa_agreement(pgm_ctx *ctx, uint32_t nrows, uint32_t ncols, uint32_t nrep, const int32_t *where, uint32_t *res_hits,
@@ -22,32 +17,26 @@ extern "C" int pgm_msa_agreement(pgm_ctx *ctx, uint32_t nrows, uint32_t ncols, u
     if (!where || !res_hits || !pair_hits) return fail(PGM_ERR_INVALID, "null argument");
     const size_t in_bytes = sizeof(int32_t) * (size_t)nrep * nrows * ncols;
     const size_t res_bytes = sizeof(uint32_t) * (size_t)nrows * ncols, pair_bytes = sizeof(uint32_t) * (size_t)nrows * nrows;
-    HIPCHK(hipSetDevice(ctx->device));
+    StageCall c(ctx, "msa agreement", &ctx->agree_ms);
     int32_t *d_where = nullptr; uint8_t *d_out = nullptr;
-    hipError_t e = scratch_dev(ctx, SC_AGREE_IN, in_bytes, (void **)&d_where);
-    if (e == hipSuccess) e = scratch_dev(ctx, SC_AGREE_OUT, res_bytes + pair_bytes, (void **)&d_out);
-    if (e == hipSuccess) e = scratch_events(ctx);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("msa agreement: ") + hipGetErrorString(e));
+    c.buf(pgm_ctx::SC_AGREE_IN, in_bytes, &d_where);
+    c.buf(pgm_ctx::SC_AGREE_OUT, res_bytes + pair_bytes, &d_out);
     uint32_t *d_res = (uint32_t *)d_out, *d_pair = (uint32_t *)(d_out + res_bytes);
-    hipStream_t s = ctx->stream;
-    HIPCHK(hipMemcpyAsync(d_where, where, in_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemsetAsync(d_out, 0, res_bytes + pair_bytes, s));
+    c.up(d_where, where, in_bytes);
+    c.zero(d_out, res_bytes + pair_bytes);
     // workgroups per tile along the reduced axis: about four workgroups per CU in all, never more than there are chunks / replicates
     const uint64_t want = 4ull * (uint64_t)std::max(1, ctx->prop.multiProcessorCount);
     const uint64_t nchunks = (uint64_t)nrep * (((uint64_t)ncols + PGM_AGREE_K - 1) / PGM_AGREE_K);
     const uint32_t psplit = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(nchunks, 65535), (want + npair_tiles - 1) / npair_tiles));
     const uint32_t rsplit = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(nrep, 65535), (want + nres_tiles - 1) / nres_tiles));
-    HIPCHK(hipEventRecord(ctx->sc_ev[0], s));
-    hipLaunchKernelGGL(pgm_agreement_pairs_kernel, dim3((uint32_t)npair_tiles, psplit), dim3(256), 0, s, (const int32_t *)d_where, nrows, ncols, nrep,
-                       (uint32_t)ntile, d_pair);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(pgm_agreement_residues_kernel, dim3((uint32_t)nres_tiles, rsplit), dim3(256), 0, s, (const int32_t *)d_where, nrows, ncols, nrep,
-                       (uint32_t)ctiles, d_res);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->sc_ev[1], s));
-    HIPCHK(hipMemcpyAsync(res_hits, d_res, res_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(pair_hits, d_pair, pair_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipEventElapsedTime(&ctx->agree_ms, ctx->sc_ev[0], ctx->sc_ev[1]));
-    return PGM_OK;
+    if (c.begin()) {
+        hipLaunchKernelGGL(pgm_agreement_pairs_kernel, dim3((uint32_t)npair_tiles, psplit), dim3(256), 0, c.s, (const int32_t *)d_where, nrows, ncols, nrep,
+                           (uint32_t)ntile, d_pair);
+        hipLaunchKernelGGL(pgm_agreement_residues_kernel, dim3((uint32_t)nres_tiles, rsplit), dim3(256), 0, c.s, (const int32_t *)d_where, nrows, ncols, nrep,
+                           (uint32_t)ctiles, d_res);
+    }
+    c.end();
+    c.down(res_hits, d_res, res_bytes);
+    c.down(pair_hits, d_pair, pair_bytes);
+    return c.finish();
 }

@@ -3,11 +3,6 @@
 // (plain launches on the context's stream: stream order is the only dependency), and copies the join log and final_d back in
 // one copy behind one synchronisation.  With a plan of joins (pgm_bionj_plan_multi) the kernels are two launches in all: the
 // preparation, then every join of every family.
-namespace {
-// scratch slots (see scratch_dev): 28 = D, T, V; 29 = sums, column minima, descriptors, index lists; 30 = join log + final_d
-enum { SC_BIONJ_MAT = 28, SC_BIONJ_VEC = 29, SC_BIONJ_OUT = 30 };
-}  // namespace
-
 extern "C" float pgm_bionj_last_kernel_ms(pgm_ctx *ctx) { return ctx ? ctx->bionj_ms : 0.0f; }
 extern "C" uint32_t pgm_bionj_last_launches(pgm_ctx *ctx) { return ctx ? ctx->bionj_launches : 0u; }
 
@@ -52,55 +47,51 @@ int bionj_run(pgm_ctx *ctx, uint32_t nfam, const uint32_t *n, const double *D, c
                  o_act1 = o_act0 + 4 * sum_n, o_brow = o_act1 + 4 * sum_n, o_plan = o_brow + 4 * sum_n,
                  vec_bytes = o_plan + (plan ? sizeof(pgm_bionj_pair) * sum_j : 0);   // (the plan behind the rest: uploaded)
     const size_t out_joins = sizeof(pgm_bionj_join) * sum_j, out_bytes = out_joins + 8 * 9 * (size_t)nfam;
-    std::vector<uint8_t> img(o_act0 - o_fam + 4 * sum_n);
-    memcpy(img.data(), fam.data(), sizeof(PgmBionjFam) * nfam);
+    HostImage img(1);   // (the device layout of o_fam .. o_act1: no padding)
+    img.put(fam.data(), sizeof(PgmBionjFam) * nfam);
     {
-        uint32_t *a = (uint32_t *)(img.data() + (o_act0 - o_fam));
+        const size_t o = img.put(nullptr, 4 * sum_n);
+        uint32_t *a = (uint32_t *)(img.bytes.data() + o);
         for (uint32_t f = 0; f < nfam; ++f)
             for (uint32_t i = 0; i < n[f]; ++i) a[fam[f].voff + i] = i;
     }
-    HIPCHK(hipSetDevice(ctx->device));
+    StageCall c(ctx, "bionj", &ctx->bionj_ms);
     uint8_t *d_mat = nullptr, *d_vec = nullptr, *d_out = nullptr;
-    hipError_t e = scratch_dev(ctx, SC_BIONJ_MAT, 3 * 8 * (size_t)sum_nn, (void **)&d_mat);
-    if (e == hipSuccess) e = scratch_dev(ctx, SC_BIONJ_VEC, vec_bytes, (void **)&d_vec);
-    if (e == hipSuccess) e = scratch_dev(ctx, SC_BIONJ_OUT, out_bytes, (void **)&d_out);
-    if (e == hipSuccess) e = scratch_events(ctx);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("bionj: ") + hipGetErrorString(e));
+    c.buf(pgm_ctx::SC_BIONJ_MAT, 3 * 8 * (size_t)sum_nn, &d_mat);
+    c.buf(pgm_ctx::SC_BIONJ_VEC, vec_bytes, &d_vec);
+    c.buf(pgm_ctx::SC_BIONJ_OUT, out_bytes, &d_out);
     PgmBionjDev S;
     S.fam = (const PgmBionjFam *)(d_vec + o_fam); S.nfam = nfam;
     S.D = (double *)d_mat; S.T = S.D + sum_nn; S.V = S.T + sum_nn;
     S.act[0] = (uint32_t *)(d_vec + o_act0); S.act[1] = (uint32_t *)(d_vec + o_act1);
     S.sums = (double *)(d_vec + o_sums); S.best_q = (double *)(d_vec + o_bq); S.best_row = (uint32_t *)(d_vec + o_brow);
     S.joins = (pgm_bionj_join *)d_out; S.final_d = (double *)(d_out + out_joins);
-    hipStream_t s = ctx->stream;
-    HIPCHK(hipMemcpyAsync(S.D, D, 8 * (size_t)sum_nn, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(S.V, V, 8 * (size_t)sum_nn, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_vec + o_fam, img.data(), img.size(), hipMemcpyHostToDevice, s));
-    if (plan) HIPCHK(hipMemcpyAsync(d_vec + o_plan, plan, sizeof(pgm_bionj_pair) * sum_j, hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(ctx->sc_ev[0], s));
+    hipStream_t s = c.s;
+    c.up(S.D, D, 8 * (size_t)sum_nn);
+    c.up(S.V, V, 8 * (size_t)sum_nn);
+    c.up(d_vec + o_fam, img.bytes.data(), img.bytes.size());
+    if (plan) c.up(d_vec + o_plan, plan, sizeof(pgm_bionj_pair) * sum_j);
     const uint32_t gy = std::min(nfam, 65535u), gz = (nfam + gy - 1) / gy;
     uint32_t launches = 0;
-    if (plan) {   // the clamp of every matrix, then one workgroup per family for all of its joins
+    const bool go = c.begin();
+    if (go && plan) {   // the clamp of every matrix, then one workgroup per family for all of its joins
         const uint32_t gx = (uint32_t)std::min<uint64_t>(((uint64_t)nmax * nmax + 255u) / 256u, 1024u);
         hipLaunchKernelGGL(pgm_bionj_prepare_kernel, dim3(gx, gy, gz), dim3(256), 0, s, S);
         hipLaunchKernelGGL(pgm_bionj_plan_kernel, dim3(1, gy, gz), dim3(256), 0, s, S, (const pgm_bionj_pair *)(d_vec + o_plan));
-        HIPCHK(hipGetLastError());
         launches = 2;
     } else {
-        for (uint32_t step = 0; step + 3u < nmax; ++step) {
+        for (uint32_t step = 0; go && step + 3u < nmax; ++step) {
             const dim3 cols((nmax - step + PGM_BIONJ_COLS - 1) / PGM_BIONJ_COLS, gy, gz);
             hipLaunchKernelGGL(pgm_bionj_sums_kernel, cols, dim3(64 * PGM_BIONJ_COLS), 0, s, S, step);
             hipLaunchKernelGGL(pgm_bionj_scan_kernel, cols, dim3(64 * PGM_BIONJ_COLS), 0, s, S, step);
             hipLaunchKernelGGL(pgm_bionj_join_kernel, dim3(1, gy, gz), dim3(256), 0, s, S, step);
-            HIPCHK(hipGetLastError());
             launches += 3;
         }
     }
-    HIPCHK(hipEventRecord(ctx->sc_ev[1], s));
+    c.end();
     std::vector<uint8_t> back(out_bytes);
-    HIPCHK(hipMemcpyAsync(back.data(), d_out, out_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipEventElapsedTime(&ctx->bionj_ms, ctx->sc_ev[0], ctx->sc_ev[1]));
+    c.down(back.data(), d_out, out_bytes);
+    if (int rc = c.finish()) return rc;
     memcpy(joins, back.data(), out_joins);
     memcpy(final_d, back.data() + out_joins, out_bytes - out_joins);
     ctx->bionj_launches = launches;

@@ -72,9 +72,40 @@ struct pgm_ctx {
     float transfer_ms = 0;                  // --bootstrap_tbe / --bootstrap_taxa transfer entries: device time of the last call
     float treelik_ms = 0;                   // --ml_tree likelihood evaluations: device time of the last call
     uint32_t bionj_launches = 0;            // BioNJ: device time and kernels of the last call
-    // grow-only scratch buffers of the all-pairs / context-profile calls (slot = position in the call's buffer list): a
-    // guide-tree stage issues many calls (one per pair tile), hipMalloc / hipFree of up to 2 GB per call would dominate them
-    enum { SC_DEV = 41, SC_HOST = 4 };
+    // grow-only scratch buffers of the satellite calls (StageCall): a guide-tree stage issues many calls, hipMalloc / hipFree of
+    // up to 2 GB per call would dominate them.  The calls of one context are serial; a slot belongs to the stage named beside it
+    // and keeps its buffer between that stage's calls.  (The all-pairs stage has buffers of its own: PgmNwState.)
+    enum {
+        SC_DIST,                            // the distance entries (pgm_dist_capi.inc), shared among them: SC_DIST + position in
+        SC_DIST_END = SC_DIST + 9,          //   the call's buffer list (the longest list, pgm_mldist_batch's, has 9 buffers)
+        SC_CS = SC_DIST_END,                // the context-profile batch: SC_CS + position in its buffer list
+        SC_CS_END = SC_CS + 8,
+        SC_MERGE_OUT = SC_CS_END,           // merged profiles of a call that is not resident
+        SC_PARS_IN,                         // gap masks and gap parsimony: input image
+        SC_PARS_OUT,                        //   outputs and the parsimony consensus scratch
+        SC_WLS_MAT,                         // WLS: the (D, W) matrix of pgm_wls_load, read by every later pgm_wls_pair_sums_batch
+        SC_WLS_IN,                          //   job image
+        SC_WLS_PART,                        //   block partials
+        SC_WLS_OUT,                         //   results
+        SC_BIONJ_MAT,                       // BioNJ: D, T, V
+        SC_BIONJ_VEC,                       //   sums, column minima, descriptors, index lists, plan
+        SC_BIONJ_OUT,                       //   join log + final_d
+        SC_AGREE_IN,                        // agreement counts: where
+        SC_AGREE_OUT,                       //   res_hits followed by pair_hits
+        SC_TRANSFER_REF,                    // pgm_transfer_min and pgm_transfer_taxa (shared): reference sets, rep_off, thresholds
+        SC_TRANSFER_REP,                    //   replicate sets
+        SC_TRANSFER_OUT,                    //   phi (taxa: phi, arg, flip, moved, counted)
+        SC_TREELIK_TREE,                    // tree likelihood: children lists, pi, rows
+        SC_TREELIK_P,                       //   the matrices
+        SC_TREELIK_U,                       //   partials and outside vectors
+        SC_TREELIK_G,                       //   per-site ratios and chunk sums
+        SC_TREELIK_OUT,                     //   the outputs
+        SC_DEV
+    };
+    enum {
+        SH_PROFILES_OUT,                    // pinned: the profiles of a merge / context-profile call on their way to the caller (shared)
+        SC_HOST
+    };
     void *sc_dev[SC_DEV] = {};
     size_t sc_dev_bytes[SC_DEV] = {};
     void *sc_host[SC_HOST] = {};      // pinned
@@ -340,6 +371,84 @@ static hipError_t scratch_events(pgm_ctx *ctx) {
         if (!ctx->sc_ev[k]) { hipError_t e = hipEventCreate(&ctx->sc_ev[k]); if (e != hipSuccess) return e; }
     return hipSuccess;
 }
+
+// `bytes` of the context's resident memory (bump allocation over chunks, in steps of 256 bytes): valid until pgm_resident_reset
+static hipError_t resident_alloc(pgm_ctx *ctx, size_t bytes, uint8_t **out) {
+    bytes = (bytes + 255) / 256 * 256;
+    while (ctx->res_chunk < ctx->res_chunks.size() && ctx->res_off + bytes > ctx->res_chunks[ctx->res_chunk].cap) { ++ctx->res_chunk; ctx->res_off = 0; }
+    if (ctx->res_chunk == ctx->res_chunks.size()) {
+        pgm_ctx::ResChunk c{nullptr, std::max<size_t>(bytes, (size_t)96 << 20)};
+        const hipError_t e = hipMalloc((void **)&c.p, c.cap);
+        if (e != hipSuccess) return e;
+        ctx->res_chunks.push_back(c); ctx->res_off = 0;
+    }
+    *out = ctx->res_chunks[ctx->res_chunk].p + ctx->res_off;
+    ctx->res_off += bytes;
+    return hipSuccess;
+}
+
+// The inputs of a call packed into one host image for one upload; put() returns the offset of its block (a multiple of `align`).
+struct HostImage {
+    size_t align;
+    std::vector<uint8_t> bytes;
+    explicit HostImage(size_t a = 256) : align(a) {}
+    size_t put(const void *src, size_t n) {
+        const size_t o = bytes.size();
+        bytes.resize(o + (n + align - 1) / align * align);
+        if (src && n) memcpy(bytes.data() + o, src, n);   // (src NULL: room only, filled in later)
+        return o;
+    }
+};
+
+// A device buffer of a call whose scratch slot is its place in the call's list (StageCall::bufs).  src: uploaded before the launch;
+// dst: copied back behind it; zero: cleared before it.
+struct Buf { void **p; size_t bytes; const void *src; void *dst; bool zero; };
+
+// One satellite call on the context's stream — every C entry but the all-pairs stage and the align batch: scratch buffers, uploads,
+// the launches between the two events of the stage's timer, the copies back, one synchronisation.  Every method does nothing after
+// the first error.  finish() synchronises the stream whenever something was queued, after a failure too: the queued copies read
+// and write host memory of the call (its locals, the caller's arrays), so no entry returns before them.
+struct StageCall {
+    pgm_ctx *ctx;
+    const char *what;   // opens the message of a device failure
+    float *ms;          // the stage's timer (NULL: none)
+    hipStream_t s;
+    hipError_t e;
+    bool alloc_failed = false, queued = false, timed = false;
+    StageCall(pgm_ctx *c, const char *w, float *t) : ctx(c), what(w), ms(t), s(c->stream), e(hipSetDevice(c->device)) {}
+    bool ok() const { return e == hipSuccess; }
+    // the result of an allocation (PGM_ERR_NOMEM comes from these alone)
+    void alloc(hipError_t r) { e = r; alloc_failed = r != hipSuccess; }
+    template <class T> void buf(int slot, size_t bytes, T **p) { if (ok()) alloc(scratch_dev(ctx, slot, bytes, (void **)p)); }
+    template <class T> void host(int slot, size_t bytes, T **p) { if (ok()) alloc(scratch_host(ctx, slot, bytes, (void **)p)); }
+    template <class T> void resident(size_t bytes, T **p) { if (ok()) alloc(resident_alloc(ctx, bytes, (uint8_t **)p)); }
+    void up(void *dst, const void *src, size_t bytes) { if (ok() && bytes) { queued = true; e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s); } }
+    void zero(void *dst, size_t bytes) { if (ok() && bytes) { queued = true; e = hipMemsetAsync(dst, 0, bytes, s); } }
+    void down(void *dst, const void *src, size_t bytes) { if (ok() && bytes) { queued = true; e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s); } }
+    // the buffers of a list in the slots [first, end): taken and, where they have a source, uploaded in the list's order
+    void bufs(int first, int end, std::initializer_list<Buf> list) {
+        if (ok() && (size_t)(end - first) < list.size()) e = hipErrorInvalidValue;   // (a list longer than its range of pgm_ctx's slot table)
+        for (const Buf &b : list) { buf(first++, b.bytes, b.p); if (b.src) up(*b.p, b.src, b.bytes); }
+    }
+    // begin() ... launches ... end(): the two events of the timer; true: launch
+    bool begin() {
+        if (ok()) e = scratch_events(ctx);
+        if (ok()) { queued = true; e = hipEventRecord(ctx->sc_ev[0], s); }
+        return ok();
+    }
+    void end() {
+        if (ok()) e = hipGetLastError();
+        if (ok()) e = hipEventRecord(ctx->sc_ev[1], s);
+        timed = ok();
+    }
+    int finish() {
+        if (queued) { const hipError_t es = hipStreamSynchronize(s); if (ok()) e = es; }
+        if (ok() && timed && ms) (void)hipEventElapsedTime(ms, ctx->sc_ev[0], ctx->sc_ev[1]);
+        if (ok()) return PGM_OK;
+        (void)hipGetLastError();
+        return fail(alloc_failed && e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+    }
+};
 
 // classes of the nodes of the lean jobs (PgmJob::cls1): once per batch, behind the upload of the inputs and the job descriptors
 static hipError_t classify_lean_jobs(pgm_ctx *ctx, pgm_align_batch *b) {

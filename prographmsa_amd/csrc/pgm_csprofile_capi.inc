@@ -32,7 +32,6 @@ static int csprofile_create_batch_impl(pgm_ctx *ctx, uint32_t nseq, const int8_t
     if (nseq && (!syms || !offs || !tau || !pi || !p_uniform || (!dev && (!out || !out_offs)))) return fail(PGM_ERR_INVALID, "null argument");
     ctx->cs_ms = 0;
     if (nseq == 0) return PGM_OK;
-    HIPCHK(hipSetDevice(ctx->device));
     std::vector<uint64_t> own_offs;
     if (dev) {
         own_offs.assign((size_t)nseq + 1, 0);
@@ -55,51 +54,30 @@ static int csprofile_create_batch_impl(pgm_ctx *ctx, uint32_t nseq, const int8_t
     uint32_t *d_offs = nullptr, *d_pos = nullptr;
     double *d_tau = nullptr, *d_pi = nullptr, *d_pu = nullptr, *d_out = nullptr;
     uint64_t *d_oo = nullptr;
-    struct Buf { void **p; size_t bytes; const void *src; };
-    Buf bufs[] = {{(void **)&d_syms, std::max(total, 1u), syms}, {(void **)&d_offs, 4 * (size_t)(nseq + 1), offs},
-                  {(void **)&d_pos, 4 * (size_t)std::max(total, 1u), pos_seq.data()}, {(void **)&d_tau, 8 * (size_t)nseq, tau},
-                  {(void **)&d_pi, 8 * 20, pi}, {(void **)&d_pu, 8 * (size_t)nseq * 20, p_uniform},
-                  {(void **)&d_oo, 8 * (size_t)(nseq + 1), out_offs}, {(void **)&d_out, dev ? 16 : 8 * out_n, nullptr}};
-    hipError_t e = hipSuccess;
-    hipStream_t s = ctx->stream;
-    int slot_ix = 12;   // scratch slots 12.. of the context (0..11: the all-pairs call)
-    for (auto &b : bufs) {
-        if (e == hipSuccess) e = scratch_dev(ctx, slot_ix++, b.bytes, b.p);
-        if (e == hipSuccess && b.src) e = hipMemcpyAsync(*b.p, b.src, b.bytes, hipMemcpyHostToDevice, s);
-    }
-    if (dev && e == hipSuccess) {   // the output in the resident arena (bump allocation, as pgm_resident_onehot)
-        const size_t need = (8 * out_n + 255) / 256 * 256;
-        while (ctx->res_chunk < ctx->res_chunks.size() && ctx->res_off + need > ctx->res_chunks[ctx->res_chunk].cap) { ++ctx->res_chunk; ctx->res_off = 0; }
-        if (ctx->res_chunk == ctx->res_chunks.size()) {
-            pgm_ctx::ResChunk c{nullptr, std::max<size_t>(need, (size_t)96 << 20)};
-            e = hipMalloc((void **)&c.p, c.cap);
-            if (e == hipSuccess) { ctx->res_chunks.push_back(c); ctx->res_off = 0; }
-        }
-        if (e == hipSuccess) { d_out = (double *)(ctx->res_chunks[ctx->res_chunk].p + ctx->res_off); ctx->res_off += need; }
-    }
+    StageCall c(ctx, "csprofile", &ctx->cs_ms);
+    c.bufs(pgm_ctx::SC_CS, pgm_ctx::SC_CS_END,
+           {{(void **)&d_syms, std::max(total, 1u), syms}, {(void **)&d_offs, 4 * (size_t)(nseq + 1), offs},
+            {(void **)&d_pos, 4 * (size_t)std::max(total, 1u), pos_seq.data()}, {(void **)&d_tau, 8 * (size_t)nseq, tau},
+            {(void **)&d_pi, 8 * 20, pi}, {(void **)&d_pu, 8 * (size_t)nseq * 20, p_uniform},
+            {(void **)&d_oo, 8 * (size_t)(nseq + 1), out_offs}, {(void **)&d_out, dev ? 16 : 8 * out_n}});
     double *h_out = nullptr;
-    if (e == hipSuccess && !dev) e = scratch_host(ctx, 2, 8 * out_n, (void **)&h_out);
-    if (e == hipSuccess) e = scratch_events(ctx);
-    hipEvent_t e0 = ctx->sc_ev[0], e1 = ctx->sc_ev[1];
-    if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, 8 * out_n, s);  // sequences of length 0 keep their two zero columns
-    if (e == hipSuccess && total) {
+    if (dev) c.resident(8 * out_n, &d_out);   // the output in the context's resident memory
+    else c.host(pgm_ctx::SH_PROFILES_OUT, 8 * out_n, &h_out);
+    c.zero(d_out, 8 * out_n);  // sequences of length 0 keep their two zero columns
+    if (total && c.begin()) {
         PgmCsArgs A;
         A.K = ctx->csK; A.ncols = ctx->csC; A.nseq = nseq;
         A.lprofiles = ctx->cs_lprofiles;
         A.syms = d_syms; A.offs = d_offs; A.pos_seq = d_pos; A.tau = d_tau; A.pi = d_pi; A.p_uniform = d_pu;
         A.out = d_out; A.out_offs = d_oo; A.total = total;
-        e = hipEventRecord(e0, s);
         const size_t cs_lds = sizeof(double) * PGM_CS_KC * (((size_t)A.ncols + 1) * 22);
-        hipLaunchKernelGGL(pgm_csprofile_kernel, dim3((total + 255) / 256), dim3(256), cs_lds, s, A);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(e1, s);
+        hipLaunchKernelGGL(pgm_csprofile_kernel, dim3((total + 255) / 256), dim3(256), cs_lds, c.s, A);
     }
-    if (e == hipSuccess && !dev) e = hipMemcpyAsync(h_out, d_out, 8 * out_n, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && total) (void)hipEventElapsedTime(&ctx->cs_ms, e0, e1);
-    if (e == hipSuccess && !dev) memcpy(out, h_out, 8 * out_n);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("csprofile: ") + hipGetErrorString(e));
+    if (total) c.end();
+    if (!dev) c.down(h_out, d_out, 8 * out_n);
+    if (int rc = c.finish()) return rc;
     if (dev) for (uint32_t q = 0; q < nseq; ++q) dev[q] = d_out + out_offs[q];
+    else memcpy(out, h_out, 8 * out_n);
     return PGM_OK;
 }
 

@@ -1,38 +1,16 @@
 // pgm_dist_capi.inc — C ABI of the distance-estimation stages (included by pgm_capi.hip).  Every entry is its argument checks, its
-// list of device buffers, the argument struct of its kernel and the launch; dist_run is the call path they share.
+// list of device buffers (Buf, in the slots SC_DIST..), the argument struct of its kernel and the launch.
 namespace {
-// A device buffer of a call.  Its place in the call's list is its scratch slot (the slots are shared with the all-pairs call: the
-// calls of one context are serial).  src: uploaded before the launch; dst: copied back behind it; zero: cleared before it.
-struct Buf { void **p; size_t bytes; const void *src; void *dst; bool zero; };
-
-// Stages the buffers, runs `launch` between the two events of ctx->ml_ms and copies the results back behind one synchronisation.
-// The stream is synchronised after a failure too: the queued copies read and write host memory of the call.
+// a StageCall whose buffers are one list: staged, `launch` timed into ctx->ml_ms, the results copied back
 template <class Launch>
 int dist_run(pgm_ctx *ctx, const char *what, std::initializer_list<Buf> bufs, const Launch &launch) {
-    HIPCHK(hipSetDevice(ctx->device));
-    hipError_t e = hipSuccess;
-    hipStream_t s = ctx->stream;
-    int slot_ix = 0;
-    for (const Buf &b : bufs) {
-        if (e == hipSuccess) e = scratch_dev(ctx, slot_ix++, b.bytes, b.p);
-        if (e == hipSuccess && b.src && b.bytes) e = hipMemcpyAsync(*b.p, b.src, b.bytes, hipMemcpyHostToDevice, s);
-    }
-    if (e == hipSuccess) e = scratch_events(ctx);
-    for (const Buf &b : bufs)
-        if (e == hipSuccess && b.zero) e = hipMemsetAsync(*b.p, 0, b.bytes, s);
-    if (e == hipSuccess) {
-        e = hipEventRecord(ctx->sc_ev[0], s);
-        launch(s);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(ctx->sc_ev[1], s);
-    }
-    for (const Buf &b : bufs)
-        if (e == hipSuccess && b.dst && b.bytes) e = hipMemcpyAsync(b.dst, *b.p, b.bytes, hipMemcpyDeviceToHost, s);
-    const hipError_t es = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = es;
-    if (e == hipSuccess) (void)hipEventElapsedTime(&ctx->ml_ms, ctx->sc_ev[0], ctx->sc_ev[1]);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-    return PGM_OK;
+    StageCall c(ctx, what, &ctx->ml_ms);
+    c.bufs(pgm_ctx::SC_DIST, pgm_ctx::SC_DIST_END, bufs);
+    for (const Buf &b : bufs) if (b.zero) c.zero(*b.p, b.bytes);
+    if (c.begin()) launch(c.s);
+    c.end();
+    for (const Buf &b : bufs) if (b.dst) c.down(b.dst, *b.p, b.bytes);
+    return c.finish();
 }
 }  // namespace
 

@@ -17,7 +17,8 @@ extern "C" int pgm_merge_profiles_batch_ex(pgm_ctx *ctx, uint32_t njobs, const p
     if (!ctx || (njobs && !jobs) || (flags & ~PGM_MERGE_RESIDENT) || (resident && njobs && !dev_profiles)) return fail(PGM_ERR_INVALID, "null argument");
     ctx->merge_ms = 0;
     if (njobs == 0) return PGM_OK;
-    HIPCHK(hipSetDevice(ctx->device));
+    StageCall c(ctx, "merge", &ctx->merge_ms);   // (the device is current from here on: merge_is_device)
+    if (!c.ok()) return c.finish();
     const uint32_t D = jobs[0].dim;
     if (D == 0 || D > 64) return fail(PGM_ERR_INVALID, "bad dimension");
     const int DP = D <= 32 ? 32 : 64, NB = 256 / DP;
@@ -45,26 +46,16 @@ extern "C" int pgm_merge_profiles_batch_ex(pgm_ctx *ctx, uint32_t njobs, const p
     const bool mprof = getenv("PGM_HOST_PROFILE") != nullptr;   // tools: where the time of the call goes
     auto now_ms = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double tm0 = now_ms();
-    hipError_t e = cache_take(ctx, pgm_ctx::C_HIN, in_bytes, (void **)&h_in, &cap_hin);
-    if (e == hipSuccess) e = cache_take(ctx, pgm_ctx::C_IN, in_bytes, (void **)&d_in, &cap_in);
+    // (given back when the call is over: behind finish(), which every return below goes through)
     struct GiveBack {
         pgm_ctx *c; uint8_t **h, **d; size_t *ch, *cd;
         ~GiveBack() { cache_give(c, pgm_ctx::C_HIN, *h, *ch); cache_give(c, pgm_ctx::C_IN, *d, *cd); }
     } give_back{ctx, &h_in, &d_in, &cap_hin, &cap_in};
-    if (e == hipSuccess && !resident) e = scratch_host(ctx, 2, out_bytes, (void **)&h_out);
-    if (e == hipSuccess && !resident) e = scratch_dev(ctx, 21, out_bytes, (void **)&d_out);
-    if (e == hipSuccess && resident) {
-        // resident results: bump allocation over the context's chunks; everything stays valid until pgm_resident_reset
-        while (ctx->res_chunk < ctx->res_chunks.size() && ctx->res_off + out_bytes > ctx->res_chunks[ctx->res_chunk].cap) { ++ctx->res_chunk; ctx->res_off = 0; }
-        if (ctx->res_chunk == ctx->res_chunks.size()) {
-            pgm_ctx::ResChunk c{nullptr, std::max<size_t>(out_bytes, (size_t)96 << 20)};
-            e = hipMalloc((void **)&c.p, c.cap);
-            if (e == hipSuccess) { ctx->res_chunks.push_back(c); ctx->res_off = 0; }
-        }
-        if (e == hipSuccess) { d_out = ctx->res_chunks[ctx->res_chunk].p + ctx->res_off; ctx->res_off += (out_bytes + 255) / 256 * 256; }
-    }
-    if (e == hipSuccess) e = scratch_events(ctx);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("merge: ") + hipGetErrorString(e));
+    c.alloc(cache_take(ctx, pgm_ctx::C_HIN, in_bytes, (void **)&h_in, &cap_hin));
+    if (c.ok()) c.alloc(cache_take(ctx, pgm_ctx::C_IN, in_bytes, (void **)&d_in, &cap_in));
+    if (resident) c.resident(out_bytes, &d_out);   // (valid until pgm_resident_reset)
+    else { c.host(pgm_ctx::SH_PROFILES_OUT, out_bytes, &h_out); c.buf(pgm_ctx::SC_MERGE_OUT, out_bytes, &d_out); }
+    if (!c.ok()) return c.finish();
     const double tm1 = now_ms();
     std::vector<PgmMergeJobDev> dj(njobs);
     size_t off = al(sizeof(PgmMergeJobDev) * njobs), ooff = 0;
@@ -96,20 +87,15 @@ extern "C" int pgm_merge_profiles_batch_ex(pgm_ctx *ctx, uint32_t njobs, const p
         (void)lib_pool().run(copies.size(), in_bytes > (8u << 20) ? 16u : 1u, [&](size_t k) { memcpy(h_in + copies[k].dst, copies[k].src, copies[k].bytes); });
     }
     const double tm2 = now_ms();
-    hipStream_t s = ctx->stream;
-    e = hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && blocks) {
+    c.up(d_in, h_in, in_bytes);
+    if (blocks && c.begin()) {
         const size_t lds = 8 * (2 * (size_t)D * D + 3 * (size_t)NB * D + NB);
-        e = hipEventRecord(ctx->sc_ev[0], s);
-        if (DP == 32) hipLaunchKernelGGL((pgm_merge_profiles_kernel<32>), dim3(blocks), dim3(256), lds, s, (const PgmMergeJobDev *)d_in, njobs);
-        else hipLaunchKernelGGL((pgm_merge_profiles_kernel<64>), dim3(blocks), dim3(256), lds, s, (const PgmMergeJobDev *)d_in, njobs);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(ctx->sc_ev[1], s);
+        if (DP == 32) hipLaunchKernelGGL((pgm_merge_profiles_kernel<32>), dim3(blocks), dim3(256), lds, c.s, (const PgmMergeJobDev *)d_in, njobs);
+        else hipLaunchKernelGGL((pgm_merge_profiles_kernel<64>), dim3(blocks), dim3(256), lds, c.s, (const PgmMergeJobDev *)d_in, njobs);
     }
-    if (e == hipSuccess && out_bytes && !resident) e = hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail(PGM_ERR_DEVICE, std::string("merge: ") + hipGetErrorString(e));
-    if (blocks) (void)hipEventElapsedTime(&ctx->merge_ms, ctx->sc_ev[0], ctx->sc_ev[1]);
+    if (blocks) c.end();
+    if (!resident) c.down(h_out, d_out, out_bytes);
+    if (int rc = c.finish()) return rc;
     const double tm3 = now_ms();
     if (resident) {
         for (uint32_t i = 0; i < njobs; ++i) dev_profiles[i] = (const double *)(d_out + out_off[i]);
@@ -144,15 +130,8 @@ extern "C" int pgm_resident_import(pgm_ctx *ctx, pgm_ctx *src_ctx, const double 
     if (!known) return fail(PGM_ERR_INVALID, "pgm_resident_import: not a resident address of the source context");
     HIPCHK(hipSetDevice(ctx->device));
     const size_t bytes = 8 * (size_t)count;
-    hipError_t e = hipSuccess;
     uint8_t *d_out = nullptr;
-    while (ctx->res_chunk < ctx->res_chunks.size() && ctx->res_off + bytes > ctx->res_chunks[ctx->res_chunk].cap) { ++ctx->res_chunk; ctx->res_off = 0; }
-    if (ctx->res_chunk == ctx->res_chunks.size()) {
-        pgm_ctx::ResChunk c{nullptr, std::max<size_t>(bytes, (size_t)96 << 20)};
-        e = hipMalloc((void **)&c.p, c.cap);
-        if (e == hipSuccess) { ctx->res_chunks.push_back(c); ctx->res_off = 0; }
-    }
-    if (e == hipSuccess) { d_out = ctx->res_chunks[ctx->res_chunk].p + ctx->res_off; ctx->res_off += (bytes + 255) / 256 * 256; }
+    hipError_t e = resident_alloc(ctx, bytes, &d_out);
     if (e == hipSuccess) e = ctx->device == src_ctx->device ? hipMemcpyAsync(d_out, src, bytes, hipMemcpyDeviceToDevice, ctx->stream)
                                                             : hipMemcpyPeerAsync(d_out, ctx->device, src, src_ctx->device, bytes, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -185,22 +164,9 @@ extern "C" int pgm_resident_onehot(pgm_ctx *ctx, uint32_t dim, uint32_t nseq, co
     std::vector<uint8_t> staging(in_bytes);
     uint8_t *h_in = staging.data(), *d_in = nullptr, *d_out = nullptr;
     t1 = now_ms();
-    hipError_t e = hipSuccess;
     t2 = now_ms();
-    {
-        const size_t need = (out_bytes + 255) / 256 * 256 + in_bytes;
-        while (ctx->res_chunk < ctx->res_chunks.size() && ctx->res_off + need > ctx->res_chunks[ctx->res_chunk].cap) { ++ctx->res_chunk; ctx->res_off = 0; }
-        if (ctx->res_chunk == ctx->res_chunks.size()) {
-            pgm_ctx::ResChunk c{nullptr, std::max<size_t>(need, (size_t)96 << 20)};
-            e = hipMalloc((void **)&c.p, c.cap);
-            if (e == hipSuccess) { ctx->res_chunks.push_back(c); ctx->res_off = 0; }
-        }
-        if (e == hipSuccess) {
-            d_out = ctx->res_chunks[ctx->res_chunk].p + ctx->res_off;
-            d_in = d_out + (out_bytes + 255) / 256 * 256;
-            ctx->res_off += (need + 255) / 256 * 256;
-        }
-    }
+    hipError_t e = resident_alloc(ctx, (out_bytes + 255) / 256 * 256 + in_bytes, &d_out);
+    d_in = d_out + (out_bytes + 255) / 256 * 256;
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("resident leaves: ") + hipGetErrorString(e));
     t3 = now_ms();
     memcpy(h_in, syms, nsym);

@@ -1,26 +1,12 @@
 // pgm_parsimony_capi.inc — C ABI of the root search's gap masks and gap parsimony (included by pgm_capi.hip).
 // The inputs of a call are packed into one host image, uploaded in one copy, and the outputs come back in one copy.
-namespace {
-struct ParsImage {
-    std::vector<uint8_t> bytes;
-    size_t put(const void *src, size_t n) {
-        const size_t o = bytes.size();
-        bytes.resize(o + (n + 255) / 256 * 256);
-        if (src && n) memcpy(bytes.data() + o, src, n);   // (src NULL: room only, filled in later)
-        return o;
-    }
-};
-// scratch slots of these calls (see scratch_dev): 22 = input image, 23 = outputs and the parsimony consensus scratch
-enum { SC_PARS_IN = 22, SC_PARS_OUT = 23 };
-}  // namespace
-
 extern "C" float pgm_parsimony_last_kernel_ms(pgm_ctx *ctx) { return ctx ? ctx->pars_ms : 0.0f; }
 
 extern "C" int pgm_gapmask_extend_batch(pgm_ctx *ctx, uint32_t njobs, const pgm_gapmask_job *jobs) {
     if (!ctx || (njobs && !jobs)) return fail(PGM_ERR_INVALID, "null argument");
     ctx->pars_ms = 0;
     if (njobs == 0) return PGM_OK;
-    ParsImage img;
+    HostImage img;
     std::vector<PgmGapmaskJobDev> dj(njobs);
     std::vector<size_t> src_off(njobs), rank_off(njobs), dst_off(njobs);
     size_t out_words = 0;
@@ -44,28 +30,22 @@ extern "C" int pgm_gapmask_extend_batch(pgm_ctx *ctx, uint32_t njobs, const pgm_
         out_words += (size_t)j.nrows * wo;
         dj[i].nrows = j.nrows; dj[i].words_in = wi; dj[i].ncols_out = j.ncols_out; dj[i].words_out = wo;
     }
-    HIPCHK(hipSetDevice(ctx->device));
+    StageCall c(ctx, "gap masks", &ctx->pars_ms);
     uint8_t *d_in = nullptr; uint64_t *d_out = nullptr;
-    hipError_t e = scratch_dev(ctx, SC_PARS_IN, img.bytes.size(), (void **)&d_in);
-    if (e == hipSuccess) e = scratch_dev(ctx, SC_PARS_OUT, 8 * out_words, (void **)&d_out);
-    if (e == hipSuccess) e = scratch_events(ctx);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("gap masks: ") + hipGetErrorString(e));
+    c.buf(pgm_ctx::SC_PARS_IN, img.bytes.size(), &d_in);
+    c.buf(pgm_ctx::SC_PARS_OUT, 8 * out_words, &d_out);
     for (uint32_t i = 0; i < njobs; ++i) {
         dj[i].src = (const uint64_t *)(d_in + src_off[i]);
         dj[i].rank = (const int32_t *)(d_in + rank_off[i]);
         dj[i].dst = d_out + dst_off[i];
     }
     memcpy(img.bytes.data(), dj.data(), sizeof(PgmGapmaskJobDev) * njobs);
-    hipStream_t s = ctx->stream;
-    HIPCHK(hipMemcpyAsync(d_in, img.bytes.data(), img.bytes.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(ctx->sc_ev[0], s));
-    hipLaunchKernelGGL(pgm_gapmask_extend_kernel, dim3(std::min<uint32_t>(njobs, 65535u)), dim3(256), 0, s, (const PgmGapmaskJobDev *)d_in, njobs);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->sc_ev[1], s));
     std::vector<uint64_t> out(out_words);
-    HIPCHK(hipMemcpyAsync(out.data(), d_out, 8 * out_words, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipEventElapsedTime(&ctx->pars_ms, ctx->sc_ev[0], ctx->sc_ev[1]));
+    c.up(d_in, img.bytes.data(), img.bytes.size());
+    if (c.begin()) hipLaunchKernelGGL(pgm_gapmask_extend_kernel, dim3(std::min<uint32_t>(njobs, 65535u)), dim3(256), 0, c.s, (const PgmGapmaskJobDev *)d_in, njobs);
+    c.end();
+    c.down(out.data(), d_out, 8 * out_words);
+    if (int rc = c.finish()) return rc;
     for (uint32_t i = 0; i < njobs; ++i)
         if (jobs[i].nrows && jobs[i].ncols_out) memcpy(jobs[i].dst, out.data() + dst_off[i], 8 * (size_t)jobs[i].nrows * dj[i].words_out);
     return PGM_OK;
@@ -75,7 +55,7 @@ extern "C" int pgm_gap_parsimony_batch(pgm_ctx *ctx, uint32_t njobs, const pgm_p
     if (!ctx || (njobs && (!jobs || !scores))) return fail(PGM_ERR_INVALID, "null argument");
     ctx->pars_ms = 0;
     if (njobs == 0) return PGM_OK;
-    ParsImage img;
+    HostImage img;
     std::vector<PgmParsimonyJobDev> dj(njobs);
     std::vector<size_t> mask_off(njobs), ch_off(njobs);
     uint64_t per_wg = 1;   // scratch words one workgroup needs: (nleaves - 2) internal consensus rows of nblocks words
@@ -104,27 +84,21 @@ extern "C" int pgm_gap_parsimony_batch(pgm_ctx *ctx, uint32_t njobs, const pgm_p
     // one workgroup per candidate, as many at a time as 256 MB of consensus scratch hold
     const uint64_t budget = (256ull << 20) / 8;
     const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({(uint64_t)njobs, budget / per_wg, 65535u}));
-    HIPCHK(hipSetDevice(ctx->device));
+    StageCall c(ctx, "gap parsimony", &ctx->pars_ms);
     uint8_t *d_in = nullptr, *d_out = nullptr;
     const size_t score_bytes = (4 * (size_t)njobs + 255) / 256 * 256;
-    hipError_t e = scratch_dev(ctx, SC_PARS_IN, img.bytes.size(), (void **)&d_in);
-    if (e == hipSuccess) e = scratch_dev(ctx, SC_PARS_OUT, score_bytes + 8 * per_wg * grid, (void **)&d_out);
-    if (e == hipSuccess) e = scratch_events(ctx);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("gap parsimony: ") + hipGetErrorString(e));
+    c.buf(pgm_ctx::SC_PARS_IN, img.bytes.size(), &d_in);
+    c.buf(pgm_ctx::SC_PARS_OUT, score_bytes + 8 * per_wg * grid, &d_out);
     for (uint32_t i = 0; i < njobs; ++i) {
         dj[i].masks = (const uint64_t *)(d_in + mask_off[i]);
         dj[i].children = (const uint32_t *)(d_in + ch_off[i]);
     }
     memcpy(img.bytes.data(), dj.data(), sizeof(PgmParsimonyJobDev) * njobs);
-    hipStream_t s = ctx->stream;
-    HIPCHK(hipMemcpyAsync(d_in, img.bytes.data(), img.bytes.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(ctx->sc_ev[0], s));
-    hipLaunchKernelGGL(pgm_gap_parsimony_kernel, dim3(grid), dim3(256), 0, s, (const PgmParsimonyJobDev *)d_in, njobs,
-                       (uint64_t *)(d_out + score_bytes), per_wg, (uint32_t *)d_out);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->sc_ev[1], s));
-    HIPCHK(hipMemcpyAsync(scores, d_out, 4 * (size_t)njobs, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipEventElapsedTime(&ctx->pars_ms, ctx->sc_ev[0], ctx->sc_ev[1]));
-    return PGM_OK;
+    c.up(d_in, img.bytes.data(), img.bytes.size());
+    if (c.begin())
+        hipLaunchKernelGGL(pgm_gap_parsimony_kernel, dim3(grid), dim3(256), 0, c.s, (const PgmParsimonyJobDev *)d_in, njobs,
+                           (uint64_t *)(d_out + score_bytes), per_wg, (uint32_t *)d_out);
+    c.end();
+    c.down(scores, d_out, 4 * (size_t)njobs);
+    return c.finish();
 }

@@ -1,11 +1,6 @@
 // pgm_transfer_capi.inc — C ABI of the transfer indices of pgmsa --bootstrap_tbe (included by pgm_capi.hip).
 // The arguments are checked on the host, then: one upload of the reference sets, the replicate offsets and the replicate sets, one
 // launch of pgm_transfer_min_kernel<false>, one copy back of phi.  pgm_transfer_taxa_capi.inc has the entry of --bootstrap_taxa.
-namespace {
-// scratch slots (see scratch_dev): 33 = reference sets followed by rep_off, 34 = replicate sets, 35 = phi
-enum { SC_TRANSFER_REF = 33, SC_TRANSFER_REP = 34, SC_TRANSFER_OUT = 35 };
-}  // namespace
-
 extern "C" float pgm_transfer_last_kernel_ms(pgm_ctx *ctx) { return ctx ? ctx->transfer_ms : 0.0f; }
 
 // the argument checks both entries share (include/pgm_hip.h: pgm_transfer_min); `what` opens the message
@@ -43,27 +38,21 @@ extern "C" int pgm_transfer_min(pgm_ctx *ctx, uint32_t nleaves, uint32_t nref, c
 
     const size_t ref_bytes = 8 * words * (size_t)nref, off_bytes = sizeof(uint32_t) * ((size_t)nrep + 1), rep_bytes = 8 * words * nsets;
     const size_t phi_bytes = sizeof(uint32_t) * (size_t)nref * nrep;
-    HIPCHK(hipSetDevice(ctx->device));
+    StageCall c(ctx, "transfer min", &ctx->transfer_ms);
     uint8_t *d_ref = nullptr; uint64_t *d_rep = nullptr; uint32_t *d_phi = nullptr;
-    hipError_t e = scratch_dev(ctx, SC_TRANSFER_REF, ref_bytes + off_bytes, (void **)&d_ref);
-    if (e == hipSuccess) e = scratch_dev(ctx, SC_TRANSFER_REP, rep_bytes, (void **)&d_rep);
-    if (e == hipSuccess) e = scratch_dev(ctx, SC_TRANSFER_OUT, phi_bytes, (void **)&d_phi);
-    if (e == hipSuccess) e = scratch_events(ctx);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("transfer min: ") + hipGetErrorString(e));
+    c.buf(pgm_ctx::SC_TRANSFER_REF, ref_bytes + off_bytes, &d_ref);
+    c.buf(pgm_ctx::SC_TRANSFER_REP, rep_bytes, &d_rep);
+    c.buf(pgm_ctx::SC_TRANSFER_OUT, phi_bytes, &d_phi);
     uint32_t *d_off = (uint32_t *)(d_ref + ref_bytes);
-    hipStream_t s = ctx->stream;
-    HIPCHK(hipMemcpyAsync(d_ref, ref, ref_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_off, rep_off, off_bytes, hipMemcpyHostToDevice, s));
-    if (rep_bytes) HIPCHK(hipMemcpyAsync(d_rep, rep, rep_bytes, hipMemcpyHostToDevice, s));
+    c.up(d_ref, ref, ref_bytes);
+    c.up(d_off, rep_off, off_bytes);
+    c.up(d_rep, rep, rep_bytes);
     const uint32_t tiles = (uint32_t)(((uint64_t)nref + PGM_TRANSFER_T - 1) / PGM_TRANSFER_T);
-    HIPCHK(hipEventRecord(ctx->sc_ev[0], s));
     // a workgroup per (reference tile, replicate); beyond the grid's y range a workgroup takes several replicates in turn
-    hipLaunchKernelGGL(pgm_transfer_min_kernel<false>, dim3(tiles, std::min<uint32_t>(nrep, 65535)), dim3(256), 0, s, (const uint32_t *)d_ref, nref,
-                       (const uint32_t *)d_rep, (const uint32_t *)d_off, nrep, nleaves, (uint32_t)(2 * words), d_phi, (uint32_t *)nullptr, (uint32_t *)nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->sc_ev[1], s));
-    HIPCHK(hipMemcpyAsync(phi, d_phi, phi_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipEventElapsedTime(&ctx->transfer_ms, ctx->sc_ev[0], ctx->sc_ev[1]));
-    return PGM_OK;
+    if (c.begin())
+        hipLaunchKernelGGL(pgm_transfer_min_kernel<false>, dim3(tiles, std::min<uint32_t>(nrep, 65535)), dim3(256), 0, c.s, (const uint32_t *)d_ref, nref,
+                           (const uint32_t *)d_rep, (const uint32_t *)d_off, nrep, nleaves, (uint32_t)(2 * words), d_phi, (uint32_t *)nullptr, (uint32_t *)nullptr);
+    c.end();
+    c.down(phi, d_phi, phi_bytes);
+    return c.finish();
 }

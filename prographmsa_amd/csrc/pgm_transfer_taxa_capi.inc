@@ -17,37 +17,31 @@ extern "C" int pgm_transfer_taxa(pgm_ctx *ctx, uint32_t nleaves, uint32_t nref, 
 
     const size_t ref_bytes = 8 * words * (size_t)nref, off_bytes = sizeof(uint32_t) * ((size_t)nrep + 1), thr_bytes = sizeof(uint32_t) * (size_t)nref;
     const size_t rep_bytes = 8 * words * nsets, phi_bytes = sizeof(uint32_t) * (size_t)nref * nrep, moved_bytes = sizeof(uint32_t) * (size_t)nref * nleaves;
-    HIPCHK(hipSetDevice(ctx->device));
+    StageCall c(ctx, "transfer taxa", &ctx->transfer_ms);
     uint8_t *d_ref = nullptr, *d_out = nullptr; uint64_t *d_rep = nullptr;
-    hipError_t e = scratch_dev(ctx, SC_TRANSFER_REF, ref_bytes + off_bytes + thr_bytes, (void **)&d_ref);
-    if (e == hipSuccess) e = scratch_dev(ctx, SC_TRANSFER_REP, rep_bytes, (void **)&d_rep);
-    if (e == hipSuccess) e = scratch_dev(ctx, SC_TRANSFER_OUT, 3 * phi_bytes + moved_bytes + thr_bytes, (void **)&d_out);   // phi, arg, flip, moved, counted
-    if (e == hipSuccess) e = scratch_events(ctx);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("transfer taxa: ") + hipGetErrorString(e));
+    c.buf(pgm_ctx::SC_TRANSFER_REF, ref_bytes + off_bytes + thr_bytes, &d_ref);
+    c.buf(pgm_ctx::SC_TRANSFER_REP, rep_bytes, &d_rep);
+    c.buf(pgm_ctx::SC_TRANSFER_OUT, 3 * phi_bytes + moved_bytes + thr_bytes, &d_out);   // phi, arg, flip, moved, counted
     uint32_t *d_off = (uint32_t *)(d_ref + ref_bytes), *d_thr = (uint32_t *)(d_ref + ref_bytes + off_bytes);
     uint32_t *d_phi = (uint32_t *)d_out, *d_arg = (uint32_t *)(d_out + phi_bytes), *d_flip = (uint32_t *)(d_out + 2 * phi_bytes);
     uint32_t *d_moved = (uint32_t *)(d_out + 3 * phi_bytes), *d_counted = (uint32_t *)(d_out + 3 * phi_bytes + moved_bytes);
-    hipStream_t s = ctx->stream;
-    HIPCHK(hipMemcpyAsync(d_ref, ref, ref_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_off, rep_off, off_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_thr, thr, thr_bytes, hipMemcpyHostToDevice, s));
-    if (rep_bytes) HIPCHK(hipMemcpyAsync(d_rep, rep, rep_bytes, hipMemcpyHostToDevice, s));
+    c.up(d_ref, ref, ref_bytes);
+    c.up(d_off, rep_off, off_bytes);
+    c.up(d_thr, thr, thr_bytes);
+    c.up(d_rep, rep, rep_bytes);
     const uint32_t tiles = (uint32_t)(((uint64_t)nref + PGM_TRANSFER_T - 1) / PGM_TRANSFER_T);
-    HIPCHK(hipEventRecord(ctx->sc_ev[0], s));
-    hipLaunchKernelGGL(pgm_transfer_min_kernel<true>, dim3(tiles, std::min<uint32_t>(nrep, 65535)), dim3(256), 0, s, (const uint32_t *)d_ref, nref,
-                       (const uint32_t *)d_rep, (const uint32_t *)d_off, nrep, nleaves, (uint32_t)(2 * words), d_phi, d_arg, d_flip);
-    HIPCHK(hipGetLastError());
-    // a workgroup per (reference set, 256 leaves); beyond the grid's y range a workgroup takes several tiles of leaves in turn
-    hipLaunchKernelGGL(pgm_transfer_moved_kernel, dim3(nref, std::min<uint32_t>((nleaves + 255) / 256, 65535)), dim3(256), 0, s, (const uint32_t *)d_ref,
-                       (const uint32_t *)d_rep, nrep, nleaves, (uint32_t)(2 * words), (const uint32_t *)d_thr, (const uint32_t *)d_phi, (const uint32_t *)d_arg,
-                       (const uint32_t *)d_flip, d_moved, d_counted);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ctx->sc_ev[1], s));
-    HIPCHK(hipMemcpyAsync(phi, d_phi, phi_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(arg, d_arg, phi_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(moved, d_moved, moved_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(counted, d_counted, thr_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipEventElapsedTime(&ctx->transfer_ms, ctx->sc_ev[0], ctx->sc_ev[1]));
-    return PGM_OK;
+    if (c.begin()) {
+        hipLaunchKernelGGL(pgm_transfer_min_kernel<true>, dim3(tiles, std::min<uint32_t>(nrep, 65535)), dim3(256), 0, c.s, (const uint32_t *)d_ref, nref,
+                           (const uint32_t *)d_rep, (const uint32_t *)d_off, nrep, nleaves, (uint32_t)(2 * words), d_phi, d_arg, d_flip);
+        // a workgroup per (reference set, 256 leaves); beyond the grid's y range a workgroup takes several tiles of leaves in turn
+        hipLaunchKernelGGL(pgm_transfer_moved_kernel, dim3(nref, std::min<uint32_t>((nleaves + 255) / 256, 65535)), dim3(256), 0, c.s, (const uint32_t *)d_ref,
+                           (const uint32_t *)d_rep, nrep, nleaves, (uint32_t)(2 * words), (const uint32_t *)d_thr, (const uint32_t *)d_phi, (const uint32_t *)d_arg,
+                           (const uint32_t *)d_flip, d_moved, d_counted);
+    }
+    c.end();
+    c.down(phi, d_phi, phi_bytes);
+    c.down(arg, d_arg, phi_bytes);
+    c.down(moved, d_moved, moved_bytes);
+    c.down(counted, d_counted, thr_bytes);
+    return c.finish();
 }

@@ -2,12 +2,6 @@
 // The arguments are checked on the host and the children lists are built there, then: one upload of the tree, the rows, pi and the
 // matrices, one launch of pgm_treelik_kernel (a workgroup per block of sites walks the whole tree), with derivs one launch of
 // pgm_treelik_sums_kernel, one copy back.  Stateless: nothing of a call is read by the next.
-namespace {
-// scratch slots (see scratch_dev): 36 = children lists, pi, rows; 37 = the matrices; 38 = partials and outside vectors;
-// 39 = per-site ratios and chunk sums; 40 = the outputs
-enum { SC_TREELIK_TREE = 36, SC_TREELIK_P = 37, SC_TREELIK_U = 38, SC_TREELIK_G = 39, SC_TREELIK_OUT = 40 };
-}  // namespace
-
 extern "C" float pgm_treelik_last_kernel_ms(pgm_ctx *ctx) { return ctx ? ctx->treelik_ms : 0.0f; }
 
 extern "C" int pgm_tree_likelihood(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
@@ -47,23 +41,17 @@ extern "C" int pgm_tree_likelihood(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves,
     const size_t u_count = (size_t)ninner * ncols * dim, nchunks = ((size_t)ncols + PGM_TREELIK_CHUNK - 1) / PGM_TREELIK_CHUNK;
     const size_t g_count = (size_t)nedges * ncols, part_count = 2 * (size_t)nedges * nchunks;
     const size_t l_bytes = 8 * (size_t)ncols, k_bytes = (4 * (size_t)ncols + 7) / 8 * 8, d_bytes = 8 * (size_t)nedges;
-    HIPCHK(hipSetDevice(ctx->device));
+    StageCall c(ctx, "tree likelihood", &ctx->treelik_ms);
     uint8_t *d_tree = nullptr, *d_out = nullptr; double *d_P = nullptr, *d_U = nullptr, *d_g = nullptr;
-    hipError_t e = scratch_dev(ctx, SC_TREELIK_TREE, rows_off + nrow, (void **)&d_tree);
-    if (e == hipSuccess) e = scratch_dev(ctx, SC_TREELIK_P, p_bytes, (void **)&d_P);
-    if (e == hipSuccess) e = scratch_dev(ctx, SC_TREELIK_U, 8 * u_count * (derivs ? 2 : 1), (void **)&d_U);
-    if (e == hipSuccess && derivs) e = scratch_dev(ctx, SC_TREELIK_G, 8 * (2 * g_count + part_count), (void **)&d_g);
-    if (e == hipSuccess) e = scratch_dev(ctx, SC_TREELIK_OUT, l_bytes + k_bytes + 2 * d_bytes, (void **)&d_out);
-    if (e == hipSuccess) e = scratch_events(ctx);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, w + hipGetErrorString(e));
-    }
-    hipStream_t s = ctx->stream;
-    HIPCHK(hipMemcpyAsync(d_tree, tree.data(), tree_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_tree + pi_off, pi, 8 * (size_t)dim, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_tree + rows_off, rows, nrow, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_P, P, p_bytes, hipMemcpyHostToDevice, s));
+    c.buf(pgm_ctx::SC_TREELIK_TREE, rows_off + nrow, &d_tree);
+    c.buf(pgm_ctx::SC_TREELIK_P, p_bytes, &d_P);
+    c.buf(pgm_ctx::SC_TREELIK_U, 8 * u_count * (derivs ? 2 : 1), &d_U);
+    if (derivs) c.buf(pgm_ctx::SC_TREELIK_G, 8 * (2 * g_count + part_count), &d_g);
+    c.buf(pgm_ctx::SC_TREELIK_OUT, l_bytes + k_bytes + 2 * d_bytes, &d_out);
+    c.up(d_tree, tree.data(), tree_bytes);
+    c.up(d_tree + pi_off, pi, 8 * (size_t)dim);
+    c.up(d_tree + rows_off, rows, nrow);
+    c.up(d_P, P, p_bytes);
 
     PgmTreelikArgs a;
     a.dim = dim; a.nleaves = nleaves; a.nnodes = nnodes; a.ncols = ncols; a.spb = PGM_TREELIK_THREADS / dim; a.derivs = derivs ? 1 : 0;
@@ -74,23 +62,18 @@ extern "C" int pgm_tree_likelihood(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves,
     a.site_l = (double *)d_out; a.site_k = (int32_t *)(d_out + l_bytes);
     double *d_d1 = (double *)(d_out + l_bytes + k_bytes), *d_d2 = d_d1 + nedges;
     const uint32_t blocks = (uint32_t)(((uint64_t)ncols + a.spb - 1) / a.spb);
-    HIPCHK(hipEventRecord(ctx->sc_ev[0], s));
-    hipLaunchKernelGGL(pgm_treelik_kernel, dim3(blocks), dim3(PGM_TREELIK_THREADS), 0, s, a);
-    HIPCHK(hipGetLastError());
-    if (derivs) {
-        hipLaunchKernelGGL(pgm_treelik_sums_kernel, dim3(nedges), dim3(PGM_TREELIK_THREADS), 0, s, (const double *)a.g, (const double *)a.h, ncols, (uint32_t)nchunks,
-                           d_g + 2 * g_count, d_d1, d_d2);
-        HIPCHK(hipGetLastError());
+    if (c.begin()) {
+        hipLaunchKernelGGL(pgm_treelik_kernel, dim3(blocks), dim3(PGM_TREELIK_THREADS), 0, c.s, a);
+        if (derivs)
+            hipLaunchKernelGGL(pgm_treelik_sums_kernel, dim3(nedges), dim3(PGM_TREELIK_THREADS), 0, c.s, (const double *)a.g, (const double *)a.h, ncols, (uint32_t)nchunks,
+                               d_g + 2 * g_count, d_d1, d_d2);
     }
-    HIPCHK(hipEventRecord(ctx->sc_ev[1], s));
-    // (pageable destinations: the copies return when the data has arrived, in stream order)
-    HIPCHK(hipMemcpyAsync(site_l, a.site_l, l_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(site_k, a.site_k, 4 * (size_t)ncols, hipMemcpyDeviceToHost, s));
+    c.end();
+    c.down(site_l, a.site_l, l_bytes);
+    c.down(site_k, a.site_k, 4 * (size_t)ncols);
     if (derivs) {
-        HIPCHK(hipMemcpyAsync(d1, d_d1, d_bytes, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(d2, d_d2, d_bytes, hipMemcpyDeviceToHost, s));
+        c.down(d1, d_d1, d_bytes);
+        c.down(d2, d_d2, d_bytes);
     }
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipEventElapsedTime(&ctx->treelik_ms, ctx->sc_ev[0], ctx->sc_ev[1]));
-    return PGM_OK;
+    return c.finish();
 }

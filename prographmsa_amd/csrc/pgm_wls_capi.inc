@@ -1,11 +1,6 @@
 // pgm_wls_capi.inc — C ABI of the weighted least-squares refinement's subtree pair sums (included by pgm_capi.hip).
-// The matrices stay on the device between calls; a call uploads its jobs' labels and offsets in one copy (ParsImage of
-// pgm_parsimony_capi.inc), runs the two kernels of pgm_wls_kernels.h once per chunk of jobs and copies the sums back.
-namespace {
-// scratch slots (see scratch_dev): 24 = the (D, W) matrix, 25 = job image, 26 = block partials, 27 = results
-enum { SC_WLS_MAT = 24, SC_WLS_IN = 25, SC_WLS_PART = 26, SC_WLS_OUT = 27 };
-}  // namespace
-
+// The matrices stay on the device between calls; a call uploads its jobs' labels and offsets in one copy (HostImage),
+// runs the two kernels of pgm_wls_kernels.h once per chunk of jobs and copies the sums back.
 extern "C" float pgm_wls_last_kernel_ms(pgm_ctx *ctx) { return ctx ? ctx->wls_ms : 0.0f; }
 extern "C" uint32_t pgm_wls_last_launches(pgm_ctx *ctx) { return ctx ? ctx->wls_launches : 0u; }
 
@@ -16,12 +11,11 @@ extern "C" int pgm_wls_load(pgm_ctx *ctx, uint32_t n, const double *D, const dou
     const size_t nn = (size_t)n * n;
     std::vector<double> dw(2 * nn);
     for (size_t i = 0; i < nn; ++i) { dw[2 * i] = D[i]; dw[2 * i + 1] = W[i]; }
-    HIPCHK(hipSetDevice(ctx->device));
+    StageCall c(ctx, "wls matrices", nullptr);
     void *d = nullptr;
-    hipError_t e = scratch_dev(ctx, SC_WLS_MAT, 16 * nn, &d);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("wls matrices: ") + hipGetErrorString(e));
-    HIPCHK(hipMemcpyAsync(d, dw.data(), 16 * nn, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    c.buf(pgm_ctx::SC_WLS_MAT, 16 * nn, &d);
+    c.up(d, dw.data(), 16 * nn);
+    if (int rc = c.finish()) return rc;
     ctx->wls_n = n;
     return PGM_OK;
 }
@@ -33,7 +27,7 @@ extern "C" int pgm_wls_pair_sums_batch(pgm_ctx *ctx, uint32_t njobs, const pgm_w
     const uint32_t n = ctx->wls_n;
     if (n == 0) return fail(PGM_ERR_INVALID, "wls: no matrices loaded (pgm_wls_load)");
     if (njobs == 0) return PGM_OK;
-    ParsImage img;
+    HostImage img;
     std::vector<PgmWlsJobDev> dj(njobs);
     std::vector<size_t> lab_off(njobs), off_off(njobs);
     img.put(nullptr, sizeof(PgmWlsJobDev) * njobs);
@@ -52,35 +46,29 @@ extern "C" int pgm_wls_pair_sums_batch(pgm_ctx *ctx, uint32_t njobs, const pgm_w
     const uint32_t nblocks = (n + PGM_WLS_ROWS - 1) / PGM_WLS_ROWS;
     const size_t part_job = (size_t)nblocks * PGM_WLS_SLOTS * 8;
     const uint32_t chunk = (uint32_t)std::max<size_t>(1, std::min<size_t>(njobs, (64ull << 20) / part_job));
-    HIPCHK(hipSetDevice(ctx->device));
+    StageCall c(ctx, "wls pair sums", &ctx->wls_ms);
     uint8_t *d_in = nullptr; double *d_part = nullptr, *d_out = nullptr;
-    hipError_t e = scratch_dev(ctx, SC_WLS_IN, img.bytes.size(), (void **)&d_in);
-    if (e == hipSuccess) e = scratch_dev(ctx, SC_WLS_PART, part_job * chunk, (void **)&d_part);
-    if (e == hipSuccess) e = scratch_dev(ctx, SC_WLS_OUT, 8 * PGM_WLS_SLOTS * (size_t)njobs, (void **)&d_out);
-    if (e == hipSuccess) e = scratch_events(ctx);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? PGM_ERR_NOMEM : PGM_ERR_DEVICE, std::string("wls pair sums: ") + hipGetErrorString(e));
+    c.buf(pgm_ctx::SC_WLS_IN, img.bytes.size(), &d_in);
+    c.buf(pgm_ctx::SC_WLS_PART, part_job * chunk, &d_part);
+    c.buf(pgm_ctx::SC_WLS_OUT, 8 * PGM_WLS_SLOTS * (size_t)njobs, &d_out);
     for (uint32_t i = 0; i < njobs; ++i) {
         dj[i].label = (const int8_t *)(d_in + lab_off[i]);
         dj[i].offset = (const double *)(d_in + off_off[i]);
     }
     memcpy(img.bytes.data(), dj.data(), sizeof(PgmWlsJobDev) * njobs);
-    hipStream_t s = ctx->stream;
-    const double2 *d_mat = (const double2 *)ctx->sc_dev[SC_WLS_MAT];
-    HIPCHK(hipMemcpyAsync(d_in, img.bytes.data(), img.bytes.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(hipEventRecord(ctx->sc_ev[0], s));
+    const double2 *d_mat = (const double2 *)ctx->sc_dev[pgm_ctx::SC_WLS_MAT];
+    c.up(d_in, img.bytes.data(), img.bytes.size());
     uint32_t launches = 0;
-    for (uint32_t j0 = 0; j0 < njobs; j0 += chunk) {
-        const uint32_t nj = std::min(chunk, njobs - j0);
-        hipLaunchKernelGGL(pgm_wls_rows_kernel, dim3(nblocks * nj), dim3(256), 0, s, d_mat, n, (const PgmWlsJobDev *)d_in + j0, nblocks, d_part);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(pgm_wls_jobs_kernel, dim3(nj), dim3(64), 0, s, (const double *)d_part, nblocks, d_out + (size_t)PGM_WLS_SLOTS * j0);
-        HIPCHK(hipGetLastError());
-        launches += 2;
-    }
-    HIPCHK(hipEventRecord(ctx->sc_ev[1], s));
-    HIPCHK(hipMemcpyAsync(out, d_out, 8 * PGM_WLS_SLOTS * (size_t)njobs, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipEventElapsedTime(&ctx->wls_ms, ctx->sc_ev[0], ctx->sc_ev[1]));
+    if (c.begin())
+        for (uint32_t j0 = 0; j0 < njobs; j0 += chunk) {
+            const uint32_t nj = std::min(chunk, njobs - j0);
+            hipLaunchKernelGGL(pgm_wls_rows_kernel, dim3(nblocks * nj), dim3(256), 0, c.s, d_mat, n, (const PgmWlsJobDev *)d_in + j0, nblocks, d_part);
+            hipLaunchKernelGGL(pgm_wls_jobs_kernel, dim3(nj), dim3(64), 0, c.s, (const double *)d_part, nblocks, d_out + (size_t)PGM_WLS_SLOTS * j0);
+            launches += 2;
+        }
+    c.end();
+    c.down(out, d_out, 8 * PGM_WLS_SLOTS * (size_t)njobs);
+    if (int rc = c.finish()) return rc;
     ctx->wls_launches = launches;
     return PGM_OK;
 }
