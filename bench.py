@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — DP cell-updates/s of the alignGraphs hot path on the BASELINE workload (256 seqs x 1000 aa, WAG).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 `python bench.py --gpus N` without a launcher (WORLD_SIZE unset, N > 1) starts that launcher itself, before anything
@@ -13,6 +13,12 @@ jobs the product driver issues (captured with `pgmsa --dump_jobs` on this GPU du
 One "step" = one pass of the hot path over that batch with the inputs resident in HBM: prep (float casts,
 T = M^T g2) + emission scores + the fill kernel (DP fill of every band and, after a job's last band, its traceback),
 then the result/mapping copy back to the host.
+
+A plain run does what the headline figure needs and no more: it captures the jobs (one run of the driver), builds the batch,
+warms up, times the steps, writes --dump-outputs and prints the result line (value, ms_per_step and `roofline`, the stage times
+that the library's HIP events recorded during those same steps).  Every other record takes runs of its own and is measured
+with --full only: the driver's own times (end_to_end, default_flow, roofline_pass), the leaf level (roofline_leaf), the
+all-pairs and context-profile satellites, configs 4 / 5, the strong-scaling legs and the CPU baseline.
 
 Multi-GPU: one process per GPU, no collective on the data path and no RCCL anywhere (torch.distributed with the gloo backend
 only provides the barrier, the max-over-ranks clock and the rendezvous store that serves the work queue's ticket counter).
@@ -47,8 +53,10 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--nseq", type=int, default=256, help="debug: smaller family (changes the workload; not the headline)")
     ap.add_argument("--len", type=int, default=1000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the sub-records (configs 4 / 5, 1024 x 600 all-pairs, strong scaling)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure every other record (driver times, leaf level, satellites, configs 4 / 5, strong scaling, CPU baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the sub-records (configs 4 / 5, 1024 x 600 all-pairs, strong scaling)")
     ap.add_argument("--only-headline", action="store_true", help="the timed loop over the headline batch and nothing else (profiling runs: every kernel launch of the process belongs to a step)")
     ap.add_argument("--only-satellites", action="store_true", help="profiling runs: the all-pairs alignPair stage and the context-profile call of the headline family, nothing else timed")
     ap.add_argument("--only-config", default=None, choices=["c4", "c5"], help="profiling runs: three passes over the jobs of BASELINE config 4 / 5 and nothing else")
@@ -204,7 +212,7 @@ def main():
         # product): the median of three by progressive_s, all three listed (a pass is 50-150 ms, and this pool's hosts stall a GPU
         # wait for ~20 ms about once a second — on some boxes several times per pass: DESIGN §4)
         runs = []
-        if rank != 0:   # (only rank 0 reports the driver's times)
+        if rank != 0 or not args.full:   # (only rank 0 of a --full run reports the driver's times)
             st = json.loads([ln for ln in r.stderr.splitlines() if ln.startswith('{"backend"')][-1])
             st["wall_s"] = None
             return js, st, hashlib.md5(r.stdout.encode()).hexdigest()
@@ -248,7 +256,7 @@ def main():
     # alignment + guide-tree re-estimation, final alignment), rank 0 only; the FASTA's md5 is checked against the fixture of
     # the reference binary's output for the headline family
     default_flow = None
-    if rank == 0:
+    if rank == 0 and args.full:
         fa0 = os.path.join(tmp, "c3.fa")
         t0 = time.time()
         r2 = subprocess.run([pg.PGMSA_PATH, "--fasta", "-a", "--stats", fa0], capture_output=True, text=True, env=env)
@@ -358,6 +366,25 @@ def main():
         if rank == 0:
             print(json.dumps({"metric": "DP cell-updates/sec (GCUPS), headline batch only", "value": round(total_cells / dt / 1e9, 4), "unit": "GCUPS", "n_gpus": world, "steps": args.steps,
                               "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "roofline": roofline}))
+        return
+    head = {
+        "metric": "DP cell-updates/sec (GCUPS) + wall-clock on 256 seqs × 1000 aa, WAG",
+        "value": round(total_cells / dt / 1e9, 4), "unit": "GCUPS",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "%d seqs x %d aa, WAG, --mldist: the %d alignGraphs jobs of one progressive pass "
+                               "(%.3e DP cells) per GPU, inputs resident in HBM" % (args.nseq, args.len, len(jobs), cells),
+                   "headline": headline, "device": devname, "cus": cus, "jobs": len(jobs), "cells_per_step": cells},
+        "roofline": roofline,
+    }
+    if not (args.full or args.only_satellites):   # a plain run ends here: every record below takes runs of its own
+        if rank == 0:
+            print(json.dumps(head))
+        batch.close()
+        ctx.close()
+        if world > 1:
+            dist.destroy_process_group()
         return
     # ---- the two other lines SURVEY section 7 asks for: the leaf level alone, and the product's whole progressive pass --------
     def is_chain(g):
@@ -607,16 +634,8 @@ def main():
         return
     out = None
     if rank == 0:
-        out = {
-            "metric": "DP cell-updates/sec (GCUPS) + wall-clock on 256 seqs × 1000 aa, WAG",
-            "value": round(total_cells / dt / 1e9, 4), "unit": "GCUPS",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": "%d seqs x %d aa, WAG, --mldist: the %d alignGraphs jobs of one progressive pass "
-                                   "(%.3e DP cells) per GPU, inputs resident in HBM" % (args.nseq, args.len, len(jobs), cells),
-                       "headline": headline, "device": devname, "cus": cus, "jobs": len(jobs), "cells_per_step": cells},
-            "roofline": roofline,
+        out = dict(head)
+        out.update({
             "roofline_leaf": roofline_leaf,
             "roofline_pass": roofline_pass,
             "all_pairs_nw": nw,
@@ -629,7 +648,7 @@ def main():
                            "progressive_s_of_3_runs": stats.get("progressive_s_of_3_runs"),
                            "note": "the median of three runs of the product driver outside the timed region (without the job dump; all three under progressive_s_of_3_runs); progressive_s incl. host merges, H2D/D2H and every allocation beyond the context's start-up pool; init_s = HIP start-up + code object load + that pool (128 MB pinned staging, 3.4 GB of device buffers: pgm_ctx_create), before the stage clocks start and inside pgmsa_wall_s",
                            "default_flow": default_flow},
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             import oracle_lib   # test-only CPU restatement, used here solely as the reported CPU baseline
             tc = time.perf_counter()

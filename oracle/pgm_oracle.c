@@ -2,7 +2,7 @@
  * pgm_oracle.c — TEST INFRASTRUCTURE ONLY.  CPU restatement (plain C99, scalar, one thread)
  * of the three hot functions of acg-team/ProGraphMSA, over the flattened structs of
  * include/pgm_hip.h.  It is the checker for the HIP path (tests/, __graft_entry__.smoke(),
- * bench.py's cpu_baseline leg); product code never links or calls it.
+ * the cpu_baseline leg of bench.py --full); product code never links or calls it.
  *
  * Parity pin: the reference's own source cannot be compiled here (Eigen/TCLAP absent), so
  * this restatement is pinned end-to-end against outputs of the reference's prebuilt binary

@@ -1,6 +1,6 @@
 """ctypes binding of the TEST-ONLY CPU oracle (oracle/_build/libpgm_oracle.so).
 
-Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
+Only tests/, __graft_entry__.smoke() and the cpu_baseline leg of bench.py --full may import this module.
 """
 import ctypes as C
 import os

@@ -85,3 +85,13 @@ def test_bench_honours_gpus_flag_dry_run(gpus):
     out = json.loads(line)
     assert out["n_gpus"] == gpus and out["dry_run"] is True
     assert out["tiles_pulled"] == out["tiles"] and out["every_tile_exactly_once"] and out["max_clock"] == float(gpus)
+
+
+def test_bench_full_is_off_by_default(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` measures the headline alone; `--full` asks for every other record."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2"])
+    a = bench.parse_args()
+    assert a.full is False and (a.steps, a.warmup, a.dump_outputs) == (3, 2, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2", "--full"])
+    assert bench.parse_args().full is True

@@ -6,7 +6,7 @@ for round in 1 2; do
 for f in prographmsa_amd/lib/libpgm_hip_*.so; do
   v=$(basename $f .so); v=${v#libpgm_hip_}
   cp $f prographmsa_amd/lib/libpgm_hip.so
-  python bench.py --no-cpu-baseline --no-extra 2>/dev/null | python -c "
+  python bench.py 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$v', d['value'], d['ms_per_step'], d['roofline']['ms'])"
 done
 done
