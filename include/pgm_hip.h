@@ -505,7 +505,31 @@ int pgm_tree_likelihood(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t n
                         uint32_t ncols, const int8_t *rows /* nleaves x ncols */, const double *pi /* dim */,
                         const double *P /* (nnodes-1) x {1 or 3} x dim x dim */, int derivs,
                         double *site_l /* ncols */, int32_t *site_k /* ncols */, double *d1, double *d2 /* nnodes-1, derivs only */);
-float pgm_treelik_last_kernel_ms(pgm_ctx *ctx);   /* device time of the kernels of the last pgm_tree_likelihood call */
+float pgm_treelik_last_kernel_ms(pgm_ctx *ctx);   /* device time of the kernels of the last pgm_tree_likelihood or pgm_tree_likelihood_rates call */
+
+/* ---- the same likelihood under a mixture of ncat rate categories (pgmsa --ml_tree --ml_gamma).
+ * Everything from dim to pi, and derivs, d1, d2, is as in pgm_tree_likelihood, with the same checks.  ncat: 1 .. PGM_TREELIK_MAXCAT;
+ * w: the ncat weights, each finite and > 0; P: ncat x (nnodes-1) x {3 or 1} x dim x dim, category-major, every matrix column-major as
+ * above.  The device sees no rates: the caller folds them into the matrices (P(r_c t_e), r_c Q P, r_c^2 Q Q P).
+ * Per category c the up pass, the scaling rule, the down pass and the three sums A^P, A^P', A^P'' of every edge are those of
+ * pgm_tree_likelihood; they give (L_c, k_c) per site and per edge and site g_c = A^P' / A^P and q_c = A^P'' / A^P (no - g g yet).
+ * Then per site, in this order:
+ *   site_k = min_c k_c
+ *   term_c = w_c * L_c, then multiplied by 2^-256 exactly (k_c - site_k) times
+ *   site_l = sum_c term_c, c ascending from 0.0;   post[c * ncols + s] = term_c / site_l
+ *   per edge  g = sum_c post_c * g_c,  q = sum_c post_c * q_c  (c ascending from 0.0, one multiply and one add per term),  h = q - g * g
+ *   d1, d2: the chunk sums of g and h as above.
+ * With ncat == 1 and w = {1.0} every output equals pgm_tree_likelihood's bit for bit (1.0 * x and 0.0 + x are exact, x / x is 1.0),
+ * and post is 1.0.  The values do not depend on the launch and equal the host statement's (tree_likelihood_rates_host) bit for bit.
+ * site_l, site_k and post (ncat x ncols) are overwritten; d1 and d2 only when derivs.  Device memory: ncat times that of
+ * pgm_tree_likelihood and 16 * (nnodes - 1) * ncols more; memory that cannot be had is PGM_ERR_NOMEM.
+ * PGM_ERR_INVALID, before anything is launched or an output is touched: what pgm_tree_likelihood refuses, ncat outside
+ * 1 .. PGM_TREELIK_MAXCAT, a null w or post, a w entry that is not finite and > 0. */
+#define PGM_TREELIK_MAXCAT 16
+int pgm_tree_likelihood_rates(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
+                              const double *pi, uint32_t ncat, const double *w /* ncat */, const double *P /* ncat x (nnodes-1) x {1 or 3} x dim x dim */,
+                              int derivs, double *site_l /* ncols */, int32_t *site_k /* ncols */, double *post /* ncat x ncols */,
+                              double *d1, double *d2 /* nnodes-1, derivs only */);
 
 #ifdef __cplusplus
 }

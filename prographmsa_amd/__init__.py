@@ -93,7 +93,7 @@ EXPORTS = [
     "pgm_bionj_plan", "pgm_bionj_plan_multi",
     "pgm_msa_agreement", "pgm_agreement_last_kernel_ms",
     "pgm_transfer_min", "pgm_transfer_last_kernel_ms", "pgm_transfer_taxa",
-    "pgm_tree_likelihood", "pgm_treelik_last_kernel_ms",
+    "pgm_tree_likelihood", "pgm_treelik_last_kernel_ms", "pgm_tree_likelihood_rates",
 ]
 
 
@@ -178,6 +178,9 @@ def _load():
         "pgm_tree_likelihood": (C.c_int, [vp, u32, u32, u32, C.POINTER(u32), u32, C.POINTER(C.c_int8), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int,
                                           C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "pgm_treelik_last_kernel_ms": (C.c_float, [vp]),
+        "pgm_tree_likelihood_rates": (C.c_int, [vp, u32, u32, u32, C.POINTER(u32), u32, C.POINTER(C.c_int8), C.POINTER(C.c_double), u32, C.POINTER(C.c_double),
+                                                C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = the library does not export a declared symbol
@@ -301,6 +304,29 @@ class Context:
         check(lib.pgm_tree_likelihood(self.handle, dim, nleaves, nnodes, P_(parent, C.c_uint32), ncols, P_(rows, C.c_int8), P_(pi, C.c_double), P_(P, C.c_double),
                                       1 if derivs else 0, P_(out[0], C.c_double), P_(out[1], C.c_int32), P_(out[2], C.c_double), P_(out[3], C.c_double)),
               "pgm_tree_likelihood")
+        return tuple(out)
+
+    def tree_likelihood_rates(self, dim, parent, rows, pi, w, P, derivs=True, out=None):
+        """pgm_tree_likelihood_rates: as tree_likelihood with the weights w (ncat) and P (ncat x (nnodes - 1) x {3 with derivs, else 1} x
+        dim x dim float64, category-major) -> (site_l, site_k, post (ncat x ncols float64), d1, d2).  Given output arrays (a tuple
+        of five, C-contiguous of those kinds) are overwritten; d1 and d2 are left as given without derivs."""
+        import numpy as np
+        parent = np.ascontiguousarray(parent, np.uint32)
+        rows = np.ascontiguousarray(rows, np.int8)
+        pi = np.ascontiguousarray(pi, np.float64)
+        w = np.ascontiguousarray(w, np.float64)
+        P = np.ascontiguousarray(P, np.float64)
+        if parent.ndim != 1 or rows.ndim != 2 or pi.shape != (dim,) or w.ndim != 1 or P.size != len(w) * (len(parent) - 1) * (3 if derivs else 1) * dim * dim:
+            raise ValueError("tree_likelihood_rates: input array of the wrong shape")
+        nnodes, (nleaves, ncols), ncat = len(parent), rows.shape, len(w)
+        kinds = [((ncols,), np.float64), ((ncols,), np.int32), ((ncat, ncols), np.float64), ((nnodes - 1,), np.float64), ((nnodes - 1,), np.float64)]
+        if out is None: out = tuple(np.zeros(s, t) for s, t in kinds)
+        if len(out) != 5 or any(a.dtype != t or a.shape != s or not a.flags.c_contiguous for a, (s, t) in zip(out, kinds)):
+            raise ValueError("tree_likelihood_rates: output array of the wrong kind")
+        P_ = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+        check(lib.pgm_tree_likelihood_rates(self.handle, dim, nleaves, nnodes, P_(parent, C.c_uint32), ncols, P_(rows, C.c_int8), P_(pi, C.c_double), ncat,
+                                            P_(w, C.c_double), P_(P, C.c_double), 1 if derivs else 0, P_(out[0], C.c_double), P_(out[1], C.c_int32),
+                                            P_(out[2], C.c_double), P_(out[3], C.c_double), P_(out[4], C.c_double)), "pgm_tree_likelihood_rates")
         return tuple(out)
 
     def close(self):

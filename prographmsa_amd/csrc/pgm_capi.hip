@@ -95,10 +95,10 @@ struct pgm_ctx {
         SC_TRANSFER_REF,                    // pgm_transfer_min and pgm_transfer_taxa (shared): reference sets, rep_off, thresholds
         SC_TRANSFER_REP,                    //   replicate sets
         SC_TRANSFER_OUT,                    //   phi (taxa: phi, arg, flip, moved, counted)
-        SC_TREELIK_TREE,                    // tree likelihood: children lists, pi, rows
+        SC_TREELIK_TREE,                    // tree likelihood, both entries (shared): children lists, pi, weights, rows
         SC_TREELIK_P,                       //   the matrices
         SC_TREELIK_U,                       //   partials and outside vectors
-        SC_TREELIK_G,                       //   per-site ratios and chunk sums
+        SC_TREELIK_G,                       //   per-site ratios and chunk sums (rates: the categories' site values and ratios first)
         SC_TREELIK_OUT,                     //   the outputs
         SC_DEV
     };
@@ -1062,3 +1062,4 @@ int pgm_align_batch_read_matrices(pgm_ctx *ctx, pgm_align_batch *b, uint32_t job
 #include "pgm_transfer_capi.inc"
 #include "pgm_transfer_taxa_capi.inc"
 #include "pgm_treelik_capi.inc"
+#include "pgm_treelik_rates_capi.inc"

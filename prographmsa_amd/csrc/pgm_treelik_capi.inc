@@ -4,16 +4,13 @@
 // pgm_treelik_sums_kernel, one copy back.  Stateless: nothing of a call is read by the next.
 extern "C" float pgm_treelik_last_kernel_ms(pgm_ctx *ctx) { return ctx ? ctx->treelik_ms : 0.0f; }
 
-extern "C" int pgm_tree_likelihood(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
-                                   const double *pi, const double *P, int derivs, double *site_l, int32_t *site_k, double *d1, double *d2) {
-    if (!ctx) return fail(PGM_ERR_INVALID, "null argument");
-    ctx->treelik_ms = 0;
+// The checks both entries share past their pointers, and the children of every node in ascending order: `tree` gets child_off
+// (nnodes + 1), then child (nnodes - 1).
+static int treelik_tree(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, std::vector<uint32_t> &tree) {
     const std::string w = "tree likelihood: ";
-    if (!parent || !rows || !pi || !P || !site_l || !site_k || (derivs && (!d1 || !d2))) return fail(PGM_ERR_INVALID, "null argument");
     if (dim < 1 || dim > 64) return fail(PGM_ERR_INVALID, w + "dim must be 1 .. 64");
     if (nleaves < 2 || ncols == 0 || nnodes <= nleaves) return fail(PGM_ERR_INVALID, w + "nleaves must be at least 2, ncols at least 1 and nnodes above nleaves");
-    // the children of every node in ascending order
-    std::vector<uint32_t> tree((size_t)nnodes + 1, 0);   // child_off, then child
+    tree.assign((size_t)nnodes + 1, 0);
     uint32_t roots = 0;
     for (uint32_t v = 0; v < nnodes; ++v) {
         if (parent[v] == UINT32_MAX) { ++roots; continue; }
@@ -25,7 +22,7 @@ extern "C" int pgm_tree_likelihood(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves,
     for (uint32_t v = nleaves; v < nnodes; ++v)
         if (tree[v + 1] < 2) return fail(PGM_ERR_INVALID, w + "inner node " + std::to_string(v) + " has fewer than 2 children");
     for (uint32_t v = 0; v < nnodes; ++v) tree[v + 1] += tree[v];
-    const uint32_t nedges = nnodes - 1, ninner = nnodes - nleaves;   // (every node but the root is a child: tree[nnodes] == nedges)
+    const uint32_t nedges = nnodes - 1;   // (every node but the root is a child: tree[nnodes] == nedges)
     tree.resize((size_t)nnodes + 1 + nedges);
     {
         std::vector<uint32_t> fill(tree.begin(), tree.begin() + nnodes);
@@ -35,6 +32,18 @@ extern "C" int pgm_tree_likelihood(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves,
     const size_t nrow = (size_t)nleaves * ncols;
     for (size_t k = 0; k < nrow; ++k)
         if (rows[k] < -2 || rows[k] >= (int)dim) return fail(PGM_ERR_INVALID, w + "row value " + std::to_string((int)rows[k]) + " outside -2 .. dim - 1");
+    return PGM_OK;
+}
+
+extern "C" int pgm_tree_likelihood(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
+                                   const double *pi, const double *P, int derivs, double *site_l, int32_t *site_k, double *d1, double *d2) {
+    if (!ctx) return fail(PGM_ERR_INVALID, "null argument");
+    ctx->treelik_ms = 0;
+    if (!parent || !rows || !pi || !P || !site_l || !site_k || (derivs && (!d1 || !d2))) return fail(PGM_ERR_INVALID, "null argument");
+    std::vector<uint32_t> tree;   // child_off, then child
+    if (const int rc = treelik_tree(dim, nleaves, nnodes, parent, ncols, rows, tree)) return rc;
+    const uint32_t nedges = nnodes - 1, ninner = nnodes - nleaves;
+    const size_t nrow = (size_t)nleaves * ncols;
 
     const size_t mat = (size_t)dim * dim, p_bytes = 8 * mat * (derivs ? 3 : 1) * nedges;
     const size_t tree_bytes = 4 * tree.size(), pi_off = (tree_bytes + 7) / 8 * 8, rows_off = pi_off + 8 * (size_t)dim;

@@ -7,6 +7,8 @@
 // nothing spins, there are no atomics.  The matrices of the edge in hand are read from global memory by every thread (lanes of one
 // site read consecutive entries of a column; the 3.2 KB to 98 KB of an edge stay in the vector L1 / L2 while the workgroups pass it).
 // pgm_treelik_sums_kernel adds the per-site ratios of an edge in the fixed order of the interface.
+// pgm_tree_likelihood_rates runs the same walk once per rate category, the categories as further workgroups of one
+// launch (pgm_treelik_rates_kernel), and combines them per site (pgm_treelik_combine_kernel) ahead of the sums.
 //
 // Every sum over states runs ascending from 0.0 with one multiply and one add per term (-ffp-contract=off): the bits are those of
 // tree_likelihood_host.  The walk is a chain of dependent steps on one wavefront, so what a step costs is the latency of its loads:
@@ -106,7 +108,9 @@ __device__ __forceinline__ bool pgm_treelik_rescale(double &v, double *sh, uint3
 
 // One edge of the down pass, for the dim threads of a site: the outside vector o (before its scaling) and T[x] = sum_j X_x(i, j) U_c(j)
 // of this thread's state.  Scales o, stores it for an inner child, and the thread of state 0 adds the three sums over the states
-// ascending and writes the two ratios.  Every thread of the workgroup calls it (barriers).
+// ascending and writes the two ratios: g and h = A''/A - g g, or with RAW (a category of pgm_tree_likelihood_rates) g and q = A''/A.
+// Every thread of the workgroup calls it (barriers).
+template <bool RAW>
 __device__ __forceinline__ void pgm_treelik_edge(const PgmTreelikArgs &a, double (*sh)[PGM_TREELIK_THREADS], double *shs, uint32_t c, uint32_t s, uint32_t i,
                                                  bool active, double o, const double (&T)[3]) {
     const uint32_t dim = a.dim;
@@ -129,11 +133,13 @@ __device__ __forceinline__ void pgm_treelik_edge(const PgmTreelikArgs &a, double
         }
         const double g = A1 / A0;
         a.g[(size_t)c * a.ncols + s] = g;
-        a.h[(size_t)c * a.ncols + s] = A2 / A0 - g * g;
+        a.h[(size_t)c * a.ncols + s] = RAW ? A2 / A0 : A2 / A0 - g * g;
     }
 }
 
-__global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_kernel(PgmTreelikArgs a) {
+// The walk of one workgroup over the whole tree for the sites of block blockIdx.x: both kernels below are this function.
+template <bool RAW>
+__device__ __forceinline__ void pgm_treelik_walk(const PgmTreelikArgs &a) {
     __shared__ double sh[3][PGM_TREELIK_THREADS];
     const uint32_t dim = a.dim, nleaves = a.nleaves, root = a.nnodes - 1;
     const uint32_t local = threadIdx.x / dim, i = threadIdx.x - local * dim;
@@ -198,8 +204,8 @@ __global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_kernel(PgmTre
                 pgm_treelik_apply<3>(a, a.P + estride * c0, mat, c0, s, i, T0);
                 pgm_treelik_apply<3>(a, a.P + estride * c1, mat, c1, s, i, T1);
             }
-            pgm_treelik_edge(a, sh, shs, c0, s, i, active, base * T1[0], T0);
-            pgm_treelik_edge(a, sh, shs, c1, s, i, active, base * T0[0], T1);
+            pgm_treelik_edge<RAW>(a, sh, shs, c0, s, i, active, base * T1[0], T0);
+            pgm_treelik_edge<RAW>(a, sh, shs, c1, s, i, active, base * T0[0], T1);
         } else {
             for (uint32_t q = q0; q < q1; ++q) {
                 const uint32_t c = a.child[q];
@@ -215,10 +221,72 @@ __global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_kernel(PgmTre
                         }
                     }
                 }
-                pgm_treelik_edge(a, sh, shs, c, s, i, active, o, T);
+                pgm_treelik_edge<RAW>(a, sh, shs, c, s, i, active, o, T);
             }
         }
         __syncthreads();   // the children's outside vectors are in memory before they are parents themselves
+    }
+}
+
+__global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_kernel(PgmTreelikArgs a) { pgm_treelik_walk<false>(a); }
+
+// pgm_tree_likelihood_rates: category blockIdx.y walks the tree with its own matrices, partials and outputs, `a`
+// holding those of category 0 and the strides the distance between two categories.  a.site_l / a.site_k get (L_c, k_c), a.g / a.h the
+// ratios (g_c, q_c) of every edge and site.  The categories are independent workgroups of one launch.
+struct PgmTreelikRatesStride { size_t P, U, G, L; };   // doubles between the categories' matrices, partials, ratios, site values
+__global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_rates_kernel(PgmTreelikArgs a, PgmTreelikRatesStride st) {
+    const size_t c = blockIdx.y;
+    a.P += st.P * c;
+    a.U += st.U * c;
+    a.site_l += st.L * c;
+    a.site_k += st.L * c;
+    if (a.derivs) { a.O += st.U * c; a.g += st.G * c; a.h += st.G * c; }
+    pgm_treelik_walk<true>(a);
+}
+
+// The categories of a site combined in the order of the interface.  A workgroup owns 64 consecutive sites (reads and writes run along
+// the sites); its thread computes site_k = min_c k_c, term_c = w_c L_c times 2^-256 (k_c - site_k) times, site_l = sum_c term_c and
+// post_c = term_c / site_l, and keeps post in shared memory.  The workgroups of blockIdx.y == 0 write these; then every workgroup
+// takes the edges blockIdx.y, blockIdx.y + gridDim.y, ... and writes g = sum_c post_c g_c and h = sum_c post_c q_c - g g of its
+// sites.  Every entry has one writer.
+struct PgmTreelikCombineArgs {
+    uint32_t ncat, ncols, nedges;
+    const double *w, *L;         // ncat; ncat x ncols
+    const int32_t *k;            // ncat x ncols
+    const double *gc, *qc;       // ncat x nedges x ncols each (nedges == 0: none)
+    double *site_l, *post, *g, *h;
+    int32_t *site_k;
+};
+__global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_combine_kernel(PgmTreelikCombineArgs a) {
+    __shared__ double post[PGM_TREELIK_MAXCAT][PGM_TREELIK_THREADS];
+    const uint64_t s64 = (uint64_t)blockIdx.x * PGM_TREELIK_THREADS + threadIdx.x;
+    if (s64 >= a.ncols) return;   // (no barrier below: a thread reads its own column of `post` only)
+    const size_t s = (size_t)s64, ncols = a.ncols;
+    int32_t kmin = a.k[s];
+    for (uint32_t c = 1; c < a.ncat; ++c) { const int32_t kc = a.k[c * ncols + s]; kmin = kc < kmin ? kc : kmin; }
+    double total = 0.0;
+    for (uint32_t c = 0; c < a.ncat; ++c) {
+        double term = a.w[c] * a.L[c * ncols + s];
+        for (int32_t d = a.k[c * ncols + s] - kmin; d > 0; --d) term = term * 0x1p-256;
+        post[c][threadIdx.x] = term;
+        total = total + term;
+    }
+    for (uint32_t c = 0; c < a.ncat; ++c) post[c][threadIdx.x] = post[c][threadIdx.x] / total;
+    if (blockIdx.y == 0) {
+        a.site_l[s] = total;
+        a.site_k[s] = kmin;
+        for (uint32_t c = 0; c < a.ncat; ++c) a.post[c * ncols + s] = post[c][threadIdx.x];
+    }
+    const size_t cat = (size_t)a.nedges * ncols;
+    for (uint32_t e = blockIdx.y; e < a.nedges; e += gridDim.y) {
+        const size_t at = (size_t)e * ncols + s;
+        double g = 0.0, q = 0.0;
+        for (uint32_t c = 0; c < a.ncat; ++c) {
+            g = g + post[c][threadIdx.x] * a.gc[cat * c + at];
+            q = q + post[c][threadIdx.x] * a.qc[cat * c + at];
+        }
+        a.g[at] = g;
+        a.h[at] = q - g * g;
     }
 }
 

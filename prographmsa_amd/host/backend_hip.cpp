@@ -152,6 +152,14 @@ struct HipBackend : Backend {
         if (rc != PGM_OK) error("pgm_tree_likelihood failed (%d): %s", rc, pgm_last_error());
         ml_tree_stats.kernel_ms += pgm_treelik_last_kernel_ms(c);
     }
+    void tree_likelihood_rates(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
+                               uint32_t ncat, const double *w, const double *P, int derivs, double *site_l, int32_t *site_k, double *post, double *d1, double *d2,
+                               int worker) override {
+        pgm_ctx *c = ctx_of(worker);
+        int rc = pgm_tree_likelihood_rates(c, dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, derivs, site_l, site_k, post, d1, d2);
+        if (rc != PGM_OK) error("pgm_tree_likelihood_rates failed (%d): %s", rc, pgm_last_error());
+        ml_tree_stats.kernel_ms += pgm_treelik_last_kernel_ms(c);
+    }
     bool bionj_multi(uint32_t nfam, const uint32_t *n, const double *D, const double *V, pgm_bionj_join *joins, double *final_d, int worker) override {
         pgm_ctx *c = ctx_of(worker);
         int rc = pgm_bionj_multi(c, nfam, n, D, V, joins, final_d);

@@ -28,7 +28,8 @@ static void usage() {
                  "             [--bootstrap <N> --bootstrap_out <file> [--bootstrap_seed <S>] [--bootstrap_tbe <file>] [--bootstrap_trees <file>]\n"
                  "              [--bootstrap_taxa <file> [--bootstrap_taxa_cutoff <X>] [--bootstrap_taxa_edges <file>]]]\n"
                  "             [--guidance <N> --guidance_out <file> [--guidance_seed <S>] [--guidance_residues <file>] [--guidance_dump <prefix>]]\n"
-                 "             [--ml_tree <file> [--ml_sites <file>] [--ml_rounds <N>] [--ml_epsilon <X>]]\n"
+                 "             [--ml_tree <file> [--ml_sites <file>] [--ml_rounds <N>] [--ml_epsilon <X>]\n"
+                 "              [--ml_gamma <K> [--ml_alpha <X>] [--ml_rates <file>]]]\n"
                  "             <fasta file>\n"
                  "       pgmsa --batch <list> [--batch_cells <cells>] [options]\n"
                  "  --batch <list>  align many families in one run: every line of <list> is input.fa<TAB>output[<TAB>guide_tree.nwk[<TAB>topology.nwk]]\n"
@@ -88,6 +89,11 @@ static void usage() {
                  "                log-likelihood of every column (column<TAB>value, columns from 1).  --ml_rounds <N> (1 <= N <= 10000, default\n"
                  "                100) bounds the rounds of the optimiser, --ml_epsilon <X> (X >= 0, default 1e-4) is the gain of lnL below\n"
                  "                which it stops.  Needs at least 3 sequences; not with --batch, -W, -r, --topology\n"
+                 "  --ml_gamma <K>  with --ml_tree: rate variation across columns by a discrete gamma of <K> (2 .. 16) equally probable\n"
+                 "                categories of mean 1; the likelihood and --ml_sites are the mixture's.  --ml_alpha <X> (0.05 <= X <= 100)\n"
+                 "                fixes the shape; without it the shape is estimated together with the branch lengths (--ml_rounds then bounds\n"
+                 "                every run of the branch-length loop).  --ml_rates <file>: `alpha<TAB>value`, per category\n"
+                 "                `rate<TAB>k<TAB>value`, then per column `column<TAB>posterior mean rate<TAB>most probable category`\n"
                  "  -W, --wls_refine  refine every guide tree estimated from distances by weighted least squares (nearest-neighbour\n"
                  "                interchanges of quartets); given twice (-WW), quintet moves as well\n";
 }
@@ -226,12 +232,12 @@ struct GuidanceOpts {   // --guidance N --guidance_out FILE --guidance_seed S --
     double cells = 2e9;   // --batch_cells: estimated DP cells of one group of replicates
 } g_guidance;
 
-struct MlTreeOpts {   // --ml_tree FILE --ml_sites FILE --ml_rounds N --ml_epsilon X
-    std::string tree, sites, rounds_text, eps_text;
-    bool tree_given = false, sites_given = false, rounds_given = false, eps_given = false;
-    long rounds = 100;
-    double eps = 1e-4;
-    bool any() const { return tree_given || sites_given || rounds_given || eps_given; }
+struct MlTreeOpts {   // --ml_tree FILE --ml_sites FILE --ml_rounds N --ml_epsilon X --ml_gamma K --ml_alpha X --ml_rates FILE
+    std::string tree, sites, rounds_text, eps_text, gamma_text, alpha_text, rates;
+    bool tree_given = false, sites_given = false, rounds_given = false, eps_given = false, gamma_given = false, alpha_given = false, rates_given = false;
+    long rounds = 100, gamma = 0;
+    double eps = 1e-4, alpha = 1.0;
+    bool any() const { return tree_given || sites_given || rounds_given || eps_given || gamma_given || alpha_given || rates_given; }
 } g_mltree;
 }  // namespace
 
@@ -299,7 +305,9 @@ static void doBootstrap(const Alphabet &a, const Family &fam, const std::map<std
 // --ml_tree: the tree of --bootstrap (TreeNJ on the final alignment without its ancestral rows, midpoint rooted) with the branch
 // lengths that maximise the likelihood of the alignment as it is written (start / stop columns re-inserted, every residue the
 // character of the input: Family::finish_rows), and --ml_sites: the log-likelihood of every column (ml_branch_lengths, DESIGN.md
-// 3.17; the device from kTreelikDeviceMin taxa or with PGM_DEVICE_TREELIK, the host loop with PGM_HOST_TREELIK)
+// 3.17; the device from kTreelikDeviceMin taxa or with PGM_DEVICE_TREELIK, the host loop with PGM_HOST_TREELIK).  With --ml_gamma the
+// likelihood is the mixture over the rate categories of the discrete gamma (the same route), and --ml_rates: the
+// shape, the categories' rates, and per column the posterior mean rate and the category of the largest posterior
 static void doMlTree(const Alphabet &a, const Family &fam, const std::map<std::string, sequence_t> &alignment) {
     std::map<std::string, sequence_t> rows;
     for (const auto &kv : alignment)
@@ -320,7 +328,9 @@ static void doMlTree(const Alphabet &a, const Family &fam, const std::map<std::s
     }
     const HostSwitches &sw = host_switches();
     const bool device = !sw.host_treelik && (sw.device_treelik || rows.size() >= kTreelikDeviceMin);
-    const MlTreeResult res = ml_branch_lengths(a, values, *fam.model_factory, *tree, (uint32_t)g_mltree.rounds, g_mltree.eps, device ? &default_backend() : nullptr);
+    MlGamma gamma;
+    if (g_mltree.gamma_given) { gamma.ncat = (uint32_t)g_mltree.gamma; gamma.estimate = !g_mltree.alpha_given; gamma.alpha = g_mltree.alpha; }
+    const MlTreeResult res = ml_branch_lengths(a, values, *fam.model_factory, *tree, (uint32_t)g_mltree.rounds, g_mltree.eps, device ? &default_backend() : nullptr, gamma);
     std::unique_ptr<PhyTree> ml(ml_tree_with_lengths(ml_tree_topology(*tree), res.lengths));
     std::ofstream out(g_mltree.tree.c_str());
     if (!out) error("error opening the ml tree output file %s", g_mltree.tree.c_str());
@@ -334,6 +344,28 @@ static void doMlTree(const Alphabet &a, const Family &fam, const std::map<std::s
         for (size_t c = 0; c < res.site_lnl.size(); ++c) {
             snprintf(buf, sizeof buf, "%zu\t%.17g\n", c + 1, res.site_lnl[c]);
             sites << buf;
+        }
+    }
+    if (g_mltree.rates_given) {
+        std::ofstream rates(g_mltree.rates.c_str());
+        if (!rates) error("error opening the ml tree output file %s", g_mltree.rates.c_str());
+        char buf[96];
+        snprintf(buf, sizeof buf, "alpha\t%.17g\n", res.alpha);
+        rates << buf;
+        const size_t ncat = res.rates.size(), ncols = res.site_lnl.size();
+        for (size_t k = 0; k < ncat; ++k) {
+            snprintf(buf, sizeof buf, "rate\t%zu\t%.17g\n", k + 1, res.rates[k]);
+            rates << buf;
+        }
+        for (size_t c = 0; c < ncols; ++c) {   // the posterior mean rate, categories ascending; the first category of the largest posterior
+            double mean = 0.0;
+            size_t top = 0;
+            for (size_t k = 0; k < ncat; ++k) {
+                mean = mean + res.post[k * ncols + c] * res.rates[k];
+                if (res.post[k * ncols + c] > res.post[top * ncols + c]) top = k;
+            }
+            snprintf(buf, sizeof buf, "%zu\t%.17g\t%zu\n", c + 1, mean, top + 1);
+            rates << buf;
         }
     }
 }
@@ -379,6 +411,8 @@ static void print_stats(double t_init, double t_tree, double t_prog, const Batch
         fprintf(stderr, ", \"ml_tree_s\": %.6f, \"ml_rounds\": %llu, \"ml_evaluations\": %llu, \"ml_lnl_start\": %.17g, \"ml_lnl\": %.17g, \"ml_kernel_ms\": %.3f",
                 ml_tree_stats.seconds, (unsigned long long)ml_tree_stats.rounds, (unsigned long long)ml_tree_stats.evaluations, ml_tree_stats.lnl_start, ml_tree_stats.lnl,
                 ml_tree_stats.kernel_ms);
+    if (g_mltree.gamma_given)   // (keys of --ml_gamma only)
+        fprintf(stderr, ", \"ml_categories\": %u, \"ml_alpha\": %.17g", ml_tree_stats.categories, ml_tree_stats.alpha);
     if (batch)   // (keys of --batch only)
         fprintf(stderr, ", \"batch_families\": %d, \"batch_failed\": %d, \"batch_chunks\": %d, \"batch_passes\": %llu, \"batch_levels\": %llu, "
                         "\"batch_align_calls\": %llu, \"batch_dist_calls\": %llu",
@@ -835,6 +869,9 @@ int main(int argc, char **argv) {
             else if (s == "--ml_sites") { g_mltree.sites_given = true; g_mltree.sites = val(); }
             else if (s == "--ml_rounds") { g_mltree.rounds_given = true; g_mltree.rounds_text = val(); }
             else if (s == "--ml_epsilon") { g_mltree.eps_given = true; g_mltree.eps_text = val(); }
+            else if (s == "--ml_gamma") { g_mltree.gamma_given = true; g_mltree.gamma_text = val(); }
+            else if (s == "--ml_alpha") { g_mltree.alpha_given = true; g_mltree.alpha_text = val(); }
+            else if (s == "--ml_rates") { g_mltree.rates_given = true; g_mltree.rates = val(); }
             else if (s == "--reroot") ++cmdlineopts.reroot_flag;
             else if (s == "--wls_refine") ++cmdlineopts.wlsrefine_flag;
             else if (s.size() >= 2 && s[0] == '-' && s.find_first_not_of('W', 1) == std::string::npos) cmdlineopts.wlsrefine_flag += (int)s.size() - 1;   // -W, -WW
@@ -888,7 +925,7 @@ int main(int argc, char **argv) {
         if (g_mltree.any()) {
             // (the rounds are a whole number in 1 .. 10000, the gain a finite number >= 0: other text, a NaN and everything outside are refused)
             char *end = nullptr;
-            bool rounds_ok = true, eps_ok = true;
+            bool rounds_ok = true, eps_ok = true, gamma_ok = true, alpha_ok = true;
             if (g_mltree.rounds_given) {
                 g_mltree.rounds = strtol(g_mltree.rounds_text.c_str(), &end, 10);
                 rounds_ok = !g_mltree.rounds_text.empty() && *end == '\0' && g_mltree.rounds >= 1 && g_mltree.rounds <= 10000;
@@ -897,7 +934,19 @@ int main(int argc, char **argv) {
                 g_mltree.eps = strtod(g_mltree.eps_text.c_str(), &end);
                 eps_ok = !g_mltree.eps_text.empty() && *end == '\0' && g_mltree.eps >= 0.0 && g_mltree.eps < INFINITY;
             }
-            const char *why = !g_mltree.tree_given ? "--ml_sites, --ml_rounds and --ml_epsilon need --ml_tree"
+            if (g_mltree.gamma_given) {   // (the categories are a whole number in 2 .. 16, the shape a number in [0.05, 100])
+                g_mltree.gamma = strtol(g_mltree.gamma_text.c_str(), &end, 10);
+                gamma_ok = !g_mltree.gamma_text.empty() && *end == '\0' && g_mltree.gamma >= 2 && g_mltree.gamma <= PGM_TREELIK_MAXCAT;
+            }
+            if (g_mltree.alpha_given) {
+                g_mltree.alpha = strtod(g_mltree.alpha_text.c_str(), &end);
+                alpha_ok = !g_mltree.alpha_text.empty() && *end == '\0' && g_mltree.alpha >= kMlMinAlpha && g_mltree.alpha <= kMlMaxAlpha;
+            }
+            const bool plain = g_mltree.sites_given || g_mltree.rounds_given || g_mltree.eps_given;   // (the flags from before --ml_gamma keep their message)
+            const char *why = !g_mltree.tree_given ? (plain ? "--ml_sites, --ml_rounds and --ml_epsilon need --ml_tree" : "--ml_gamma, --ml_alpha and --ml_rates need --ml_tree")
+                              : (!g_mltree.gamma_given && (g_mltree.alpha_given || g_mltree.rates_given)) ? "--ml_alpha and --ml_rates need --ml_gamma"
+                              : !gamma_ok ? "--ml_gamma takes a number of categories from 2 to 16"
+                              : !alpha_ok ? "--ml_alpha takes a number X with 0.05 <= X <= 100"
                               : !rounds_ok ? "--ml_rounds takes a number of rounds from 1 to 10000"
                               : !eps_ok ? "--ml_epsilon takes a number X >= 0"
                               : cmdlineopts.wlsrefine_flag ? "--ml_tree cannot be combined with -W"

@@ -341,6 +341,11 @@ struct Backend {
     // include/pgm_hip.h: pgm_tree_likelihood).  The default is the host statement, tree_likelihood_host: the same bits.
     virtual void tree_likelihood(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
                                  const double *P, int derivs, double *site_l, int32_t *site_k, double *d1, double *d2, int worker = 0);
+    // The same under a mixture of rate categories (--ml_gamma; include/pgm_hip.h: pgm_tree_likelihood_rates).  The default is the host
+    // statement, tree_likelihood_rates_host: the same bits.
+    virtual void tree_likelihood_rates(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
+                                       uint32_t ncat, const double *w, const double *P, int derivs, double *site_l, int32_t *site_k, double *post, double *d1, double *d2,
+                                       int worker = 0);
     // calls the host code made of the align-batch entry and of the distance entries (all-pairs tiles, pair counts, cosine, ML
     // distances): `pgmsa --batch --stats` shows with them that a stage was shared by the families of a chunk
     std::atomic<uint64_t> calls_align{0}, calls_dist{0};
@@ -738,13 +743,23 @@ std::string taxa_edges_text(const TaxaSupport &t);
 // treelik_lnl: sum over the sites of log(site_l) - 256 ln 2 site_k, sites ascending; site_lnl (may be null) gets the terms.
 // ml_branch_lengths: the optimiser.  rows: the alignment's rows in sorted-name order as state values (0..dim-1, -1 a gap, -2 a residue
 //   without a value), all of one length.  be: the backend whose tree_likelihood runs, nullptr for the host loop.
+// --ml_gamma (host/treelik_rates.inc):
+// tree_likelihood_rates_host: pgm_tree_likelihood_rates by the same loop, Backend::tree_likelihood_rates's default.
+// gamma_rates: the K rates of the discrete gamma of shape alpha (Yang 1994, category means), equally probable, their mean 1.
+// treelik_matrices with rates: category-major, for category c and edge e P(r_c t_e), r_c Q P, r_c^2 Q Q P.
+// MlGamma: what ml_branch_lengths is asked for (ncat < 2: one rate for every column, the loop of --ml_tree alone); with `estimate`
+//   alpha starts at 1 and the branch-length loop alternates with a golden-section search on ln alpha.
 const double kMlMinLength = 1e-6, kMlMaxLength = 10.0;   // the interval every branch length stays in
+const double kMlMinAlpha = 0.05, kMlMaxAlpha = 100.0;     // ... and the shape of the gamma
+const uint32_t kMlAlphaEvaluations = 12, kMlMaxPairs = 20;   // one search on ln alpha; branch-length loop + search pairs at the most
 // alignments of this many taxa and more go to the device by default: the smallest size at which the two routes were timed, and the
 // device was faster there and at every larger one (measured once); below it the host loop runs, untimed
 const uint32_t kTreelikDeviceMin = 24;
 struct MlTreeStats {   // `pgmsa --ml_tree --stats`
     double seconds = 0, kernel_ms = 0, lnl_start = 0, lnl = 0;
     uint64_t rounds = 0, evaluations = 0;
+    uint32_t categories = 0;   // --ml_gamma only
+    double alpha = 0;
 };
 extern MlTreeStats ml_tree_stats;
 struct MlTreeTopology {
@@ -758,14 +773,25 @@ void tree_likelihood_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const
                           const double *P, int derivs, double *site_l, int32_t *site_k, double *d1, double *d2);
 void treelik_matrices(const ModelFactory &mf, const std::vector<double> &t /* nnodes - 1 */, bool derivs, std::vector<double> &P);
 double treelik_lnl(uint32_t ncols, const double *site_l, const int32_t *site_k, double *site_lnl);
+void tree_likelihood_rates_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
+                                uint32_t ncat, const double *w, const double *P, int derivs, double *site_l, int32_t *site_k, double *post, double *d1, double *d2);
+std::vector<double> gamma_rates(double alpha, uint32_t K);
+void treelik_matrices(const ModelFactory &mf, const std::vector<double> &t, bool derivs, const std::vector<double> &rates, std::vector<double> &P);
+struct MlGamma {
+    uint32_t ncat = 0;
+    bool estimate = true;
+    double alpha = 1.0;
+};
 struct MlTreeResult {
     std::vector<double> lengths;    // per edge (node below it)
     std::vector<double> site_lnl;   // per column, at `lengths`
     double lnl_start = 0, lnl = 0;
     uint32_t rounds = 0, evaluations = 0;
+    double alpha = 0;               // --ml_gamma only: the shape, the categories' rates, post (ncat x ncols) at `lengths`
+    std::vector<double> rates, post;
 };
 MlTreeResult ml_branch_lengths(const Alphabet &a, const std::vector<std::vector<int8_t>> &rows, const ModelFactory &model_factory, const PhyTree &tree,
-                               uint32_t rounds, double eps, Backend *be = nullptr);
+                               uint32_t rounds, double eps, Backend *be = nullptr, const MlGamma &gamma = MlGamma());
 // a copy of `tree` whose edge above topo.node[e] has length lengths[e]
 PhyTree *ml_tree_with_lengths(const MlTreeTopology &topo, const std::vector<double> &lengths);
 

@@ -1,7 +1,7 @@
 // treelik.inc — the host parts of `pgmsa --ml_tree` (included by model_factory.cpp; DESIGN.md 3.17): the host statement of
 // pgm_tree_likelihood (Backend::tree_likelihood's default, what pgmsa_oracle runs), the matrices of every edge, the log-likelihood
-// both drivers share, the numbering of a tree's nodes, and the branch-length optimiser.  The flow that writes the files is doMlTree
-// in main.cpp.
+// both drivers share, the numbering of a tree's nodes, and the optimiser of the branch lengths (and, with --ml_gamma, of the gamma's
+// shape: treelik_rates.inc has the categories' side, DESIGN.md 3.18).  The flow that writes the files is doMlTree in main.cpp.
 //
 // The arithmetic is Felsenstein pruning per site with both derivatives by every branch length.  Every sum runs over its index
 // ascending from 0.0 with one multiply and one add per term, every product over the children in node order, and only + - * / occur:
@@ -70,84 +70,114 @@ inline bool treelik_rescale(double *v, uint32_t dim) {
     for (uint32_t i = 0; i < dim; ++i) v[i] = v[i] * kTreelikScale;
     return true;
 }
-}  // namespace
-
-void tree_likelihood_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
-                          const double *P, int derivs, double *site_l, int32_t *site_k, double *d1, double *d2) {
-    const TreelikChildren ch = treelik_check_host(dim, nleaves, nnodes, parent, ncols, rows, pi, P, derivs, site_l, site_k, d1, d2);
-    const uint32_t ninner = nnodes - nleaves, nedges = nnodes - 1, root = nnodes - 1;
-    const size_t mat = (size_t)dim * dim, estride = derivs ? 3 * mat : mat;
-    const size_t nchunks = ((size_t)ncols + kTreelikChunk - 1) / kTreelikChunk;
-    uint32_t max_kids = 2;
-    for (uint32_t v = nleaves; v < nnodes; ++v) max_kids = std::max(max_kids, ch.off[v + 1] - ch.off[v]);
-    std::vector<double> c1, c2;   // per chunk and edge: the sums of g and h over the chunk's sites, ascending
-    if (derivs) { c1.assign(nchunks * nedges, 0.0); c2.assign(nchunks * nedges, 0.0); }
-
-    parallel_for(nchunks, [&](size_t chunk) {
-        std::vector<double> U((size_t)ninner * dim), O(derivs ? (size_t)ninner * dim : 0), S((size_t)max_kids * dim), base(dim), o(dim), T(3 * (size_t)dim);
-        const uint32_t s0 = (uint32_t)(chunk * kTreelikChunk), s1 = (uint32_t)std::min<size_t>(ncols, (size_t)s0 + kTreelikChunk);
-        for (uint32_t s = s0; s < s1; ++s) {
-            auto partial = [&](uint32_t c) -> const double * { return c < nleaves ? nullptr : &U[(size_t)(c - nleaves) * dim]; };
-            auto value = [&](uint32_t c) -> int { return c < nleaves ? (int)rows[(size_t)c * ncols + s] : 0; };
-            // up pass
-            int32_t k = 0;
-            for (uint32_t v = nleaves; v < nnodes; ++v) {
-                double *Uv = &U[(size_t)(v - nleaves) * dim];
-                for (uint32_t q = ch.off[v]; q < ch.off[v + 1]; ++q) {
-                    const uint32_t c = ch.idx[q];
-                    treelik_apply(P + estride * c, dim, partial(c), value(c), S.data());
-                    if (q == ch.off[v]) for (uint32_t i = 0; i < dim; ++i) Uv[i] = S[i];
-                    else for (uint32_t i = 0; i < dim; ++i) Uv[i] = Uv[i] * S[i];
-                }
-                if (treelik_rescale(Uv, dim)) ++k;
-            }
-            double L = 0.0;
-            for (uint32_t i = 0; i < dim; ++i) L = L + pi[i] * U[(size_t)(root - nleaves) * dim + i];
-            site_l[s] = L;
-            site_k[s] = k;
-            if (!derivs) continue;
-            // down pass: the outside vector of every edge, then the three sums of the edge
-            for (uint32_t v = root; v >= nleaves; --v) {
-                if (v == root) for (uint32_t i = 0; i < dim; ++i) base[i] = pi[i];
-                else {
-                    const double *Ov = &O[(size_t)(v - nleaves) * dim], *Pv = P + estride * v;
-                    for (uint32_t i = 0; i < dim; ++i) {
-                        double acc = 0.0;
-                        for (uint32_t h = 0; h < dim; ++h) acc = acc + Ov[h] * Pv[h + (size_t)dim * i];
-                        base[i] = acc;
-                    }
-                }
-                const uint32_t q0 = ch.off[v], q1 = ch.off[v + 1];
-                for (uint32_t q = q0; q < q1; ++q) treelik_apply(P + estride * ch.idx[q], dim, partial(ch.idx[q]), value(ch.idx[q]), &S[(size_t)(q - q0) * dim]);
-                for (uint32_t q = q0; q < q1; ++q) {
-                    const uint32_t c = ch.idx[q];
-                    for (uint32_t i = 0; i < dim; ++i) o[i] = base[i];
-                    for (uint32_t r = q0; r < q1; ++r)
-                        if (r != q) for (uint32_t i = 0; i < dim; ++i) o[i] = o[i] * S[(size_t)(r - q0) * dim + i];
-                    treelik_rescale(o.data(), dim);
-                    if (c >= nleaves) std::copy(o.begin(), o.end(), O.begin() + (size_t)(c - nleaves) * dim);
-                    double A[3];
-                    for (int x = 0; x < 3; ++x) {
-                        if (x == 0) std::copy(S.begin() + (size_t)(q - q0) * dim, S.begin() + (size_t)(q - q0 + 1) * dim, T.begin());
-                        else treelik_apply(P + estride * c + mat * x, dim, partial(c), value(c), T.data());
-                        double acc = 0.0;
-                        for (uint32_t i = 0; i < dim; ++i) acc = acc + o[i] * T[i];
-                        A[x] = acc;
-                    }
-                    const double g = A[1] / A[0], h = A[2] / A[0] - g * g;
-                    c1[chunk * nedges + c] = c1[chunk * nedges + c] + g;
-                    c2[chunk * nedges + c] = c2[chunk * nedges + c] + h;
-                }
-            }
-        }
-    });
-    if (!derivs) return;
+// d1[e], d2[e]: the chunk sums of edge e, chunks ascending
+inline void treelik_chunk_totals(const std::vector<double> &c1, const std::vector<double> &c2, size_t nchunks, uint32_t nedges, double *d1, double *d2) {
     for (uint32_t e = 0; e < nedges; ++e) {
         double a1 = 0.0, a2 = 0.0;
         for (size_t chunk = 0; chunk < nchunks; ++chunk) { a1 = a1 + c1[chunk * nedges + e]; a2 = a2 + c2[chunk * nedges + e]; }
         d1[e] = a1;
         d2[e] = a2;
     }
+}
+
+// The walk over the tree for one site at a time, with the scratch of one thread: the up pass, the scaling rule, and with derivs the
+// down pass and the three sums of every edge.  Both host statements are loops over it.
+struct TreelikSiteWalk {
+    const TreelikChildren &ch;
+    uint32_t dim, nleaves, nnodes, ncols;
+    const int8_t *rows;
+    const double *pi;
+    bool derivs;
+    std::vector<double> U, O, S, base, o, T;
+    TreelikSiteWalk(const TreelikChildren &ch_, uint32_t dim_, uint32_t nleaves_, uint32_t nnodes_, uint32_t ncols_, const int8_t *rows_, const double *pi_, bool derivs_)
+        : ch(ch_), dim(dim_), nleaves(nleaves_), nnodes(nnodes_), ncols(ncols_), rows(rows_), pi(pi_), derivs(derivs_) {
+        uint32_t max_kids = 2;
+        for (uint32_t v = nleaves; v < nnodes; ++v) max_kids = std::max(max_kids, ch.off[v + 1] - ch.off[v]);
+        const size_t ninner = nnodes - nleaves;
+        U.resize(ninner * dim); O.resize(derivs ? ninner * dim : 0); S.resize((size_t)max_kids * dim); base.resize(dim); o.resize(dim); T.resize(3 * (size_t)dim);
+    }
+    // site s under the matrices P: (L, k), and with derivs g[e] = A^P' / A^P and q[e] = A^P'' / A^P of every edge e
+    void operator()(uint32_t s, const double *P, double &L_out, int32_t &k_out, double *g, double *q) {
+        const uint32_t root = nnodes - 1;
+        const size_t mat = (size_t)dim * dim, estride = derivs ? 3 * mat : mat;
+        auto partial = [&](uint32_t c) -> const double * { return c < nleaves ? nullptr : &U[(size_t)(c - nleaves) * dim]; };
+        auto value = [&](uint32_t c) -> int { return c < nleaves ? (int)rows[(size_t)c * ncols + s] : 0; };
+        // up pass
+        int32_t k = 0;
+        for (uint32_t v = nleaves; v < nnodes; ++v) {
+            double *Uv = &U[(size_t)(v - nleaves) * dim];
+            for (uint32_t qq = ch.off[v]; qq < ch.off[v + 1]; ++qq) {
+                const uint32_t c = ch.idx[qq];
+                treelik_apply(P + estride * c, dim, partial(c), value(c), S.data());
+                if (qq == ch.off[v]) for (uint32_t i = 0; i < dim; ++i) Uv[i] = S[i];
+                else for (uint32_t i = 0; i < dim; ++i) Uv[i] = Uv[i] * S[i];
+            }
+            if (treelik_rescale(Uv, dim)) ++k;
+        }
+        double L = 0.0;
+        for (uint32_t i = 0; i < dim; ++i) L = L + pi[i] * U[(size_t)(root - nleaves) * dim + i];
+        L_out = L;
+        k_out = k;
+        if (!derivs) return;
+        // down pass: the outside vector of every edge, then the three sums of the edge
+        for (uint32_t v = root; v >= nleaves; --v) {
+            if (v == root) for (uint32_t i = 0; i < dim; ++i) base[i] = pi[i];
+            else {
+                const double *Ov = &O[(size_t)(v - nleaves) * dim], *Pv = P + estride * v;
+                for (uint32_t i = 0; i < dim; ++i) {
+                    double acc = 0.0;
+                    for (uint32_t h = 0; h < dim; ++h) acc = acc + Ov[h] * Pv[h + (size_t)dim * i];
+                    base[i] = acc;
+                }
+            }
+            const uint32_t q0 = ch.off[v], q1 = ch.off[v + 1];
+            for (uint32_t qq = q0; qq < q1; ++qq) treelik_apply(P + estride * ch.idx[qq], dim, partial(ch.idx[qq]), value(ch.idx[qq]), &S[(size_t)(qq - q0) * dim]);
+            for (uint32_t qq = q0; qq < q1; ++qq) {
+                const uint32_t c = ch.idx[qq];
+                for (uint32_t i = 0; i < dim; ++i) o[i] = base[i];
+                for (uint32_t r = q0; r < q1; ++r)
+                    if (r != qq) for (uint32_t i = 0; i < dim; ++i) o[i] = o[i] * S[(size_t)(r - q0) * dim + i];
+                treelik_rescale(o.data(), dim);
+                if (c >= nleaves) std::copy(o.begin(), o.end(), O.begin() + (size_t)(c - nleaves) * dim);
+                double A[3];
+                for (int x = 0; x < 3; ++x) {
+                    if (x == 0) std::copy(S.begin() + (size_t)(qq - q0) * dim, S.begin() + (size_t)(qq - q0 + 1) * dim, T.begin());
+                    else treelik_apply(P + estride * c + mat * x, dim, partial(c), value(c), T.data());
+                    double acc = 0.0;
+                    for (uint32_t i = 0; i < dim; ++i) acc = acc + o[i] * T[i];
+                    A[x] = acc;
+                }
+                g[c] = A[1] / A[0];
+                q[c] = A[2] / A[0];
+            }
+        }
+    }
+};
+}  // namespace
+
+void tree_likelihood_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
+                          const double *P, int derivs, double *site_l, int32_t *site_k, double *d1, double *d2) {
+    const TreelikChildren ch = treelik_check_host(dim, nleaves, nnodes, parent, ncols, rows, pi, P, derivs, site_l, site_k, d1, d2);
+    const uint32_t nedges = nnodes - 1;
+    const size_t nchunks = ((size_t)ncols + kTreelikChunk - 1) / kTreelikChunk;
+    std::vector<double> c1, c2;   // per chunk and edge: the sums of g and h over the chunk's sites, ascending
+    if (derivs) { c1.assign(nchunks * nedges, 0.0); c2.assign(nchunks * nedges, 0.0); }
+
+    parallel_for(nchunks, [&](size_t chunk) {
+        TreelikSiteWalk walk(ch, dim, nleaves, nnodes, ncols, rows, pi, derivs != 0);
+        std::vector<double> g(nedges), q(nedges);
+        const uint32_t s0 = (uint32_t)(chunk * kTreelikChunk), s1 = (uint32_t)std::min<size_t>(ncols, (size_t)s0 + kTreelikChunk);
+        for (uint32_t s = s0; s < s1; ++s) {
+            walk(s, P, site_l[s], site_k[s], g.data(), q.data());
+            if (!derivs) continue;
+            for (uint32_t e = 0; e < nedges; ++e) {
+                c1[chunk * nedges + e] = c1[chunk * nedges + e] + g[e];
+                c2[chunk * nedges + e] = c2[chunk * nedges + e] + (q[e] - g[e] * g[e]);
+            }
+        }
+    });
+    if (!derivs) return;
+    treelik_chunk_totals(c1, c2, nchunks, nedges, d1, d2);
 }
 
 void Backend::tree_likelihood(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
@@ -233,7 +263,7 @@ PhyTree *ml_tree_with_lengths(const MlTreeTopology &topo, const std::vector<doub
 }
 
 MlTreeResult ml_branch_lengths(const Alphabet &a, const std::vector<std::vector<int8_t>> &rows, const ModelFactory &model_factory, const PhyTree &tree,
-                               uint32_t rounds, double eps, Backend *be) {
+                               uint32_t rounds, double eps, Backend *be, const MlGamma &gamma) {
     const auto t0 = std::chrono::steady_clock::now();
     const MlTreeTopology topo = ml_tree_topology(tree);
     const uint32_t dim = (uint32_t)model_factory.dim(), nleaves = topo.nleaves, nnodes = topo.nnodes, nedges = nnodes - 1;
@@ -248,41 +278,95 @@ MlTreeResult ml_branch_lengths(const Alphabet &a, const std::vector<std::vector<
         std::copy(rows[r].begin(), rows[r].end(), flat.begin() + (size_t)r * ncols);
     }
     auto clamp = [](double t) { return !(t > kMlMinLength) ? kMlMinLength : t > kMlMaxLength ? kMlMaxLength : t; };   // (a NaN: the lower bound)
+    const uint32_t ncat = gamma.ncat >= 2 ? gamma.ncat : 0;   // 0: one rate, the entry without categories
+    if (ncat > PGM_TREELIK_MAXCAT) error("ml tree: %u rate categories", ncat);
 
     MlTreeResult res;
     std::vector<double> t(nedges), P, site_l(ncols), trial_l(ncols), d1(nedges), d2(nedges), target(nedges), trial(nedges);
     std::vector<int32_t> site_k(ncols), trial_k(ncols);
+    std::vector<double> rates, post((size_t)ncat * ncols), trial_post(post.size());   // (with categories only)
+    const std::vector<double> weights(ncat, ncat ? 1.0 / (double)ncat : 0.0);
+    double alpha = gamma.estimate ? 1.0 : gamma.alpha;
+    if (ncat) rates = gamma_rates(alpha, ncat);
     for (uint32_t e = 0; e < nedges; ++e) t[e] = clamp(topo.node[e]->getBranchLength());
-    auto evaluate = [&](const std::vector<double> &at, bool derivs, double *l, int32_t *k) {
-        treelik_matrices(model_factory, at, derivs, P);
-        if (be) be->tree_likelihood(dim, nleaves, nnodes, topo.parent.data(), ncols, flat.data(), model_factory.freqs().data(), P.data(), derivs ? 1 : 0, l, k, d1.data(), d2.data());
-        else tree_likelihood_host(dim, nleaves, nnodes, topo.parent.data(), ncols, flat.data(), model_factory.freqs().data(), P.data(), derivs ? 1 : 0, l, k, d1.data(), d2.data());
+    const double *pi = model_factory.freqs().data();
+    // lnL at the lengths `at` (and the categories' rates `r`): the site values into l, k (and pp), with derivs d1 and d2
+    auto evaluate = [&](const std::vector<double> &at, const std::vector<double> &r, bool derivs, double *l, int32_t *k, double *pp) {
+        if (ncat) {
+            treelik_matrices(model_factory, at, derivs, r, P);
+            if (be) be->tree_likelihood_rates(dim, nleaves, nnodes, topo.parent.data(), ncols, flat.data(), pi, ncat, weights.data(), P.data(), derivs ? 1 : 0, l, k, pp, d1.data(), d2.data());
+            else tree_likelihood_rates_host(dim, nleaves, nnodes, topo.parent.data(), ncols, flat.data(), pi, ncat, weights.data(), P.data(), derivs ? 1 : 0, l, k, pp, d1.data(), d2.data());
+        } else {
+            treelik_matrices(model_factory, at, derivs, P);
+            if (be) be->tree_likelihood(dim, nleaves, nnodes, topo.parent.data(), ncols, flat.data(), pi, P.data(), derivs ? 1 : 0, l, k, d1.data(), d2.data());
+            else tree_likelihood_host(dim, nleaves, nnodes, topo.parent.data(), ncols, flat.data(), pi, P.data(), derivs ? 1 : 0, l, k, d1.data(), d2.data());
+        }
         ++res.evaluations;
         return treelik_lnl(ncols, l, k, nullptr);
     };
     double lnl = 0;
-    for (uint32_t round = 0; round < rounds; ++round) {
-        const double here = evaluate(t, true, site_l.data(), site_k.data());   // (the up pass of the accepted point again: the same bits)
-        if (round == 0) res.lnl_start = here;
-        lnl = here;
-        ++res.rounds;
-        for (uint32_t e = 0; e < nedges; ++e)
-            target[e] = clamp(d2[e] < 0 ? t[e] - d1[e] / d2[e] : d1[e] > 0 ? 2 * t[e] : t[e] / 2);
-        bool accepted = false;
-        double gain = 0, lambda = 1.0;
-        for (int step = 0; step <= 10 && !accepted; ++step, lambda *= 0.5) {
-            for (uint32_t e = 0; e < nedges; ++e) trial[e] = clamp(t[e] + lambda * (target[e] - t[e]));
-            const double there = evaluate(trial, false, trial_l.data(), trial_k.data());
-            if (there > lnl) { accepted = true; gain = there - lnl; lnl = there; }
+    bool started = false;
+    // the branch-length loop at the rates in hand, until it stops by its own rules
+    auto branch_lengths = [&]() {
+        for (uint32_t round = 0; round < rounds; ++round) {
+            const double here = evaluate(t, rates, true, site_l.data(), site_k.data(), post.data());   // (the up pass of the accepted point again: the same bits)
+            if (!started) { res.lnl_start = here; started = true; }
+            lnl = here;
+            ++res.rounds;
+            for (uint32_t e = 0; e < nedges; ++e)
+                target[e] = clamp(d2[e] < 0 ? t[e] - d1[e] / d2[e] : d1[e] > 0 ? 2 * t[e] : t[e] / 2);
+            bool accepted = false;
+            double gain = 0, lambda = 1.0;
+            for (int step = 0; step <= 10 && !accepted; ++step, lambda *= 0.5) {
+                for (uint32_t e = 0; e < nedges; ++e) trial[e] = clamp(t[e] + lambda * (target[e] - t[e]));
+                const double there = evaluate(trial, rates, false, trial_l.data(), trial_k.data(), trial_post.data());
+                if (there > lnl) { accepted = true; gain = there - lnl; lnl = there; }
+            }
+            if (!accepted) break;
+            t.swap(trial); site_l.swap(trial_l); site_k.swap(trial_k); post.swap(trial_post);
+            if (gain < eps) break;
         }
-        if (!accepted) break;
-        t.swap(trial); site_l.swap(trial_l); site_k.swap(trial_k);
-        if (gain < eps) break;
+    };
+    if (!ncat || !gamma.estimate) branch_lengths();
+    else {
+        // the loop above and a golden-section search on x = ln alpha in turns.  The search: kMlAlphaEvaluations evaluations without
+        // derivatives inside [x - W / 2, x + W / 2] cut to [ln kMlMinAlpha, ln kMlMaxAlpha], W the whole range in the first pair and a
+        // quarter of the previous W in every later one; its best point is taken only if its lnL is strictly above the one in hand
+        const double x_lo = std::log(kMlMinAlpha), x_hi = std::log(kMlMaxAlpha), ratio = (std::sqrt(5.0) - 1.0) / 2.0;
+        double width = x_hi - x_lo;
+        std::vector<double> best_l(ncols), best_post(post.size());
+        std::vector<int32_t> best_k(ncols);
+        for (uint32_t pair = 0; pair < kMlMaxPairs; ++pair, width *= 0.25) {
+            const double before = pair == 0 ? -INFINITY : lnl;
+            branch_lengths();
+            const double x = std::log(alpha);
+            double lo = pair == 0 ? x_lo : std::max(x_lo, x - width / 2), hi = pair == 0 ? x_hi : std::min(x_hi, x + width / 2);
+            double best = lnl, best_x = x;
+            bool found = false;
+            auto probe = [&](double at) {
+                const double v = evaluate(t, gamma_rates(std::exp(at), ncat), false, trial_l.data(), trial_k.data(), trial_post.data());
+                if (v > best) { best = v; best_x = at; found = true; best_l.swap(trial_l); best_k.swap(trial_k); best_post.swap(trial_post); }
+                return v;
+            };
+            double x1 = hi - ratio * (hi - lo), x2 = lo + ratio * (hi - lo), f1 = probe(x1), f2 = probe(x2);
+            for (uint32_t n = 2; n < kMlAlphaEvaluations; ++n) {
+                if (f1 < f2) { lo = x1; x1 = x2; f1 = f2; x2 = lo + ratio * (hi - lo); f2 = probe(x2); }
+                else { hi = x2; x2 = x1; f2 = f1; x1 = hi - ratio * (hi - lo); f1 = probe(x1); }
+            }
+            if (found) {
+                alpha = std::exp(best_x);           // (a point strictly inside the range)
+                rates = gamma_rates(alpha, ncat);   // (the rates the probe had: the site values in hand are those of (t, alpha))
+                lnl = best;
+                site_l.swap(best_l); site_k.swap(best_k); post.swap(best_post);
+            }
+            if (!found || lnl - before < eps) break;
+        }
     }
     res.lengths = t;
     res.lnl = lnl;
     res.site_lnl.resize(ncols);
     (void)treelik_lnl(ncols, site_l.data(), site_k.data(), res.site_lnl.data());
+    if (ncat) { res.alpha = alpha; res.rates = rates; res.post = post; ml_tree_stats.categories = ncat; ml_tree_stats.alpha = alpha; }
     ml_tree_stats.rounds += res.rounds; ml_tree_stats.evaluations += res.evaluations;
     ml_tree_stats.lnl_start = res.lnl_start; ml_tree_stats.lnl = res.lnl;
     ml_tree_stats.seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
