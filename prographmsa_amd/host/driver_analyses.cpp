@@ -1,0 +1,239 @@
+// driver_analyses.cpp — what the solo run computes from its final alignment besides writing it: --bootstrap, --ml_tree, --guidance.
+#include "driver.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <fstream>
+#include <sstream>
+
+namespace pgm {
+
+// the alignment's rows without the ancestral sequences
+static std::map<std::string, sequence_t> sequence_rows(const std::map<std::string, sequence_t> &alignment) {
+    std::map<std::string, sequence_t> rows;
+    for (const auto &kv : alignment)
+        if (kv.first.empty() || kv.first[0] != '(') rows.insert(kv);
+    return rows;
+}
+// `what`: "bootstrap output", "ml tree output", "guidance output", "guidance residue", "guidance dump"
+static std::ofstream open_output(const std::string &path, const char *what) {
+    std::ofstream out(path.c_str());
+    if (!out) error("error opening the %s file %s", what, path.c_str());
+    return out;
+}
+
+// --bootstrap: the tree TreeNJ estimates from the final alignment without its ancestral rows (the re-estimation step of the
+// iterations: main.cpp:404-430, DistanceFactoryPrealigned.h:34-90, TreeNJ.h:27-59), the support of its internal edges among the
+// trees of N column resamplings, and the file: formatNewick()'s text with the counts as node labels.  --bootstrap_tbe: the same
+// text with the transfer bootstrap expectation of every labelled node (transfer_support; the device from kTransferDeviceMin taxa
+// or with PGM_DEVICE_TRANSFER, the host loop with PGM_HOST_TRANSFER); --bootstrap_trees: formatNewick() of every replicate's tree;
+// --bootstrap_taxa / --bootstrap_taxa_edges: taxa_support by the same route, taxa_text and taxa_edges_text
+void doBootstrap(const Alphabet &a, const DriverOptions &o, const Family &fam, const std::map<std::string, sequence_t> &alignment) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::map<std::string, sequence_t> rows = sequence_rows(alignment);
+    std::unique_ptr<PhyTree> tree(TreeNJ(a, rows, fam.model_factory.get(), true));
+    const BootstrapOpts &bo = o.bootstrap;
+    std::vector<PhyTree *> reps = bootstrap_trees(a, rows, fam.model_factory.get(), (uint32_t)bo.n, bo.seed);
+    std::string text, tbe_text, trees_text, taxa_file_text, taxa_edges_file_text;
+    try {
+        const std::vector<const PhyTree *> replicates(reps.begin(), reps.end());
+        text = tree->formatNewick(bipartition_support(*tree, replicates));
+        const HostSwitches &sw = host_switches();
+        Backend *device = !sw.host_transfer && (sw.device_transfer || rows.size() >= kTransferDeviceMin) ? &default_backend() : nullptr;
+        if (!bo.tbe.empty())
+            tbe_text = tree->formatNewick(transfer_labels(transfer_support(*tree, replicates, device), (uint32_t)replicates.size()));
+        if (!bo.taxa.empty()) {
+            const TaxaSupport taxa = taxa_support(*tree, replicates, bo.cutoff, device);
+            taxa_file_text = taxa_text(taxa, bo.cutoff);
+            if (!bo.taxa_edges.empty()) taxa_edges_file_text = taxa_edges_text(taxa);
+        }
+        if (!bo.trees.empty())
+            for (const PhyTree *t : replicates) trees_text += t->formatNewick() + "\n";
+    } catch (...) {
+        for (PhyTree *t : reps) delete t;
+        throw;
+    }
+    for (PhyTree *t : reps) delete t;
+    open_output(bo.out, "bootstrap output") << text << std::endl;
+    if (!bo.tbe.empty()) open_output(bo.tbe, "bootstrap output") << tbe_text << std::endl;
+    if (!bo.trees.empty()) open_output(bo.trees, "bootstrap output") << trees_text << std::flush;
+    if (!bo.taxa.empty()) open_output(bo.taxa, "bootstrap output") << taxa_file_text << std::flush;
+    if (!bo.taxa_edges.empty()) open_output(bo.taxa_edges, "bootstrap output") << taxa_edges_file_text << std::flush;
+    bootstrap_stats.seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// --ml_tree: the tree of --bootstrap (TreeNJ on the final alignment without its ancestral rows, midpoint rooted) with the branch
+// lengths that maximise the likelihood of the alignment as it is written (start / stop columns re-inserted, every residue the
+// character of the input: Family::finish_rows), and --ml_sites: the log-likelihood of every column (ml_branch_lengths, DESIGN.md
+// 3.17; the device from kTreelikDeviceMin taxa or with PGM_DEVICE_TREELIK, the host loop with PGM_HOST_TREELIK).  With --ml_gamma the
+// likelihood is the mixture over the rate categories of the discrete gamma (the same route), and --ml_rates: the
+// shape, the categories' rates, and per column the posterior mean rate and the category of the largest posterior
+void doMlTree(const Alphabet &a, const DriverOptions &o, const Family &fam, const std::map<std::string, sequence_t> &alignment) {
+    const std::map<std::string, sequence_t> rows = sequence_rows(alignment);
+    std::unique_ptr<PhyTree> tree(TreeNJ(a, rows, fam.model_factory.get(), true));
+    std::vector<std::vector<int8_t>> values;   // the rows in sorted-name order: the leaves' order
+    for (const auto &kv : rows) {
+        const sequence_t written = fam.written_row(a, kv.first, kv.second), orig = sequenceFromString(a, fam.seqs.at(kv.first));
+        std::vector<int8_t> v(written.size());
+        size_t j = 0;
+        for (size_t k = 0; k < written.size(); ++k) {
+            if (a.isGap(written[k])) { v[k] = -1; continue; }
+            const int x = j < orig.size() ? a.value(orig[j]) : -1;
+            ++j;
+            v[k] = (int8_t)(x >= 0 && x < a.DIM ? x : -2);
+        }
+        values.push_back(std::move(v));
+    }
+    const HostSwitches &sw = host_switches();
+    const bool device = !sw.host_treelik && (sw.device_treelik || rows.size() >= kTreelikDeviceMin);
+    const MlTreeOpts &mo = o.mltree;
+    MlGamma gamma;
+    if (mo.gamma_given) { gamma.ncat = (uint32_t)mo.gamma; gamma.estimate = !mo.alpha_given; gamma.alpha = mo.alpha; }
+    const MlTreeResult res = ml_branch_lengths(a, values, *fam.model_factory, *tree, (uint32_t)mo.rounds, mo.eps, device ? &default_backend() : nullptr, gamma);
+    std::unique_ptr<PhyTree> ml(ml_tree_with_lengths(ml_tree_topology(*tree), res.lengths));
+    open_output(mo.tree, "ml tree output") << ml->formatNewick() << std::endl;
+    if (mo.sites_given) {
+        std::ofstream sites = open_output(mo.sites, "ml tree output");
+        char buf[64];
+        snprintf(buf, sizeof buf, "lnL %.17g\n", res.lnl);
+        sites << buf;
+        for (size_t c = 0; c < res.site_lnl.size(); ++c) {
+            snprintf(buf, sizeof buf, "%zu\t%.17g\n", c + 1, res.site_lnl[c]);
+            sites << buf;
+        }
+    }
+    if (mo.rates_given) {
+        std::ofstream rates = open_output(mo.rates, "ml tree output");
+        char buf[96];
+        snprintf(buf, sizeof buf, "alpha\t%.17g\n", res.alpha);
+        rates << buf;
+        const size_t ncat = res.rates.size(), ncols = res.site_lnl.size();
+        for (size_t k = 0; k < ncat; ++k) {
+            snprintf(buf, sizeof buf, "rate\t%zu\t%.17g\n", k + 1, res.rates[k]);
+            rates << buf;
+        }
+        for (size_t c = 0; c < ncols; ++c) {   // the posterior mean rate, categories ascending; the first category of the largest posterior
+            double mean = 0.0;
+            size_t top = 0;
+            for (size_t k = 0; k < ncat; ++k) {
+                mean = mean + res.post[k * ncols + c] * res.rates[k];
+                if (res.post[k * ncols + c] > res.post[top * ncols + c]) top = k;
+            }
+            snprintf(buf, sizeof buf, "%zu\t%.17g\t%zu\n", c + 1, mean, top + 1);
+            rates << buf;
+        }
+    }
+}
+// --guidance (Penn et al. 2010, GUIDANCE: the guide tree as the source of alignment uncertainty): the final alignment's columns are
+// resampled N times as --bootstrap resamples them, every replicate's BioNJ tree, midpoint rooted and written with exact branch
+// lengths, is read back as `-t` reads a tree and used as the guide tree of a realignment of the family's sequences (forest passes
+// over groups of replicates within --batch_cells), and Backend::msa_agreement counts per group how often the residue pairs of the
+// alignment as written (start / stop columns re-inserted, ancestral rows left out) share a column in the replicates' alignments.
+void doGuidance(const Alphabet &a, const DriverOptions &o, const Family &fam, const CSProfile *csprofile) {
+    typedef std::chrono::steady_clock clk;
+    const auto t0 = clk::now();
+    Backend &be = default_backend();
+    const GuidanceOpts &go = o.guidance;
+    const uint32_t N = (uint32_t)go.n;
+    const std::map<std::string, sequence_t> rows = sequence_rows(fam.result.aligned_sequences);
+    if (rows.size() < 4) error("--guidance needs at least 4 sequences");
+    std::vector<std::string> names;
+    std::vector<sequence_t> base;
+    for (const auto &kv : rows) { names.push_back(kv.first); base.push_back(fam.written_row(a, kv.first, kv.second)); }
+    const size_t n = names.size(), L = base[0].size();
+    if (L == 0 || L > 0x7fffffffull) error("guidance: an alignment of %zu columns", L);
+
+    // the replicates' guide trees
+    std::vector<std::unique_ptr<PhyTree>> trees(N);
+    {
+        const BootstrapStats kept = bootstrap_stats;   // (the keys of --bootstrap count its own replicates only)
+        std::vector<PhyTree *> unrooted = bootstrap_trees(a, rows, fam.model_factory.get(), N, go.seed);
+        bootstrap_stats = kept;
+        for (uint32_t r = 0; r < N; ++r) trees[r].reset(unrooted[r]);
+        for (uint32_t r = 0; r < N; ++r) {
+            trees[r].reset(midpointRoot(trees[r].release()));
+            const std::string text = format_newick_exact(*trees[r]);
+            if (!go.dump.empty()) {
+                open_output(go.dump + "." + std::to_string(r) + ".nwk", "guidance dump") << text << std::endl;
+            }
+            std::istringstream in(text);
+            trees[r].reset(parse_newick(in));   // (as -t reads it: every branch support 1)
+        }
+    }
+    // groups of replicates in order while the estimated cells of a pass stay within the bound; a larger replicate alone
+    std::vector<double> cells(N, 0.0);
+    std::vector<std::pair<uint32_t, uint32_t>> groups;
+    {
+        double sum = 0;
+        for (uint32_t r = 0; r < N; ++r) {
+            subtree_cells(*trees[r], fam.seqs2, cells[r]);
+            if (groups.empty() || sum + cells[r] > o.batch_cells) { groups.emplace_back(r, r); sum = 0; }
+            ++groups.back().second;
+            sum += cells[r];
+        }
+    }
+    GuidanceCounts G;
+    G.nrows = (uint32_t)n; G.ncols = (uint32_t)L; G.nrep = N;
+    G.res_hits.assign(n * L, 0); G.pair_hits.assign(n * n, 0);
+    const uint32_t per_call = guidance_call_replicates(G.nrows, G.ncols);
+    std::vector<int32_t> where;
+    std::vector<uint32_t> res32(n * L), pair32(n * n);
+    for (const auto &grp : groups) {
+        const uint32_t g = grp.second - grp.first;
+        const auto ta = clk::now();
+        std::vector<ProgressiveAlignmentResult> res(g);
+        {
+            std::vector<ForestFamily> ff(g);
+            std::vector<uint64_t> cost(g);
+            for (uint32_t k = 0; k < g; ++k) {
+                ff[k].sequences = &fam.seqs2; ff[k].tree = trees[grp.first + k].get(); ff[k].model_factory = fam.model_factory.get();
+                ff[k].repeats = fam.repeats; ff[k].result = &res[k];
+                cost[k] = (uint64_t)cells[grp.first + k] + 1u;
+            }
+            const std::vector<std::vector<uint32_t>> shards = farm_shards(cost, be.workers());   // (as doBatch deals families)
+            for (size_t w = 0; w < shards.size(); ++w) for (uint32_t k : shards[w]) ff[k].worker = (int)w;
+            progressive_alignment_forest(a, ff, csprofile);
+            ++guidance_stats.passes;
+            for (uint32_t k = 0; k < g; ++k) if (!ff[k].error.empty()) throw pgm_exception(ff[k].error);
+        }
+        guidance_stats.align_s += std::chrono::duration<double>(clk::now() - ta).count();
+        std::vector<std::vector<sequence_t>> written(g);
+        parallel_for(g, [&](size_t k) {
+            for (const std::string &name : names) {
+                const auto it = res[k].aligned_sequences.find(name);
+                if (it == res[k].aligned_sequences.end()) error("guidance: a replicate alignment without sequence %s", name.c_str());
+                written[k].push_back(fam.written_row(a, name, it->second));
+            }
+            if (!go.dump.empty()) {   // the replicate's alignment as `-t <its tree>` writes it
+                const uint32_t r = grp.first + (uint32_t)k;
+                std::map<std::string, std::string> aligned;
+                fam.finish_rows(a, res[k].aligned_sequences, aligned);
+                std::ofstream out = open_output(go.dump + "." + std::to_string(r) + ".fa", "guidance dump");
+                write_fasta(aligned, cmdlineopts.inputorder_flag ? fam.input_order : get_tree_order(trees[r].get()), out);
+            }
+            res[k] = ProgressiveAlignmentResult();
+        });
+        for (uint32_t k0 = 0; k0 < g; k0 += per_call) {
+            const uint32_t m = std::min(per_call, g - k0);
+            where.resize((size_t)m * n * L);
+            parallel_for(m, [&](size_t k) { guidance_where(a, base, written[k0 + k], where.data() + k * n * L); });
+            const auto tg = clk::now();
+            be.msa_agreement(G.nrows, G.ncols, m, where.data(), res32.data(), pair32.data());
+            guidance_stats.agreement_s += std::chrono::duration<double>(clk::now() - tg).count();
+            ++guidance_stats.agreement_calls;
+            for (size_t k = 0; k < res32.size(); ++k) G.res_hits[k] += res32[k];
+            for (size_t k = 0; k < pair32.size(); ++k) G.pair_hits[k] += pair32[k];
+        }
+    }
+    std::vector<int32_t> where0(n * L);   // (the gaps of the base alignment)
+    for (size_t i = 0; i < n; ++i)
+        for (size_t c = 0; c < L; ++c) where0[i * L + c] = a.isGap(base[i][c]) ? -1 : 0;
+    std::ofstream out = open_output(go.out, "guidance output"), rout;
+    if (!go.residues.empty()) rout = open_output(go.residues, "guidance residue");
+    guidance_write(G, names, where0.data(), go.seed, out, go.residues.empty() ? nullptr : &rout);
+    guidance_stats.replicates += (int)N;
+    guidance_stats.seconds += std::chrono::duration<double>(clk::now() - t0).count();
+}
+
+}  // namespace pgm

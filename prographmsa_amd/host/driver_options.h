@@ -1,0 +1,52 @@
+// driver_options.h — what the command line asks of the driver itself (main.cpp and the driver_*.cpp files).  What the whole host
+// reads stays in cmdlineopts (pgm_host.h); parse_driver_options fills both.
+#pragma once
+#include "pgm_host.h"
+
+namespace pgm {
+
+struct BootstrapOpts {   // --bootstrap N --bootstrap_out FILE --bootstrap_seed S
+    bool given = false, out_given = false;
+    long long n = 0;
+    std::string out, tbe, trees;   // --bootstrap_tbe FILE, --bootstrap_trees FILE
+    std::string taxa, taxa_edges;   // --bootstrap_taxa FILE, --bootstrap_taxa_edges FILE
+    bool cutoff_given = false;   // --bootstrap_taxa_cutoff X
+    double cutoff = 0.3;
+    uint64_t seed = 1;
+    bool any_taxa() const { return !taxa.empty() || !taxa_edges.empty() || cutoff_given; }
+    bool any() const { return given || out_given || !tbe.empty() || !trees.empty() || any_taxa(); }
+};
+
+struct GuidanceOpts {   // --guidance N --guidance_out FILE --guidance_seed S --guidance_residues FILE --guidance_dump PREFIX
+    bool given = false, out_given = false;
+    long long n = 0;
+    std::string out, residues, dump;
+    uint64_t seed = 1;
+    bool any() const { return given || out_given || !residues.empty() || !dump.empty(); }
+};
+
+struct MlTreeOpts {   // --ml_tree FILE --ml_sites FILE --ml_rounds N --ml_epsilon X --ml_gamma K --ml_alpha X --ml_rates FILE
+    std::string tree, sites, rates;
+    bool tree_given = false, sites_given = false, rounds_given = false, eps_given = false, gamma_given = false, alpha_given = false, rates_given = false;
+    long rounds = 100, gamma = 0;
+    double eps = 1e-4, alpha = 1.0;
+    bool any() const { return tree_given || sites_given || rounds_given || eps_given || gamma_given || alpha_given || rates_given; }
+};
+
+struct DriverOptions {
+    BootstrapOpts bootstrap;
+    GuidanceOpts guidance;
+    MlTreeOpts mltree;
+    bool iters_set = false, stats = false;
+    bool indel_set = false, edgehl_set = false, maxdist_set = false, cutdist_set = false;   // (the defaults --codon rescales)
+    std::string dump, dist_dump, joins_dump;   // --dump_jobs, --dump_dist, --dump_joins
+    std::string batch_list, topo_file;   // --batch, --topology
+    double batch_cells = 2e9;   // --batch_cells: estimated DP cells of one chunk of families, of one group of --guidance replicates
+};
+
+void usage();
+// The command line into cmdlineopts and `o`.  Returns -1 to go on, or the exit code of a command line that ends the run here: the
+// usage text or the message is then written.
+int parse_driver_options(int argc, char **argv, DriverOptions &o);
+
+}  // namespace pgm

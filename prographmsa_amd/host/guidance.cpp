@@ -1,7 +1,7 @@
 // guidance.cpp — the host parts of `pgmsa --guidance` that need no driver state: the residue map
 // between the base alignment and a replicate alignment, the host statement of the agreement counts (Backend::msa_agreement's
 // default, what pgmsa_oracle runs), the bounds of one agreement call, the exact newick text of a replicate's guide tree and the
-// two score files.  The flow that joins them (bootstrap trees, forest passes, groups) is doGuidance in main.cpp.
+// two score files.  The flow that joins them (bootstrap trees, forest passes, groups) is doGuidance in driver_analyses.cpp.
 #include "pgm_host.h"
 
 #include <algorithm>

@@ -663,7 +663,7 @@ extern BootstrapStats bootstrap_stats;
 std::vector<PhyTree *> bootstrap_trees(const Alphabet &a, const std::map<std::string, sequence_t> &rows, const ModelFactory *mf, uint32_t nrep, uint64_t seed);
 
 // --guidance: how often the residue pairs of the base alignment stand in one column again in the alignments of N bootstrap guide
-// trees (host/guidance.cpp; the flow is doGuidance in main.cpp).
+// trees (host/guidance.cpp; the flow is doGuidance in driver_analyses.cpp).
 // guidance_where: one replicate's residue map, where[i * ncols + c] = the column of `rep` that holds the residue row i of `base`
 //   has in column c, -1 for a gap (rows as written, one symbol a column; both alignments hold the same residues in the same order).
 // msa_agreement_host: the counts of pgm_msa_agreement by plain loops on the host threads (Backend::msa_agreement's default).

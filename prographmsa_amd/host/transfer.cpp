@@ -1,7 +1,7 @@
 // transfer.cpp — the host parts of `pgmsa --bootstrap_tbe` and `--bootstrap_taxa`: the host statement of the transfer indices
 // (Backend::transfer_min's default, what pgmsa_oracle runs), the bounds of one call, and the support of every internal edge of a
 // tree.  The leaf numbering and the bipartition walk are those of bipartition_support (phytree.cpp); the flow that writes the
-// files is doBootstrap in main.cpp.
+// files is doBootstrap in driver_analyses.cpp.
 // --bootstrap_taxa (below the TBE part): the host statement of the moved-taxon counts (Backend::transfer_taxa's default), the
 // per-taxon sums over the distinct bipartitions of a tree, and the two file texts.
 #include "pgm_host.h"

@@ -4,12 +4,7 @@
 # stay silent.
 set -e
 cd "$(dirname "$0")/.."
-mkdir -p oracle/_build
-H=prographmsa_amd/host
-FL="-O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -ffp-contract=off"
-gcc $FL -c -o oracle/_build/pgm_oracle_asan.o oracle/pgm_oracle.c
-g++ $FL -std=c++17 -pthread -DPGM_HOST_SPLIT=2 -o oracle/_build/pgmsa_oracle_asan $H/alphabet.cpp $H/model_factory.cpp $H/graph.cpp $H/graph_align.cpp \
-    $H/phytree.cpp $H/host_threads.cpp $H/progressive.cpp $H/root_search.cpp $H/repeats.cpp $H/guidance.cpp $H/transfer.cpp $H/distance.cpp $H/mldist.cpp $H/bionj.cpp $H/wls.cpp $H/csprofile.cpp $H/main.cpp oracle/backend_oracle.cpp oracle/_build/pgm_oracle_asan.o -ldl -lm -lquadmath
+make -s -C oracle _build/pgmsa_oracle_asan
 B=oracle/_build/pgmsa_oracle_asan G=tests/golden
 chk() { local want=$1; shift; local got; got=$("$B" "$@" 2> oracle/_build/asan.err | md5sum | cut -d' ' -f1)
         [ "$got" = "$(md5sum < "$want" | cut -d' ' -f1)" ] && [ ! -s oracle/_build/asan.err ] && echo "ok   $*" || { echo "FAIL $*"; cat oracle/_build/asan.err; exit 1; }; }
