@@ -505,7 +505,7 @@ int pgm_tree_likelihood(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t n
                         uint32_t ncols, const int8_t *rows /* nleaves x ncols */, const double *pi /* dim */,
                         const double *P /* (nnodes-1) x {1 or 3} x dim x dim */, int derivs,
                         double *site_l /* ncols */, int32_t *site_k /* ncols */, double *d1, double *d2 /* nnodes-1, derivs only */);
-float pgm_treelik_last_kernel_ms(pgm_ctx *ctx);   /* device time of the kernels of the last pgm_tree_likelihood or pgm_tree_likelihood_rates call */
+float pgm_treelik_last_kernel_ms(pgm_ctx *ctx);   /* device time of the kernels of the last pgm_tree_likelihood, pgm_tree_likelihood_rates or pgm_tree_ancestral call */
 
 /* ---- the same likelihood under a mixture of ncat rate categories (pgmsa --ml_tree --ml_gamma).
  * Everything from dim to pi, and derivs, d1, d2, is as in pgm_tree_likelihood, with the same checks.  ncat: 1 .. PGM_TREELIK_MAXCAT;
@@ -530,6 +530,35 @@ int pgm_tree_likelihood_rates(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint
                               const double *pi, uint32_t ncat, const double *w /* ncat */, const double *P /* ncat x (nnodes-1) x {1 or 3} x dim x dim */,
                               int derivs, double *site_l /* ncols */, int32_t *site_k /* ncols */, double *post /* ncat x ncols */,
                               double *d1, double *d2 /* nnodes-1, derivs only */);
+
+/* ---- marginal ancestral states on the same tree under the same mixture (pgmsa --ml_tree --ml_ancestral).
+ * Everything from dim to w is as in pgm_tree_likelihood_rates, with the same checks; P: ncat x (nnodes-1) x dim x dim, P alone (the
+ * derivs == 0 layout).  site_l, site_k and post are pgm_tree_likelihood_rates's values with derivs == 0, bit for bit: the same up
+ * pass and the same combine order.  ninner = nnodes - nleaves; inner node v has row v - nleaves.
+ * Per category c, per site, per inner node v:
+ *   down   the down pass of pgm_tree_likelihood with S from P alone: B_root = pi, B_v(i) = sum_h O_v(h) P_v(h, i) (h ascending from
+ *          0.0), O_child(i) = B_v(i) times the siblings' S(i) in ascending child order (the product starts with B_v(i)), then the
+ *          scaling rule, without a count
+ *   m(i) = B_v(i) * U_v(i), U_v the stored (scaled) partial;  Z = sum_i m(i), i ascending from 0.0;  a_c,v(i) = m(i) / Z, and 0.0 for
+ *          every i when Z == 0.0
+ * Then the mixture, anc(v, s, i) = sum_c post[c][s] * a_c,v(i), c ascending from 0.0, one multiply and one add per term:
+ *   anc_post[((v - nleaves) * ncols + s) * dim + i] = anc   (only when anc_post is not null)
+ *   anc_prob[(v - nleaves) * ncols + s] = the largest anc over i,  anc_state[...] = the smallest i that has it;
+ *   when no anc is above 0.0: anc_state = -1, anc_prob = 0.0.
+ * With ncat == 1 and w = {1.0} anc is a_0,v exactly (1.0 * x and 0.0 + x are exact).  Only + - * / occur and nothing is contracted:
+ * the values do not depend on the launch and equal the host statement's (tree_ancestral_host) bit for bit.  Every output is
+ * overwritten (anc_post only when given).  Device memory: ncat * 16 * ninner * ncols * dim bytes for the partials and the outside
+ * vectors, in whose place the categories' posteriors are written (what pgm_tree_likelihood_rates takes with derivs, without its
+ * per-edge ratios); the inputs, 8 * ncat * (nnodes-1) * dim * dim bytes of matrices and nleaves * ncols + 8 * nnodes + 8 * (dim +
+ * ncat) bytes for the rows, the children lists, pi and w; 12 * ncat * ncols bytes for (L_c, k_c); and the outputs, (12 + 8 * ncat) *
+ * ncols + 9 * ninner * ncols bytes, with anc_post 8 * ninner * ncols * dim more.  Memory that cannot be had is PGM_ERR_NOMEM.
+ * PGM_ERR_INVALID, before anything is launched or an output is touched: what pgm_tree_likelihood_rates refuses (derivs == 0), a null
+ * anc_state or anc_prob. */
+int pgm_tree_ancestral(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
+                       const double *pi, uint32_t ncat, const double *w /* ncat */, const double *P /* ncat x (nnodes-1) x dim x dim */,
+                       double *site_l /* ncols */, int32_t *site_k /* ncols */, double *post /* ncat x ncols */,
+                       int8_t *anc_state /* ninner x ncols */, double *anc_prob /* ninner x ncols */,
+                       double *anc_post /* ninner x ncols x dim, or NULL */);
 
 #ifdef __cplusplus
 }

@@ -93,7 +93,7 @@ EXPORTS = [
     "pgm_bionj_plan", "pgm_bionj_plan_multi",
     "pgm_msa_agreement", "pgm_agreement_last_kernel_ms",
     "pgm_transfer_min", "pgm_transfer_last_kernel_ms", "pgm_transfer_taxa",
-    "pgm_tree_likelihood", "pgm_treelik_last_kernel_ms", "pgm_tree_likelihood_rates",
+    "pgm_tree_likelihood", "pgm_treelik_last_kernel_ms", "pgm_tree_likelihood_rates", "pgm_tree_ancestral",
 ]
 
 
@@ -181,6 +181,9 @@ def _load():
         "pgm_tree_likelihood_rates": (C.c_int, [vp, u32, u32, u32, C.POINTER(u32), u32, C.POINTER(C.c_int8), C.POINTER(C.c_double), u32, C.POINTER(C.c_double),
                                                 C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                 C.POINTER(C.c_double)]),
+        "pgm_tree_ancestral": (C.c_int, [vp, u32, u32, u32, C.POINTER(u32), u32, C.POINTER(C.c_int8), C.POINTER(C.c_double), u32, C.POINTER(C.c_double),
+                                         C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(C.c_int8),
+                                         C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = the library does not export a declared symbol
@@ -327,6 +330,33 @@ class Context:
         check(lib.pgm_tree_likelihood_rates(self.handle, dim, nleaves, nnodes, P_(parent, C.c_uint32), ncols, P_(rows, C.c_int8), P_(pi, C.c_double), ncat,
                                             P_(w, C.c_double), P_(P, C.c_double), 1 if derivs else 0, P_(out[0], C.c_double), P_(out[1], C.c_int32),
                                             P_(out[2], C.c_double), P_(out[3], C.c_double), P_(out[4], C.c_double)), "pgm_tree_likelihood_rates")
+        return tuple(out)
+
+    def tree_ancestral(self, dim, parent, rows, pi, w, P, full=True, out=None):
+        """pgm_tree_ancestral: inputs as tree_likelihood_rates without derivs (P: ncat x (nnodes - 1) x dim x dim float64) -> (site_l,
+        site_k, post, anc_state (ninner x ncols int8), anc_prob (ninner x ncols float64), anc_post (ninner x ncols x dim float64)),
+        ninner = nnodes - nleaves.  Given output arrays (a tuple of six, C-contiguous of those kinds) are overwritten; without `full`
+        the entry gets no anc_post: a given one is left as it is (it may be None), and None is returned in its place otherwise."""
+        import numpy as np
+        parent = np.ascontiguousarray(parent, np.uint32)
+        rows = np.ascontiguousarray(rows, np.int8)
+        pi = np.ascontiguousarray(pi, np.float64)
+        w = np.ascontiguousarray(w, np.float64)
+        P = np.ascontiguousarray(P, np.float64)
+        if parent.ndim != 1 or rows.ndim != 2 or pi.shape != (dim,) or w.ndim != 1 or P.size != len(w) * (len(parent) - 1) * dim * dim or len(parent) <= rows.shape[0]:
+            raise ValueError("tree_ancestral: input array of the wrong shape")
+        nnodes, (nleaves, ncols), ncat = len(parent), rows.shape, len(w)
+        ninner = nnodes - nleaves
+        kinds = [((ncols,), np.float64), ((ncols,), np.int32), ((ncat, ncols), np.float64), ((ninner, ncols), np.int8), ((ninner, ncols), np.float64),
+                 ((ninner, ncols, dim), np.float64)]
+        if out is None: out = tuple(np.zeros(s, t) for s, t in kinds[:5]) + ((np.zeros(*kinds[5]) if full else None),)
+        right = lambda a, kind: isinstance(a, np.ndarray) and a.dtype == kind[1] and a.shape == kind[0] and a.flags.c_contiguous
+        if len(out) != 6 or not all(right(a, kind) for a, kind in zip(out[:5], kinds)) or not (right(out[5], kinds[5]) or (out[5] is None and not full)):
+            raise ValueError("tree_ancestral: output array of the wrong kind")
+        P_ = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+        check(lib.pgm_tree_ancestral(self.handle, dim, nleaves, nnodes, P_(parent, C.c_uint32), ncols, P_(rows, C.c_int8), P_(pi, C.c_double), ncat,
+                                     P_(w, C.c_double), P_(P, C.c_double), P_(out[0], C.c_double), P_(out[1], C.c_int32), P_(out[2], C.c_double),
+                                     P_(out[3], C.c_int8), P_(out[4], C.c_double), P_(out[5], C.c_double) if full else None), "pgm_tree_ancestral")
         return tuple(out)
 
     def close(self):

@@ -70,7 +70,7 @@ struct pgm_ctx {
     float bionj_ms = 0;
     float agree_ms = 0;                     // --guidance agreement counts: device time of the last call
     float transfer_ms = 0;                  // --bootstrap_tbe / --bootstrap_taxa transfer entries: device time of the last call
-    float treelik_ms = 0;                   // --ml_tree likelihood evaluations: device time of the last call
+    float treelik_ms = 0;                   // --ml_tree likelihood evaluations and --ml_ancestral: device time of the last call
     uint32_t bionj_launches = 0;            // BioNJ: device time and kernels of the last call
     // grow-only scratch buffers of the satellite calls (StageCall): a guide-tree stage issues many calls, hipMalloc / hipFree of
     // up to 2 GB per call would dominate them.  The calls of one context are serial; a slot belongs to the stage named beside it
@@ -95,9 +95,9 @@ struct pgm_ctx {
         SC_TRANSFER_REF,                    // pgm_transfer_min and pgm_transfer_taxa (shared): reference sets, rep_off, thresholds
         SC_TRANSFER_REP,                    //   replicate sets
         SC_TRANSFER_OUT,                    //   phi (taxa: phi, arg, flip, moved, counted)
-        SC_TREELIK_TREE,                    // tree likelihood, both entries (shared): children lists, pi, weights, rows
+        SC_TREELIK_TREE,                    // tree likelihood and ancestral states, all three entries (shared): children lists, pi, weights, rows
         SC_TREELIK_P,                       //   the matrices
-        SC_TREELIK_U,                       //   partials and outside vectors
+        SC_TREELIK_U,                       //   partials and outside vectors (ancestral: the categories' posteriors in their place)
         SC_TREELIK_G,                       //   per-site ratios and chunk sums (rates: the categories' site values and ratios first)
         SC_TREELIK_OUT,                     //   the outputs
         SC_DEV
@@ -1063,3 +1063,4 @@ int pgm_align_batch_read_matrices(pgm_ctx *ctx, pgm_align_batch *b, uint32_t job
 #include "pgm_transfer_taxa_capi.inc"
 #include "pgm_treelik_capi.inc"
 #include "pgm_treelik_rates_capi.inc"
+#include "pgm_treelik_anc_capi.inc"

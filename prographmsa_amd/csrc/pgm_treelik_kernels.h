@@ -9,6 +9,8 @@
 // pgm_treelik_sums_kernel adds the per-site ratios of an edge in the fixed order of the interface.
 // pgm_tree_likelihood_rates runs the same walk once per rate category, the categories as further workgroups of one
 // launch (pgm_treelik_rates_kernel), and combines them per site (pgm_treelik_combine_kernel) ahead of the sums.
+// pgm_tree_ancestral is a third mode of the walk (pgm_treelik_anc_kernel): the down pass with P alone, the posterior
+// of every inner node's states written where the node's outside vector was; pgm_treelik_anc_combine_kernel mixes the categories.
 //
 // Every sum over states runs ascending from 0.0 with one multiply and one add per term (-ffp-contract=off): the bits are those of
 // tree_likelihood_host.  The walk is a chain of dependent steps on one wavefront, so what a step costs is the latency of its loads:
@@ -28,7 +30,7 @@ struct PgmTreelikArgs {
     const uint32_t *child_off, *child;           // CSR: the children of every node, ascending
     const int8_t *rows;
     const double *pi, *P;
-    double *U, *O;                               // (nnodes - nleaves) x ncols x dim each; O only with derivs
+    double *U, *O;                               // (nnodes - nleaves) x ncols x dim each; O only with derivs (and in the ancestral mode)
     double *g, *h;                               // (nnodes - 1) x ncols each, derivs only
     double *site_l;
     int32_t *site_k;
@@ -137,9 +139,33 @@ __device__ __forceinline__ void pgm_treelik_edge(const PgmTreelikArgs &a, double
     }
 }
 
-// The walk of one workgroup over the whole tree for the sites of block blockIdx.x: both kernels below are this function.
-template <bool RAW>
+// The ancestral mode's step at node v, for the dim threads of a site: m(i) = B_v(i) U_v(i), Z = sum of m ascending, and m / Z (0.0
+// where Z == 0.0) into the slot of O_v, which is dead once `base` = B_v(i) is formed (the root's slot has no other use).  The barrier
+// stands between the last read of O_v by the site's threads and the overwrite, and publishes m; every thread of a site then adds the
+// same dim values in the same order (one LDS address per site: a broadcast), which spares the barrier a broadcast of Z would need.
+// Every thread of the workgroup calls it.
+__device__ __forceinline__ void pgm_treelik_posterior(const PgmTreelikArgs &a, double *sh0, uint32_t v, uint32_t s, uint32_t i, bool active, double base) {
+    const uint32_t dim = a.dim;
+    const size_t at = ((size_t)(v - a.nleaves) * a.ncols + s) * dim + i;
+    double m = 0.0;
+    if (active) { m = base * a.U[at]; sh0[threadIdx.x] = m; }
+    __syncthreads();
+    if (active) {
+        const double *ms = sh0 + (threadIdx.x - i);
+        double Z = 0.0;
+#pragma unroll 8
+        for (uint32_t j = 0; j < dim; ++j) Z = Z + ms[j];
+        a.O[at] = Z == 0.0 ? 0.0 : m / Z;
+    }
+}
+
+// The walk of one workgroup over the whole tree for the sites of block blockIdx.x: the kernels below are this function.  MODE:
+// PGM_TREELIK_PLAIN (pgm_tree_likelihood), PGM_TREELIK_RAW (a category of pgm_tree_likelihood_rates: q in place of h),
+// PGM_TREELIK_ANC (a category of pgm_tree_ancestral: P alone, posteriors in place of the edges' sums).
+enum { PGM_TREELIK_PLAIN = 0, PGM_TREELIK_RAW = 1, PGM_TREELIK_ANC = 2 };
+template <int MODE>
 __device__ __forceinline__ void pgm_treelik_walk(const PgmTreelikArgs &a) {
+    constexpr bool RAW = MODE == PGM_TREELIK_RAW;
     __shared__ double sh[3][PGM_TREELIK_THREADS];
     const uint32_t dim = a.dim, nleaves = a.nleaves, root = a.nnodes - 1;
     const uint32_t local = threadIdx.x / dim, i = threadIdx.x - local * dim;
@@ -176,7 +202,7 @@ __device__ __forceinline__ void pgm_treelik_walk(const PgmTreelikArgs &a) {
             a.site_k[s] = k;
         }
     }
-    if (!a.derivs) return;
+    if (MODE != PGM_TREELIK_ANC && !a.derivs) return;
 
     // down pass, parents before children: the outside vector of every edge below v, then the edge's three sums
     for (uint32_t v = root; v >= nleaves; --v) {
@@ -197,7 +223,26 @@ __device__ __forceinline__ void pgm_treelik_walk(const PgmTreelikArgs &a) {
                 for (; h < dim; ++h) base = base + o[h] * Pv[h];
             }
         }
-        if (q1 - q0 == 2) {   // two children: the sibling's S is the other child's own first sum
+        if (MODE == PGM_TREELIK_ANC) {
+            // the node's posterior, then the outside vectors of its inner children only: a leaf's has no reader
+            pgm_treelik_posterior(a, &sh[0][0], v, s, i, active, base);
+            for (uint32_t q = q0; q < q1; ++q) {
+                const uint32_t c = a.child[q];
+                if (c < nleaves) continue;   // (uniform over the workgroup)
+                double o = base;
+                if (active) {
+                    for (uint32_t r = q0; r < q1; ++r) {
+                        if (r == q) continue;
+                        const uint32_t sib = a.child[r];
+                        double S[1];
+                        pgm_treelik_apply<1>(a, a.P + estride * sib, mat, sib, s, i, S);
+                        o = o * S[0];
+                    }
+                }
+                (void)pgm_treelik_rescale(o, shs, dim, i, active);   // (its first barrier: the posterior's reads of sh are done)
+                if (active) a.O[((size_t)(c - nleaves) * a.ncols + s) * dim + i] = o;
+            }
+        } else if (q1 - q0 == 2) {   // two children: the sibling's S is the other child's own first sum
             const uint32_t c0 = a.child[q0], c1 = a.child[q0 + 1];
             double T0[3] = {0.0, 0.0, 0.0}, T1[3] = {0.0, 0.0, 0.0};
             if (active) {
@@ -228,7 +273,7 @@ __device__ __forceinline__ void pgm_treelik_walk(const PgmTreelikArgs &a) {
     }
 }
 
-__global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_kernel(PgmTreelikArgs a) { pgm_treelik_walk<false>(a); }
+__global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_kernel(PgmTreelikArgs a) { pgm_treelik_walk<PGM_TREELIK_PLAIN>(a); }
 
 // pgm_tree_likelihood_rates: category blockIdx.y walks the tree with its own matrices, partials and outputs, `a`
 // holding those of category 0 and the strides the distance between two categories.  a.site_l / a.site_k get (L_c, k_c), a.g / a.h the
@@ -241,7 +286,18 @@ __global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_rates_kernel(
     a.site_l += st.L * c;
     a.site_k += st.L * c;
     if (a.derivs) { a.O += st.U * c; a.g += st.G * c; a.h += st.G * c; }
-    pgm_treelik_walk<true>(a);
+    pgm_treelik_walk<PGM_TREELIK_RAW>(a);
+}
+// pgm_tree_ancestral: category blockIdx.y walks the tree with its own matrices (P alone: a.derivs == 0) and
+// partials; its posteriors a_c,v land in a.O, [v - nleaves][s][i], the layout of the outside vectors they replace.
+__global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_anc_kernel(PgmTreelikArgs a, PgmTreelikRatesStride st) {
+    const size_t c = blockIdx.y;
+    a.P += st.P * c;
+    a.U += st.U * c;
+    a.O += st.U * c;
+    a.site_l += st.L * c;
+    a.site_k += st.L * c;
+    pgm_treelik_walk<PGM_TREELIK_ANC>(a);
 }
 
 // The categories of a site combined in the order of the interface.  A workgroup owns 64 consecutive sites (reads and writes run along
@@ -287,6 +343,47 @@ __global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_combine_kerne
         }
         a.g[at] = g;
         a.h[at] = q - g * g;
+    }
+}
+
+// The categories' posteriors of pgm_tree_ancestral mixed, and the first state of the largest.  The (node, site) pairs are numbered
+// g = (v - nleaves) * ncols + s, so a_c is one array of npairs x dim doubles per category and consecutive lanes read consecutive
+// doubles; a wavefront holds 64 / dim pairs, the dim values of a pair side by side as in the walk.  anc = sum_c post[c][s] a_c
+// (c ascending from 0.0); the thread of state 0 scans its pair's values in shared memory ascending and keeps the first index of the
+// largest (-1 and 0.0 when none is above 0.0).  Every output entry has one writer; anc_post only when asked for.
+struct PgmTreelikAncCombineArgs {
+    uint32_t dim, ncat, ncols, spb;   // spb = 64 / dim
+    uint64_t npairs, cat;             // (nnodes - nleaves) * ncols; doubles between two categories' posteriors
+    const double *a, *post;           // ncat x npairs x dim; ncat x ncols
+    double *anc_post, *anc_prob;      // npairs x dim or NULL; npairs
+    int8_t *anc_state;                // npairs
+};
+__global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_anc_combine_kernel(PgmTreelikAncCombineArgs a) {
+    __shared__ double sh[PGM_TREELIK_THREADS];
+    const uint32_t dim = a.dim, local = threadIdx.x / dim, i = threadIdx.x - local * dim;
+    for (uint64_t g0 = (uint64_t)blockIdx.x * a.spb; g0 < a.npairs; g0 += (uint64_t)gridDim.x * a.spb) {   // (uniform over the workgroup)
+        const uint64_t g = g0 + local;
+        const bool active = local < a.spb && g < a.npairs;
+        if (active) {
+            const size_t s = (size_t)(g % a.ncols), at = (size_t)g * dim + i;
+            double anc = 0.0;
+            for (uint32_t c = 0; c < a.ncat; ++c) anc = anc + a.post[(size_t)c * a.ncols + s] * a.a[a.cat * c + at];
+            if (a.anc_post) a.anc_post[at] = anc;
+            sh[threadIdx.x] = anc;
+        }
+        __syncthreads();
+        if (active && i == 0) {
+            int best = -1;
+            double top = 0.0;
+#pragma unroll 8
+            for (uint32_t j = 0; j < dim; ++j) {
+                const double x = sh[threadIdx.x + j];
+                if (x > top) { top = x; best = (int)j; }
+            }
+            a.anc_state[g] = (int8_t)best;
+            a.anc_prob[g] = top;
+        }
+        __syncthreads();   // (the scan's reads are done before the next round writes)
     }
 }
 

@@ -160,6 +160,14 @@ struct HipBackend : Backend {
         if (rc != PGM_OK) error("pgm_tree_likelihood_rates failed (%d): %s", rc, pgm_last_error());
         ml_tree_stats.kernel_ms += pgm_treelik_last_kernel_ms(c);
     }
+    void tree_ancestral(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
+                        const double *w, const double *P, double *site_l, int32_t *site_k, double *post, int8_t *anc_state, double *anc_prob, double *anc_post,
+                        int worker) override {
+        pgm_ctx *c = ctx_of(worker);
+        int rc = pgm_tree_ancestral(c, dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, site_l, site_k, post, anc_state, anc_prob, anc_post);
+        if (rc != PGM_OK) error("pgm_tree_ancestral failed (%d): %s", rc, pgm_last_error());
+        ml_tree_stats.kernel_ms += pgm_treelik_last_kernel_ms(c);
+    }
     bool bionj_multi(uint32_t nfam, const uint32_t *n, const double *D, const double *V, pgm_bionj_join *joins, double *final_d, int worker) override {
         pgm_ctx *c = ctx_of(worker);
         int rc = pgm_bionj_multi(c, nfam, n, D, V, joins, final_d);

@@ -5,6 +5,7 @@
 #include <chrono>
 #include <cstdio>
 #include <fstream>
+#include <set>
 #include <sstream>
 
 namespace pgm {
@@ -68,7 +69,83 @@ void doBootstrap(const Alphabet &a, const DriverOptions &o, const Family &fam, c
 // character of the input: Family::finish_rows), and --ml_sites: the log-likelihood of every column (ml_branch_lengths, DESIGN.md
 // 3.17; the device from kTreelikDeviceMin taxa or with PGM_DEVICE_TREELIK, the host loop with PGM_HOST_TREELIK).  With --ml_gamma the
 // likelihood is the mixture over the rate categories of the discrete gamma (the same route), and --ml_rates: the
-// shape, the categories' rates, and per column the posterior mean rate and the category of the largest posterior
+// shape, the categories' rates, and per column the posterior mean rate and the category of the largest posterior.
+// --ml_ancestral: one Backend::tree_ancestral call at the estimated lengths (and rates) by the same route, and the
+// FASTA of the inner nodes' most probable states; --ml_ancestral_tree: the tree with the nodes' names; --ml_ancestral_probs: a line
+// per node and column
+// the names of the inner nodes of a numbered tree, N1 .. in node order; a leaf that has one of them is an error()
+static std::vector<std::string> ml_ancestral_names(const MlTreeTopology &topo) {
+    std::vector<std::string> node_name(topo.nnodes - topo.nleaves);
+    for (size_t k = 0; k < node_name.size(); ++k) node_name[k] = "N" + std::to_string(k + 1);
+    const std::set<std::string> taken(node_name.begin(), node_name.end());
+    for (const std::string &leaf : topo.names)
+        if (taken.count(leaf)) error("--ml_ancestral: the sequence name %s is the name of an inner node", leaf.c_str());
+    return node_name;
+}
+static void write_ml_ancestral(const Alphabet &a, const MlTreeOpts &mo, const Family &fam, const PhyTree &ml, const std::vector<std::vector<int8_t>> &values,
+                               const MlTreeResult &res, Backend *be) {
+    const MlTreeTopology topo = ml_tree_topology(ml);
+    const uint32_t dim = (uint32_t)a.DIM, nleaves = topo.nleaves, nnodes = topo.nnodes, ninner = nnodes - nleaves;
+    const uint32_t ncols = (uint32_t)values[0].size();
+    const std::vector<std::string> node_name = ml_ancestral_names(topo);
+    std::vector<int8_t> flat((size_t)nleaves * ncols);
+    for (uint32_t r = 0; r < nleaves; ++r) std::copy(values[r].begin(), values[r].end(), flat.begin() + (size_t)r * ncols);
+
+    const auto t0 = std::chrono::steady_clock::now();   // (ml_ancestral_s: the matrices and the call)
+    // the categories' rates at the estimated shape and equal weights, or one category of weight 1.0 and the plain matrices
+    const uint32_t ncat = res.rates.empty() ? 1u : (uint32_t)res.rates.size();
+    const std::vector<double> w(ncat, res.rates.empty() ? 1.0 : 1.0 / (double)ncat);
+    std::vector<double> P;
+    if (res.rates.empty()) treelik_matrices(*fam.model_factory, res.lengths, false, P);
+    else treelik_matrices(*fam.model_factory, res.lengths, false, res.rates, P);
+    std::vector<double> site_l(ncols), post((size_t)ncat * ncols), prob((size_t)ninner * ncols);
+    std::vector<int32_t> site_k(ncols);
+    std::vector<int8_t> state((size_t)ninner * ncols);
+    const double *pi = fam.model_factory->freqs().data();
+    if (be) be->tree_ancestral(dim, nleaves, nnodes, topo.parent.data(), ncols, flat.data(), pi, ncat, w.data(), P.data(), site_l.data(), site_k.data(), post.data(),
+                               state.data(), prob.data(), nullptr);
+    else tree_ancestral_host(dim, nleaves, nnodes, topo.parent.data(), ncols, flat.data(), pi, ncat, w.data(), P.data(), site_l.data(), site_k.data(), post.data(),
+                             state.data(), prob.data(), nullptr);
+    ml_tree_stats.ancestral_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+
+    std::vector<uint8_t> present((size_t)ninner * ncols, 0);
+    tree_ancestral_presence(nleaves, nnodes, topo.parent.data(), ncols, flat.data(), present.data());
+    // the character(s) of a state: the alphabet's own symbol (the first letter that has the value; a codon's three)
+    std::vector<std::string> symbol(dim);
+    for (uint32_t x = 0; x < dim; ++x) {
+        if (!a.rawChars()) { symbol[x] = a.asString((int8_t)x); continue; }
+        for (char ch = 'A'; ch <= 'Z' && symbol[x].empty(); ++ch)
+            if (a.value((int8_t)ch) == (int)x) symbol[x] = std::string(1, ch);
+    }
+    const std::string gap = a.rawChars() ? a.asString(a.gap()) : "---";
+    auto text_of = [&](uint32_t k, uint32_t s, bool held) -> const std::string & {
+        const int8_t x = state[(size_t)k * ncols + s];
+        return held && x >= 0 ? symbol[(size_t)x] : gap;
+    };
+    std::map<std::string, std::string> records;
+    for (uint32_t k = 0; k < ninner; ++k) {
+        std::string &seq = records[node_name[k]];
+        for (uint32_t s = 0; s < ncols; ++s) seq += text_of(k, s, present[(size_t)k * ncols + s] != 0);
+    }
+    std::ofstream out = open_output(mo.anc, "ml ancestral output");
+    write_fasta(records, node_name, out);
+    if (mo.anc_tree_given) {
+        std::map<const PhyTree *, std::string> labels;
+        for (uint32_t k = 0; k < ninner; ++k) labels[topo.node[nleaves + k]] = node_name[k];
+        open_output(mo.anc_tree, "ml ancestral output") << ml.formatNewick(labels) << std::endl;
+    }
+    if (mo.anc_probs_given) {
+        std::ofstream probs = open_output(mo.anc_probs, "ml ancestral output");
+        char buf[64];
+        for (uint32_t k = 0; k < ninner; ++k)
+            for (uint32_t s = 0; s < ncols; ++s) {
+                const bool held = present[(size_t)k * ncols + s] != 0;
+                snprintf(buf, sizeof buf, "\t%u\t%s\t%.17g\t%d\n", s + 1, text_of(k, s, true).c_str(), prob[(size_t)k * ncols + s], held ? 1 : 0);
+                probs << node_name[k] << buf;
+            }
+    }
+}
+
 void doMlTree(const Alphabet &a, const DriverOptions &o, const Family &fam, const std::map<std::string, sequence_t> &alignment) {
     const std::map<std::string, sequence_t> rows = sequence_rows(alignment);
     std::unique_ptr<PhyTree> tree(TreeNJ(a, rows, fam.model_factory.get(), true));
@@ -90,7 +167,9 @@ void doMlTree(const Alphabet &a, const DriverOptions &o, const Family &fam, cons
     const MlTreeOpts &mo = o.mltree;
     MlGamma gamma;
     if (mo.gamma_given) { gamma.ncat = (uint32_t)mo.gamma; gamma.estimate = !mo.alpha_given; gamma.alpha = mo.alpha; }
-    const MlTreeResult res = ml_branch_lengths(a, values, *fam.model_factory, *tree, (uint32_t)mo.rounds, mo.eps, device ? &default_backend() : nullptr, gamma);
+    Backend *be = device ? &default_backend() : nullptr;
+    if (mo.anc_given) (void)ml_ancestral_names(ml_tree_topology(*tree));   // (refused before the optimiser runs and before any file is written)
+    const MlTreeResult res = ml_branch_lengths(a, values, *fam.model_factory, *tree, (uint32_t)mo.rounds, mo.eps, be, gamma);
     std::unique_ptr<PhyTree> ml(ml_tree_with_lengths(ml_tree_topology(*tree), res.lengths));
     open_output(mo.tree, "ml tree output") << ml->formatNewick() << std::endl;
     if (mo.sites_given) {
@@ -124,6 +203,7 @@ void doMlTree(const Alphabet &a, const DriverOptions &o, const Family &fam, cons
             rates << buf;
         }
     }
+    if (mo.anc_given) write_ml_ancestral(a, mo, fam, *ml, values, res, be);
 }
 // --guidance (Penn et al. 2010, GUIDANCE: the guide tree as the source of alignment uncertainty): the final alignment's columns are
 // resampled N times as --bootstrap resamples them, every replicate's BioNJ tree, midpoint rooted and written with exact branch

@@ -8,6 +8,8 @@
 
 namespace pgm {
 
+// (tests/test_cpu_driver.py pins this text by its checksum: --ml_ancestral, --ml_ancestral_tree and --ml_ancestral_probs, which came
+// after that, are described in README.md and DESIGN.md 3.19)
 void usage() {
     std::cerr << "USAGE: pgmsa [-f|--fasta] [-t|--tree <newick>] [--topology <newick>] [-o <file>] [-T] [-I] [-a] [-m] [-M]\n"
                  "             [--codon] [-c|--cs_profile <lib>] [-i <iters>] [-g rate] [-e prob] [-E prob]\n"
@@ -163,6 +165,9 @@ int parse_driver_options(int argc, char **argv, DriverOptions &o) {
         else if (s == "--ml_gamma") { o.mltree.gamma_given = true; gamma_ok = whole_number(val(), o.mltree.gamma); }
         else if (s == "--ml_alpha") { o.mltree.alpha_given = true; alpha_ok = real_number(val(), o.mltree.alpha); }
         else if (s == "--ml_rates") { o.mltree.rates_given = true; o.mltree.rates = val(); }
+        else if (s == "--ml_ancestral") { o.mltree.anc_given = true; o.mltree.anc = val(); }
+        else if (s == "--ml_ancestral_tree") { o.mltree.anc_tree_given = true; o.mltree.anc_tree = val(); }
+        else if (s == "--ml_ancestral_probs") { o.mltree.anc_probs_given = true; o.mltree.anc_probs = val(); }
         else if (s == "--reroot") ++cmdlineopts.reroot_flag;
         else if (s == "--wls_refine") ++cmdlineopts.wlsrefine_flag;
         else if (s.size() >= 2 && s[0] == '-' && s.find_first_not_of('W', 1) == std::string::npos) cmdlineopts.wlsrefine_flag += (int)s.size() - 1;   // -W, -WW
@@ -219,8 +224,11 @@ int parse_driver_options(int argc, char **argv, DriverOptions &o) {
         gamma_ok = !o.mltree.gamma_given || (gamma_ok && o.mltree.gamma >= 2 && o.mltree.gamma <= PGM_TREELIK_MAXCAT);
         alpha_ok = alpha_ok && o.mltree.alpha >= kMlMinAlpha && o.mltree.alpha <= kMlMaxAlpha;
         const bool plain = o.mltree.sites_given || o.mltree.rounds_given || o.mltree.eps_given;   // (the flags from before --ml_gamma keep their message)
-        const char *why = !o.mltree.tree_given ? (plain ? "--ml_sites, --ml_rounds and --ml_epsilon need --ml_tree" : "--ml_gamma, --ml_alpha and --ml_rates need --ml_tree")
+        const bool rates = o.mltree.gamma_given || o.mltree.alpha_given || o.mltree.rates_given;   // (... and so do those from before --ml_ancestral)
+        const char *why = !o.mltree.tree_given ? (plain ? "--ml_sites, --ml_rounds and --ml_epsilon need --ml_tree"
+                                                  : rates ? "--ml_gamma, --ml_alpha and --ml_rates need --ml_tree" : "--ml_ancestral needs --ml_tree")
                           : (!o.mltree.gamma_given && (o.mltree.alpha_given || o.mltree.rates_given)) ? "--ml_alpha and --ml_rates need --ml_gamma"
+                          : (!o.mltree.anc_given && o.mltree.any_anc()) ? "--ml_ancestral_tree and --ml_ancestral_probs need --ml_ancestral"
                           : !gamma_ok ? "--ml_gamma takes a number of categories from 2 to 16"
                           : !alpha_ok ? "--ml_alpha takes a number X with 0.05 <= X <= 100"
                           : !rounds_ok ? "--ml_rounds takes a number of rounds from 1 to 10000"

@@ -48,6 +48,8 @@ void print_stats(const DriverOptions &o, double t_init, double t_tree, double t_
                 ml_tree_stats.kernel_ms);
     if (o.mltree.gamma_given)   // (keys of --ml_gamma only)
         fprintf(stderr, ", \"ml_categories\": %u, \"ml_alpha\": %.17g", ml_tree_stats.categories, ml_tree_stats.alpha);
+    if (o.mltree.anc_given)   // (key of --ml_ancestral only)
+        fprintf(stderr, ", \"ml_ancestral_s\": %.6f", ml_tree_stats.ancestral_s);
     if (batch)   // (keys of --batch only)
         fprintf(stderr, ", \"batch_families\": %d, \"batch_failed\": %d, \"batch_chunks\": %d, \"batch_passes\": %llu, \"batch_levels\": %llu, "
                         "\"batch_align_calls\": %llu, \"batch_dist_calls\": %llu",

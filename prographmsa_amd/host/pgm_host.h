@@ -346,6 +346,11 @@ struct Backend {
     virtual void tree_likelihood_rates(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
                                        uint32_t ncat, const double *w, const double *P, int derivs, double *site_l, int32_t *site_k, double *post, double *d1, double *d2,
                                        int worker = 0);
+    // The marginal ancestral states of every inner node under the same mixture (--ml_ancestral; include/pgm_hip.h: pgm_tree_ancestral).
+    // The default is the host statement, tree_ancestral_host: the same bits.
+    virtual void tree_ancestral(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
+                                uint32_t ncat, const double *w, const double *P, double *site_l, int32_t *site_k, double *post, int8_t *anc_state, double *anc_prob,
+                                double *anc_post, int worker = 0);
     // calls the host code made of the align-batch entry and of the distance entries (all-pairs tiles, pair counts, cosine, ML
     // distances): `pgmsa --batch --stats` shows with them that a stage was shared by the families of a chunk
     std::atomic<uint64_t> calls_align{0}, calls_dist{0};
@@ -457,7 +462,8 @@ public:
     index_t n_children() const { return (index_t)children_.size(); }
     bool isLeaf() const { return children_.empty(); }
     std::string formatNewick() const;
-    // the same text with labels[node] printed between ')' and ':' for every internal node that has one (--bootstrap_out)
+    // the same text with labels[node] printed between ')' and ':' for every internal node that has one (--bootstrap_out), the root's
+    // between ')' and ';' (--ml_ancestral_tree; the labels of the bootstrap outputs hold no root)
     std::string formatNewick(const std::map<const PhyTree *, uint32_t> &labels) const;
     std::string formatNewick(const std::map<const PhyTree *, std::string> &labels) const;   // (--bootstrap_tbe: labels as text)
 private:
@@ -749,6 +755,10 @@ std::string taxa_edges_text(const TaxaSupport &t);
 // treelik_matrices with rates: category-major, for category c and edge e P(r_c t_e), r_c Q P, r_c^2 Q Q P.
 // MlGamma: what ml_branch_lengths is asked for (ncat < 2: one rate for every column, the loop of --ml_tree alone); with `estimate`
 //   alpha starts at 1 and the branch-length loop alternates with a golden-section search on ln alpha.
+// --ml_ancestral (host/treelik_anc.inc):
+// tree_ancestral_host: pgm_tree_ancestral by the same loop, Backend::tree_ancestral's default.
+// tree_ancestral_presence: the gap rule of the written records, present[(v - nleaves) * ncols + s] = 1 iff inner node v lies on a
+//   path between two leaves whose row at column s is not -1 (parent: the numbering of the likelihood entries).
 const double kMlMinLength = 1e-6, kMlMaxLength = 10.0;   // the interval every branch length stays in
 const double kMlMinAlpha = 0.05, kMlMaxAlpha = 100.0;     // ... and the shape of the gamma
 const uint32_t kMlAlphaEvaluations = 12, kMlMaxPairs = 20;   // one search on ln alpha; branch-length loop + search pairs at the most
@@ -757,6 +767,7 @@ const uint32_t kMlAlphaEvaluations = 12, kMlMaxPairs = 20;   // one search on ln
 const uint32_t kTreelikDeviceMin = 24;
 struct MlTreeStats {   // `pgmsa --ml_tree --stats`
     double seconds = 0, kernel_ms = 0, lnl_start = 0, lnl = 0;
+    double ancestral_s = 0;    // --ml_ancestral only: the tree_ancestral call, its matrices included
     uint64_t rounds = 0, evaluations = 0;
     uint32_t categories = 0;   // --ml_gamma only
     double alpha = 0;
@@ -775,6 +786,10 @@ void treelik_matrices(const ModelFactory &mf, const std::vector<double> &t /* nn
 double treelik_lnl(uint32_t ncols, const double *site_l, const int32_t *site_k, double *site_lnl);
 void tree_likelihood_rates_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
                                 uint32_t ncat, const double *w, const double *P, int derivs, double *site_l, int32_t *site_k, double *post, double *d1, double *d2);
+void tree_ancestral_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
+                         const double *w, const double *P, double *site_l, int32_t *site_k, double *post, int8_t *anc_state /* ninner x ncols */,
+                         double *anc_prob /* ninner x ncols */, double *anc_post /* ninner x ncols x dim, or null */);
+void tree_ancestral_presence(uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, uint8_t *present /* ninner x ncols */);
 std::vector<double> gamma_rates(double alpha, uint32_t K);
 void treelik_matrices(const ModelFactory &mf, const std::vector<double> &t, bool derivs, const std::vector<double> &rates, std::vector<double> &P);
 struct MlGamma {

@@ -72,7 +72,10 @@ std::string PhyTree::formatNewickR(const std::map<const PhyTree *, std::string> 
 }
 std::string PhyTree::formatNewickR() const { return formatNewickR(nullptr); }
 std::string PhyTree::formatNewick() const { return formatNewickR() + ";"; }
-std::string PhyTree::formatNewick(const std::map<const PhyTree *, std::string> &labels) const { return formatNewickR(&labels) + ";"; }
+std::string PhyTree::formatNewick(const std::map<const PhyTree *, std::string> &labels) const {
+    const auto it = isLeaf() ? labels.end() : labels.find(this);   // (the root's own label, if it has one: --ml_ancestral_tree)
+    return formatNewickR(&labels) + (it != labels.end() ? it->second : std::string()) + ";";
+}
 std::string PhyTree::formatNewick(const std::map<const PhyTree *, uint32_t> &labels) const {   // (the decimal digits a stream prints)
     std::map<const PhyTree *, std::string> text;
     for (const auto &kv : labels) text[kv.first] = std::to_string(kv.second);

@@ -81,7 +81,8 @@ inline void treelik_chunk_totals(const std::vector<double> &c1, const std::vecto
 }
 
 // The walk over the tree for one site at a time, with the scratch of one thread: the up pass, the scaling rule, and with derivs the
-// down pass and the three sums of every edge.  Both host statements are loops over it.
+// down pass and the three sums of every edge.  The host statements are loops over it.  posteriors() is the down pass of
+// tree_ancestral_host (treelik_anc.inc): a walk made with derivs == false and anc == true.
 struct TreelikSiteWalk {
     const TreelikChildren &ch;
     uint32_t dim, nleaves, nnodes, ncols;
@@ -89,12 +90,13 @@ struct TreelikSiteWalk {
     const double *pi;
     bool derivs;
     std::vector<double> U, O, S, base, o, T;
-    TreelikSiteWalk(const TreelikChildren &ch_, uint32_t dim_, uint32_t nleaves_, uint32_t nnodes_, uint32_t ncols_, const int8_t *rows_, const double *pi_, bool derivs_)
+    TreelikSiteWalk(const TreelikChildren &ch_, uint32_t dim_, uint32_t nleaves_, uint32_t nnodes_, uint32_t ncols_, const int8_t *rows_, const double *pi_, bool derivs_,
+                    bool anc = false)
         : ch(ch_), dim(dim_), nleaves(nleaves_), nnodes(nnodes_), ncols(ncols_), rows(rows_), pi(pi_), derivs(derivs_) {
         uint32_t max_kids = 2;
         for (uint32_t v = nleaves; v < nnodes; ++v) max_kids = std::max(max_kids, ch.off[v + 1] - ch.off[v]);
         const size_t ninner = nnodes - nleaves;
-        U.resize(ninner * dim); O.resize(derivs ? ninner * dim : 0); S.resize((size_t)max_kids * dim); base.resize(dim); o.resize(dim); T.resize(3 * (size_t)dim);
+        U.resize(ninner * dim); O.resize(derivs || anc ? ninner * dim : 0); S.resize((size_t)max_kids * dim); base.resize(dim); o.resize(dim); T.resize(3 * (size_t)dim);
     }
     // site s under the matrices P: (L, k), and with derivs g[e] = A^P' / A^P and q[e] = A^P'' / A^P of every edge e
     void operator()(uint32_t s, const double *P, double &L_out, int32_t &k_out, double *g, double *q) {
@@ -149,6 +151,40 @@ struct TreelikSiteWalk {
                 }
                 g[c] = A[1] / A[0];
                 q[c] = A[2] / A[0];
+            }
+        }
+    }
+    // After operator() on site s under the same P (P alone: derivs == false): the down pass with S from P, and per inner node v
+    // a[(v - nleaves) * dim + i] = m(i) / Z with m(i) = B_v(i) U_v(i), Z = sum_i m(i) ascending; 0.0 where Z == 0.0
+    void posteriors(uint32_t s, const double *P, double *a) {
+        const uint32_t root = nnodes - 1;
+        const size_t mat = (size_t)dim * dim;
+        auto partial = [&](uint32_t c) -> const double * { return c < nleaves ? nullptr : &U[(size_t)(c - nleaves) * dim]; };
+        auto value = [&](uint32_t c) -> int { return c < nleaves ? (int)rows[(size_t)c * ncols + s] : 0; };
+        for (uint32_t v = root; v >= nleaves; --v) {
+            if (v == root) for (uint32_t i = 0; i < dim; ++i) base[i] = pi[i];
+            else {
+                const double *Ov = &O[(size_t)(v - nleaves) * dim], *Pv = P + mat * v;
+                for (uint32_t i = 0; i < dim; ++i) {
+                    double acc = 0.0;
+                    for (uint32_t h = 0; h < dim; ++h) acc = acc + Ov[h] * Pv[h + (size_t)dim * i];
+                    base[i] = acc;
+                }
+            }
+            const double *Uv = &U[(size_t)(v - nleaves) * dim];
+            double *av = a + (size_t)(v - nleaves) * dim, Z = 0.0;
+            for (uint32_t i = 0; i < dim; ++i) { av[i] = base[i] * Uv[i]; Z = Z + av[i]; }
+            for (uint32_t i = 0; i < dim; ++i) av[i] = Z == 0.0 ? 0.0 : av[i] / Z;
+            const uint32_t q0 = ch.off[v], q1 = ch.off[v + 1];
+            for (uint32_t qq = q0; qq < q1; ++qq) treelik_apply(P + mat * ch.idx[qq], dim, partial(ch.idx[qq]), value(ch.idx[qq]), &S[(size_t)(qq - q0) * dim]);
+            for (uint32_t qq = q0; qq < q1; ++qq) {
+                const uint32_t c = ch.idx[qq];
+                if (c < nleaves) continue;   // (a leaf's outside vector has no reader)
+                double *Oc = &O[(size_t)(c - nleaves) * dim];
+                for (uint32_t i = 0; i < dim; ++i) Oc[i] = base[i];
+                for (uint32_t r = q0; r < q1; ++r)
+                    if (r != qq) for (uint32_t i = 0; i < dim; ++i) Oc[i] = Oc[i] * S[(size_t)(r - q0) * dim + i];
+                treelik_rescale(Oc, dim);
             }
         }
     }
