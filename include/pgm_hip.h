@@ -505,7 +505,7 @@ int pgm_tree_likelihood(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t n
                         uint32_t ncols, const int8_t *rows /* nleaves x ncols */, const double *pi /* dim */,
                         const double *P /* (nnodes-1) x {1 or 3} x dim x dim */, int derivs,
                         double *site_l /* ncols */, int32_t *site_k /* ncols */, double *d1, double *d2 /* nnodes-1, derivs only */);
-float pgm_treelik_last_kernel_ms(pgm_ctx *ctx);   /* device time of the kernels of the last pgm_tree_likelihood, pgm_tree_likelihood_rates or pgm_tree_ancestral call */
+float pgm_treelik_last_kernel_ms(pgm_ctx *ctx);   /* device time of the kernels of the last pgm_tree_likelihood, pgm_tree_likelihood_rates, pgm_tree_ancestral or pgm_tree_nni call */
 
 /* ---- the same likelihood under a mixture of ncat rate categories (pgmsa --ml_tree --ml_gamma).
  * Everything from dim to pi, and derivs, d1, d2, is as in pgm_tree_likelihood, with the same checks.  ncat: 1 .. PGM_TREELIK_MAXCAT;
@@ -559,6 +559,39 @@ int pgm_tree_ancestral(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nn
                        double *site_l /* ncols */, int32_t *site_k /* ncols */, double *post /* ncat x ncols */,
                        int8_t *anc_state /* ninner x ncols */, double *anc_prob /* ninner x ncols */,
                        double *anc_post /* ninner x ncols x dim, or NULL */);
+
+/* ---- the nearest-neighbour interchanges of the same tree under the same mixture (pgmsa --ml_tree --ml_search).
+ * Everything from dim to P is as in pgm_tree_ancestral, with the same checks.  site_l, site_k and post are
+ * pgm_tree_likelihood_rates's values with derivs == 0, bit for bit.
+ * Candidate q = (v, a, c) = (cand_v[q], cand_a[q], cand_c[q]): v an inner node that is not the root, u = parent[v], a a child of v, c a
+ * child of u other than v.  The neighbour tree has a and c exchanged: both keep their own edges and matrices, v keeps its own, the
+ * root stays (rooted NNI; the parent -> child direction of every matrix is kept, so a generator need not be reversible).  Nodes of
+ * any arity; a binary tree has two candidates per inner node below the root.
+ * Per category k, site s and candidate, with S_x(i) = sum_j P_x(i, j) U_x(j) and the stored (scaled) partials U and outside vectors O
+ * of the down pass of pgm_tree_ancestral (P alone):
+ *   B_u(i) = pi[i] if u is the root, else sum_h O_u(h) P_u(h, i), h ascending from 0.0
+ *   R(i) = B_u(i) times S_c'(i) of the children c' of u other than v and c, in child order (the product starts with B_u(i))
+ *   T(j) = the product of S_b(j) over the children b of v other than a, in child order (the product starts with its first factor)
+ *   for (x, y) = (a, c), the tree as it is: (D, k_D); for (x, y) = (c, a), the neighbour: (N, k_N):
+ *     X(j) = T(j) * S_x(j), then the scaling rule on its dim values (largest below 2^-256 and above 0: times 2^256, count one)
+ *     Y(i) = R(i) * S_y(i), then the same rule
+ *     W(i) = sum_j P_v(i, j) X(j), j ascending from 0.0;   A = sum_i Y(i) * W(i), i ascending from 0.0;   k = the two counts added
+ *   rho_k = 0.0 when D == 0.0, else N / D multiplied by 2^-256 exactly (k_N - k_D) times, or by 2^256 exactly (k_D - k_N) times
+ *   rho[q * ncols + s] = sum_k post[k][s] * rho_k, k ascending from 0.0
+ * N and D are multilinear in the same four scaled pieces, so the stored scale factors cancel: rho is the neighbour's site likelihood
+ * over the current one, and the mixture with post is sum_k w_k L'_k / sum_k w_k L_k.  Only + - * / occur and nothing is contracted:
+ * the values do not depend on the launch and equal the host statement's (tree_nni_host) bit for bit.  site_l, site_k, post and rho
+ * are overwritten.  Device memory: ncat * 16 * ninner * ncols * dim bytes for the partials and the outside vectors; the inputs,
+ * 8 * ncat * (nnodes-1) * dim * dim bytes of matrices and nleaves * ncols + 12 * nnodes + 12 * ncand + 8 * (dim + ncat) bytes for the
+ * rows, the children lists, the parents, the candidates, pi and w; 12 * ncat * ncols bytes for (L_c, k_c); and the outputs,
+ * (12 + 8 * ncat) * ncols + 8 * ncand * ncols bytes.  Memory that cannot be had is PGM_ERR_NOMEM.
+ * PGM_ERR_INVALID, before anything is launched or an output is touched: what pgm_tree_ancestral refuses (its own outputs aside),
+ * ncand == 0, a null candidate array or rho, a candidate whose v is a leaf, the root or >= nnodes, parent[a] != v,
+ * parent[c] != parent[v], c == v. */
+int pgm_tree_nni(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
+                 const double *pi, uint32_t ncat, const double *w /* ncat */, const double *P /* ncat x (nnodes-1) x dim x dim */,
+                 uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c /* ncand each */,
+                 double *site_l /* ncols */, int32_t *site_k /* ncols */, double *post /* ncat x ncols */, double *rho /* ncand x ncols */);
 
 #ifdef __cplusplus
 }

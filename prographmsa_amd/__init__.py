@@ -93,7 +93,7 @@ EXPORTS = [
     "pgm_bionj_plan", "pgm_bionj_plan_multi",
     "pgm_msa_agreement", "pgm_agreement_last_kernel_ms",
     "pgm_transfer_min", "pgm_transfer_last_kernel_ms", "pgm_transfer_taxa",
-    "pgm_tree_likelihood", "pgm_treelik_last_kernel_ms", "pgm_tree_likelihood_rates", "pgm_tree_ancestral",
+    "pgm_tree_likelihood", "pgm_treelik_last_kernel_ms", "pgm_tree_likelihood_rates", "pgm_tree_ancestral", "pgm_tree_nni",
 ]
 
 
@@ -184,6 +184,9 @@ def _load():
         "pgm_tree_ancestral": (C.c_int, [vp, u32, u32, u32, C.POINTER(u32), u32, C.POINTER(C.c_int8), C.POINTER(C.c_double), u32, C.POINTER(C.c_double),
                                          C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(C.c_int8),
                                          C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "pgm_tree_nni": (C.c_int, [vp, u32, u32, u32, C.POINTER(u32), u32, C.POINTER(C.c_int8), C.POINTER(C.c_double), u32, C.POINTER(C.c_double),
+                                   C.POINTER(C.c_double), u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(i32),
+                                   C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = the library does not export a declared symbol
@@ -357,6 +360,30 @@ class Context:
         check(lib.pgm_tree_ancestral(self.handle, dim, nleaves, nnodes, P_(parent, C.c_uint32), ncols, P_(rows, C.c_int8), P_(pi, C.c_double), ncat,
                                      P_(w, C.c_double), P_(P, C.c_double), P_(out[0], C.c_double), P_(out[1], C.c_int32), P_(out[2], C.c_double),
                                      P_(out[3], C.c_int8), P_(out[4], C.c_double), P_(out[5], C.c_double) if full else None), "pgm_tree_ancestral")
+        return tuple(out)
+
+    def tree_nni(self, dim, parent, rows, pi, w, P, cand, out=None):
+        """pgm_tree_nni: inputs as tree_ancestral; cand: ncand x 3 uint32, a row (v, a, c) -> (site_l, site_k, post, rho (ncand x ncols
+        float64)).  Given output arrays (a tuple of four, C-contiguous of those kinds) are overwritten."""
+        import numpy as np
+        parent = np.ascontiguousarray(parent, np.uint32)
+        rows = np.ascontiguousarray(rows, np.int8)
+        pi = np.ascontiguousarray(pi, np.float64)
+        w = np.ascontiguousarray(w, np.float64)
+        P = np.ascontiguousarray(P, np.float64)
+        cand = np.asarray(cand, np.uint32)
+        if parent.ndim != 1 or rows.ndim != 2 or pi.shape != (dim,) or w.ndim != 1 or P.size != len(w) * (len(parent) - 1) * dim * dim or cand.ndim != 2 or cand.shape[1] != 3:
+            raise ValueError("tree_nni: input array of the wrong shape")
+        nnodes, (nleaves, ncols), ncat, ncand = len(parent), rows.shape, len(w), len(cand)
+        cv, ca, cc = (np.ascontiguousarray(cand[:, k]) for k in range(3))
+        kinds = [((ncols,), np.float64), ((ncols,), np.int32), ((ncat, ncols), np.float64), ((ncand, ncols), np.float64)]
+        if out is None: out = tuple(np.zeros(s, t) for s, t in kinds)
+        if len(out) != 4 or any(a.dtype != t or a.shape != s or not a.flags.c_contiguous for a, (s, t) in zip(out, kinds)):
+            raise ValueError("tree_nni: output array of the wrong kind")
+        P_ = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+        check(lib.pgm_tree_nni(self.handle, dim, nleaves, nnodes, P_(parent, C.c_uint32), ncols, P_(rows, C.c_int8), P_(pi, C.c_double), ncat, P_(w, C.c_double),
+                               P_(P, C.c_double), ncand, P_(cv, C.c_uint32), P_(ca, C.c_uint32), P_(cc, C.c_uint32), P_(out[0], C.c_double), P_(out[1], C.c_int32),
+                               P_(out[2], C.c_double), P_(out[3], C.c_double)), "pgm_tree_nni")
         return tuple(out)
 
     def close(self):

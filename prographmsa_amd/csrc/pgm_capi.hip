@@ -95,7 +95,7 @@ struct pgm_ctx {
         SC_TRANSFER_REF,                    // pgm_transfer_min and pgm_transfer_taxa (shared): reference sets, rep_off, thresholds
         SC_TRANSFER_REP,                    //   replicate sets
         SC_TRANSFER_OUT,                    //   phi (taxa: phi, arg, flip, moved, counted)
-        SC_TREELIK_TREE,                    // tree likelihood and ancestral states, all three entries (shared): children lists, pi, weights, rows
+        SC_TREELIK_TREE,                    // tree likelihood, ancestral states and NNI scores, all four entries (shared): children lists, pi, weights, rows
         SC_TREELIK_P,                       //   the matrices
         SC_TREELIK_U,                       //   partials and outside vectors (ancestral: the categories' posteriors in their place)
         SC_TREELIK_G,                       //   per-site ratios and chunk sums (rates: the categories' site values and ratios first)
@@ -1064,3 +1064,4 @@ int pgm_align_batch_read_matrices(pgm_ctx *ctx, pgm_align_batch *b, uint32_t job
 #include "pgm_treelik_capi.inc"
 #include "pgm_treelik_rates_capi.inc"
 #include "pgm_treelik_anc_capi.inc"
+#include "pgm_treelik_nni_capi.inc"

@@ -11,6 +11,8 @@
 // launch (pgm_treelik_rates_kernel), and combines them per site (pgm_treelik_combine_kernel) ahead of the sums.
 // pgm_tree_ancestral is a third mode of the walk (pgm_treelik_anc_kernel): the down pass with P alone, the posterior
 // of every inner node's states written where the node's outside vector was; pgm_treelik_anc_combine_kernel mixes the categories.
+// pgm_tree_nni is a fourth mode (pgm_treelik_nni_walk_kernel): that down pass without the posteriors, so the outside
+// vectors stay; pgm_treelik_nni_kernel then scores every nearest-neighbour interchange from four stored pieces around its edge.
 //
 // Every sum over states runs ascending from 0.0 with one multiply and one add per term (-ffp-contract=off): the bits are those of
 // tree_likelihood_host.  The walk is a chain of dependent steps on one wavefront, so what a step costs is the latency of its loads:
@@ -161,11 +163,12 @@ __device__ __forceinline__ void pgm_treelik_posterior(const PgmTreelikArgs &a, d
 
 // The walk of one workgroup over the whole tree for the sites of block blockIdx.x: the kernels below are this function.  MODE:
 // PGM_TREELIK_PLAIN (pgm_tree_likelihood), PGM_TREELIK_RAW (a category of pgm_tree_likelihood_rates: q in place of h),
-// PGM_TREELIK_ANC (a category of pgm_tree_ancestral: P alone, posteriors in place of the edges' sums).
-enum { PGM_TREELIK_PLAIN = 0, PGM_TREELIK_RAW = 1, PGM_TREELIK_ANC = 2 };
+// PGM_TREELIK_ANC (a category of pgm_tree_ancestral: P alone, posteriors in place of the edges' sums), PGM_TREELIK_NNI (a category of
+// pgm_tree_nni: the ANC mode without the posteriors, the outside vector of every inner node but the root stays in a.O).
+enum { PGM_TREELIK_PLAIN = 0, PGM_TREELIK_RAW = 1, PGM_TREELIK_ANC = 2, PGM_TREELIK_NNI = 3 };
 template <int MODE>
 __device__ __forceinline__ void pgm_treelik_walk(const PgmTreelikArgs &a) {
-    constexpr bool RAW = MODE == PGM_TREELIK_RAW;
+    constexpr bool RAW = MODE == PGM_TREELIK_RAW, PALONE = MODE == PGM_TREELIK_ANC || MODE == PGM_TREELIK_NNI;
     __shared__ double sh[3][PGM_TREELIK_THREADS];
     const uint32_t dim = a.dim, nleaves = a.nleaves, root = a.nnodes - 1;
     const uint32_t local = threadIdx.x / dim, i = threadIdx.x - local * dim;
@@ -202,7 +205,7 @@ __device__ __forceinline__ void pgm_treelik_walk(const PgmTreelikArgs &a) {
             a.site_k[s] = k;
         }
     }
-    if (MODE != PGM_TREELIK_ANC && !a.derivs) return;
+    if (!PALONE && !a.derivs) return;
 
     // down pass, parents before children: the outside vector of every edge below v, then the edge's three sums
     for (uint32_t v = root; v >= nleaves; --v) {
@@ -223,9 +226,9 @@ __device__ __forceinline__ void pgm_treelik_walk(const PgmTreelikArgs &a) {
                 for (; h < dim; ++h) base = base + o[h] * Pv[h];
             }
         }
-        if (MODE == PGM_TREELIK_ANC) {
+        if (PALONE) {
             // the node's posterior, then the outside vectors of its inner children only: a leaf's has no reader
-            pgm_treelik_posterior(a, &sh[0][0], v, s, i, active, base);
+            if (MODE == PGM_TREELIK_ANC) pgm_treelik_posterior(a, &sh[0][0], v, s, i, active, base);
             for (uint32_t q = q0; q < q1; ++q) {
                 const uint32_t c = a.child[q];
                 if (c < nleaves) continue;   // (uniform over the workgroup)
@@ -298,6 +301,17 @@ __global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_anc_kernel(Pg
     a.site_l += st.L * c;
     a.site_k += st.L * c;
     pgm_treelik_walk<PGM_TREELIK_ANC>(a);
+}
+
+// pgm_tree_nni: as pgm_treelik_anc_kernel, but a.O keeps the outside vectors O_v.
+__global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_nni_walk_kernel(PgmTreelikArgs a, PgmTreelikRatesStride st) {
+    const size_t c = blockIdx.y;
+    a.P += st.P * c;
+    a.U += st.U * c;
+    a.O += st.U * c;
+    a.site_l += st.L * c;
+    a.site_k += st.L * c;
+    pgm_treelik_walk<PGM_TREELIK_NNI>(a);
 }
 
 // The categories of a site combined in the order of the interface.  A workgroup owns 64 consecutive sites (reads and writes run along
@@ -384,6 +398,133 @@ __global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_anc_combine_k
             a.anc_prob[g] = top;
         }
         __syncthreads();   // (the scan's reads are done before the next round writes)
+    }
+}
+
+// The nearest-neighbour interchanges of pgm_tree_nni scored from the stored pieces.  Candidate q = (v, a, c): a a
+// child of v, c a child of u = parent[v] other than v; the neighbour tree has a and c exchanged.  A workgroup of PGM_TREELIK_NNI_WAVES
+// wavefronts owns that many times 64 / dim consecutive sites, a wavefront's threads laid out per (site, state) as in the walk, and
+// takes the candidates blockIdx.y, blockIdx.y + gridDim.y, ...; the categories run inside, ascending, so the mixture
+// rho = sum_k post[k][s] rho_k needs no buffer.  Per category the thread of state i forms B_u(i), R(i), T(i), S_a(i), S_c(i) from global
+// memory (the walk's sums: eight operands ahead of eight ordered adds), the four products X_D = T S_a, Y_D = R S_c, X_N = T S_c,
+// Y_N = R S_a meet the scaling rule through shared memory together, W = P_v X reads the scaled X of its site from shared memory, and the
+// thread of state 0 adds Y(i) W(i) over the states ascending for both trees and takes the ratio.  No workgroup waits for another, there
+// are no atomics and every rho entry has one writer.  Every thread of the workgroup reaches every barrier: the loops over candidates,
+// categories and children are uniform.
+#define PGM_TREELIK_NNI_WAVES 4
+#define PGM_TREELIK_NNI_THREADS (PGM_TREELIK_THREADS * PGM_TREELIK_NNI_WAVES)
+struct PgmTreelikNniArgs {
+    PgmTreelikArgs t;                      // the tree, rows, pi, and category 0's P, U, O (site_l, site_k, g, h unused)
+    PgmTreelikRatesStride st;              // doubles between two categories' matrices (P) and partials (U)
+    uint32_t ncat, ncand;
+    const uint32_t *parent;                // nnodes
+    const uint32_t *cand_v, *cand_a, *cand_c;
+    const double *post;                    // ncat x ncols
+    double *rho;                           // ncand x ncols
+};
+__global__ __launch_bounds__(PGM_TREELIK_NNI_THREADS) void pgm_treelik_nni_kernel(PgmTreelikNniArgs n) {
+    __shared__ double sh[8][PGM_TREELIK_NNI_THREADS];   // 0 .. 3: the four products before scaling; 4, 5: X_D, X_N scaled; 6, 7: Y W of D, N
+    const uint32_t dim = n.t.dim, nleaves = n.t.nleaves, root = n.t.nnodes - 1, spb = n.t.spb, ncols = n.t.ncols;
+    const uint32_t wave = threadIdx.x / PGM_TREELIK_THREADS, lane = threadIdx.x - wave * PGM_TREELIK_THREADS;
+    const uint32_t local = lane / dim, i = lane - local * dim;
+    const uint64_t s64 = ((uint64_t)blockIdx.x * PGM_TREELIK_NNI_WAVES + wave) * spb + local;
+    const bool active = local < spb && s64 < ncols;
+    const uint32_t s = (uint32_t)s64, first = threadIdx.x - i;   // first: the slot of this site's state 0
+    const size_t mat = (size_t)dim * dim;
+
+    for (uint32_t q = blockIdx.y; q < n.ncand; q += gridDim.y) {   // (uniform over the workgroup)
+        const uint32_t v = n.cand_v[q], ca = n.cand_a[q], cc = n.cand_c[q], u = n.parent[v];
+        const uint32_t u0 = n.t.child_off[u], u1 = n.t.child_off[u + 1], v0 = n.t.child_off[v], v1 = n.t.child_off[v + 1];
+        double rho = 0.0;
+        for (uint32_t k = 0; k < n.ncat; ++k) {
+            PgmTreelikArgs a = n.t;
+            a.P += n.st.P * k;
+            a.U += n.st.U * k;
+            a.O += n.st.U * k;
+            double XD = 0.0, YD = 0.0, XN = 0.0, YN = 0.0;
+            if (active) {
+                double R = 0.0;
+                if (u == root) R = a.pi[i];
+                else {
+                    const double *o = a.O + ((size_t)(u - nleaves) * ncols + s) * dim, *Pu = a.P + mat * u + (size_t)dim * i;
+                    uint32_t h = 0;
+                    for (; h + 8 <= dim; h += 8) {
+                        double ov[8], pv[8];
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) { ov[e] = o[h + e]; pv[e] = Pu[h + e]; }
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) R = R + ov[e] * pv[e];
+                    }
+                    for (; h < dim; ++h) R = R + o[h] * Pu[h];
+                }
+                double S[1];
+                for (uint32_t r = u0; r < u1; ++r) {
+                    const uint32_t sib = a.child[r];
+                    if (sib == v || sib == cc) continue;
+                    pgm_treelik_apply<1>(a, a.P + mat * sib, mat, sib, s, i, S);
+                    R = R * S[0];
+                }
+                double T = 0.0;
+                bool have = false;
+                for (uint32_t r = v0; r < v1; ++r) {
+                    const uint32_t b = a.child[r];
+                    if (b == ca) continue;
+                    pgm_treelik_apply<1>(a, a.P + mat * b, mat, b, s, i, S);
+                    T = have ? T * S[0] : S[0];
+                    have = true;
+                }
+                double Sa[1], Sc[1];
+                pgm_treelik_apply<1>(a, a.P + mat * ca, mat, ca, s, i, Sa);
+                pgm_treelik_apply<1>(a, a.P + mat * cc, mat, cc, s, i, Sc);
+                XD = T * Sa[0]; YD = R * Sc[0]; XN = T * Sc[0]; YN = R * Sa[0];
+                sh[0][threadIdx.x] = XD; sh[1][threadIdx.x] = YD; sh[2][threadIdx.x] = XN; sh[3][threadIdx.x] = YN;
+            }
+            __syncthreads();
+            int32_t kD = 0, kN = 0;
+            if (active) {   // the scaling rule on the four vectors of the site (every thread of the site finds the same maxima)
+                double m0 = sh[0][first], m1 = sh[1][first], m2 = sh[2][first], m3 = sh[3][first];
+#pragma unroll 8
+                for (uint32_t j = 1; j < dim; ++j) {
+                    const double x0 = sh[0][first + j], x1 = sh[1][first + j], x2 = sh[2][first + j], x3 = sh[3][first + j];
+                    m0 = x0 > m0 ? x0 : m0; m1 = x1 > m1 ? x1 : m1; m2 = x2 > m2 ? x2 : m2; m3 = x3 > m3 ? x3 : m3;
+                }
+                if (m0 < 0x1p-256 && m0 > 0.0) { XD = XD * 0x1p256; ++kD; }
+                if (m1 < 0x1p-256 && m1 > 0.0) { YD = YD * 0x1p256; ++kD; }
+                if (m2 < 0x1p-256 && m2 > 0.0) { XN = XN * 0x1p256; ++kN; }
+                if (m3 < 0x1p-256 && m3 > 0.0) { YN = YN * 0x1p256; ++kN; }
+                sh[4][threadIdx.x] = XD; sh[5][threadIdx.x] = XN;
+            }
+            __syncthreads();
+            if (active) {   // W(i) = sum_j P_v(i, j) X(j), then Y(i) W(i)
+                const double *col = a.P + mat * v + i, *xd = &sh[4][first], *xn = &sh[5][first];
+                double WD = 0.0, WN = 0.0;
+                uint32_t j = 0;
+                for (; j + 8 <= dim; j += 8) {
+                    double pv[8];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) pv[e] = col[(size_t)dim * (j + e)];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) { WD = WD + pv[e] * xd[j + e]; WN = WN + pv[e] * xn[j + e]; }
+                }
+                for (; j < dim; ++j) { const double pj = col[(size_t)dim * j]; WD = WD + pj * xd[j]; WN = WN + pj * xn[j]; }
+                sh[6][threadIdx.x] = YD * WD; sh[7][threadIdx.x] = YN * WN;
+            }
+            __syncthreads();
+            if (active && i == 0) {
+                double D = 0.0, N = 0.0;
+#pragma unroll 8
+                for (uint32_t j = 0; j < dim; ++j) { D = D + sh[6][threadIdx.x + j]; N = N + sh[7][threadIdx.x + j]; }
+                double r = 0.0;
+                if (D != 0.0) {
+                    r = N / D;
+                    for (int32_t d = kN - kD; d > 0; --d) r = r * 0x1p-256;
+                    for (int32_t d = kD - kN; d > 0; --d) r = r * 0x1p256;
+                }
+                rho = rho + n.post[(size_t)k * ncols + s] * r;
+            }
+            // (the next round writes sh[0 .. 3] only; sh[6], sh[7] are written again after two more barriers)
+        }
+        if (active && i == 0) n.rho[(size_t)q * ncols + s] = rho;
     }
 }
 

@@ -168,6 +168,14 @@ struct HipBackend : Backend {
         if (rc != PGM_OK) error("pgm_tree_ancestral failed (%d): %s", rc, pgm_last_error());
         ml_tree_stats.kernel_ms += pgm_treelik_last_kernel_ms(c);
     }
+    void tree_nni(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
+                  const double *w, const double *P, uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c, double *site_l, int32_t *site_k,
+                  double *post, double *rho, int worker) override {
+        pgm_ctx *c = ctx_of(worker);
+        int rc = pgm_tree_nni(c, dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, ncand, cand_v, cand_a, cand_c, site_l, site_k, post, rho);
+        if (rc != PGM_OK) error("pgm_tree_nni failed (%d): %s", rc, pgm_last_error());
+        ml_search_stats.kernel_ms += pgm_treelik_last_kernel_ms(c);
+    }
     bool bionj_multi(uint32_t nfam, const uint32_t *n, const double *D, const double *V, pgm_bionj_join *joins, double *final_d, int worker) override {
         pgm_ctx *c = ctx_of(worker);
         int rc = pgm_bionj_multi(c, nfam, n, D, V, joins, final_d);

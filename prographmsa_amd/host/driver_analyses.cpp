@@ -72,7 +72,9 @@ void doBootstrap(const Alphabet &a, const DriverOptions &o, const Family &fam, c
 // shape, the categories' rates, and per column the posterior mean rate and the category of the largest posterior.
 // --ml_ancestral: one Backend::tree_ancestral call at the estimated lengths (and rates) by the same route, and the
 // FASTA of the inner nodes' most probable states; --ml_ancestral_tree: the tree with the nodes' names; --ml_ancestral_probs: a line
-// per node and column
+// per node and column.  --ml_search N: up to N rounds of nearest-neighbour interchanges from the start tree, every
+// candidate of a round scored by one Backend::tree_nni call (the same route); --ml_start FILE: a newick in place of the BioNJ tree;
+// --ml_search_log FILE: a line per round
 // the names of the inner nodes of a numbered tree, N1 .. in node order; a leaf that has one of them is an error()
 static std::vector<std::string> ml_ancestral_names(const MlTreeTopology &topo) {
     std::vector<std::string> node_name(topo.nnodes - topo.nleaves);
@@ -148,7 +150,9 @@ static void write_ml_ancestral(const Alphabet &a, const MlTreeOpts &mo, const Fa
 
 void doMlTree(const Alphabet &a, const DriverOptions &o, const Family &fam, const std::map<std::string, sequence_t> &alignment) {
     const std::map<std::string, sequence_t> rows = sequence_rows(alignment);
-    std::unique_ptr<PhyTree> tree(TreeNJ(a, rows, fam.model_factory.get(), true));
+    const MlTreeOpts &mo = o.mltree;
+    // the start tree: the BioNJ tree of the alignment, or --ml_start's (its lengths go through the optimiser's clamp)
+    std::unique_ptr<PhyTree> tree(mo.start_tree ? mo.start_tree->copy() : TreeNJ(a, rows, fam.model_factory.get(), true));
     std::vector<std::vector<int8_t>> values;   // the rows in sorted-name order: the leaves' order
     for (const auto &kv : rows) {
         const sequence_t written = fam.written_row(a, kv.first, kv.second), orig = sequenceFromString(a, fam.seqs.at(kv.first));
@@ -164,12 +168,26 @@ void doMlTree(const Alphabet &a, const DriverOptions &o, const Family &fam, cons
     }
     const HostSwitches &sw = host_switches();
     const bool device = !sw.host_treelik && (sw.device_treelik || rows.size() >= kTreelikDeviceMin);
-    const MlTreeOpts &mo = o.mltree;
     MlGamma gamma;
     if (mo.gamma_given) { gamma.ncat = (uint32_t)mo.gamma; gamma.estimate = !mo.alpha_given; gamma.alpha = mo.alpha; }
     Backend *be = device ? &default_backend() : nullptr;
     if (mo.anc_given) (void)ml_ancestral_names(ml_tree_topology(*tree));   // (refused before the optimiser runs and before any file is written)
-    const MlTreeResult res = ml_branch_lengths(a, values, *fam.model_factory, *tree, (uint32_t)mo.rounds, mo.eps, be, gamma);
+    MlTreeResult res;
+    if (mo.search_given) {   // --ml_search: every file below describes the searched tree
+        MlSearchResult found = ml_topology_search(a, values, *fam.model_factory, *tree, (uint32_t)mo.search, (uint32_t)mo.rounds, mo.eps, be, gamma);
+        tree = std::move(found.tree);
+        res = std::move(found.res);
+        if (mo.anc_given) (void)ml_ancestral_names(ml_tree_topology(*tree));
+        if (mo.search_log_given) {
+            std::ofstream log = open_output(mo.search_log, "ml search output");
+            char buf[256];
+            for (const MlSearchRound &r : found.log) {
+                snprintf(buf, sizeof buf, "%u\t%u\t%u\t%u\t%.17g\t%.17g\t%.17g\t%.17g\n", r.round, r.candidates, r.positive, r.applied, r.best_gain, r.lnl_before,
+                         r.lnl_applied, r.lnl_after);
+                log << buf;
+            }
+        }
+    } else res = ml_branch_lengths(a, values, *fam.model_factory, *tree, (uint32_t)mo.rounds, mo.eps, be, gamma);
     std::unique_ptr<PhyTree> ml(ml_tree_with_lengths(ml_tree_topology(*tree), res.lengths));
     open_output(mo.tree, "ml tree output") << ml->formatNewick() << std::endl;
     if (mo.sites_given) {

@@ -103,7 +103,7 @@ static bool real_number(const std::string &text, double &v) {
 
 int parse_driver_options(int argc, char **argv, DriverOptions &o) {
     bool missing = false;   // a flag without its value
-    bool cutoff_ok = true, rounds_ok = true, eps_ok = true, gamma_ok = true, alpha_ok = true;
+    bool cutoff_ok = true, rounds_ok = true, eps_ok = true, gamma_ok = true, alpha_ok = true, search_ok = true;
     for (int i = 1; i < argc && !missing; ++i) {
         std::string s = argv[i];
         auto val = [&]() -> std::string { if (i + 1 >= argc) { missing = true; return ""; } return argv[++i]; };
@@ -168,6 +168,9 @@ int parse_driver_options(int argc, char **argv, DriverOptions &o) {
         else if (s == "--ml_ancestral") { o.mltree.anc_given = true; o.mltree.anc = val(); }
         else if (s == "--ml_ancestral_tree") { o.mltree.anc_tree_given = true; o.mltree.anc_tree = val(); }
         else if (s == "--ml_ancestral_probs") { o.mltree.anc_probs_given = true; o.mltree.anc_probs = val(); }
+        else if (s == "--ml_search") { o.mltree.search_given = true; search_ok = whole_number(val(), o.mltree.search); }
+        else if (s == "--ml_start") { o.mltree.start_given = true; o.mltree.start = val(); }
+        else if (s == "--ml_search_log") { o.mltree.search_log_given = true; o.mltree.search_log = val(); }
         else if (s == "--reroot") ++cmdlineopts.reroot_flag;
         else if (s == "--wls_refine") ++cmdlineopts.wlsrefine_flag;
         else if (s.size() >= 2 && s[0] == '-' && s.find_first_not_of('W', 1) == std::string::npos) cmdlineopts.wlsrefine_flag += (int)s.size() - 1;   // -W, -WW
@@ -223,12 +226,16 @@ int parse_driver_options(int argc, char **argv, DriverOptions &o) {
         eps_ok = eps_ok && o.mltree.eps >= 0.0 && o.mltree.eps < INFINITY;
         gamma_ok = !o.mltree.gamma_given || (gamma_ok && o.mltree.gamma >= 2 && o.mltree.gamma <= PGM_TREELIK_MAXCAT);
         alpha_ok = alpha_ok && o.mltree.alpha >= kMlMinAlpha && o.mltree.alpha <= kMlMaxAlpha;
+        search_ok = !o.mltree.search_given || (search_ok && o.mltree.search >= 1 && o.mltree.search <= 1000);
         const bool plain = o.mltree.sites_given || o.mltree.rounds_given || o.mltree.eps_given;   // (the flags from before --ml_gamma keep their message)
         const bool rates = o.mltree.gamma_given || o.mltree.alpha_given || o.mltree.rates_given;   // (... and so do those from before --ml_ancestral)
         const char *why = !o.mltree.tree_given ? (plain ? "--ml_sites, --ml_rounds and --ml_epsilon need --ml_tree"
-                                                  : rates ? "--ml_gamma, --ml_alpha and --ml_rates need --ml_tree" : "--ml_ancestral needs --ml_tree")
+                                                  : rates ? "--ml_gamma, --ml_alpha and --ml_rates need --ml_tree"
+                                                  : o.mltree.any_anc() ? "--ml_ancestral needs --ml_tree" : "--ml_search, --ml_start and --ml_search_log need --ml_tree")
                           : (!o.mltree.gamma_given && (o.mltree.alpha_given || o.mltree.rates_given)) ? "--ml_alpha and --ml_rates need --ml_gamma"
                           : (!o.mltree.anc_given && o.mltree.any_anc()) ? "--ml_ancestral_tree and --ml_ancestral_probs need --ml_ancestral"
+                          : (!o.mltree.search_given && o.mltree.search_log_given) ? "--ml_search_log needs --ml_search"
+                          : !search_ok ? "--ml_search takes a number of rounds from 1 to 1000"
                           : !gamma_ok ? "--ml_gamma takes a number of categories from 2 to 16"
                           : !alpha_ok ? "--ml_alpha takes a number X with 0.05 <= X <= 100"
                           : !rounds_ok ? "--ml_rounds takes a number of rounds from 1 to 10000"

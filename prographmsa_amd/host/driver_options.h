@@ -26,14 +26,19 @@ struct GuidanceOpts {   // --guidance N --guidance_out FILE --guidance_seed S --
 };
 
 struct MlTreeOpts {   // --ml_tree FILE --ml_sites FILE --ml_rounds N --ml_epsilon X --ml_gamma K --ml_alpha X --ml_rates FILE
-                      // --ml_ancestral FILE --ml_ancestral_tree FILE --ml_ancestral_probs FILE
+                      // --ml_ancestral FILE --ml_ancestral_tree FILE --ml_ancestral_probs FILE --ml_search N --ml_start FILE --ml_search_log FILE
     std::string tree, sites, rates, anc, anc_tree, anc_probs;
     bool anc_given = false, anc_tree_given = false, anc_probs_given = false;
     bool any_anc() const { return anc_given || anc_tree_given || anc_probs_given; }
     bool tree_given = false, sites_given = false, rounds_given = false, eps_given = false, gamma_given = false, alpha_given = false, rates_given = false;
     long rounds = 100, gamma = 0;
     double eps = 1e-4, alpha = 1.0;
-    bool any() const { return tree_given || sites_given || rounds_given || eps_given || gamma_given || alpha_given || rates_given || any_anc(); }
+    bool search_given = false, start_given = false, search_log_given = false;
+    long search = 0;
+    std::string start, search_log;
+    std::shared_ptr<PhyTree> start_tree;   // --ml_start as read and checked against the family's names, before any work (main.cpp)
+    bool any_search() const { return search_given || start_given || search_log_given; }
+    bool any() const { return tree_given || sites_given || rounds_given || eps_given || gamma_given || alpha_given || rates_given || any_anc() || any_search(); }
 };
 
 struct DriverOptions {

@@ -50,6 +50,10 @@ void print_stats(const DriverOptions &o, double t_init, double t_tree, double t_
         fprintf(stderr, ", \"ml_categories\": %u, \"ml_alpha\": %.17g", ml_tree_stats.categories, ml_tree_stats.alpha);
     if (o.mltree.anc_given)   // (key of --ml_ancestral only)
         fprintf(stderr, ", \"ml_ancestral_s\": %.6f", ml_tree_stats.ancestral_s);
+    if (o.mltree.search_given)   // (keys of --ml_search only)
+        fprintf(stderr, ", \"ml_search_s\": %.6f, \"ml_search_rounds\": %llu, \"ml_nni_applied\": %llu, \"ml_nni_calls\": %llu, \"ml_nni_kernel_ms\": %.3f",
+                ml_search_stats.seconds, (unsigned long long)ml_search_stats.rounds, (unsigned long long)ml_search_stats.applied,
+                (unsigned long long)ml_search_stats.calls, ml_search_stats.kernel_ms);
     if (batch)   // (keys of --batch only)
         fprintf(stderr, ", \"batch_families\": %d, \"batch_failed\": %d, \"batch_chunks\": %d, \"batch_passes\": %llu, \"batch_levels\": %llu, "
                         "\"batch_align_calls\": %llu, \"batch_dist_calls\": %llu",

@@ -245,6 +245,22 @@ int main(int argc, char **argv) {
         if (o.bootstrap.given && fam.seqs.size() < 4) error("--bootstrap needs at least 4 sequences");
         if (o.guidance.given && fam.seqs.size() < 4) error("--guidance needs at least 4 sequences");
         if (o.mltree.tree_given && fam.seqs.size() < 3) error("--ml_tree needs at least 3 sequences");
+        if (o.mltree.tree_given && o.mltree.start_given) {   // (--ml_start is read as -t reads a tree, and refused before any work or file)
+            std::ifstream ts(o.mltree.start.c_str());
+            if (!ts) error("cannot open the --ml_start tree file %s", o.mltree.start.c_str());
+            o.mltree.start_tree.reset(parse_newick(ts));
+            std::vector<std::string> held, own;
+            std::function<void(const PhyTree &)> walk = [&](const PhyTree &t) {
+                if (t.isLeaf()) { held.push_back(t.getName()); return; }
+                if (t.n_children() < 2) error("--ml_start: an inner node with one child");
+                for (index_t c = 0; c < t.n_children(); ++c) walk(t[(int)c]);
+            };
+            walk(*o.mltree.start_tree);
+            for (const auto &kv : fam.seqs) own.push_back(kv.first);
+            std::sort(held.begin(), held.end());
+            std::sort(own.begin(), own.end());
+            if (held != own) error("--ml_start: the leaves of the tree are not the sequences of the input");
+        }
         std::ofstream custom_out;
         std::ostream *out = &std::cout;
         if (!cmdlineopts.output_file.empty()) {

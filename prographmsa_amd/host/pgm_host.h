@@ -351,6 +351,11 @@ struct Backend {
     virtual void tree_ancestral(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
                                 uint32_t ncat, const double *w, const double *P, double *site_l, int32_t *site_k, double *post, int8_t *anc_state, double *anc_prob,
                                 double *anc_post, int worker = 0);
+    // The likelihood ratio of every nearest-neighbour interchange at every column (--ml_search; include/pgm_hip.h: pgm_tree_nni).  The
+    // default is the host statement, tree_nni_host: the same bits.
+    virtual void tree_nni(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
+                          const double *w, const double *P, uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c, double *site_l,
+                          int32_t *site_k, double *post, double *rho, int worker = 0);
     // calls the host code made of the align-batch entry and of the distance entries (all-pairs tiles, pair counts, cosine, ML
     // distances): `pgmsa --batch --stats` shows with them that a stage was shared by the families of a chunk
     std::atomic<uint64_t> calls_align{0}, calls_dist{0};
@@ -759,6 +764,15 @@ std::string taxa_edges_text(const TaxaSupport &t);
 // tree_ancestral_host: pgm_tree_ancestral by the same loop, Backend::tree_ancestral's default.
 // tree_ancestral_presence: the gap rule of the written records, present[(v - nleaves) * ncols + s] = 1 iff inner node v lies on a
 //   path between two leaves whose row at column s is not -1 (parent: the numbering of the likelihood entries).
+// --ml_search (host/treelik_nni.inc):
+// tree_nni_host: pgm_tree_nni per block of column chunks (the walk's partials and outside vectors of a block are held, 256 MB by
+//   default) by a loop over the block's columns, then over candidates x column chunks; Backend::tree_nni's default.
+// treelik_nni_gain: gain[q] = sum over the sites ascending of log rho[q][s] (log 0 is -infinity).
+// ml_topology_search: ml_branch_lengths on the start tree, then up to `search_rounds` rounds of: one tree_nni call over every
+//   candidate (v ascending, a in child order, c in child order), the candidates of gain > eps by gain descending then index, picked
+//   greedily while no two share a node of {u, v, a, c}; the first m picked applied (m from all of them, halved while the evaluation at
+//   the carried lengths is not above lnL; none left: the search ends), then ml_branch_lengths again from the carried lengths and
+//   the shape in hand.  lnL never decreases.
 const double kMlMinLength = 1e-6, kMlMaxLength = 10.0;   // the interval every branch length stays in
 const double kMlMinAlpha = 0.05, kMlMaxAlpha = 100.0;     // ... and the shape of the gamma
 const uint32_t kMlAlphaEvaluations = 12, kMlMaxPairs = 20;   // one search on ln alpha; branch-length loop + search pairs at the most
@@ -796,6 +810,7 @@ struct MlGamma {
     uint32_t ncat = 0;
     bool estimate = true;
     double alpha = 1.0;
+    double start = 1.0;   // with `estimate`: the shape the search starts from
 };
 struct MlTreeResult {
     std::vector<double> lengths;    // per edge (node below it)
@@ -807,6 +822,28 @@ struct MlTreeResult {
 };
 MlTreeResult ml_branch_lengths(const Alphabet &a, const std::vector<std::vector<int8_t>> &rows, const ModelFactory &model_factory, const PhyTree &tree,
                                uint32_t rounds, double eps, Backend *be = nullptr, const MlGamma &gamma = MlGamma());
+const size_t kTreelikNniBlockBytes = (size_t)256 << 20;
+void tree_nni_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
+                   const double *w, const double *P, uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c /* ncand each */,
+                   double *site_l, int32_t *site_k, double *post, double *rho /* ncand x ncols */,
+                   size_t block_bytes = kTreelikNniBlockBytes /* the partials and outside vectors held at a time, about; at least one column chunk */);
+void treelik_nni_gain(uint32_t ncand, uint32_t ncols, const double *rho, double *gain /* ncand */);
+struct MlSearchStats {   // `pgmsa --ml_tree --ml_search --stats`
+    double seconds = 0, kernel_ms = 0;
+    uint64_t rounds = 0, applied = 0, calls = 0;   // accepted rounds, moves applied in them, tree_nni calls
+};
+extern MlSearchStats ml_search_stats;
+struct MlSearchRound {   // a line of --ml_search_log
+    uint32_t round = 0, candidates = 0, positive = 0, applied = 0;
+    double best_gain = 0, lnl_before = 0, lnl_applied = 0, lnl_after = 0;
+};
+struct MlSearchResult {
+    std::unique_ptr<PhyTree> tree;   // the searched tree; `res` is ml_branch_lengths's result on it (lnl_start: the start tree's)
+    MlTreeResult res;
+    std::vector<MlSearchRound> log;
+};
+MlSearchResult ml_topology_search(const Alphabet &a, const std::vector<std::vector<int8_t>> &rows, const ModelFactory &model_factory, const PhyTree &start,
+                                  uint32_t search_rounds, uint32_t rounds, double eps, Backend *be = nullptr, const MlGamma &gamma = MlGamma());
 // a copy of `tree` whose edge above topo.node[e] has length lengths[e]
 PhyTree *ml_tree_with_lengths(const MlTreeTopology &topo, const std::vector<double> &lengths);
 

@@ -171,10 +171,12 @@ struct TreelikSiteWalk {
                     base[i] = acc;
                 }
             }
-            const double *Uv = &U[(size_t)(v - nleaves) * dim];
-            double *av = a + (size_t)(v - nleaves) * dim, Z = 0.0;
-            for (uint32_t i = 0; i < dim; ++i) { av[i] = base[i] * Uv[i]; Z = Z + av[i]; }
-            for (uint32_t i = 0; i < dim; ++i) av[i] = Z == 0.0 ? 0.0 : av[i] / Z;
+            if (a) {   // (null: the outside vectors alone, what tree_nni_host reads)
+                const double *Uv = &U[(size_t)(v - nleaves) * dim];
+                double *av = a + (size_t)(v - nleaves) * dim, Z = 0.0;
+                for (uint32_t i = 0; i < dim; ++i) { av[i] = base[i] * Uv[i]; Z = Z + av[i]; }
+                for (uint32_t i = 0; i < dim; ++i) av[i] = Z == 0.0 ? 0.0 : av[i] / Z;
+            }
             const uint32_t q0 = ch.off[v], q1 = ch.off[v + 1];
             for (uint32_t qq = q0; qq < q1; ++qq) treelik_apply(P + mat * ch.idx[qq], dim, partial(ch.idx[qq]), value(ch.idx[qq]), &S[(size_t)(qq - q0) * dim]);
             for (uint32_t qq = q0; qq < q1; ++qq) {
@@ -322,7 +324,7 @@ MlTreeResult ml_branch_lengths(const Alphabet &a, const std::vector<std::vector<
     std::vector<int32_t> site_k(ncols), trial_k(ncols);
     std::vector<double> rates, post((size_t)ncat * ncols), trial_post(post.size());   // (with categories only)
     const std::vector<double> weights(ncat, ncat ? 1.0 / (double)ncat : 0.0);
-    double alpha = gamma.estimate ? 1.0 : gamma.alpha;
+    double alpha = gamma.estimate ? gamma.start : gamma.alpha;
     if (ncat) rates = gamma_rates(alpha, ncat);
     for (uint32_t e = 0; e < nedges; ++e) t[e] = clamp(topo.node[e]->getBranchLength());
     const double *pi = model_factory.freqs().data();
