@@ -19,6 +19,7 @@ import gen
 import mldist_general_ref as M
 import test_cpu_mlgamma as TG
 import test_cpu_mltree as TM
+import test_cpu_treelik_shapes as SH
 import transfer_ref as T
 import treelik_anc_ref as A
 import treelik_rates_ref as G
@@ -244,7 +245,7 @@ NOT_FULL = [(20, 33, "balanced8", 4), (61, 17, "balanced8", 2), (4, 17, "balance
 ONE_CATEGORY = [(4, 33, "balanced8", 1), (20, 17, "balanced8", 1), (61, 33, "trifurcating", 1), (64, 17, "balanced24", 1)]
 MIXED_SHAPES = [(20, 33, "balanced8", 16), (4, 1, "balanced8", 2), (64, 33, "balanced24", 4), (4, 300, "balanced8", 4), (4, 17, "balanced8", 1)]
 SMALL_VALID = (4, 15, "balanced8", 2)   # what the rejections change
-NATIVE_CASES = list(dict.fromkeys(GRID + OTHER_TREES + [MANY_COLUMNS] + ONE_CATEGORY + MIXED_SHAPES + NOT_FULL + [SMALL_VALID]))
+NATIVE_CASES = list(dict.fromkeys(GRID + OTHER_TREES + [MANY_COLUMNS] + ONE_CATEGORY + MIXED_SHAPES + NOT_FULL + [SMALL_VALID] + SH.NATIVE_ANC))   # (SH: the other dims, polytomies)
 
 
 def _case_bytes(c, full=1, **kw):

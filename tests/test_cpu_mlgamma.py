@@ -18,6 +18,7 @@ import batch_util as bu
 import gen
 import mldist_general_ref as M
 import test_cpu_mltree as TM
+import test_cpu_treelik_shapes as SH
 import treelik_rates_ref as G
 import treelik_ref as R
 
@@ -81,7 +82,8 @@ def test_mixed_scaling_cases_hold_what_they_claim():
 # ---- the host loop and the rates, stand-alone ---------------------------------------------------------------------------------------------
 NATIVE_CASES = [(4, n, "balanced8", k) for n in (1, 16, 17, 33) for k in (1, 2, 4)] + [(20, 33, "balanced8", 16), (64, 17, "balanced8", 2), (61, 33, "balanced8", 4),
                                                                                       (4, 33, "two", 4), (20, 33, "three", 4), (61, 15, "trifurcating", 4),
-                                                                                      (20, 33, "balanced24", 4), (4, 17, "caterpillar96", 2)]
+                                                                                      (20, 33, "balanced24", 4), (4, 17, "caterpillar96", 2)] + \
+    SH.NATIVE_RATES   # (tests/test_cpu_treelik_shapes.py: the other dims, more than 1024 columns, polytomies)
 
 
 def _case_text(c, **kw):

@@ -17,6 +17,7 @@ import mldist_general_ref as M
 import test_cpu_mlancestral as TA
 import test_cpu_mlgamma as TG
 import test_cpu_mltree as TM
+import test_cpu_treelik_shapes as SH
 import transfer_ref as T
 import treelik_nni_ref as N
 import treelik_rates_ref as G
@@ -119,7 +120,7 @@ ARITY = [(dim, 17, tree, 2) for dim in DIMS for tree in ("trifurcating", "inner3
 LARGER = [(20, 33, "balanced24", 4), (4, 17, "caterpillar96", 1), (20, 17, "caterpillar96", 2)]
 ORDER = [(4, 33, "balanced8", 4, "one"), (20, 17, "balanced8", 2, "shuffled"), (4, 33, "inner3", 4, "shuffled")]
 SMALL_VALID = (4, 15, "balanced8", 2)   # what the rejections change
-NATIVE_CASES = list(dict.fromkeys(GRID + SMALL_TREES + ARITY + LARGER + ORDER + [SMALL_VALID]))
+NATIVE_CASES = list(dict.fromkeys(GRID + SMALL_TREES + ARITY + LARGER + ORDER + [SMALL_VALID] + SH.NATIVE_NNI))   # (SH: the other dims, polytomies)
 
 
 def leaf_case():

@@ -1,6 +1,7 @@
 """`--ml_tree`, `--ml_sites`, `--ml_rounds` and `--ml_epsilon` through the CPU oracle driver (pgmsa_oracle: Backend::tree_likelihood's
 default, the host loop), and the pieces below it:
-  - tests/treelik_ref.py itself against brute force on a 4-leaf tree (scipy's expm, a sum over the states of the two inner nodes);
+  - tests/treelik_ref.py itself against brute force on a 4-leaf tree and on a tree with an inner node of four children (scipy's expm,
+    a sum over the states of the inner nodes below the root), from one state to 20;
   - tree_likelihood_host in a stand-alone program (tests/native/treelik_test.cpp), its %a output equal to treelik_ref bit for bit,
     built once plainly and once under AddressSanitizer and UBSan;
   - the driver: refusals, every other output unchanged, topology, the two files against treelik_ref on the written tree and the
@@ -15,6 +16,7 @@ import pytest
 import batch_util as bu
 import gen
 import mldist_general_ref as M
+import test_cpu_treelik_shapes as SH
 import treelik_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,38 +24,54 @@ KEYS = ("ml_tree_s", "ml_rounds", "ml_evaluations", "ml_lnl_start", "ml_lnl", "m
 
 
 # ---- the statement against brute force --------------------------------------------------------------------------------------------
-def brute_site_l(Q, pi, lengths, rows):
-    """((0,1)4,(2,3)5)6 by a sum over the states of nodes 4 and 5 (einsum over explicit matrices; scipy's expm)."""
+def brute_site_l(Q, pi, lengths, rows, tree="balanced4"):
+    """A sum over the states of the inner nodes below the root (einsum over explicit matrices, every index looped; scipy's expm):
+    ((0,1)4,(2,3)5)6, or treelik_ref's inner4, (6,(4,5,(0,1)7,(2,3)8)9)10."""
     from scipy.linalg import expm
     P = [expm(Q * t) for t in lengths]
     n = len(pi)
     out = []
     for s in range(rows.shape[1]):
-        u = [np.ones(n) if rows[l, s] < 0 else np.eye(n)[rows[l, s]] for l in range(4)]
-        out.append(np.einsum("r,ra,a,a,rb,b,b->", pi, P[4], P[0] @ u[0], P[1] @ u[1], P[5], P[2] @ u[2], P[3] @ u[3]))
+        u = [np.ones(n) if rows[l, s] < 0 else np.eye(n)[rows[l, s]] for l in range(rows.shape[0])]
+        if tree == "balanced4":
+            out.append(np.einsum("r,ra,a,a,rb,b,b->", pi, P[4], P[0] @ u[0], P[1] @ u[1], P[5], P[2] @ u[2], P[3] @ u[3]))
+        else:
+            assert tree == "inner4"
+            out.append(np.einsum("r,r,rc,c,c,ca,a,a,cb,b,b->", pi, P[6] @ u[6], P[9], P[4] @ u[4], P[5] @ u[5], P[7], P[0] @ u[0], P[1] @ u[1],
+                                 P[8], P[2] @ u[2], P[3] @ u[3]))
     return np.array(out)
 
 
-@pytest.mark.parametrize("dim", [4, 20])
-def test_reference_against_brute_force(dim):
+BRUTE = [(dim, tree) for tree in ("balanced4", "inner4") for dim in (1, 3, 4, 8, 20)]
+
+
+@pytest.mark.parametrize("dim,tree", BRUTE, ids=[str(dim) if tree == "balanced4" else "%d-%s" % (dim, tree) for dim, tree in BRUTE])
+def test_reference_against_brute_force(dim, tree):
     """L_s within 1e-10 relative (at most 3 * 64^2 terms of one sign: rounding is far below it); d1 and d2 within 1e-5 (relative
-    to max(1, |value|)) of the first and second central differences of the brute-force lnL at step 1e-4."""
+    to max(1, |value|)) of the first and second central differences of the brute-force lnL at step 1e-4.  inner4 has a node of four
+    children below the root, two of them inner: the general branch of the down pass with an outside vector behind it.  One state has
+    one generator, Q = 0: every likelihood is 1 and every derivative 0."""
     rng = np.random.default_rng(dim)
-    Q = M.random_generator(dim, 40 + dim)   # (not reversible: the direction parent -> child matters)
+    Q = M.random_generator(dim, 40 + dim) if dim > 1 else np.zeros((1, 1))   # (not reversible: the direction parent -> child matters)
     pi = rng.dirichlet(np.ones(dim) * 3)
-    parent = R.balanced(4)
-    assert list(parent) == [4, 4, 5, 5, 6, 6, R.ROOT]
-    lengths = rng.uniform(0.05, 0.6, 6)
-    rows = rng.integers(0, dim, (4, 12)).astype(np.int8)
+    if tree == "balanced4":
+        nleaves, parent = 4, R.balanced(4)
+        assert list(parent) == [4, 4, 5, 5, 6, 6, R.ROOT]
+    else:
+        nleaves, parent = R.TREES["inner4"]()
+        assert list(parent) == [7, 7, 8, 8, 9, 9, 10, 9, 9, 10, R.ROOT]
+    nedges = len(parent) - 1
+    lengths = rng.uniform(0.05, 0.6, nedges)
+    rows = rng.integers(0, dim, (nleaves, 12)).astype(np.int8)
     rows[1, 2] = -1; rows[:, 5] = -1; rows[3, 7] = -2
-    got = R.evaluate(dim, 4, parent, rows, pi, R.matrices(Q, lengths))
-    want = brute_site_l(Q, pi, lengths, rows)
+    got = R.evaluate(dim, nleaves, parent, rows, pi, R.matrices(Q, lengths))
+    want = brute_site_l(Q, pi, lengths, rows, tree)
     assert np.all(got["site_k"] == 0)
     assert np.max(np.abs(got["site_l"] - want) / want) < 1e-10
     assert abs(want[5] - 1.0) < 1e-12   # (a column of gaps)
-    lnl = lambda t: float(np.sum(np.log(brute_site_l(Q, pi, t, rows))))
+    lnl = lambda t: float(np.sum(np.log(brute_site_l(Q, pi, t, rows, tree))))
     step = 1e-4
-    for e in range(6):
+    for e in range(nedges):
         up, dn = lengths.copy(), lengths.copy()
         up[e] += step; dn[e] -= step
         fd1 = (lnl(up) - lnl(dn)) / (2 * step)
@@ -88,7 +106,8 @@ def test_reference_scaling_is_exact():
 # ---- the host loop, bit for bit -------------------------------------------------------------------------------------------------------
 NATIVE_CASES = [(4, n, "balanced8", True) for n in (1, 15, 16, 17, 33, 300)] + [(20, n, "balanced8", True) for n in (1, 16, 17, 33)] + \
     [(64, 17, "balanced8", True), (61, 33, "balanced8", True), (4, 33, "two", True), (20, 33, "three", True), (61, 15, "trifurcating", True), (4, 33, "trifurcating", True),
-     (20, 33, "balanced24", True), (4, 17, "caterpillar96", True), (20, 17, "caterpillar96", True), (20, 33, "balanced8", False), (4, 17, "caterpillar96", False)]
+     (20, 33, "balanced24", True), (4, 17, "caterpillar96", True), (20, 17, "caterpillar96", True), (20, 33, "balanced8", False), (4, 17, "caterpillar96", False)] + \
+    SH.NATIVE_PLAIN   # (tests/test_cpu_treelik_shapes.py: the other dims, more than 1024 columns, polytomies)
 
 
 def _hex(values):

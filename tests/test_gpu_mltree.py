@@ -72,9 +72,11 @@ def test_without_derivatives(ctx, dim, ncols, tree):
 
 def test_calls_of_different_shapes_on_one_context(ctx):
     """Large, small, large again, without derivatives in between: nothing of a call is read by the next (the scratch buffers are
-    reused and hold the previous call's partials)."""
+    reused and hold the previous call's partials).  At the end other thread layouts in turn: 3 states (21 sites per wavefront and an
+    idle lane) behind 64 (one site), 33 states (one site, 31 idle lanes) behind 2 (32 sites)."""
     order = [(20, 300, "balanced8", True), (4, 1, "balanced8", True), (64, 33, "balanced24", True), (20, 33, "balanced8", False), (4, 33, "two", True),
-             (61, 17, "caterpillar96", True), (20, 300, "balanced8", True), (4, 17, "caterpillar96", False), (20, 33, "three", True)]
+             (61, 17, "caterpillar96", True), (20, 300, "balanced8", True), (4, 17, "caterpillar96", False), (20, 33, "three", True),
+             (64, 17, "balanced8", True), (3, 85, "balanced8", True), (2, 129, "balanced8", True), (33, 5, "balanced8", True)]
     for k, key in enumerate(order):
         check(ctx, R.make_case(*key), ("call %d" % k,) + key)
 

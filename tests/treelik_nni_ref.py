@@ -171,14 +171,11 @@ def exchanged(nleaves, parent, v, a, c):
     return np.array(out, np.uint32), np.array(order)
 
 
-def inner_trifurcation():
-    """Six leaves: node 6 = (0, 1, 2), 7 = (6, 3), 8 = (7, 4), the root 9 = (8, 5): a non-root inner node with three children."""
-    return 6, np.array([6, 6, 6, 7, 8, 9, 7, 8, 9, ROOT], np.uint32)
-
+inner_trifurcation = R.inner_trifurcation
 
 TREES = dict(R.TREES)
 TREES["four"] = lambda: (4, R.balanced(4))
-TREES["inner3"] = inner_trifurcation
+OWN_DRAW = ("four", "inner3")   # the trees whose cases make_case draws itself (inner3 since before treelik_ref had it: its cases keep their bits)
 
 
 # ---- seeded cases ----------------------------------------------------------------------------------------------------------------------
@@ -192,7 +189,7 @@ def make_case(dim, ncols, tree, ncat, which="all"):
     key = (dim, ncols, tree, ncat, which)
     if key in _cases:
         return _cases[key]
-    if tree in R.TREES:
+    if tree not in OWN_DRAW:
         base = A.make_case(dim, ncols, tree, ncat)
         nleaves, parent, rows, pi, P, w = base["nleaves"], base["parent"], base["rows"], base["pi"], base["P"], base["w"]
     else:

@@ -126,13 +126,14 @@ def weights_of(ncat, kind="equal"):
     return np.array([0.1, 0.2, 0.3, 0.4])
 
 
-def make_case(dim, ncols, tree, ncat, derivs=True, weights="equal"):
+def make_case(dim, ncols, tree, ncat, derivs=True, weights="equal", plain_want=True):
     """Category 0 is treelik_ref.make_case's case itself (rows, pi, its matrices); the further categories have matrices of their own,
-    drawn the same way.  With ncat == 1 the inputs are exactly those of treelik_ref.make_case."""
+    drawn the same way.  With ncat == 1 the inputs are exactly those of treelik_ref.make_case.  plain_want=False: that case's own
+    expectation is not computed (a large tree)."""
     key = (dim, ncols, tree, ncat, derivs, weights)
     if key in _cases:
         return _cases[key]
-    base = R.make_case(dim, ncols, tree, derivs)
+    base = R.make_case(dim, ncols, tree, derivs, want=plain_want)
     nedges = len(base["parent"]) - 1
     rng = np.random.default_rng(77 + 1000 * dim + 7 * ncols + 13 * ncat + sum(map(ord, tree)))
     parts = [base["P"]]

@@ -185,6 +185,32 @@ def trifurcating(n):
     return np.array(parent, np.uint32)
 
 
+def inner_trifurcation():
+    """Six leaves: node 6 = (0, 1, 2), 7 = (6, 3), 8 = (7, 4), the root 9 = (8, 5): a non-root inner node with three children."""
+    return 6, np.array([6, 6, 6, 7, 8, 9, 7, 8, 9, ROOT], np.uint32)
+
+
+def inner_quadrifurcation():
+    """Seven leaves: 7 = (0, 1), 8 = (2, 3), 9 = (4, 5, 7, 8), the root 10 = (6, 9): a non-root inner node with four children, two of
+    them inner, under a binary root."""
+    return 7, np.array([7, 7, 8, 8, 9, 9, 10, 9, 9, 10, ROOT], np.uint32)
+
+
+def four_leaves_beside_a_cherry():
+    """Six leaves: 6 = (0, 1, 2, 3), 7 = (4, 5), the root 8 = (6, 7): a non-root inner node whose four children are all leaves."""
+    return 6, np.array([6, 6, 6, 6, 7, 7, 8, 8, ROOT], np.uint32)
+
+
+def star(n):
+    """A root with n leaf children and no other inner node."""
+    return n, np.array([n] * n + [ROOT], np.uint32)
+
+
+def mixed_root():
+    """Six leaves: 6 = (0, 1, 2), 7 = (3, 4), the root 8 = (5, 6, 7): a root with a leaf, a trifurcation and a cherry below it."""
+    return 6, np.array([6, 6, 6, 7, 7, 8, 8, 8, ROOT], np.uint32)
+
+
 def from_newick(text):
     """The numbering of ml_tree_topology: the leaves in sorted-name order, the inner nodes in post-order, the root last.
     Returns (names, parent, lengths per edge)."""
@@ -301,17 +327,25 @@ TREES = {
     "balanced24": lambda: (24, balanced(24)),
     "trifurcating": lambda: (7, trifurcating(7)),
     "caterpillar96": lambda: (96, caterpillar(96)),
+    # polytomies below the root, and roots of other arities (tests/test_cpu_treelik_shapes.py)
+    "inner3": inner_trifurcation,
+    "inner4": inner_quadrifurcation,
+    "leaves4": four_leaves_beside_a_cherry,
+    "star5": lambda: star(5),
+    "mixed3": mixed_root,
+    "balanced32770": lambda: (32770, balanced(32770)),   # 65538 edges: more than the second grid dimension holds
 }
 _cases = {}
 
 
-def make_case(dim, ncols, tree, derivs=True):
-    """One seeded case and its expectation (computed once per process): a dict with nleaves, parent, rows, pi, P and `want`.
+def make_case(dim, ncols, tree, derivs=True, want=True):
+    """One seeded case and its expectation (computed once per process): a dict with nleaves, parent, rows, pi, P and `want`
+    (None when not asked for: the inputs alone, for a caller with an expectation of its own).
     P: row-stochastic matrices of entries above 0.01 / dim, P' and P'' signed; for the caterpillar every entry of all three in
     [0.03, 0.07].  Columns from 15 sites on: site 3 is all gaps, sites 5 and 6 hold -2 entries; from 3 leaves on leaf 1 is all gaps
     in half of the trees' cases (by dim); 4 % of the other entries are gaps.  The caterpillar keeps its even sites free of gaps."""
     key = (dim, ncols, tree, derivs)
-    if key in _cases:
+    if key in _cases and (_cases[key]["want"] is not None or not want):
         return _cases[key]
     nleaves, parent = TREES[tree]()
     nedges = len(parent) - 1
@@ -339,7 +373,7 @@ def make_case(dim, ncols, tree, derivs=True):
         rows[1, :] = -1
     P = pack(X)
     case = dict(dim=dim, nleaves=nleaves, parent=parent, rows=rows, pi=pi, P=P, derivs=derivs, tree=tree,
-                want=evaluate(dim, nleaves, parent, rows, pi, P, derivs))
+                want=evaluate(dim, nleaves, parent, rows, pi, P, derivs) if want else None)
     _cases[key] = case
     return case
 
