@@ -593,6 +593,21 @@ int pgm_tree_nni(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, 
                  uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c /* ncand each */,
                  double *site_l /* ncols */, int32_t *site_k /* ncols */, double *post /* ncat x ncols */, double *rho /* ncand x ncols */);
 
+/* The sums of every row of a matrix over nrep resamplings of its columns (`pgmsa --ml_tree --ml_support`): with
+ * x = log rho of pgm_tree_nni, the resampled log-likelihood gain of every neighbour of the tree in every bootstrap replicate.
+ *   out[q * nrep + r] = sum over k of x[q * ncols + cols[r * ncols + k]], k ascending from 0.0
+ * Every step is one IEEE fp64 addition: no multiplication, no contraction, no pairwise or tree order.  The values therefore do not
+ * depend on the launch and equal the host statement's (resampled_sums_host) bit for bit.  Entries of -infinity are allowed and
+ * propagate (-infinity + finite = -infinity).  The caller must pass neither a NaN nor +infinity: this is NOT checked.  cols is laid out
+ * as pgm_prealigned_counts_resampled reads it.  out is overwritten.
+ * Device memory: 8 * nrow * ncols bytes for x and 8 * ceil(nrow / 64) * 64 * ncols for its transpose, 4 * nrep * ncols for cols and
+ * 8 * nrow * nrep for out.  Memory that cannot be had is PGM_ERR_NOMEM.
+ * PGM_ERR_INVALID, before anything is launched or out is touched: a null pointer, nrow, ncols or nrep == 0, nrow * nrep or
+ * nrep * ncols beyond 32 bits, a cols entry >= ncols. */
+int pgm_resampled_sums(pgm_ctx *ctx, uint32_t nrow, uint32_t ncols, const double *x /* nrow x ncols, row-major */, uint32_t nrep,
+                       const uint32_t *cols /* nrep x ncols */, double *out /* nrow x nrep */);
+float pgm_resample_last_kernel_ms(pgm_ctx *ctx);   /* device time of the two kernels of the last pgm_resampled_sums call */
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,6 +94,7 @@ EXPORTS = [
     "pgm_msa_agreement", "pgm_agreement_last_kernel_ms",
     "pgm_transfer_min", "pgm_transfer_last_kernel_ms", "pgm_transfer_taxa",
     "pgm_tree_likelihood", "pgm_treelik_last_kernel_ms", "pgm_tree_likelihood_rates", "pgm_tree_ancestral", "pgm_tree_nni",
+    "pgm_resampled_sums", "pgm_resample_last_kernel_ms",
 ]
 
 
@@ -187,6 +188,8 @@ def _load():
         "pgm_tree_nni": (C.c_int, [vp, u32, u32, u32, C.POINTER(u32), u32, C.POINTER(C.c_int8), C.POINTER(C.c_double), u32, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(i32),
                                    C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "pgm_resampled_sums": (C.c_int, [vp, u32, u32, C.POINTER(C.c_double), u32, C.POINTER(u32), C.POINTER(C.c_double)]),
+        "pgm_resample_last_kernel_ms": (C.c_float, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # AttributeError here = the library does not export a declared symbol
@@ -385,6 +388,22 @@ class Context:
                                P_(P, C.c_double), ncand, P_(cv, C.c_uint32), P_(ca, C.c_uint32), P_(cc, C.c_uint32), P_(out[0], C.c_double), P_(out[1], C.c_int32),
                                P_(out[2], C.c_double), P_(out[3], C.c_double)), "pgm_tree_nni")
         return tuple(out)
+
+    def resampled_sums(self, x, cols, out=None):
+        """pgm_resampled_sums: x nrow x ncols float64 (no NaN, no +inf), cols nrep x ncols uint32 -> out (nrow x nrep float64),
+        out[q, r] = the sum over k ascending of x[q, cols[r, k]].  A given output array (C-contiguous of that kind) is overwritten."""
+        import numpy as np
+        x = np.ascontiguousarray(x, np.float64)
+        cols = np.ascontiguousarray(cols, np.uint32)
+        if x.ndim != 2 or cols.ndim != 2 or cols.shape[1] != x.shape[1]:
+            raise ValueError("resampled_sums: input array of the wrong shape")
+        (nrow, ncols), nrep = x.shape, cols.shape[0]
+        if out is None: out = np.zeros((nrow, nrep), np.float64)
+        if out.dtype != np.float64 or out.shape != (nrow, nrep) or not out.flags.c_contiguous:
+            raise ValueError("resampled_sums: output array of the wrong kind")
+        P_ = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+        check(lib.pgm_resampled_sums(self.handle, nrow, ncols, P_(x, C.c_double), nrep, P_(cols, C.c_uint32), P_(out, C.c_double)), "pgm_resampled_sums")
+        return out
 
     def close(self):
         if self.handle:

@@ -32,6 +32,7 @@
 #include "pgm_agreement_kernels.h"
 #include "pgm_transfer_kernels.h"
 #include "pgm_treelik_kernels.h"
+#include "pgm_resample_kernels.h"
 #include "pgm_pool.h"
 #include "pgm_plan.h"
 static_assert(kC3Bytes == PGM_C3_BYTES, "pgm_plan.h plans the LDS of a crit3 sweep with PGM_C3_BYTES");
@@ -71,6 +72,7 @@ struct pgm_ctx {
     float agree_ms = 0;                     // --guidance agreement counts: device time of the last call
     float transfer_ms = 0;                  // --bootstrap_tbe / --bootstrap_taxa transfer entries: device time of the last call
     float treelik_ms = 0;                   // --ml_tree likelihood evaluations and --ml_ancestral: device time of the last call
+    float resample_ms = 0;                  // --ml_support sums over resampled columns: device time of the last call
     uint32_t bionj_launches = 0;            // BioNJ: device time and kernels of the last call
     // grow-only scratch buffers of the satellite calls (StageCall): a guide-tree stage issues many calls, hipMalloc / hipFree of
     // up to 2 GB per call would dominate them.  The calls of one context are serial; a slot belongs to the stage named beside it
@@ -100,6 +102,10 @@ struct pgm_ctx {
         SC_TREELIK_U,                       //   partials and outside vectors (ancestral: the categories' posteriors in their place)
         SC_TREELIK_G,                       //   per-site ratios and chunk sums (rates: the categories' site values and ratios first)
         SC_TREELIK_OUT,                     //   the outputs
+        SC_RESAMPLE_X,                      // sums over resampled columns: x as it arrives
+        SC_RESAMPLE_XT,                     //   x transposed, rows padded to the q-tile
+        SC_RESAMPLE_COLS,                   //   the replicates' columns
+        SC_RESAMPLE_OUT,                    //   the sums
         SC_DEV
     };
     enum {
@@ -1065,3 +1071,4 @@ int pgm_align_batch_read_matrices(pgm_ctx *ctx, pgm_align_batch *b, uint32_t job
 #include "pgm_treelik_rates_capi.inc"
 #include "pgm_treelik_anc_capi.inc"
 #include "pgm_treelik_nni_capi.inc"
+#include "pgm_resample_capi.inc"

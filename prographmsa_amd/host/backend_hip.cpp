@@ -176,6 +176,12 @@ struct HipBackend : Backend {
         if (rc != PGM_OK) error("pgm_tree_nni failed (%d): %s", rc, pgm_last_error());
         ml_search_stats.kernel_ms += pgm_treelik_last_kernel_ms(c);
     }
+    void resampled_sums(uint32_t nrow, uint32_t ncols, const double *x, uint32_t nrep, const uint32_t *cols, double *out, int worker) override {
+        pgm_ctx *c = ctx_of(worker);
+        int rc = pgm_resampled_sums(c, nrow, ncols, x, nrep, cols, out);
+        if (rc != PGM_OK) error("pgm_resampled_sums failed (%d): %s", rc, pgm_last_error());
+        ml_support_stats.kernel_ms += pgm_resample_last_kernel_ms(c);
+    }
     bool bionj_multi(uint32_t nfam, const uint32_t *n, const double *D, const double *V, pgm_bionj_join *joins, double *final_d, int worker) override {
         pgm_ctx *c = ctx_of(worker);
         int rc = pgm_bionj_multi(c, nfam, n, D, V, joins, final_d);

@@ -607,13 +607,6 @@ void TreeNJ_multi(const Alphabet &a, std::vector<TreeJob> &jobs, bool prealigned
 // ==== --bootstrap: the trees of resampled columns of one alignment =====================================================
 BootstrapStats bootstrap_stats;
 
-uint64_t splitmix64(uint64_t &state) {
-    uint64_t z = (state += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 bool Backend::prealigned_counts_resampled(uint32_t dim, uint32_t nrows, uint32_t ncols, const int8_t *rows, uint32_t nrep, const uint32_t *cols,
                                           uint32_t npairs, const uint32_t *pi, const uint32_t *pj, int32_t *counts, uint32_t *gaps, int worker) {
     std::vector<int8_t> gathered((size_t)nrows * ncols);
@@ -643,9 +636,7 @@ std::vector<PhyTree *> bootstrap_trees(const Alphabet &a, const std::map<std::st
     Backend &be = default_backend();
     std::vector<int8_t> mat((size_t)n * ncols);
     parallel_for(n, [&](size_t i) { prealigned_row(a, *seq[i], mat.data() + i * ncols); });
-    std::vector<uint32_t> cols((size_t)nrep * ncols);
-    uint64_t state = seed;
-    for (size_t k = 0; k < cols.size(); ++k) cols[k] = (uint32_t)(splitmix64(state) % ncols);
+    const std::vector<uint32_t> cols = bootstrap_columns(nrep, ncols, seed);
     std::vector<uint32_t> pi, pj;
     for (uint32_t i = 0; i < n; ++i)
         for (uint32_t j = i + 1; j < n; ++j) { pi.push_back(i); pj.push_back(j); }

@@ -148,6 +148,40 @@ static void write_ml_ancestral(const Alphabet &a, const MlTreeOpts &mo, const Fa
     }
 }
 
+// --ml_support: ml_branch_support on the tree the run ends with, at the estimated lengths (and rates), by the same
+// route; the tree with %.6f of sh_hits / N as the label of every supported node, and --ml_support_table: a line per supported node
+static void write_ml_support(const Alphabet &a, const MlTreeOpts &mo, const Family &fam, const PhyTree &ml, const std::vector<std::vector<int8_t>> &values,
+                             const MlTreeResult &res, Backend *be) {
+    const MlTreeTopology topo = ml_tree_topology(ml);
+    const uint32_t dim = (uint32_t)a.DIM, nleaves = topo.nleaves, nnodes = topo.nnodes, ncols = (uint32_t)values[0].size(), nrep = (uint32_t)mo.support_reps;
+    std::vector<int8_t> flat((size_t)nleaves * ncols);
+    for (uint32_t r = 0; r < nleaves; ++r) std::copy(values[r].begin(), values[r].end(), flat.begin() + (size_t)r * ncols);
+    const uint32_t ncat = res.rates.empty() ? 1u : (uint32_t)res.rates.size();
+    const std::vector<double> w(ncat, res.rates.empty() ? 1.0 : 1.0 / (double)ncat);
+    std::vector<double> P;
+    if (res.rates.empty()) treelik_matrices(*fam.model_factory, res.lengths, false, P);
+    else treelik_matrices(*fam.model_factory, res.lengths, false, res.rates, P);
+    const std::vector<uint32_t> cols = bootstrap_columns(nrep, ncols, mo.support_seed);
+    const std::vector<MlSupportNode> nodes = ml_branch_support(dim, nleaves, nnodes, topo.parent.data(), ncols, flat.data(), fam.model_factory->freqs().data(), ncat, w.data(),
+                                                               P.data(), nrep, cols.data(), be);
+    std::map<const PhyTree *, std::string> labels;
+    char buf[160];
+    for (const MlSupportNode &s : nodes) {
+        snprintf(buf, sizeof buf, "%.6f", (double)s.sh_hits / (double)nrep);
+        labels[topo.node[s.node]] = buf;
+    }
+    open_output(mo.support, "ml support output") << ml.formatNewick(labels) << std::endl;
+    if (mo.support_table_given) {
+        std::ofstream table = open_output(mo.support_table, "ml support output");
+        snprintf(buf, sizeof buf, "replicates\t%u\nseed\t%llu\n", nrep, (unsigned long long)mo.support_seed);
+        table << buf;
+        for (const MlSupportNode &s : nodes) {
+            snprintf(buf, sizeof buf, "N%u\t%u\t%.17g\t%u\t%u\n", s.node - nleaves + 1, s.candidates, s.alrt, s.sh_hits, s.rell_hits);
+            table << buf;
+        }
+    }
+}
+
 void doMlTree(const Alphabet &a, const DriverOptions &o, const Family &fam, const std::map<std::string, sequence_t> &alignment) {
     const std::map<std::string, sequence_t> rows = sequence_rows(alignment);
     const MlTreeOpts &mo = o.mltree;
@@ -222,6 +256,7 @@ void doMlTree(const Alphabet &a, const DriverOptions &o, const Family &fam, cons
         }
     }
     if (mo.anc_given) write_ml_ancestral(a, mo, fam, *ml, values, res, be);
+    if (mo.support_given) write_ml_support(a, mo, fam, *ml, values, res, be);
 }
 // --guidance (Penn et al. 2010, GUIDANCE: the guide tree as the source of alignment uncertainty): the final alignment's columns are
 // resampled N times as --bootstrap resamples them, every replicate's BioNJ tree, midpoint rooted and written with exact branch

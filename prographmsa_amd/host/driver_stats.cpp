@@ -54,6 +54,9 @@ void print_stats(const DriverOptions &o, double t_init, double t_tree, double t_
         fprintf(stderr, ", \"ml_search_s\": %.6f, \"ml_search_rounds\": %llu, \"ml_nni_applied\": %llu, \"ml_nni_calls\": %llu, \"ml_nni_kernel_ms\": %.3f",
                 ml_search_stats.seconds, (unsigned long long)ml_search_stats.rounds, (unsigned long long)ml_search_stats.applied,
                 (unsigned long long)ml_search_stats.calls, ml_search_stats.kernel_ms);
+    if (o.mltree.support_given)   // (keys of --ml_support only)
+        fprintf(stderr, ", \"ml_support_s\": %.6f, \"ml_support_nodes\": %llu, \"ml_support_calls\": %llu, \"ml_support_kernel_ms\": %.3f", ml_support_stats.seconds,
+                (unsigned long long)ml_support_stats.nodes, (unsigned long long)ml_support_stats.calls, ml_support_stats.kernel_ms);
     if (batch)   // (keys of --batch only)
         fprintf(stderr, ", \"batch_families\": %d, \"batch_failed\": %d, \"batch_chunks\": %d, \"batch_passes\": %llu, \"batch_levels\": %llu, "
                         "\"batch_align_calls\": %llu, \"batch_dist_calls\": %llu",

@@ -245,6 +245,7 @@ int main(int argc, char **argv) {
         if (o.bootstrap.given && fam.seqs.size() < 4) error("--bootstrap needs at least 4 sequences");
         if (o.guidance.given && fam.seqs.size() < 4) error("--guidance needs at least 4 sequences");
         if (o.mltree.tree_given && fam.seqs.size() < 3) error("--ml_tree needs at least 3 sequences");
+        if (o.mltree.support_given && fam.seqs.size() < 4) error("--ml_support needs at least 4 sequences");
         if (o.mltree.tree_given && o.mltree.start_given) {   // (--ml_start is read as -t reads a tree, and refused before any work or file)
             std::ifstream ts(o.mltree.start.c_str());
             if (!ts) error("cannot open the --ml_start tree file %s", o.mltree.start.c_str());

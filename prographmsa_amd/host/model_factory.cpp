@@ -340,3 +340,4 @@ Model ModelFactory::getModel(distance_t distance, distance_t gap_distance) const
 #include "treelik_rates.inc"
 #include "treelik_anc.inc"
 #include "treelik_nni.inc"
+#include "treelik_support.inc"

@@ -356,6 +356,9 @@ struct Backend {
     virtual void tree_nni(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
                           const double *w, const double *P, uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c, double *site_l,
                           int32_t *site_k, double *post, double *rho, int worker = 0);
+    // The sums of every row of x over nrep resamplings of its columns (--ml_support; include/pgm_hip.h: pgm_resampled_sums).  The
+    // default is the host statement, resampled_sums_host: the same bits.
+    virtual void resampled_sums(uint32_t nrow, uint32_t ncols, const double *x, uint32_t nrep, const uint32_t *cols, double *out, int worker = 0);
     // calls the host code made of the align-batch entry and of the distance entries (all-pairs tiles, pair counts, cosine, ML
     // distances): `pgmsa --batch --stats` shows with them that a stage was shared by the families of a chunk
     std::atomic<uint64_t> calls_align{0}, calls_dist{0};
@@ -663,7 +666,19 @@ void TreeNJ_multi(const Alphabet &a, std::vector<TreeJob> &jobs, bool prealigned
 // in order, from one stream seeded with `seed`.  The pair counts of every replicate come from Backend::prealigned_counts_resampled,
 // in groups of replicates whose counts stay within kBootstrapCountBytes per call; the estimator and the joins are those of TreeNJ
 // (prealigned == true) without -W and without rooting.  The caller owns the trees.
-uint64_t splitmix64(uint64_t &state);
+// bootstrap_columns: those columns, nrep x ncols: what bootstrap_trees and --ml_support both draw.
+inline uint64_t splitmix64(uint64_t &state) {
+    uint64_t z = (state += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+inline std::vector<uint32_t> bootstrap_columns(uint32_t nrep, uint32_t ncols, uint64_t seed) {
+    std::vector<uint32_t> cols((size_t)nrep * ncols);
+    uint64_t state = seed;
+    for (size_t k = 0; k < cols.size(); ++k) cols[k] = (uint32_t)(splitmix64(state) % ncols);
+    return cols;
+}
 const size_t kBootstrapCountBytes = (size_t)1 << 30;   // count output of one prealigned_counts_resampled call
 struct BootstrapStats {   // `pgmsa --bootstrap --stats`
     int replicates = 0;
@@ -844,6 +859,34 @@ struct MlSearchResult {
 };
 MlSearchResult ml_topology_search(const Alphabet &a, const std::vector<std::vector<int8_t>> &rows, const ModelFactory &model_factory, const PhyTree &start,
                                   uint32_t search_rounds, uint32_t rounds, double eps, Backend *be = nullptr, const MlGamma &gamma = MlGamma());
+// --ml_support (host/treelik_support.inc):
+// resampled_sums_host: pgm_resampled_sums by a loop over rows x chunks of replicates on the host threads, the same contract and the
+//   same bits; what it rejects is an error().  Backend::resampled_sums's default.
+// ml_support_candidates: the supported nodes (every inner node v below the root whose parent is not a root of exactly two children),
+//   ascending, and their candidates (v, a, c), a in child order, then c in child order: the other resolutions around the edge above v.
+// ml_branch_support: one tree_nni call over those candidates, x = log rho, the observed gains (treelik_nni_gain), the resampled gains
+//   D[q][r] by resampled_sums in groups of rows whose x stays within x_bytes, and per node with the candidates C whose gain is not
+//   -infinity: d_obs = -max gain, alrt = 2 d_obs, sh_hits = the replicates whose largest of {0, D[q][r] - mean_q} is less than d_obs
+//   ahead of the second largest (0 when d_obs <= 0), rell_hits = the replicates with D[q][r] <= 0 for every q of C; C empty:
+//   alrt = +infinity and both counts nrep.  be: the backend whose tree_nni and resampled_sums run, nullptr for the host loops.
+const size_t kSupportBytes = (size_t)1 << 30;   // x of one resampled_sums call
+struct MlSupportStats {   // `pgmsa --ml_tree --ml_support --stats`
+    double seconds = 0, kernel_ms = 0;
+    uint64_t nodes = 0, calls = 0;   // supported nodes, resampled_sums calls
+};
+extern MlSupportStats ml_support_stats;
+struct MlSupportNode {
+    uint32_t node = 0, candidates = 0;   // the node's number, the candidates around the edge above it
+    double alrt = 0;
+    uint32_t sh_hits = 0, rell_hits = 0;
+};
+void resampled_sums_host(uint32_t nrow, uint32_t ncols, const double *x /* nrow x ncols */, uint32_t nrep, const uint32_t *cols /* nrep x ncols */,
+                         double *out /* nrow x nrep */);
+void ml_support_candidates(uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, std::vector<uint32_t> &node, std::vector<uint32_t> &cand_v,
+                           std::vector<uint32_t> &cand_a, std::vector<uint32_t> &cand_c);
+std::vector<MlSupportNode> ml_branch_support(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
+                                             uint32_t ncat, const double *w, const double *P /* ncat x (nnodes-1) x dim x dim */, uint32_t nrep,
+                                             const uint32_t *cols /* nrep x ncols */, Backend *be = nullptr, size_t x_bytes = kSupportBytes);
 // a copy of `tree` whose edge above topo.node[e] has length lengths[e]
 PhyTree *ml_tree_with_lengths(const MlTreeTopology &topo, const std::vector<double> &lengths);
 
