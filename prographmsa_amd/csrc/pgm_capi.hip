@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <numeric>
+#include <optional>
 #include <mutex>
 #include <string>
 #include <unordered_set>
@@ -35,6 +36,8 @@
 #include "pgm_resample_kernels.h"
 #include "pgm_pool.h"
 #include "pgm_plan.h"
+#include "pgm_treelik_check.h"
+#include "pgm_treelik_plan.h"
 static_assert(kC3Bytes == PGM_C3_BYTES, "pgm_plan.h plans the LDS of a crit3 sweep with PGM_C3_BYTES");
 
 static thread_local std::string g_err;
@@ -97,7 +100,7 @@ struct pgm_ctx {
         SC_TRANSFER_REF,                    // pgm_transfer_min and pgm_transfer_taxa (shared): reference sets, rep_off, thresholds
         SC_TRANSFER_REP,                    //   replicate sets
         SC_TRANSFER_OUT,                    //   phi (taxa: phi, arg, flip, moved, counted)
-        SC_TREELIK_TREE,                    // tree likelihood, ancestral states and NNI scores, all four entries (shared): children lists, pi, weights, rows
+        SC_TREELIK_TREE,                    // tree likelihood, ancestral states and NNI scores, all four entries (shared; pgm_treelik_plan.h has the layouts): children lists, pi, weights, rows
         SC_TREELIK_P,                       //   the matrices
         SC_TREELIK_U,                       //   partials and outside vectors (ancestral: the categories' posteriors in their place)
         SC_TREELIK_G,                       //   per-site ratios and chunk sums (rates: the categories' site values and ratios first)
@@ -1068,7 +1071,4 @@ int pgm_align_batch_read_matrices(pgm_ctx *ctx, pgm_align_batch *b, uint32_t job
 #include "pgm_transfer_capi.inc"
 #include "pgm_transfer_taxa_capi.inc"
 #include "pgm_treelik_capi.inc"
-#include "pgm_treelik_rates_capi.inc"
-#include "pgm_treelik_anc_capi.inc"
-#include "pgm_treelik_nni_capi.inc"
 #include "pgm_resample_capi.inc"

@@ -1,88 +1,173 @@
-// pgm_treelik_capi.inc — C ABI of the tree likelihood of pgmsa --ml_tree (included by pgm_capi.hip).
-// The arguments are checked on the host and the children lists are built there, then: one upload of the tree, the rows, pi and the
-// matrices, one launch of pgm_treelik_kernel (a workgroup per block of sites walks the whole tree), with derivs one launch of
-// pgm_treelik_sums_kernel, one copy back.  Stateless: nothing of a call is read by the next.
+// pgm_treelik_capi.inc — C ABI of the tree likelihood and what is built on it (included by pgm_capi.hip): pgm_tree_likelihood
+// (pgmsa --ml_tree, DESIGN.md 3.17), pgm_tree_likelihood_rates (--ml_gamma, 3.18), pgm_tree_ancestral (--ml_ancestral, 3.19) and
+// pgm_tree_nni (--ml_search, 3.20).  The arguments are checked on the host and the children lists are built there
+// (pgm_treelik_check.h), then: one upload of the inputs, the launches, one copy back.  The four entries share five scratch slots,
+// laid out by pgm_treelik_plan.h.  Stateless: nothing of a call is read by the next.
 extern "C" float pgm_treelik_last_kernel_ms(pgm_ctx *ctx) { return ctx ? ctx->treelik_ms : 0.0f; }
 
-// The checks both entries share past their pointers, and the children of every node in ascending order: `tree` gets child_off
-// (nnodes + 1), then child (nnodes - 1).
-static int treelik_tree(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, std::vector<uint32_t> &tree) {
-    const std::string w = "tree likelihood: ";
-    if (dim < 1 || dim > 64) return fail(PGM_ERR_INVALID, w + "dim must be 1 .. 64");
-    if (nleaves < 2 || ncols == 0 || nnodes <= nleaves) return fail(PGM_ERR_INVALID, w + "nleaves must be at least 2, ncols at least 1 and nnodes above nleaves");
-    tree.assign((size_t)nnodes + 1, 0);
-    uint32_t roots = 0;
-    for (uint32_t v = 0; v < nnodes; ++v) {
-        if (parent[v] == UINT32_MAX) { ++roots; continue; }
-        if (parent[v] <= v || parent[v] >= nnodes) return fail(PGM_ERR_INVALID, w + "the parent of node " + std::to_string(v) + " is not above it");
-        if (parent[v] < nleaves) return fail(PGM_ERR_INVALID, w + "leaf " + std::to_string(parent[v]) + " is a parent");
-        ++tree[parent[v] + 1];
-    }
-    if (roots != 1) return fail(PGM_ERR_INVALID, w + std::to_string(roots) + " roots");
-    for (uint32_t v = nleaves; v < nnodes; ++v)
-        if (tree[v + 1] < 2) return fail(PGM_ERR_INVALID, w + "inner node " + std::to_string(v) + " has fewer than 2 children");
-    for (uint32_t v = 0; v < nnodes; ++v) tree[v + 1] += tree[v];
-    const uint32_t nedges = nnodes - 1;   // (every node but the root is a child: tree[nnodes] == nedges)
-    tree.resize((size_t)nnodes + 1 + nedges);
-    {
-        std::vector<uint32_t> fill(tree.begin(), tree.begin() + nnodes);
-        for (uint32_t v = 0; v < nnodes; ++v)
-            if (parent[v] != UINT32_MAX) tree[(size_t)nnodes + 1 + fill[parent[v]]++] = v;
-    }
-    const size_t nrow = (size_t)nleaves * ncols;
-    for (size_t k = 0; k < nrow; ++k)
-        if (rows[k] < -2 || rows[k] >= (int)dim) return fail(PGM_ERR_INVALID, w + "row value " + std::to_string((int)rows[k]) + " outside -2 .. dim - 1");
-    return PGM_OK;
-}
+// What every entry does past its own null checks: the shared refusals (ncat and the weights, the tree, the candidates), the slots,
+// the upload of the inputs, and the arguments of the walk (a, st) and of pgm_treelik_combine_kernel (m) from the plan.
+struct TreelikIn {
+    uint32_t dim, nleaves, nnodes; const uint32_t *parent; uint32_t ncols; const int8_t *rows; const double *pi;
+    uint32_t ncat; const double *w, *P; int derivs;   // (ncat, w: all but the plain entry)
+    uint32_t ncand; const uint32_t *cand_v, *cand_a, *cand_c; bool full;
+};
+static_assert(pgm_ctx::SC_TREELIK_OUT - pgm_ctx::SC_TREELIK_TREE == PGM_TL_SLOT_OUT, "the five slots in the order of pgm_treelik_plan.h");
+struct TreelikCall {
+    std::optional<StageCall> c;   // (opened once nothing is refused any more)
+    PgmTreelikPlan pl;
+    uint8_t *slot[PGM_TL_NSLOTS] = {};
+    PgmTreelikArgs a;
+    PgmTreelikRatesStride st;
+    PgmTreelikCombineArgs m;
+    uint32_t blocks, cblocks;     // of the walk (sites / spb) and of the combine kernel (sites / 64)
+    template <class T> T *at(int region) const { return pl.r[region].bytes ? (T *)(slot[pl.r[region].slot] + pl.r[region].off) : nullptr; }
 
+    int open(pgm_ctx *ctx, const char *what, int mode, const TreelikIn &in) {
+        std::string bad = mode != PGM_TREELIK_CALL_PLAIN ? pgm_treelik_check_rates(in.ncat, in.w) : std::string();
+        std::vector<uint32_t> tree;   // child_off, then child
+        if (bad.empty()) bad = pgm_treelik_check_tree(in.dim, in.nleaves, in.nnodes, in.parent, in.ncols, in.rows, tree);
+        if (bad.empty() && mode == PGM_TREELIK_CALL_NNI) bad = pgm_treelik_check_candidates(in.nleaves, in.nnodes, in.parent, in.ncand, in.cand_v, in.cand_a, in.cand_c);
+        if (!bad.empty()) return fail(PGM_ERR_INVALID, bad);
+        pl = pgm_treelik_plan(mode, in.dim, in.nleaves, in.nnodes, in.ncols, in.ncat, in.derivs != 0, in.ncand, in.full);
+        c.emplace(ctx, what, &ctx->treelik_ms);
+        for (int k = 0; k < PGM_TL_NSLOTS; ++k)
+            if (pl.slot_bytes[k]) c->buf(pgm_ctx::SC_TREELIK_TREE + k, pl.slot_bytes[k], &slot[k]);
+        c->up(at<void>(PGM_TL_CHILD), tree.data(), pl.r[PGM_TL_CHILD].bytes);
+        c->up(at<void>(PGM_TL_PI), in.pi, pl.r[PGM_TL_PI].bytes);
+        c->up(at<void>(PGM_TL_W), in.w, pl.r[PGM_TL_W].bytes);
+        c->up(at<void>(PGM_TL_PARENT), in.parent, pl.r[PGM_TL_PARENT].bytes);
+        if (pl.r[PGM_TL_CAND].bytes) {
+            c->up(at<uint32_t>(PGM_TL_CAND), in.cand_v, 4 * (size_t)in.ncand);
+            c->up(at<uint32_t>(PGM_TL_CAND) + in.ncand, in.cand_a, 4 * (size_t)in.ncand);
+            c->up(at<uint32_t>(PGM_TL_CAND) + 2 * (size_t)in.ncand, in.cand_c, 4 * (size_t)in.ncand);
+        }
+        c->up(at<void>(PGM_TL_ROWS), in.rows, pl.r[PGM_TL_ROWS].bytes);
+        c->up(at<void>(PGM_TL_P), in.P, pl.r[PGM_TL_P].bytes);
+
+        const bool cats = mode != PGM_TREELIK_CALL_PLAIN;   // the walk writes the categories' values; the combine kernel the outputs
+        a.dim = in.dim; a.nleaves = in.nleaves; a.nnodes = in.nnodes; a.ncols = in.ncols; a.spb = PGM_TREELIK_THREADS / in.dim; a.derivs = in.derivs ? 1 : 0;
+        a.child_off = at<const uint32_t>(PGM_TL_CHILD); a.child = a.child_off + in.nnodes + 1;
+        a.pi = at<const double>(PGM_TL_PI); a.rows = at<const int8_t>(PGM_TL_ROWS); a.P = at<const double>(PGM_TL_P);
+        a.U = at<double>(PGM_TL_U); a.O = at<double>(PGM_TL_O);
+        a.g = at<double>(cats ? PGM_TL_GC : PGM_TL_G); a.h = at<double>(cats ? PGM_TL_QC : PGM_TL_H);
+        a.site_l = at<double>(cats ? PGM_TL_CL : PGM_TL_SITE_L); a.site_k = at<int32_t>(cats ? PGM_TL_CK : PGM_TL_SITE_K);
+        st = {pl.p_count, pl.u_count, pl.g_count, (size_t)in.ncols};
+        m.ncat = in.ncat; m.ncols = in.ncols; m.nedges = in.derivs ? pl.nedges : 0;
+        m.w = at<const double>(PGM_TL_W); m.L = a.site_l; m.k = a.site_k; m.gc = a.g; m.qc = a.h;
+        m.site_l = at<double>(PGM_TL_SITE_L); m.site_k = at<int32_t>(PGM_TL_SITE_K); m.post = at<double>(PGM_TL_POST);
+        m.g = at<double>(PGM_TL_G); m.h = at<double>(PGM_TL_H);
+        blocks = (uint32_t)(((uint64_t)in.ncols + a.spb - 1) / a.spb);
+        cblocks = (uint32_t)(((uint64_t)in.ncols + PGM_TREELIK_THREADS - 1) / PGM_TREELIK_THREADS);
+        return PGM_OK;
+    }
+    // with derivs: the sums of the per-site ratios into D1 and D2
+    void launch_sums() {
+        hipLaunchKernelGGL(pgm_treelik_sums_kernel, dim3(pl.nedges), dim3(PGM_TREELIK_THREADS), 0, c->s, at<const double>(PGM_TL_G), at<const double>(PGM_TL_H), a.ncols,
+                           (uint32_t)pl.nchunks, at<double>(PGM_TL_PART), at<double>(PGM_TL_D1), at<double>(PGM_TL_D2));
+    }
+    // the outputs every entry has (post, d1, d2: where the call has them)
+    void down(double *site_l, int32_t *site_k, double *post, double *d1, double *d2) {
+        c->down(site_l, at<void>(PGM_TL_SITE_L), pl.r[PGM_TL_SITE_L].bytes);
+        c->down(site_k, at<void>(PGM_TL_SITE_K), pl.r[PGM_TL_SITE_K].bytes);
+        c->down(post, at<void>(PGM_TL_POST), pl.r[PGM_TL_POST].bytes);
+        c->down(d1, at<void>(PGM_TL_D1), pl.r[PGM_TL_D1].bytes);
+        c->down(d2, at<void>(PGM_TL_D2), pl.r[PGM_TL_D2].bytes);
+    }
+};
+
+// One launch of pgm_treelik_kernel (a workgroup per block of sites walks the whole tree), with derivs one of pgm_treelik_sums_kernel.
 extern "C" int pgm_tree_likelihood(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
                                    const double *pi, const double *P, int derivs, double *site_l, int32_t *site_k, double *d1, double *d2) {
     if (!ctx) return fail(PGM_ERR_INVALID, "null argument");
     ctx->treelik_ms = 0;
     if (!parent || !rows || !pi || !P || !site_l || !site_k || (derivs && (!d1 || !d2))) return fail(PGM_ERR_INVALID, "null argument");
-    std::vector<uint32_t> tree;   // child_off, then child
-    if (const int rc = treelik_tree(dim, nleaves, nnodes, parent, ncols, rows, tree)) return rc;
-    const uint32_t nedges = nnodes - 1, ninner = nnodes - nleaves;
-    const size_t nrow = (size_t)nleaves * ncols;
-
-    const size_t mat = (size_t)dim * dim, p_bytes = 8 * mat * (derivs ? 3 : 1) * nedges;
-    const size_t tree_bytes = 4 * tree.size(), pi_off = (tree_bytes + 7) / 8 * 8, rows_off = pi_off + 8 * (size_t)dim;
-    const size_t u_count = (size_t)ninner * ncols * dim, nchunks = ((size_t)ncols + PGM_TREELIK_CHUNK - 1) / PGM_TREELIK_CHUNK;
-    const size_t g_count = (size_t)nedges * ncols, part_count = 2 * (size_t)nedges * nchunks;
-    const size_t l_bytes = 8 * (size_t)ncols, k_bytes = (4 * (size_t)ncols + 7) / 8 * 8, d_bytes = 8 * (size_t)nedges;
-    StageCall c(ctx, "tree likelihood", &ctx->treelik_ms);
-    uint8_t *d_tree = nullptr, *d_out = nullptr; double *d_P = nullptr, *d_U = nullptr, *d_g = nullptr;
-    c.buf(pgm_ctx::SC_TREELIK_TREE, rows_off + nrow, &d_tree);
-    c.buf(pgm_ctx::SC_TREELIK_P, p_bytes, &d_P);
-    c.buf(pgm_ctx::SC_TREELIK_U, 8 * u_count * (derivs ? 2 : 1), &d_U);
-    if (derivs) c.buf(pgm_ctx::SC_TREELIK_G, 8 * (2 * g_count + part_count), &d_g);
-    c.buf(pgm_ctx::SC_TREELIK_OUT, l_bytes + k_bytes + 2 * d_bytes, &d_out);
-    c.up(d_tree, tree.data(), tree_bytes);
-    c.up(d_tree + pi_off, pi, 8 * (size_t)dim);
-    c.up(d_tree + rows_off, rows, nrow);
-    c.up(d_P, P, p_bytes);
-
-    PgmTreelikArgs a;
-    a.dim = dim; a.nleaves = nleaves; a.nnodes = nnodes; a.ncols = ncols; a.spb = PGM_TREELIK_THREADS / dim; a.derivs = derivs ? 1 : 0;
-    a.child_off = (const uint32_t *)d_tree; a.child = a.child_off + nnodes + 1;
-    a.pi = (const double *)(d_tree + pi_off); a.rows = (const int8_t *)(d_tree + rows_off); a.P = d_P;
-    a.U = d_U; a.O = derivs ? d_U + u_count : nullptr;
-    a.g = derivs ? d_g : nullptr; a.h = derivs ? d_g + g_count : nullptr;
-    a.site_l = (double *)d_out; a.site_k = (int32_t *)(d_out + l_bytes);
-    double *d_d1 = (double *)(d_out + l_bytes + k_bytes), *d_d2 = d_d1 + nedges;
-    const uint32_t blocks = (uint32_t)(((uint64_t)ncols + a.spb - 1) / a.spb);
-    if (c.begin()) {
-        hipLaunchKernelGGL(pgm_treelik_kernel, dim3(blocks), dim3(PGM_TREELIK_THREADS), 0, c.s, a);
-        if (derivs)
-            hipLaunchKernelGGL(pgm_treelik_sums_kernel, dim3(nedges), dim3(PGM_TREELIK_THREADS), 0, c.s, (const double *)a.g, (const double *)a.h, ncols, (uint32_t)nchunks,
-                               d_g + 2 * g_count, d_d1, d_d2);
+    TreelikCall t;
+    if (const int rc = t.open(ctx, "tree likelihood", PGM_TREELIK_CALL_PLAIN, {dim, nleaves, nnodes, parent, ncols, rows, pi, 0, nullptr, P, derivs, 0, nullptr, nullptr, nullptr, false}))
+        return rc;
+    if (t.c->begin()) {
+        hipLaunchKernelGGL(pgm_treelik_kernel, dim3(t.blocks), dim3(PGM_TREELIK_THREADS), 0, t.c->s, t.a);
+        if (derivs) t.launch_sums();
     }
-    c.end();
-    c.down(site_l, a.site_l, l_bytes);
-    c.down(site_k, a.site_k, 4 * (size_t)ncols);
-    if (derivs) {
-        c.down(d1, d_d1, d_bytes);
-        c.down(d2, d_d2, d_bytes);
+    t.c->end();
+    t.down(site_l, site_k, nullptr, d1, d2);
+    return t.c->finish();
+}
+
+// One launch of the walk over (site block x category), one of pgm_treelik_combine_kernel, with derivs one of pgm_treelik_sums_kernel.
+extern "C" int pgm_tree_likelihood_rates(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
+                                         const double *pi, uint32_t ncat, const double *w, const double *P, int derivs, double *site_l, int32_t *site_k, double *post,
+                                         double *d1, double *d2) {
+    if (!ctx) return fail(PGM_ERR_INVALID, "null argument");
+    ctx->treelik_ms = 0;
+    if (!parent || !rows || !pi || !w || !P || !site_l || !site_k || !post || (derivs && (!d1 || !d2))) return fail(PGM_ERR_INVALID, "null argument");
+    TreelikCall t;
+    if (const int rc = t.open(ctx, "tree likelihood", PGM_TREELIK_CALL_RATES, {dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, derivs, 0, nullptr, nullptr, nullptr, false}))
+        return rc;
+    if (t.c->begin()) {
+        hipLaunchKernelGGL(pgm_treelik_cat_kernel<PGM_TREELIK_RAW>, dim3(t.blocks, ncat), dim3(PGM_TREELIK_THREADS), 0, t.c->s, t.a, t.st);
+        hipLaunchKernelGGL(pgm_treelik_combine_kernel, dim3(t.cblocks, derivs ? std::min<uint32_t>(t.pl.nedges, 65535u) : 1u), dim3(PGM_TREELIK_THREADS), 0, t.c->s, t.m);
+        if (derivs) t.launch_sums();
     }
-    return c.finish();
+    t.c->end();
+    t.down(site_l, site_k, post, d1, d2);
+    return t.c->finish();
+}
+
+// The walk in its ancestral mode over (site block x category), pgm_treelik_combine_kernel for site_l, site_k and post, then
+// pgm_treelik_anc_combine_kernel.  The categories' posteriors stand where pgm_tree_likelihood_rates keeps the outside vectors.
+extern "C" int pgm_tree_ancestral(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
+                                  const double *pi, uint32_t ncat, const double *w, const double *P, double *site_l, int32_t *site_k, double *post,
+                                  int8_t *anc_state, double *anc_prob, double *anc_post) {
+    if (!ctx) return fail(PGM_ERR_INVALID, "null argument");
+    ctx->treelik_ms = 0;
+    if (!parent || !rows || !pi || !w || !P || !site_l || !site_k || !post || !anc_state || !anc_prob) return fail(PGM_ERR_INVALID, "null argument");
+    TreelikCall t;
+    if (const int rc = t.open(ctx, "tree ancestral", PGM_TREELIK_CALL_ANC, {dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, 0, 0, nullptr, nullptr, nullptr, anc_post != nullptr}))
+        return rc;
+    PgmTreelikAncCombineArgs x;
+    x.dim = dim; x.ncat = ncat; x.ncols = ncols; x.spb = t.a.spb; x.npairs = t.pl.npairs; x.cat = t.pl.u_count;
+    x.a = t.a.O; x.post = t.m.post;
+    x.anc_prob = t.at<double>(PGM_TL_ANC_PROB); x.anc_state = t.at<int8_t>(PGM_TL_ANC_STATE); x.anc_post = t.at<double>(PGM_TL_ANC_POST);
+    const uint32_t xblocks = (uint32_t)std::min<uint64_t>(((uint64_t)x.npairs + x.spb - 1) / x.spb, (uint64_t)1 << 20);   // (the kernel strides over the rest)
+    if (t.c->begin()) {
+        hipLaunchKernelGGL(pgm_treelik_cat_kernel<PGM_TREELIK_ANC>, dim3(t.blocks, ncat), dim3(PGM_TREELIK_THREADS), 0, t.c->s, t.a, t.st);
+        hipLaunchKernelGGL(pgm_treelik_combine_kernel, dim3(t.cblocks, 1u), dim3(PGM_TREELIK_THREADS), 0, t.c->s, t.m);
+        hipLaunchKernelGGL(pgm_treelik_anc_combine_kernel, dim3(xblocks), dim3(PGM_TREELIK_THREADS), 0, t.c->s, x);
+    }
+    t.c->end();
+    t.down(site_l, site_k, post, nullptr, nullptr);
+    t.c->down(anc_prob, x.anc_prob, t.pl.r[PGM_TL_ANC_PROB].bytes);
+    t.c->down(anc_state, x.anc_state, t.pl.r[PGM_TL_ANC_STATE].bytes);
+    t.c->down(anc_post, x.anc_post, t.pl.r[PGM_TL_ANC_POST].bytes);
+    return t.c->finish();
+}
+
+// The walk in its nni mode over (site block x category), which leaves the partials and the outside vectors in device memory,
+// pgm_treelik_combine_kernel for site_l, site_k and post, then pgm_treelik_nni_kernel over (site block x candidate).
+extern "C" int pgm_tree_nni(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
+                            const double *pi, uint32_t ncat, const double *w, const double *P, uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a,
+                            const uint32_t *cand_c, double *site_l, int32_t *site_k, double *post, double *rho) {
+    if (!ctx) return fail(PGM_ERR_INVALID, "null argument");
+    ctx->treelik_ms = 0;
+    if (!parent || !rows || !pi || !w || !P || !site_l || !site_k || !post || !cand_v || !cand_a || !cand_c || !rho) return fail(PGM_ERR_INVALID, "null argument");
+    TreelikCall t;
+    if (const int rc = t.open(ctx, "tree nni", PGM_TREELIK_CALL_NNI, {dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, 0, ncand, cand_v, cand_a, cand_c, false}))
+        return rc;
+    PgmTreelikNniArgs x;
+    x.t = t.a; x.st = t.st; x.ncat = ncat; x.ncand = ncand;
+    x.parent = t.at<const uint32_t>(PGM_TL_PARENT);
+    x.cand_v = t.at<const uint32_t>(PGM_TL_CAND); x.cand_a = x.cand_v + ncand; x.cand_c = x.cand_a + ncand;
+    x.post = t.m.post; x.rho = t.at<double>(PGM_TL_RHO);
+    const uint32_t per = t.a.spb * PGM_TREELIK_NNI_WAVES;   // sites per workgroup of the candidates' kernel
+    const uint32_t xblocks = (uint32_t)(((uint64_t)ncols + per - 1) / per);
+    if (t.c->begin()) {
+        hipLaunchKernelGGL(pgm_treelik_cat_kernel<PGM_TREELIK_NNI>, dim3(t.blocks, ncat), dim3(PGM_TREELIK_THREADS), 0, t.c->s, t.a, t.st);
+        hipLaunchKernelGGL(pgm_treelik_combine_kernel, dim3(t.cblocks, 1u), dim3(PGM_TREELIK_THREADS), 0, t.c->s, t.m);
+        hipLaunchKernelGGL(pgm_treelik_nni_kernel, dim3(xblocks, std::min<uint32_t>(ncand, 65535u)), dim3(PGM_TREELIK_NNI_THREADS), 0, t.c->s, x);   // (the kernel strides over the rest)
+    }
+    t.c->end();
+    t.down(site_l, site_k, post, nullptr, nullptr);
+    t.c->down(rho, x.rho, t.pl.r[PGM_TL_RHO].bytes);
+    return t.c->finish();
 }

@@ -1,0 +1,68 @@
+// pgm_treelik_check.h — what the tree-likelihood entries refuse past their null pointers, once for the C ABI (pgm_treelik_capi.inc,
+// which wraps a message in fail(PGM_ERR_INVALID, ...)) and for the host statements (host/treelik*.cpp, which wrap it in error(...)).
+// Plain C++: arguments and structure only, no likelihood arithmetic.  Every function returns an empty string or the message.
+#ifndef PGM_TREELIK_CHECK_H_
+#define PGM_TREELIK_CHECK_H_
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/pgm_hip.h"
+
+// ncat and the categories' weights (pgm_tree_likelihood_rates, pgm_tree_ancestral, pgm_tree_nni)
+inline std::string pgm_treelik_check_rates(uint32_t ncat, const double *w) {
+    if (ncat < 1 || ncat > PGM_TREELIK_MAXCAT) return "tree likelihood: ncat must be 1 .. " + std::to_string(PGM_TREELIK_MAXCAT);
+    for (uint32_t c = 0; c < ncat; ++c)
+        if (!(w[c] > 0.0 && w[c] < INFINITY)) return "tree likelihood: weight " + std::to_string(c) + " is not finite and above 0";
+    return std::string();
+}
+
+// The sizes, the tree and the rows (include/pgm_hip.h: pgm_tree_likelihood), and the children of every node in ascending order:
+// `tree` gets child_off (nnodes + 1), then child (nnodes - 1).
+inline std::string pgm_treelik_check_tree(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
+                                          std::vector<uint32_t> &tree) {
+    const std::string w = "tree likelihood: ";
+    if (dim < 1 || dim > 64) return w + "dim must be 1 .. 64";
+    if (nleaves < 2 || ncols == 0 || nnodes <= nleaves) return w + "nleaves must be at least 2, ncols at least 1 and nnodes above nleaves";
+    tree.assign((size_t)nnodes + 1, 0);
+    uint32_t roots = 0;
+    for (uint32_t v = 0; v < nnodes; ++v) {
+        if (parent[v] == UINT32_MAX) { ++roots; continue; }
+        if (parent[v] <= v || parent[v] >= nnodes) return w + "the parent of node " + std::to_string(v) + " is not above it";
+        if (parent[v] < nleaves) return w + "leaf " + std::to_string(parent[v]) + " is a parent";
+        ++tree[parent[v] + 1];
+    }
+    if (roots != 1) return w + std::to_string(roots) + " roots";
+    for (uint32_t v = nleaves; v < nnodes; ++v)
+        if (tree[v + 1] < 2) return w + "inner node " + std::to_string(v) + " has fewer than 2 children";
+    for (uint32_t v = 0; v < nnodes; ++v) tree[v + 1] += tree[v];
+    const uint32_t nedges = nnodes - 1;   // (every node but the root is a child: tree[nnodes] == nedges)
+    tree.resize((size_t)nnodes + 1 + nedges);
+    {
+        std::vector<uint32_t> fill(tree.begin(), tree.begin() + nnodes);
+        for (uint32_t v = 0; v < nnodes; ++v)
+            if (parent[v] != UINT32_MAX) tree[(size_t)nnodes + 1 + fill[parent[v]]++] = v;
+    }
+    const size_t nrow = (size_t)nleaves * ncols;
+    for (size_t k = 0; k < nrow; ++k)
+        if (rows[k] < -2 || rows[k] >= (int)dim) return w + "row value " + std::to_string((int)rows[k]) + " outside -2 .. dim - 1";
+    return std::string();
+}
+
+// the candidates of pgm_tree_nni on a tree that passed pgm_treelik_check_tree
+inline std::string pgm_treelik_check_candidates(uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a,
+                                                const uint32_t *cand_c) {
+    if (ncand == 0) return "tree nni: no candidate";
+    for (uint32_t q = 0; q < ncand; ++q) {
+        const uint32_t v = cand_v[q], a = cand_a[q], c = cand_c[q];
+        const std::string what = "tree nni: candidate " + std::to_string(q) + ": ";
+        if (v >= nnodes || v < nleaves || parent[v] == UINT32_MAX) return what + "v is not an inner node below the root";
+        if (a >= nnodes || parent[a] != v) return what + "a is not a child of v";
+        if (c >= nnodes || c == v || parent[c] != parent[v]) return what + "c is not another child of the parent of v";
+    }
+    return std::string();
+}
+
+#endif

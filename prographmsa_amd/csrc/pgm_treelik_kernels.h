@@ -8,10 +8,10 @@
 // site read consecutive entries of a column; the 3.2 KB to 98 KB of an edge stay in the vector L1 / L2 while the workgroups pass it).
 // pgm_treelik_sums_kernel adds the per-site ratios of an edge in the fixed order of the interface.
 // pgm_tree_likelihood_rates runs the same walk once per rate category, the categories as further workgroups of one
-// launch (pgm_treelik_rates_kernel), and combines them per site (pgm_treelik_combine_kernel) ahead of the sums.
-// pgm_tree_ancestral is a third mode of the walk (pgm_treelik_anc_kernel): the down pass with P alone, the posterior
+// launch (pgm_treelik_cat_kernel), and combines them per site (pgm_treelik_combine_kernel) ahead of the sums.
+// pgm_tree_ancestral is a third mode of the walk (PGM_TREELIK_ANC): the down pass with P alone, the posterior
 // of every inner node's states written where the node's outside vector was; pgm_treelik_anc_combine_kernel mixes the categories.
-// pgm_tree_nni is a fourth mode (pgm_treelik_nni_walk_kernel): that down pass without the posteriors, so the outside
+// pgm_tree_nni is a fourth mode (PGM_TREELIK_NNI): that down pass without the posteriors, so the outside
 // vectors stay; pgm_treelik_nni_kernel then scores every nearest-neighbour interchange from four stored pieces around its edge.
 //
 // Every sum over states runs ascending from 0.0 with one multiply and one add per term (-ffp-contract=off): the bits are those of
@@ -278,40 +278,24 @@ __device__ __forceinline__ void pgm_treelik_walk(const PgmTreelikArgs &a) {
 
 __global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_kernel(PgmTreelikArgs a) { pgm_treelik_walk<PGM_TREELIK_PLAIN>(a); }
 
-// pgm_tree_likelihood_rates: category blockIdx.y walks the tree with its own matrices, partials and outputs, `a`
-// holding those of category 0 and the strides the distance between two categories.  a.site_l / a.site_k get (L_c, k_c), a.g / a.h the
-// ratios (g_c, q_c) of every edge and site.  The categories are independent workgroups of one launch.
+// The walk once per rate category: category blockIdx.y walks the tree with its own matrices, partials and
+// outputs, `a` holding those of category 0 and the strides the distance between two categories.  The categories are independent
+// workgroups of one launch.  a.site_l / a.site_k get (L_c, k_c).  MODE PGM_TREELIK_RAW (pgm_tree_likelihood_rates): with derivs
+// a.g / a.h get the ratios (g_c, q_c) of every edge and site.  PGM_TREELIK_ANC (pgm_tree_ancestral; P alone: a.derivs == 0): the
+// posteriors a_c,v land in a.O, [v - nleaves][s][i], the layout of the outside vectors they replace.  PGM_TREELIK_NNI (pgm_tree_nni):
+// as ANC, but a.O keeps the outside vectors O_v.
 struct PgmTreelikRatesStride { size_t P, U, G, L; };   // doubles between the categories' matrices, partials, ratios, site values
-__global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_rates_kernel(PgmTreelikArgs a, PgmTreelikRatesStride st) {
+template <int MODE>
+__global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_cat_kernel(PgmTreelikArgs a, PgmTreelikRatesStride st) {
     const size_t c = blockIdx.y;
     a.P += st.P * c;
     a.U += st.U * c;
     a.site_l += st.L * c;
     a.site_k += st.L * c;
-    if (a.derivs) { a.O += st.U * c; a.g += st.G * c; a.h += st.G * c; }
-    pgm_treelik_walk<PGM_TREELIK_RAW>(a);
-}
-// pgm_tree_ancestral: category blockIdx.y walks the tree with its own matrices (P alone: a.derivs == 0) and
-// partials; its posteriors a_c,v land in a.O, [v - nleaves][s][i], the layout of the outside vectors they replace.
-__global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_anc_kernel(PgmTreelikArgs a, PgmTreelikRatesStride st) {
-    const size_t c = blockIdx.y;
-    a.P += st.P * c;
-    a.U += st.U * c;
-    a.O += st.U * c;
-    a.site_l += st.L * c;
-    a.site_k += st.L * c;
-    pgm_treelik_walk<PGM_TREELIK_ANC>(a);
-}
-
-// pgm_tree_nni: as pgm_treelik_anc_kernel, but a.O keeps the outside vectors O_v.
-__global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_nni_walk_kernel(PgmTreelikArgs a, PgmTreelikRatesStride st) {
-    const size_t c = blockIdx.y;
-    a.P += st.P * c;
-    a.U += st.U * c;
-    a.O += st.U * c;
-    a.site_l += st.L * c;
-    a.site_k += st.L * c;
-    pgm_treelik_walk<PGM_TREELIK_NNI>(a);
+    if constexpr (MODE == PGM_TREELIK_RAW) {
+        if (a.derivs) { a.O += st.U * c; a.g += st.G * c; a.h += st.G * c; }
+    } else a.O += st.U * c;
+    pgm_treelik_walk<MODE>(a);
 }
 
 // The categories of a site combined in the order of the interface.  A workgroup owns 64 consecutive sites (reads and writes run along

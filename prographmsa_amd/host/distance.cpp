@@ -15,13 +15,6 @@
 #include <fstream>
 #include <functional>
 #include <thread>
-// The source lists name all four files of the guide tree and define PGM_HOST_SPLIT.  A list from before the split names this file
-// alone and defines nothing: the other three are then compiled here, so that it still links a whole host.
-#ifndef PGM_HOST_SPLIT
-#include "mldist.cpp"
-#include "bionj.cpp"
-#include "wls.cpp"
-#endif
 
 namespace pgm {
 static std::string g_dist_dump;

@@ -12,14 +12,6 @@
 #include <malloc.h>
 #include <unistd.h>
 #include <thread>
-// The source lists name every file of the driver and define PGM_HOST_SPLIT=3 (host/sources.mk).  A list from before this file was
-// split names it alone and defines PGM_HOST_SPLIT=2 or less: the files that were cut out of it are then compiled here.
-#if !defined(PGM_HOST_SPLIT) || (PGM_HOST_SPLIT + 0) < 3
-#include "driver_options.cpp"
-#include "driver_family.cpp"
-#include "driver_analyses.cpp"
-#include "driver_stats.cpp"
-#endif
 
 using namespace pgm;
 

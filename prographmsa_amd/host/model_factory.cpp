@@ -334,10 +334,3 @@ Model ModelFactory::getModel(distance_t distance, distance_t gap_distance) const
 }
 
 }  // namespace pgm
-
-// --ml_tree: tree likelihood, its derivatives and the branch-length optimiser (kept in a file of their own, built with this unit)
-#include "treelik.inc"
-#include "treelik_rates.inc"
-#include "treelik_anc.inc"
-#include "treelik_nni.inc"
-#include "treelik_support.inc"

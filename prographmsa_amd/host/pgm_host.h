@@ -759,138 +759,9 @@ TaxaSupport taxa_support(const PhyTree &tree, const std::vector<const PhyTree *>
 std::string taxa_text(const TaxaSupport &t, double cutoff);
 std::string taxa_edges_text(const TaxaSupport &t);
 
-// --ml_tree: the likelihood of an alignment on a rooted tree and maximum-likelihood branch lengths on its fixed topology
-// (host/treelik.inc).
-// tree_likelihood_host: pgm_tree_likelihood (include/pgm_hip.h) by a loop over the sites on the host threads, the same contract and
-//   the same bits; what it rejects is an error().  Backend::tree_likelihood's default.
-// MlTreeTopology: the nodes of a tree numbered children before parents, the leaves first in sorted-name order, the inner nodes in
-//   post-order, the root last; edge e is the edge above node e.
-// treelik_matrices: P(t_e), Q P(t_e), Q Q P(t_e) of every edge back to back (derivs) or P(t_e) alone, as pgm_tree_likelihood reads them.
-// treelik_lnl: sum over the sites of log(site_l) - 256 ln 2 site_k, sites ascending; site_lnl (may be null) gets the terms.
-// ml_branch_lengths: the optimiser.  rows: the alignment's rows in sorted-name order as state values (0..dim-1, -1 a gap, -2 a residue
-//   without a value), all of one length.  be: the backend whose tree_likelihood runs, nullptr for the host loop.
-// --ml_gamma (host/treelik_rates.inc):
-// tree_likelihood_rates_host: pgm_tree_likelihood_rates by the same loop, Backend::tree_likelihood_rates's default.
-// gamma_rates: the K rates of the discrete gamma of shape alpha (Yang 1994, category means), equally probable, their mean 1.
-// treelik_matrices with rates: category-major, for category c and edge e P(r_c t_e), r_c Q P, r_c^2 Q Q P.
-// MlGamma: what ml_branch_lengths is asked for (ncat < 2: one rate for every column, the loop of --ml_tree alone); with `estimate`
-//   alpha starts at 1 and the branch-length loop alternates with a golden-section search on ln alpha.
-// --ml_ancestral (host/treelik_anc.inc):
-// tree_ancestral_host: pgm_tree_ancestral by the same loop, Backend::tree_ancestral's default.
-// tree_ancestral_presence: the gap rule of the written records, present[(v - nleaves) * ncols + s] = 1 iff inner node v lies on a
-//   path between two leaves whose row at column s is not -1 (parent: the numbering of the likelihood entries).
-// --ml_search (host/treelik_nni.inc):
-// tree_nni_host: pgm_tree_nni per block of column chunks (the walk's partials and outside vectors of a block are held, 256 MB by
-//   default) by a loop over the block's columns, then over candidates x column chunks; Backend::tree_nni's default.
-// treelik_nni_gain: gain[q] = sum over the sites ascending of log rho[q][s] (log 0 is -infinity).
-// ml_topology_search: ml_branch_lengths on the start tree, then up to `search_rounds` rounds of: one tree_nni call over every
-//   candidate (v ascending, a in child order, c in child order), the candidates of gain > eps by gain descending then index, picked
-//   greedily while no two share a node of {u, v, a, c}; the first m picked applied (m from all of them, halved while the evaluation at
-//   the carried lengths is not above lnL; none left: the search ends), then ml_branch_lengths again from the carried lengths and
-//   the shape in hand.  lnL never decreases.
-const double kMlMinLength = 1e-6, kMlMaxLength = 10.0;   // the interval every branch length stays in
-const double kMlMinAlpha = 0.05, kMlMaxAlpha = 100.0;     // ... and the shape of the gamma
-const uint32_t kMlAlphaEvaluations = 12, kMlMaxPairs = 20;   // one search on ln alpha; branch-length loop + search pairs at the most
-// alignments of this many taxa and more go to the device by default: the smallest size at which the two routes were timed, and the
-// device was faster there and at every larger one (measured once); below it the host loop runs, untimed
-const uint32_t kTreelikDeviceMin = 24;
-struct MlTreeStats {   // `pgmsa --ml_tree --stats`
-    double seconds = 0, kernel_ms = 0, lnl_start = 0, lnl = 0;
-    double ancestral_s = 0;    // --ml_ancestral only: the tree_ancestral call, its matrices included
-    uint64_t rounds = 0, evaluations = 0;
-    uint32_t categories = 0;   // --ml_gamma only
-    double alpha = 0;
-};
-extern MlTreeStats ml_tree_stats;
-struct MlTreeTopology {
-    uint32_t nleaves = 0, nnodes = 0;
-    std::vector<uint32_t> parent;           // nnodes, the root's: UINT32_MAX
-    std::vector<const PhyTree *> node;      // nnodes
-    std::vector<std::string> names;         // the leaves' names, sorted
-};
-MlTreeTopology ml_tree_topology(const PhyTree &tree);
-void tree_likelihood_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
-                          const double *P, int derivs, double *site_l, int32_t *site_k, double *d1, double *d2);
-void treelik_matrices(const ModelFactory &mf, const std::vector<double> &t /* nnodes - 1 */, bool derivs, std::vector<double> &P);
-double treelik_lnl(uint32_t ncols, const double *site_l, const int32_t *site_k, double *site_lnl);
-void tree_likelihood_rates_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
-                                uint32_t ncat, const double *w, const double *P, int derivs, double *site_l, int32_t *site_k, double *post, double *d1, double *d2);
-void tree_ancestral_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
-                         const double *w, const double *P, double *site_l, int32_t *site_k, double *post, int8_t *anc_state /* ninner x ncols */,
-                         double *anc_prob /* ninner x ncols */, double *anc_post /* ninner x ncols x dim, or null */);
-void tree_ancestral_presence(uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, uint8_t *present /* ninner x ncols */);
-std::vector<double> gamma_rates(double alpha, uint32_t K);
-void treelik_matrices(const ModelFactory &mf, const std::vector<double> &t, bool derivs, const std::vector<double> &rates, std::vector<double> &P);
-struct MlGamma {
-    uint32_t ncat = 0;
-    bool estimate = true;
-    double alpha = 1.0;
-    double start = 1.0;   // with `estimate`: the shape the search starts from
-};
-struct MlTreeResult {
-    std::vector<double> lengths;    // per edge (node below it)
-    std::vector<double> site_lnl;   // per column, at `lengths`
-    double lnl_start = 0, lnl = 0;
-    uint32_t rounds = 0, evaluations = 0;
-    double alpha = 0;               // --ml_gamma only: the shape, the categories' rates, post (ncat x ncols) at `lengths`
-    std::vector<double> rates, post;
-};
-MlTreeResult ml_branch_lengths(const Alphabet &a, const std::vector<std::vector<int8_t>> &rows, const ModelFactory &model_factory, const PhyTree &tree,
-                               uint32_t rounds, double eps, Backend *be = nullptr, const MlGamma &gamma = MlGamma());
-const size_t kTreelikNniBlockBytes = (size_t)256 << 20;
-void tree_nni_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
-                   const double *w, const double *P, uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c /* ncand each */,
-                   double *site_l, int32_t *site_k, double *post, double *rho /* ncand x ncols */,
-                   size_t block_bytes = kTreelikNniBlockBytes /* the partials and outside vectors held at a time, about; at least one column chunk */);
-void treelik_nni_gain(uint32_t ncand, uint32_t ncols, const double *rho, double *gain /* ncand */);
-struct MlSearchStats {   // `pgmsa --ml_tree --ml_search --stats`
-    double seconds = 0, kernel_ms = 0;
-    uint64_t rounds = 0, applied = 0, calls = 0;   // accepted rounds, moves applied in them, tree_nni calls
-};
-extern MlSearchStats ml_search_stats;
-struct MlSearchRound {   // a line of --ml_search_log
-    uint32_t round = 0, candidates = 0, positive = 0, applied = 0;
-    double best_gain = 0, lnl_before = 0, lnl_applied = 0, lnl_after = 0;
-};
-struct MlSearchResult {
-    std::unique_ptr<PhyTree> tree;   // the searched tree; `res` is ml_branch_lengths's result on it (lnl_start: the start tree's)
-    MlTreeResult res;
-    std::vector<MlSearchRound> log;
-};
-MlSearchResult ml_topology_search(const Alphabet &a, const std::vector<std::vector<int8_t>> &rows, const ModelFactory &model_factory, const PhyTree &start,
-                                  uint32_t search_rounds, uint32_t rounds, double eps, Backend *be = nullptr, const MlGamma &gamma = MlGamma());
-// --ml_support (host/treelik_support.inc):
-// resampled_sums_host: pgm_resampled_sums by a loop over rows x chunks of replicates on the host threads, the same contract and the
-//   same bits; what it rejects is an error().  Backend::resampled_sums's default.
-// ml_support_candidates: the supported nodes (every inner node v below the root whose parent is not a root of exactly two children),
-//   ascending, and their candidates (v, a, c), a in child order, then c in child order: the other resolutions around the edge above v.
-// ml_branch_support: one tree_nni call over those candidates, x = log rho, the observed gains (treelik_nni_gain), the resampled gains
-//   D[q][r] by resampled_sums in groups of rows whose x stays within x_bytes, and per node with the candidates C whose gain is not
-//   -infinity: d_obs = -max gain, alrt = 2 d_obs, sh_hits = the replicates whose largest of {0, D[q][r] - mean_q} is less than d_obs
-//   ahead of the second largest (0 when d_obs <= 0), rell_hits = the replicates with D[q][r] <= 0 for every q of C; C empty:
-//   alrt = +infinity and both counts nrep.  be: the backend whose tree_nni and resampled_sums run, nullptr for the host loops.
-const size_t kSupportBytes = (size_t)1 << 30;   // x of one resampled_sums call
-struct MlSupportStats {   // `pgmsa --ml_tree --ml_support --stats`
-    double seconds = 0, kernel_ms = 0;
-    uint64_t nodes = 0, calls = 0;   // supported nodes, resampled_sums calls
-};
-extern MlSupportStats ml_support_stats;
-struct MlSupportNode {
-    uint32_t node = 0, candidates = 0;   // the node's number, the candidates around the edge above it
-    double alrt = 0;
-    uint32_t sh_hits = 0, rell_hits = 0;
-};
-void resampled_sums_host(uint32_t nrow, uint32_t ncols, const double *x /* nrow x ncols */, uint32_t nrep, const uint32_t *cols /* nrep x ncols */,
-                         double *out /* nrow x nrep */);
-void ml_support_candidates(uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, std::vector<uint32_t> &node, std::vector<uint32_t> &cand_v,
-                           std::vector<uint32_t> &cand_a, std::vector<uint32_t> &cand_c);
-std::vector<MlSupportNode> ml_branch_support(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
-                                             uint32_t ncat, const double *w, const double *P /* ncat x (nnodes-1) x dim x dim */, uint32_t nrep,
-                                             const uint32_t *cols /* nrep x ncols */, Backend *be = nullptr, size_t x_bytes = kSupportBytes);
-// a copy of `tree` whose edge above topo.node[e] has length lengths[e]
-PhyTree *ml_tree_with_lengths(const MlTreeTopology &topo, const std::vector<double> &lengths);
-
 std::string data_dir();   // directory holding wag.qmat etc.
 
 }  // namespace pgm
+
+#include "treelik.h"   // the --ml_* analyses
 #endif

@@ -14,16 +14,6 @@
 #include <cstdio>
 #include <iostream>
 #include <thread>
-// The source lists name every file of the host and define PGM_HOST_SPLIT=3 (2 before main.cpp was split: see there).  A list from before this file was split names it alone
-// and defines PGM_HOST_SPLIT without a value (1: distance.cpp's split only) or nothing: the files that were cut out of it (and
-// farm_shards / farm_run, once in graph_align.cpp) are then compiled here.
-#if !defined(PGM_HOST_SPLIT) || (PGM_HOST_SPLIT + 0) < 2
-#include "host_threads.cpp"
-#include "repeats.cpp"
-#include "root_search.cpp"
-#include "guidance.cpp"
-#include "transfer.cpp"
-#endif
 
 namespace pgm {
 

@@ -1,15 +1,14 @@
-// treelik_anc.inc — marginal ancestral states for `pgmsa --ml_tree --ml_ancestral` (included by model_factory.cpp behind
-// treelik_rates.inc, whose walk and checks it shares): the host statement of pgm_tree_ancestral
+// treelik_anc.cpp — marginal ancestral states for `pgmsa --ml_tree --ml_ancestral` (the walk and the checks are
+// treelik_internal.h's): the host statement of pgm_tree_ancestral
 // (Backend::tree_ancestral's default, what pgmsa_oracle runs).
+#include "treelik_internal.h"
 
 namespace pgm {
 
 void tree_ancestral_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
                          const double *w, const double *P, double *site_l, int32_t *site_k, double *post, int8_t *anc_state, double *anc_prob, double *anc_post) {
     if (!w || !post || !anc_state || !anc_prob) error("tree likelihood: null argument");
-    if (ncat < 1 || ncat > PGM_TREELIK_MAXCAT) error("tree likelihood: ncat must be 1 .. %d", PGM_TREELIK_MAXCAT);
-    for (uint32_t c = 0; c < ncat; ++c)
-        if (!(w[c] > 0.0 && w[c] < INFINITY)) error("tree likelihood: weight %u is not finite and above 0", c);
+    treelik_check_rates_host(ncat, w);
     const TreelikChildren ch = treelik_check_host(dim, nleaves, nnodes, parent, ncols, rows, pi, P, 0, site_l, site_k, nullptr, nullptr);
     const uint32_t nedges = nnodes - 1, ninner = nnodes - nleaves;
     const size_t nchunks = ((size_t)ncols + kTreelikChunk - 1) / kTreelikChunk, pstride = (size_t)dim * dim * nedges, astride = (size_t)ninner * dim;

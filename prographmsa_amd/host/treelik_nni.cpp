@@ -1,7 +1,10 @@
-// treelik_nni.inc — nearest-neighbour interchanges for `pgmsa --ml_tree --ml_search` (included by model_factory.cpp behind
-// treelik_anc.inc, whose walk and checks it shares): the host statement of pgm_tree_nni (Backend::tree_nni's
+// treelik_nni.cpp — nearest-neighbour interchanges for `pgmsa --ml_tree --ml_search` (the walk and the checks are
+// treelik_internal.h's): the host statement of pgm_tree_nni (Backend::tree_nni's
 // default, what pgmsa_oracle runs), the gain of a candidate both drivers share, and the topology search, which is host code and the
 // same for every backend.
+#include "treelik_internal.h"
+
+#include <chrono>
 
 namespace pgm {
 
@@ -11,17 +14,10 @@ void tree_nni_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32
                    const double *w, const double *P, uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c, double *site_l,
                    int32_t *site_k, double *post, double *rho, size_t block_bytes) {
     if (!w || !post || !cand_v || !cand_a || !cand_c || !rho) error("tree likelihood: null argument");
-    if (ncat < 1 || ncat > PGM_TREELIK_MAXCAT) error("tree likelihood: ncat must be 1 .. %d", PGM_TREELIK_MAXCAT);
-    for (uint32_t c = 0; c < ncat; ++c)
-        if (!(w[c] > 0.0 && w[c] < INFINITY)) error("tree likelihood: weight %u is not finite and above 0", c);
+    treelik_check_rates_host(ncat, w);
     const TreelikChildren ch = treelik_check_host(dim, nleaves, nnodes, parent, ncols, rows, pi, P, 0, site_l, site_k, nullptr, nullptr);
-    if (ncand == 0) error("tree nni: no candidate");
-    for (uint32_t q = 0; q < ncand; ++q) {
-        const uint32_t v = cand_v[q], a = cand_a[q], c = cand_c[q];
-        if (v >= nnodes || v < nleaves || parent[v] == UINT32_MAX) error("tree nni: candidate %u: v is not an inner node below the root", q);
-        if (a >= nnodes || parent[a] != v) error("tree nni: candidate %u: a is not a child of v", q);
-        if (c >= nnodes || c == v || parent[c] != parent[v]) error("tree nni: candidate %u: c is not another child of the parent of v", q);
-    }
+    const std::string bad = pgm_treelik_check_candidates(nleaves, nnodes, parent, ncand, cand_v, cand_a, cand_c);
+    if (!bad.empty()) error("%s", bad.c_str());
     const uint32_t nedges = nnodes - 1, ninner = nnodes - nleaves, root = nnodes - 1;
     const size_t nchunks = ((size_t)ncols + kTreelikChunk - 1) / kTreelikChunk, mat = (size_t)dim * dim, pstride = mat * nedges;
     // The partials and the outside vectors are kept for a block of column chunks at a time, [category][site of the block][inner node]

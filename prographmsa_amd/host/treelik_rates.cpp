@@ -1,15 +1,14 @@
-// treelik_rates.inc — rate variation across sites for `pgmsa --ml_tree --ml_gamma` (included by model_factory.cpp behind treelik.inc,
-// whose walk it shares): the host statement of pgm_tree_likelihood_rates (Backend::tree_likelihood_rates's default,
+// treelik_rates.cpp — rate variation across sites for `pgmsa --ml_tree --ml_gamma` (the walk is treelik_internal.h's;
+// DESIGN.md 3.18): the host statement of pgm_tree_likelihood_rates (Backend::tree_likelihood_rates's default,
 // what pgmsa_oracle runs), the rates of the discrete gamma, and the rate-folded matrices of every category and edge.
+#include "treelik_internal.h"
 
 namespace pgm {
 
 void tree_likelihood_rates_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
                                 uint32_t ncat, const double *w, const double *P, int derivs, double *site_l, int32_t *site_k, double *post, double *d1, double *d2) {
     if (!w || !post) error("tree likelihood: null argument");
-    if (ncat < 1 || ncat > PGM_TREELIK_MAXCAT) error("tree likelihood: ncat must be 1 .. %d", PGM_TREELIK_MAXCAT);
-    for (uint32_t c = 0; c < ncat; ++c)
-        if (!(w[c] > 0.0 && w[c] < INFINITY)) error("tree likelihood: weight %u is not finite and above 0", c);
+    treelik_check_rates_host(ncat, w);
     const TreelikChildren ch = treelik_check_host(dim, nleaves, nnodes, parent, ncols, rows, pi, P, derivs, site_l, site_k, d1, d2);
     const uint32_t nedges = nnodes - 1;
     const size_t nchunks = ((size_t)ncols + kTreelikChunk - 1) / kTreelikChunk, pstride = (size_t)dim * dim * (derivs ? 3 : 1) * nedges;

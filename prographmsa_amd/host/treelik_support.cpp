@@ -1,7 +1,12 @@
-// treelik_support.inc — branch support on the ML tree for `pgmsa --ml_tree --ml_support` (included by model_factory.cpp behind
-// treelik_nni.inc, whose candidates' scores it reads): the host statement of pgm_resampled_sums
+// treelik_support.cpp — branch support on the ML tree for `pgmsa --ml_tree --ml_support` (it reads the candidates' scores of
+// treelik_nni.cpp): the host statement of pgm_resampled_sums
 // (Backend::resampled_sums's default, what pgmsa_oracle runs), and the aLRT, SH-like and RELL values of every supported node, which
 // are host code and the same for every backend.
+#include "pgm_host.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
 
 namespace pgm {
 

@@ -1,4 +1,4 @@
-// resample_test.cpp — resampled_sums_host, bootstrap_columns and ml_branch_support (host/treelik_support.inc, pgm_host.h) on cases read
+// resample_test.cpp — resampled_sums_host, bootstrap_columns and ml_branch_support (host/treelik_support.cpp, pgm_host.h) on cases read
 // from a file, the results printed as hexadecimal floats (%a: every bit) for tests/test_cpu_mlsupport.py to compare with
 // tests/resample_ref.py.  Host code only; built once plainly and once under AddressSanitizer and UBSan.
 //

@@ -1,4 +1,4 @@
-// treelik_anc_test.cpp — tree_ancestral_host and tree_ancestral_presence (host/treelik_anc.inc) on cases read from a file, the results
+// treelik_anc_test.cpp — tree_ancestral_host and tree_ancestral_presence (host/treelik_anc.cpp) on cases read from a file, the results
 // printed as hexadecimal floats (%a: every bit) for tests/test_cpu_mlancestral.py to compare with tests/treelik_anc_ref.py.  Host code
 // only; built once plainly and once under AddressSanitizer and UBSan.
 //

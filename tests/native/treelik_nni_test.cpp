@@ -1,4 +1,4 @@
-// treelik_nni_test.cpp — tree_nni_host and treelik_nni_gain (host/treelik_nni.inc) on cases read from a file, the results printed as
+// treelik_nni_test.cpp — tree_nni_host and treelik_nni_gain (host/treelik_nni.cpp) on cases read from a file, the results printed as
 // hexadecimal floats (%a: every bit) for tests/test_cpu_mlsearch.py to compare with tests/treelik_nni_ref.py.  Host code only; built
 // once plainly and once under AddressSanitizer and UBSan.
 //

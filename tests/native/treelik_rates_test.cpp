@@ -1,4 +1,4 @@
-// treelik_rates_test.cpp — tree_likelihood_rates_host and gamma_rates (host/treelik_rates.inc) on cases read from a file, the results
+// treelik_rates_test.cpp — tree_likelihood_rates_host and gamma_rates (host/treelik_rates.cpp) on cases read from a file, the results
 // printed as hexadecimal floats (%a: every bit) for tests/test_cpu_mlgamma.py to compare with tests/treelik_rates_ref.py.  Host code
 // only; built once plainly and once under AddressSanitizer and UBSan.
 //

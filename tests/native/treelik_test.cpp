@@ -1,4 +1,4 @@
-// treelik_test.cpp — tree_likelihood_host (host/treelik.inc) on cases read from a file, the results printed as hexadecimal floats
+// treelik_test.cpp — tree_likelihood_host (host/treelik.cpp) on cases read from a file, the results printed as hexadecimal floats
 // (%a: every bit) for tests/test_cpu_mltree.py to compare with tests/treelik_ref.py.  Host code only; built once plainly and once
 // under AddressSanitizer and UBSan.
 //

@@ -395,8 +395,8 @@ def test_refusals(exe, usage_text, tmp_path, k):
 
 
 def test_oracle_rebuilds_after_an_included_file_changes(tmp_path):
-    """`make -C oracle` in a copy of the tree: up to date after a build, out of date once treelik.inc (included by
-    model_factory.cpp) is touched, up to date again after the next build."""
+    """`make -C oracle` in a copy of the tree: up to date after a build, out of date once treelik_internal.h (included by
+    treelik.cpp) is touched, up to date again after the next build."""
     root = str(tmp_path / "tree")
     for d in ("oracle", "include", os.path.join("prographmsa_amd", "host"), os.path.join("prographmsa_amd", "csrc")):
         shutil.copytree(os.path.join(ROOT, d), os.path.join(root, d), ignore=shutil.ignore_patterns("_build", "_ref", "*.so", "*.o", "data"))
@@ -414,7 +414,7 @@ def test_oracle_rebuilds_after_an_included_file_changes(tmp_path):
     for f in os.listdir(build):   # (the products older than the touch below, newer than every source)
         os.utime(os.path.join(build, f), (old + 500, old + 500))
     assert make("-q").returncode == 0
-    os.utime(os.path.join(root, "prographmsa_amd", "host", "treelik.inc"))
+    os.utime(os.path.join(root, "prographmsa_amd", "host", "treelik_internal.h"))
     assert make("-q").returncode == 1
     again = make()
     assert again.returncode == 0, again.stderr

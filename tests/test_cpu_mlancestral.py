@@ -24,6 +24,7 @@ import transfer_ref as T
 import treelik_anc_ref as A
 import treelik_rates_ref as G
 import treelik_ref as R
+from treelik_sources import TREELIK_HOST_SOURCES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ULP = 2.0 ** -52
@@ -276,7 +277,7 @@ def native(tmp_path_factory):
     """The stand-alone program built twice and run on the cases: {build: stdout lines}."""
     d = tmp_path_factory.mktemp("anc_native")
     host = os.path.join(ROOT, "prographmsa_amd", "host")
-    src = [os.path.join(ROOT, "tests", "native", "treelik_anc_test.cpp")] + [os.path.join(host, f) for f in ("model_factory.cpp", "phytree.cpp", "alphabet.cpp", "host_threads.cpp")]
+    src = [os.path.join(ROOT, "tests", "native", "treelik_anc_test.cpp")] + [os.path.join(host, f) for f in TREELIK_HOST_SOURCES]
     hand, pattern = presence_case()
     cases = [A.make_case(*k) for k in NATIVE_CASES] + [A.make_case(*UNEQUAL)] + [A.make_mixed_scaling_case(*k) for k in MIXED_SCALING] + \
         [with_want(tie_case()), with_want(zero_case()), with_want(hand)]

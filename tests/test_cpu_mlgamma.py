@@ -21,6 +21,7 @@ import test_cpu_mltree as TM
 import test_cpu_treelik_shapes as SH
 import treelik_rates_ref as G
 import treelik_ref as R
+from treelik_sources import TREELIK_HOST_SOURCES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ALPHA_MIN, ALPHA_MAX = 0.05, 100.0
@@ -114,7 +115,7 @@ def native(tmp_path_factory):
     """The stand-alone program built twice and run on the cases and the grid: {build: stdout lines}."""
     d = tmp_path_factory.mktemp("rates_native")
     host = os.path.join(ROOT, "prographmsa_amd", "host")
-    src = [os.path.join(ROOT, "tests", "native", "treelik_rates_test.cpp")] + [os.path.join(host, f) for f in ("model_factory.cpp", "phytree.cpp", "alphabet.cpp", "host_threads.cpp")]
+    src = [os.path.join(ROOT, "tests", "native", "treelik_rates_test.cpp")] + [os.path.join(host, f) for f in TREELIK_HOST_SOURCES]
     cases = [G.make_case(d_, n, t, k) for d_, n, t, k in NATIVE_CASES] + [G.make_case(20, 33, "balanced8", 4, False), G.make_case(4, 33, "balanced8", 4, True, "unequal"),
                                                                          G.make_mixed_scaling_case(4), G.make_mixed_scaling_case(20, 1e-6, 5)]
     bad = _bad_cases()

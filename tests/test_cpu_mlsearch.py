@@ -22,6 +22,7 @@ import transfer_ref as T
 import treelik_nni_ref as N
 import treelik_rates_ref as G
 import treelik_ref as R
+from treelik_sources import TREELIK_HOST_SOURCES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STEP = 256.0 * math.log(2.0)
@@ -182,7 +183,7 @@ def native(tmp_path_factory):
     """The stand-alone program built twice and run on the cases: {build: stdout lines}."""
     d = tmp_path_factory.mktemp("nni_native")
     host = os.path.join(ROOT, "prographmsa_amd", "host")
-    src = [os.path.join(ROOT, "tests", "native", "treelik_nni_test.cpp")] + [os.path.join(host, f) for f in ("model_factory.cpp", "phytree.cpp", "alphabet.cpp", "host_threads.cpp")]
+    src = [os.path.join(ROOT, "tests", "native", "treelik_nni_test.cpp")] + [os.path.join(host, f) for f in TREELIK_HOST_SOURCES]
     cases = [N.make_case(*k) for k in NATIVE_CASES] + [leaf_case(), many_candidates_case()]
     bad = _bad_cases()
     path = str(d / "cases.bin")

@@ -18,6 +18,7 @@ import gen
 import mldist_general_ref as M
 import test_cpu_treelik_shapes as SH
 import treelik_ref as R
+from treelik_sources import TREELIK_HOST_SOURCES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = ("ml_tree_s", "ml_rounds", "ml_evaluations", "ml_lnl_start", "ml_lnl", "ml_kernel_ms")
@@ -137,7 +138,7 @@ def _bad_cases():
 
 def test_host_loop_equals_the_statement(tmp_path):
     host = os.path.join(ROOT, "prographmsa_amd", "host")
-    src = [os.path.join(ROOT, "tests", "native", "treelik_test.cpp")] + [os.path.join(host, f) for f in ("model_factory.cpp", "phytree.cpp", "alphabet.cpp", "host_threads.cpp")]
+    src = [os.path.join(ROOT, "tests", "native", "treelik_test.cpp")] + [os.path.join(host, f) for f in TREELIK_HOST_SOURCES]
     cases = [R.make_case(*k) for k in NATIVE_CASES]
     bad = _bad_cases()
     path = str(tmp_path / "cases.txt")
