@@ -505,7 +505,7 @@ int pgm_tree_likelihood(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t n
                         uint32_t ncols, const int8_t *rows /* nleaves x ncols */, const double *pi /* dim */,
                         const double *P /* (nnodes-1) x {1 or 3} x dim x dim */, int derivs,
                         double *site_l /* ncols */, int32_t *site_k /* ncols */, double *d1, double *d2 /* nnodes-1, derivs only */);
-float pgm_treelik_last_kernel_ms(pgm_ctx *ctx);   /* device time of the kernels of the last pgm_tree_likelihood, pgm_tree_likelihood_rates, pgm_tree_ancestral or pgm_tree_nni call */
+float pgm_treelik_last_kernel_ms(pgm_ctx *ctx);   /* device time of the kernels of the last pgm_tree_likelihood, pgm_tree_likelihood_rates, pgm_tree_ancestral, pgm_tree_nni or pgm_tree_nni_edge call */
 
 /* ---- the same likelihood under a mixture of ncat rate categories (pgmsa --ml_tree --ml_gamma).
  * Everything from dim to pi, and derivs, d1, d2, is as in pgm_tree_likelihood, with the same checks.  ncat: 1 .. PGM_TREELIK_MAXCAT;
@@ -592,6 +592,34 @@ int pgm_tree_nni(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, 
                  const double *pi, uint32_t ncat, const double *w /* ncat */, const double *P /* ncat x (nnodes-1) x dim x dim */,
                  uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c /* ncand each */,
                  double *site_l /* ncols */, int32_t *site_k /* ncols */, double *post /* ncat x ncols */, double *rho /* ncand x ncols */);
+
+/* ---- the same interchanges, each at a trial length of its own central edge, with the derivatives of its log-likelihood by that
+ * length (pgmsa --ml_tree --ml_search / --ml_support with --ml_nni_opt).
+ * Everything from dim to cand_c, and site_l, site_k, post, is as in pgm_tree_nni, with the same checks.  Pc: ncat x ncand x 3 x dim x
+ * dim doubles, category-major, every matrix column-major: for category k and candidate q the three matrices P, P', P'' back to back
+ * of the edge above v = cand_v[q] in the neighbour tree at that candidate's trial length, the category's rate folded in (P(r_k t),
+ * r_k Q P, r_k^2 Q Q P: what pgm_tree_likelihood_rates reads for an edge with derivs).  The device sees no rates and no lengths.
+ * Per category k, site s and candidate: B_u, R, T, S_a, S_c, X_D = T S_a, Y_D = R S_c, X_N = T S_c, Y_N = R S_a, the scaling rule, the
+ * counts k_D and k_N, and D = sum_i Y_D(i) (sum_j P_v(i, j) X_D(j)) exactly as in pgm_tree_nni, P_v the tree's own matrix from P.  Then
+ *   for Z = P, P', P'' of Pc[k][q]:  W^Z(i) = sum_j Z(i, j) X_N(j), j ascending from 0.0;  N^Z = sum_i Y_N(i) W^Z(i), i ascending from 0.0
+ *   r^Z_k = 0.0 when D == 0.0, else N^Z / D multiplied by 2^-256 exactly (k_N - k_D) times, or by 2^256 exactly (k_D - k_N) times
+ *   rho = sum_k post_k r^P_k,  G = sum_k post_k r^P'_k,  Q = sum_k post_k r^P''_k  (k ascending from 0.0, one multiply and one add per term)
+ *   g = G / rho,  h = Q / rho - g * g;  both 0.0 when rho == 0.0
+ *   rho[q * ncols + s] = rho;  d1[q] = sum_s g,  d2[q] = sum_s h: sites ascending within consecutive chunks of PGM_TREELIK_CHUNK sites,
+ *   then the chunk sums ascending, as pgm_tree_likelihood sums an edge.
+ * D and post do not depend on the trial length, so d1[q] and d2[q] are the first and second derivative of the neighbour's
+ * log-likelihood by the length of its central edge, at the trial length.  Where the P block of Pc[k][q] equals P_v of category k, rho
+ * equals pgm_tree_nni's bit for bit.  Only + - * / occur and nothing is contracted: the values do not depend on the launch and equal
+ * the host statement's (tree_nni_edge_host) bit for bit.  site_l, site_k, post, rho, d1 and d2 (ncand each) are overwritten.
+ * Device memory: that of pgm_tree_nni, and 24 * ncat * ncand * dim * dim bytes for Pc, 16 * ncand * ncols for the per-site ratios,
+ * 16 * ncand * nchunks for the chunk sums (nchunks = ceil(ncols / PGM_TREELIK_CHUNK)) and 16 * ncand for d1 and d2.  Memory that
+ * cannot be had is PGM_ERR_NOMEM.  pgm_treelik_last_kernel_ms covers the call.
+ * PGM_ERR_INVALID, before anything is launched or an output is touched: what pgm_tree_nni refuses, a null Pc, d1 or d2. */
+int pgm_tree_nni_edge(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
+                      const double *pi, uint32_t ncat, const double *w /* ncat */, const double *P /* ncat x (nnodes-1) x dim x dim */,
+                      uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c /* ncand each */,
+                      const double *Pc /* ncat x ncand x 3 x dim x dim */, double *site_l /* ncols */, int32_t *site_k /* ncols */,
+                      double *post /* ncat x ncols */, double *rho /* ncand x ncols */, double *d1, double *d2 /* ncand each */);
 
 /* The sums of every row of a matrix over nrep resamplings of its columns (`pgmsa --ml_tree --ml_support`): with
  * x = log rho of pgm_tree_nni, the resampled log-likelihood gain of every neighbour of the tree in every bootstrap replicate.

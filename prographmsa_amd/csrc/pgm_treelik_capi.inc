@@ -1,7 +1,7 @@
 // pgm_treelik_capi.inc — C ABI of the tree likelihood and what is built on it (included by pgm_capi.hip): pgm_tree_likelihood
-// (pgmsa --ml_tree, DESIGN.md 3.17), pgm_tree_likelihood_rates (--ml_gamma, 3.18), pgm_tree_ancestral (--ml_ancestral, 3.19) and
-// pgm_tree_nni (--ml_search, 3.20).  The arguments are checked on the host and the children lists are built there
-// (pgm_treelik_check.h), then: one upload of the inputs, the launches, one copy back.  The four entries share five scratch slots,
+// (pgmsa --ml_tree, DESIGN.md 3.17), pgm_tree_likelihood_rates (--ml_gamma, 3.18), pgm_tree_ancestral (--ml_ancestral, 3.19),
+// pgm_tree_nni (--ml_search, 3.20) and pgm_tree_nni_edge (--ml_nni_opt, 3.22).  The arguments are checked on the host and the children lists are built there
+// (pgm_treelik_check.h), then: one upload of the inputs, the launches, one copy back.  The five entries share five scratch slots,
 // laid out by pgm_treelik_plan.h.  Stateless: nothing of a call is read by the next.
 extern "C" float pgm_treelik_last_kernel_ms(pgm_ctx *ctx) { return ctx ? ctx->treelik_ms : 0.0f; }
 
@@ -11,6 +11,7 @@ struct TreelikIn {
     uint32_t dim, nleaves, nnodes; const uint32_t *parent; uint32_t ncols; const int8_t *rows; const double *pi;
     uint32_t ncat; const double *w, *P; int derivs;   // (ncat, w: all but the plain entry)
     uint32_t ncand; const uint32_t *cand_v, *cand_a, *cand_c; bool full;
+    const double *Pc = nullptr;   // (pgm_tree_nni_edge alone)
 };
 static_assert(pgm_ctx::SC_TREELIK_OUT - pgm_ctx::SC_TREELIK_TREE == PGM_TL_SLOT_OUT, "the five slots in the order of pgm_treelik_plan.h");
 struct TreelikCall {
@@ -27,7 +28,7 @@ struct TreelikCall {
         std::string bad = mode != PGM_TREELIK_CALL_PLAIN ? pgm_treelik_check_rates(in.ncat, in.w) : std::string();
         std::vector<uint32_t> tree;   // child_off, then child
         if (bad.empty()) bad = pgm_treelik_check_tree(in.dim, in.nleaves, in.nnodes, in.parent, in.ncols, in.rows, tree);
-        if (bad.empty() && mode == PGM_TREELIK_CALL_NNI) bad = pgm_treelik_check_candidates(in.nleaves, in.nnodes, in.parent, in.ncand, in.cand_v, in.cand_a, in.cand_c);
+        if (bad.empty() && (mode == PGM_TREELIK_CALL_NNI || mode == PGM_TREELIK_CALL_NNI_EDGE)) bad = pgm_treelik_check_candidates(in.nleaves, in.nnodes, in.parent, in.ncand, in.cand_v, in.cand_a, in.cand_c);
         if (!bad.empty()) return fail(PGM_ERR_INVALID, bad);
         pl = pgm_treelik_plan(mode, in.dim, in.nleaves, in.nnodes, in.ncols, in.ncat, in.derivs != 0, in.ncand, in.full);
         c.emplace(ctx, what, &ctx->treelik_ms);
@@ -44,6 +45,7 @@ struct TreelikCall {
         }
         c->up(at<void>(PGM_TL_ROWS), in.rows, pl.r[PGM_TL_ROWS].bytes);
         c->up(at<void>(PGM_TL_P), in.P, pl.r[PGM_TL_P].bytes);
+        c->up(at<void>(PGM_TL_PC), in.Pc, pl.r[PGM_TL_PC].bytes);
 
         const bool cats = mode != PGM_TREELIK_CALL_PLAIN;   // the walk writes the categories' values; the combine kernel the outputs
         a.dim = in.dim; a.nleaves = in.nleaves; a.nnodes = in.nnodes; a.ncols = in.ncols; a.spb = PGM_TREELIK_THREADS / in.dim; a.derivs = in.derivs ? 1 : 0;
@@ -61,9 +63,9 @@ struct TreelikCall {
         cblocks = (uint32_t)(((uint64_t)in.ncols + PGM_TREELIK_THREADS - 1) / PGM_TREELIK_THREADS);
         return PGM_OK;
     }
-    // with derivs: the sums of the per-site ratios into D1 and D2
-    void launch_sums() {
-        hipLaunchKernelGGL(pgm_treelik_sums_kernel, dim3(pl.nedges), dim3(PGM_TREELIK_THREADS), 0, c->s, at<const double>(PGM_TL_G), at<const double>(PGM_TL_H), a.ncols,
+    // with derivs: the sums of the per-site ratios into D1 and D2, per edge (pgm_tree_nni_edge: `rows` candidates in their place)
+    void launch_sums(uint32_t rows) {
+        hipLaunchKernelGGL(pgm_treelik_sums_kernel, dim3(rows), dim3(PGM_TREELIK_THREADS), 0, c->s, at<const double>(PGM_TL_G), at<const double>(PGM_TL_H), a.ncols,
                            (uint32_t)pl.nchunks, at<double>(PGM_TL_PART), at<double>(PGM_TL_D1), at<double>(PGM_TL_D2));
     }
     // the outputs every entry has (post, d1, d2: where the call has them)
@@ -87,7 +89,7 @@ extern "C" int pgm_tree_likelihood(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves,
         return rc;
     if (t.c->begin()) {
         hipLaunchKernelGGL(pgm_treelik_kernel, dim3(t.blocks), dim3(PGM_TREELIK_THREADS), 0, t.c->s, t.a);
-        if (derivs) t.launch_sums();
+        if (derivs) t.launch_sums(t.pl.nedges);
     }
     t.c->end();
     t.down(site_l, site_k, nullptr, d1, d2);
@@ -107,7 +109,7 @@ extern "C" int pgm_tree_likelihood_rates(pgm_ctx *ctx, uint32_t dim, uint32_t nl
     if (t.c->begin()) {
         hipLaunchKernelGGL(pgm_treelik_cat_kernel<PGM_TREELIK_RAW>, dim3(t.blocks, ncat), dim3(PGM_TREELIK_THREADS), 0, t.c->s, t.a, t.st);
         hipLaunchKernelGGL(pgm_treelik_combine_kernel, dim3(t.cblocks, derivs ? std::min<uint32_t>(t.pl.nedges, 65535u) : 1u), dim3(PGM_TREELIK_THREADS), 0, t.c->s, t.m);
-        if (derivs) t.launch_sums();
+        if (derivs) t.launch_sums(t.pl.nedges);
     }
     t.c->end();
     t.down(site_l, site_k, post, d1, d2);
@@ -159,15 +161,49 @@ extern "C" int pgm_tree_nni(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32
     x.parent = t.at<const uint32_t>(PGM_TL_PARENT);
     x.cand_v = t.at<const uint32_t>(PGM_TL_CAND); x.cand_a = x.cand_v + ncand; x.cand_c = x.cand_a + ncand;
     x.post = t.m.post; x.rho = t.at<double>(PGM_TL_RHO);
+    x.Pc = nullptr; x.g = x.h = nullptr;
     const uint32_t per = t.a.spb * PGM_TREELIK_NNI_WAVES;   // sites per workgroup of the candidates' kernel
     const uint32_t xblocks = (uint32_t)(((uint64_t)ncols + per - 1) / per);
     if (t.c->begin()) {
         hipLaunchKernelGGL(pgm_treelik_cat_kernel<PGM_TREELIK_NNI>, dim3(t.blocks, ncat), dim3(PGM_TREELIK_THREADS), 0, t.c->s, t.a, t.st);
         hipLaunchKernelGGL(pgm_treelik_combine_kernel, dim3(t.cblocks, 1u), dim3(PGM_TREELIK_THREADS), 0, t.c->s, t.m);
-        hipLaunchKernelGGL(pgm_treelik_nni_kernel, dim3(xblocks, std::min<uint32_t>(ncand, 65535u)), dim3(PGM_TREELIK_NNI_THREADS), 0, t.c->s, x);   // (the kernel strides over the rest)
+        hipLaunchKernelGGL(pgm_treelik_nni_kernel<false>, dim3(xblocks, std::min<uint32_t>(ncand, 65535u)), dim3(PGM_TREELIK_NNI_THREADS), 0, t.c->s, x);   // (the kernel strides over the rest)
     }
     t.c->end();
     t.down(site_l, site_k, post, nullptr, nullptr);
+    t.c->down(rho, x.rho, t.pl.r[PGM_TL_RHO].bytes);
+    return t.c->finish();
+}
+
+// pgm_tree_nni with the candidates' own matrices of the edge above v: the same walk and combine launches, pgm_treelik_nni_kernel in
+// its EDGE form over (site block x candidate), which also writes the per-site g and h of every candidate, then
+// pgm_treelik_sums_kernel with the candidates in the place of the edges.
+extern "C" int pgm_tree_nni_edge(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
+                                 const double *pi, uint32_t ncat, const double *w, const double *P, uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a,
+                                 const uint32_t *cand_c, const double *Pc, double *site_l, int32_t *site_k, double *post, double *rho, double *d1, double *d2) {
+    if (!ctx) return fail(PGM_ERR_INVALID, "null argument");
+    ctx->treelik_ms = 0;
+    if (!parent || !rows || !pi || !w || !P || !site_l || !site_k || !post || !cand_v || !cand_a || !cand_c || !rho || !Pc || !d1 || !d2)
+        return fail(PGM_ERR_INVALID, "null argument");
+    TreelikCall t;
+    if (const int rc = t.open(ctx, "tree nni edge", PGM_TREELIK_CALL_NNI_EDGE, {dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, 0, ncand, cand_v, cand_a, cand_c, false, Pc}))
+        return rc;
+    PgmTreelikNniArgs x;
+    x.t = t.a; x.st = t.st; x.ncat = ncat; x.ncand = ncand;
+    x.parent = t.at<const uint32_t>(PGM_TL_PARENT);
+    x.cand_v = t.at<const uint32_t>(PGM_TL_CAND); x.cand_a = x.cand_v + ncand; x.cand_c = x.cand_a + ncand;
+    x.post = t.m.post; x.rho = t.at<double>(PGM_TL_RHO);
+    x.Pc = t.at<const double>(PGM_TL_PC); x.g = t.at<double>(PGM_TL_G); x.h = t.at<double>(PGM_TL_H);
+    const uint32_t per = t.a.spb * PGM_TREELIK_NNI_WAVES;
+    const uint32_t xblocks = (uint32_t)(((uint64_t)ncols + per - 1) / per);
+    if (t.c->begin()) {
+        hipLaunchKernelGGL(pgm_treelik_cat_kernel<PGM_TREELIK_NNI>, dim3(t.blocks, ncat), dim3(PGM_TREELIK_THREADS), 0, t.c->s, t.a, t.st);
+        hipLaunchKernelGGL(pgm_treelik_combine_kernel, dim3(t.cblocks, 1u), dim3(PGM_TREELIK_THREADS), 0, t.c->s, t.m);
+        hipLaunchKernelGGL(pgm_treelik_nni_kernel<true>, dim3(xblocks, std::min<uint32_t>(ncand, 65535u)), dim3(PGM_TREELIK_NNI_THREADS), 0, t.c->s, x);   // (the kernel strides over the rest)
+        t.launch_sums(ncand);
+    }
+    t.c->end();
+    t.down(site_l, site_k, post, d1, d2);
     t.c->down(rho, x.rho, t.pl.r[PGM_TL_RHO].bytes);
     return t.c->finish();
 }

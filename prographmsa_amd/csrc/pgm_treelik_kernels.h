@@ -13,6 +13,7 @@
 // of every inner node's states written where the node's outside vector was; pgm_treelik_anc_combine_kernel mixes the categories.
 // pgm_tree_nni is a fourth mode (PGM_TREELIK_NNI): that down pass without the posteriors, so the outside
 // vectors stay; pgm_treelik_nni_kernel then scores every nearest-neighbour interchange from four stored pieces around its edge.
+// pgm_tree_nni_edge is that kernel's second instantiation: the neighbour's edge with three matrices of its own.
 //
 // Every sum over states runs ascending from 0.0 with one multiply and one add per term (-ffp-contract=off): the bits are those of
 // tree_likelihood_host.  The walk is a chain of dependent steps on one wavefront, so what a step costs is the latency of its loads:
@@ -395,6 +396,11 @@ __global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_anc_combine_k
 // thread of state 0 adds Y(i) W(i) over the states ascending for both trees and takes the ratio.  No workgroup waits for another, there
 // are no atomics and every rho entry has one writer.  Every thread of the workgroup reaches every barrier: the loops over candidates,
 // categories and children are uniform.
+// EDGE (pgm_tree_nni_edge): the neighbour's W is formed three times, from P, P' and P'' of the candidate's own edge
+// above v (n.Pc: [category][candidate][3] matrices, read from global memory as the walk reads an edge's three), the tree's own from
+// P_v as before; four reductions (D, N, N', N'') through two more rows of shared memory; the thread of state 0 keeps rho, G and Q
+// across the categories and writes rho and the per-site g = G / rho and h = Q / rho - g g, which pgm_treelik_sums_kernel adds per
+// candidate.  The instantiation without EDGE is the kernel as it was: everything new stands behind `if constexpr (EDGE)`.
 #define PGM_TREELIK_NNI_WAVES 4
 #define PGM_TREELIK_NNI_THREADS (PGM_TREELIK_THREADS * PGM_TREELIK_NNI_WAVES)
 struct PgmTreelikNniArgs {
@@ -405,9 +411,13 @@ struct PgmTreelikNniArgs {
     const uint32_t *cand_v, *cand_a, *cand_c;
     const double *post;                    // ncat x ncols
     double *rho;                           // ncand x ncols
+    const double *Pc;                      // EDGE: ncat x ncand x 3 x dim x dim
+    double *g, *h;                         // EDGE: ncand x ncols each
 };
+template <bool EDGE>
 __global__ __launch_bounds__(PGM_TREELIK_NNI_THREADS) void pgm_treelik_nni_kernel(PgmTreelikNniArgs n) {
-    __shared__ double sh[8][PGM_TREELIK_NNI_THREADS];   // 0 .. 3: the four products before scaling; 4, 5: X_D, X_N scaled; 6, 7: Y W of D, N
+    // 0 .. 3: the four products before scaling; 4, 5: X_D, X_N scaled; 6, 7: Y W of D, N; EDGE: 8, 9: Y W of N', N''
+    __shared__ double sh[EDGE ? 10 : 8][PGM_TREELIK_NNI_THREADS];
     const uint32_t dim = n.t.dim, nleaves = n.t.nleaves, root = n.t.nnodes - 1, spb = n.t.spb, ncols = n.t.ncols;
     const uint32_t wave = threadIdx.x / PGM_TREELIK_THREADS, lane = threadIdx.x - wave * PGM_TREELIK_THREADS;
     const uint32_t local = lane / dim, i = lane - local * dim;
@@ -419,7 +429,7 @@ __global__ __launch_bounds__(PGM_TREELIK_NNI_THREADS) void pgm_treelik_nni_kerne
     for (uint32_t q = blockIdx.y; q < n.ncand; q += gridDim.y) {   // (uniform over the workgroup)
         const uint32_t v = n.cand_v[q], ca = n.cand_a[q], cc = n.cand_c[q], u = n.parent[v];
         const uint32_t u0 = n.t.child_off[u], u1 = n.t.child_off[u + 1], v0 = n.t.child_off[v], v1 = n.t.child_off[v + 1];
-        double rho = 0.0;
+        double rho = 0.0, G = 0.0, Q = 0.0;   // (G, Q: EDGE only)
         for (uint32_t k = 0; k < n.ncat; ++k) {
             PgmTreelikArgs a = n.t;
             a.P += n.st.P * k;
@@ -483,37 +493,83 @@ __global__ __launch_bounds__(PGM_TREELIK_NNI_THREADS) void pgm_treelik_nni_kerne
                 const double *col = a.P + mat * v + i, *xd = &sh[4][first], *xn = &sh[5][first];
                 double WD = 0.0, WN = 0.0;
                 uint32_t j = 0;
-                for (; j + 8 <= dim; j += 8) {
-                    double pv[8];
+                if constexpr (EDGE) {   // the neighbour's three sums from the candidate's own matrices, the tree's from P_v
+                    const double *cz = n.Pc + ((size_t)k * n.ncand + q) * 3 * mat + i;
+                    double W1 = 0.0, W2 = 0.0;
+                    for (; j + 8 <= dim; j += 8) {
+                        double pv[8], zv[3][8];
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) pv[e] = col[(size_t)dim * (j + e)];
+                        for (int e = 0; e < 8; ++e) {
+                            pv[e] = col[(size_t)dim * (j + e)];
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) { WD = WD + pv[e] * xd[j + e]; WN = WN + pv[e] * xn[j + e]; }
+                            for (int x = 0; x < 3; ++x) zv[x][e] = cz[mat * x + (size_t)dim * (j + e)];
+                        }
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) {
+                            WD = WD + pv[e] * xd[j + e];
+                            WN = WN + zv[0][e] * xn[j + e]; W1 = W1 + zv[1][e] * xn[j + e]; W2 = W2 + zv[2][e] * xn[j + e];
+                        }
+                    }
+                    for (; j < dim; ++j) {
+                        const double pj = col[(size_t)dim * j], z0 = cz[(size_t)dim * j], z1 = cz[mat + (size_t)dim * j], z2 = cz[2 * mat + (size_t)dim * j];
+                        WD = WD + pj * xd[j];
+                        WN = WN + z0 * xn[j]; W1 = W1 + z1 * xn[j]; W2 = W2 + z2 * xn[j];
+                    }
+                    sh[8][threadIdx.x] = YN * W1; sh[9][threadIdx.x] = YN * W2;
+                } else {
+                    for (; j + 8 <= dim; j += 8) {
+                        double pv[8];
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) pv[e] = col[(size_t)dim * (j + e)];
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) { WD = WD + pv[e] * xd[j + e]; WN = WN + pv[e] * xn[j + e]; }
+                    }
+                    for (; j < dim; ++j) { const double pj = col[(size_t)dim * j]; WD = WD + pj * xd[j]; WN = WN + pj * xn[j]; }
                 }
-                for (; j < dim; ++j) { const double pj = col[(size_t)dim * j]; WD = WD + pj * xd[j]; WN = WN + pj * xn[j]; }
                 sh[6][threadIdx.x] = YD * WD; sh[7][threadIdx.x] = YN * WN;
             }
             __syncthreads();
             if (active && i == 0) {
-                double D = 0.0, N = 0.0;
+                double D = 0.0, N = 0.0, N1 = 0.0, N2 = 0.0;
 #pragma unroll 8
-                for (uint32_t j = 0; j < dim; ++j) { D = D + sh[6][threadIdx.x + j]; N = N + sh[7][threadIdx.x + j]; }
-                double r = 0.0;
+                for (uint32_t j = 0; j < dim; ++j) {
+                    D = D + sh[6][threadIdx.x + j]; N = N + sh[7][threadIdx.x + j];
+                    if constexpr (EDGE) { N1 = N1 + sh[8][threadIdx.x + j]; N2 = N2 + sh[9][threadIdx.x + j]; }
+                }
+                double r = 0.0, r1 = 0.0, r2 = 0.0;
                 if (D != 0.0) {
                     r = N / D;
-                    for (int32_t d = kN - kD; d > 0; --d) r = r * 0x1p-256;
-                    for (int32_t d = kD - kN; d > 0; --d) r = r * 0x1p256;
+                    if constexpr (EDGE) { r1 = N1 / D; r2 = N2 / D; }
+                    for (int32_t d = kN - kD; d > 0; --d) {
+                        r = r * 0x1p-256;
+                        if constexpr (EDGE) { r1 = r1 * 0x1p-256; r2 = r2 * 0x1p-256; }
+                    }
+                    for (int32_t d = kD - kN; d > 0; --d) {
+                        r = r * 0x1p256;
+                        if constexpr (EDGE) { r1 = r1 * 0x1p256; r2 = r2 * 0x1p256; }
+                    }
                 }
-                rho = rho + n.post[(size_t)k * ncols + s] * r;
+                const double pk = n.post[(size_t)k * ncols + s];
+                rho = rho + pk * r;
+                if constexpr (EDGE) { G = G + pk * r1; Q = Q + pk * r2; }
             }
-            // (the next round writes sh[0 .. 3] only; sh[6], sh[7] are written again after two more barriers)
+            // (the next round writes sh[0 .. 3] only; sh[6 ..] are written again after two more barriers)
         }
-        if (active && i == 0) n.rho[(size_t)q * ncols + s] = rho;
+        if (active && i == 0) {
+            n.rho[(size_t)q * ncols + s] = rho;
+            if constexpr (EDGE) {
+                double g = 0.0, h = 0.0;
+                if (rho != 0.0) { g = G / rho; h = Q / rho - g * g; }
+                n.g[(size_t)q * ncols + s] = g;
+                n.h[(size_t)q * ncols + s] = h;
+            }
+        }
     }
 }
 
 // d1[e] = sum of g[e][.], d2[e] = sum of h[e][.]: sites ascending within chunks of PGM_TREELIK_CHUNK, then the chunk sums ascending.
 // A workgroup per edge; chunk sums into `part` (nedges x 2 x nchunks), then thread 0 adds those of g and thread 1 those of h.
+// pgm_tree_nni_edge runs it with its candidates in the place of the edges.
 __global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_sums_kernel(const double *g, const double *h, uint32_t ncols, uint32_t nchunks, double *part,
                                                                                 double *d1, double *d2) {
     const uint32_t e = blockIdx.x;

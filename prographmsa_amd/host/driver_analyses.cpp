@@ -74,7 +74,8 @@ void doBootstrap(const Alphabet &a, const DriverOptions &o, const Family &fam, c
 // FASTA of the inner nodes' most probable states; --ml_ancestral_tree: the tree with the nodes' names; --ml_ancestral_probs: a line
 // per node and column.  --ml_search N: up to N rounds of nearest-neighbour interchanges from the start tree, every
 // candidate of a round scored by one Backend::tree_nni call (the same route); --ml_start FILE: a newick in place of the BioNJ tree;
-// --ml_search_log FILE: a line per round
+// --ml_search_log FILE: a line per round; --ml_nni_opt N: the candidates of the search and of --ml_support each at a
+// central length of their own, N Newton rounds by Backend::tree_nni_edge calls (the same route)
 // the names of the inner nodes of a numbered tree, N1 .. in node order; a leaf that has one of them is an error()
 static std::vector<std::string> ml_ancestral_names(const MlTreeTopology &topo) {
     std::vector<std::string> node_name(topo.nnodes - topo.nleaves);
@@ -162,8 +163,10 @@ static void write_ml_support(const Alphabet &a, const MlTreeOpts &mo, const Fami
     if (res.rates.empty()) treelik_matrices(*fam.model_factory, res.lengths, false, P);
     else treelik_matrices(*fam.model_factory, res.lengths, false, res.rates, P);
     const std::vector<uint32_t> cols = bootstrap_columns(nrep, ncols, mo.support_seed);
+    MlSupportOpt opt;   // --ml_nni_opt: every neighbour at a central length of its own
+    opt.rounds = mo.nni_opt_given ? (uint32_t)mo.nni_opt : 0u; opt.mf = fam.model_factory.get(); opt.rates = &res.rates; opt.lengths = &res.lengths;
     const std::vector<MlSupportNode> nodes = ml_branch_support(dim, nleaves, nnodes, topo.parent.data(), ncols, flat.data(), fam.model_factory->freqs().data(), ncat, w.data(),
-                                                               P.data(), nrep, cols.data(), be);
+                                                               P.data(), nrep, cols.data(), be, kSupportBytes, &opt);
     std::map<const PhyTree *, std::string> labels;
     char buf[160];
     for (const MlSupportNode &s : nodes) {
@@ -208,7 +211,8 @@ void doMlTree(const Alphabet &a, const DriverOptions &o, const Family &fam, cons
     if (mo.anc_given) (void)ml_ancestral_names(ml_tree_topology(*tree));   // (refused before the optimiser runs and before any file is written)
     MlTreeResult res;
     if (mo.search_given) {   // --ml_search: every file below describes the searched tree
-        MlSearchResult found = ml_topology_search(a, values, *fam.model_factory, *tree, (uint32_t)mo.search, (uint32_t)mo.rounds, mo.eps, be, gamma);
+        MlSearchResult found = ml_topology_search(a, values, *fam.model_factory, *tree, (uint32_t)mo.search, (uint32_t)mo.rounds, mo.eps, be, gamma,
+                                                  mo.nni_opt_given ? (uint32_t)mo.nni_opt : 0u);
         tree = std::move(found.tree);
         res = std::move(found.res);
         if (mo.anc_given) (void)ml_ancestral_names(ml_tree_topology(*tree));

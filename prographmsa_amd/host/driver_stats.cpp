@@ -57,6 +57,9 @@ void print_stats(const DriverOptions &o, double t_init, double t_tree, double t_
     if (o.mltree.support_given)   // (keys of --ml_support only)
         fprintf(stderr, ", \"ml_support_s\": %.6f, \"ml_support_nodes\": %llu, \"ml_support_calls\": %llu, \"ml_support_kernel_ms\": %.3f", ml_support_stats.seconds,
                 (unsigned long long)ml_support_stats.nodes, (unsigned long long)ml_support_stats.calls, ml_support_stats.kernel_ms);
+    if (o.mltree.nni_opt_given)   // (keys of --ml_nni_opt only)
+        fprintf(stderr, ", \"ml_nni_opt_s\": %.6f, \"ml_nni_opt_calls\": %llu, \"ml_nni_opt_kernel_ms\": %.3f", ml_nni_opt_stats.seconds,
+                (unsigned long long)ml_nni_opt_stats.calls, ml_nni_opt_stats.kernel_ms);
     if (batch)   // (keys of --batch only)
         fprintf(stderr, ", \"batch_families\": %d, \"batch_failed\": %d, \"batch_chunks\": %d, \"batch_passes\": %llu, \"batch_levels\": %llu, "
                         "\"batch_align_calls\": %llu, \"batch_dist_calls\": %llu",

@@ -2,6 +2,8 @@
 #pragma once
 #include "pgm_host.h"
 
+#include <functional>
+
 namespace pgm {
 
 // --ml_tree: the likelihood of an alignment on a rooted tree and maximum-likelihood branch lengths on its fixed topology
@@ -32,7 +34,8 @@ namespace pgm {
 //   candidate (v ascending, a in child order, c in child order), the candidates of gain > eps by gain descending then index, picked
 //   greedily while no two share a node of {u, v, a, c}; the first m picked applied (m from all of them, halved while the evaluation at
 //   the carried lengths is not above lnL; none left: the search ends), then ml_branch_lengths again from the carried lengths and
-//   the shape in hand.  lnL never decreases.
+//   the shape in hand.  lnL never decreases.  With nni_opt the candidates are ranked by ml_nni_edge_lengths's gain_opt and an applied
+//   move gives the edge above v its t_opt.
 const double kMlMinLength = 1e-6, kMlMaxLength = 10.0;   // the interval every branch length stays in
 const double kMlMinAlpha = 0.05, kMlMaxAlpha = 100.0;     // ... and the shape of the gamma
 const uint32_t kMlAlphaEvaluations = 12, kMlMaxPairs = 20;   // one search on ln alpha; branch-length loop + search pairs at the most
@@ -88,6 +91,41 @@ void tree_nni_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32
                    double *site_l, int32_t *site_k, double *post, double *rho /* ncand x ncols */,
                    size_t block_bytes = kTreelikNniBlockBytes /* the partials and outside vectors held at a time, about; at least one column chunk */);
 void treelik_nni_gain(uint32_t ncand, uint32_t ncols, const double *rho, double *gain /* ncand */);
+// --ml_nni_opt (host/treelik_nni.cpp):
+// tree_nni_edge_host: pgm_tree_nni_edge blocked as tree_nni_host, the same contract and bits; Backend::tree_nni_edge's default.
+// ml_nni_edge_lengths: the central branch of every candidate re-optimised, every candidate at once.  Round 0 evaluates every candidate
+//   at the tree's own length of the edge above v (rho is tree_nni's bit for bit); rounds 1 .. `rounds` a trial
+//   clamp(t_best + lambda (clamp(target) - t_best)), target = d2 < 0 ? t - d1 / d2 : d1 > 0 ? 2 t : t / 2 from the derivatives at t_best
+//   (ml_branch_lengths's rule, the clamp to kMlMinLength .. kMlMaxLength).  A trial whose gain (treelik_nni_gain of its row) is higher
+//   becomes the best, takes its derivatives, keeps its rho row and sets lambda to 1; otherwise lambda halves.  So gain_opt[q] is never
+//   below the gain at the tree's own length.  rates: empty for one rate; P, lengths: the tree's matrices (P alone) and lengths.  The
+//   candidates go in groups whose Pc stays within pc_bytes, one tree_nni_edge call per group and round.
+const size_t kNniEdgeBytes = (size_t)256 << 20;   // Pc of one tree_nni_edge call
+void tree_nni_edge_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
+                        const double *w, const double *P, uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c,
+                        const double *Pc /* ncat x ncand x 3 x dim x dim */, double *site_l, int32_t *site_k, double *post, double *rho /* ncand x ncols */,
+                        double *d1, double *d2 /* ncand each */, size_t block_bytes = kTreelikNniBlockBytes);
+struct MlNniOptStats {   // `--ml_nni_opt --stats`
+    double seconds = 0, kernel_ms = 0;
+    uint64_t calls = 0;   // tree_nni_edge calls
+};
+extern MlNniOptStats ml_nni_opt_stats;
+struct MlNniEdgeResult {
+    std::vector<double> t_opt, gain_opt, rho;   // ncand; ncand; ncand x ncols, the rows at t_opt
+    std::vector<double> site_l, post;           // the tree's own, as tree_nni gives them
+    std::vector<int32_t> site_k;
+};
+MlNniEdgeResult ml_nni_edge_lengths(const ModelFactory &mf, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
+                                    const std::vector<double> &rates, const double *P /* ncat x (nnodes-1) x dim x dim */, const std::vector<double> &lengths /* nnodes - 1 */,
+                                    uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c, uint32_t rounds, Backend *be = nullptr,
+                                    size_t pc_bytes = kNniEdgeBytes);
+// ... and with the matrices of the trial lengths from the caller: matrices(t, Pc) writes Pc (ncat x t.size() x 3 x dim x dim) for the
+// candidates' lengths t, as treelik_matrices(mf, t, true, rates, Pc) does above
+typedef std::function<void(const std::vector<double> &t, std::vector<double> &Pc)> MlNniEdgeMatrices;
+MlNniEdgeResult ml_nni_edge_lengths(const MlNniEdgeMatrices &matrices, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols,
+                                    const int8_t *rows, const double *pi, uint32_t ncat, const double *w, const double *P, const std::vector<double> &lengths, uint32_t ncand,
+                                    const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c, uint32_t rounds, Backend *be = nullptr,
+                                    size_t pc_bytes = kNniEdgeBytes);
 struct MlSearchStats {   // `pgmsa --ml_tree --ml_search --stats`
     double seconds = 0, kernel_ms = 0;
     uint64_t rounds = 0, applied = 0, calls = 0;   // accepted rounds, moves applied in them, tree_nni calls
@@ -103,7 +141,8 @@ struct MlSearchResult {
     std::vector<MlSearchRound> log;
 };
 MlSearchResult ml_topology_search(const Alphabet &a, const std::vector<std::vector<int8_t>> &rows, const ModelFactory &model_factory, const PhyTree &start,
-                                  uint32_t search_rounds, uint32_t rounds, double eps, Backend *be = nullptr, const MlGamma &gamma = MlGamma());
+                                  uint32_t search_rounds, uint32_t rounds, double eps, Backend *be = nullptr, const MlGamma &gamma = MlGamma(),
+                                  uint32_t nni_opt = 0 /* --ml_nni_opt: the Newton rounds of ml_nni_edge_lengths, 0: rank at the lengths in hand */);
 // --ml_support (host/treelik_support.cpp):
 // resampled_sums_host: pgm_resampled_sums by a loop over rows x chunks of replicates on the host threads, the same contract and the
 //   same bits; what it rejects is an error().  Backend::resampled_sums's default.
@@ -125,13 +164,19 @@ struct MlSupportNode {
     double alrt = 0;
     uint32_t sh_hits = 0, rell_hits = 0;
 };
+struct MlSupportOpt {   // --ml_nni_opt for ml_branch_support: x = log of ml_nni_edge_lengths's rho rows at t_opt
+    uint32_t rounds = 0;
+    const ModelFactory *mf = nullptr;
+    const std::vector<double> *rates = nullptr, *lengths = nullptr;   // the categories' rates (empty: one rate), the tree's lengths
+};
 void resampled_sums_host(uint32_t nrow, uint32_t ncols, const double *x /* nrow x ncols */, uint32_t nrep, const uint32_t *cols /* nrep x ncols */,
                          double *out /* nrow x nrep */);
 void ml_support_candidates(uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, std::vector<uint32_t> &node, std::vector<uint32_t> &cand_v,
                            std::vector<uint32_t> &cand_a, std::vector<uint32_t> &cand_c);
 std::vector<MlSupportNode> ml_branch_support(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
                                              uint32_t ncat, const double *w, const double *P /* ncat x (nnodes-1) x dim x dim */, uint32_t nrep,
-                                             const uint32_t *cols /* nrep x ncols */, Backend *be = nullptr, size_t x_bytes = kSupportBytes);
+                                             const uint32_t *cols /* nrep x ncols */, Backend *be = nullptr, size_t x_bytes = kSupportBytes,
+                                             const MlSupportOpt *opt = nullptr);
 // a copy of `tree` whose edge above topo.node[e] has length lengths[e]
 PhyTree *ml_tree_with_lengths(const MlTreeTopology &topo, const std::vector<double> &lengths);
 

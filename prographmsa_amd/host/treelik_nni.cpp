@@ -1,7 +1,8 @@
 // treelik_nni.cpp — nearest-neighbour interchanges for `pgmsa --ml_tree --ml_search` (the walk and the checks are
 // treelik_internal.h's): the host statement of pgm_tree_nni (Backend::tree_nni's
 // default, what pgmsa_oracle runs), the gain of a candidate both drivers share, and the topology search, which is host code and the
-// same for every backend.
+// same for every backend.  For --ml_nni_opt: the host statement of pgm_tree_nni_edge and ml_nni_edge_lengths, the
+// optimiser of every candidate's central branch, host code the search and ml_branch_support (treelik_support.cpp) share.
 #include "treelik_internal.h"
 
 #include <chrono>
@@ -9,10 +10,13 @@
 namespace pgm {
 
 MlSearchStats ml_search_stats;
+MlNniOptStats ml_nni_opt_stats;
 
-void tree_nni_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
-                   const double *w, const double *P, uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c, double *site_l,
-                   int32_t *site_k, double *post, double *rho, size_t block_bytes) {
+namespace {
+// tree_nni_host (Pc, d1, d2 null) and tree_nni_edge_host: one body, so the pieces both share are formed by the same lines
+void tree_nni_body(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
+                   const double *w, const double *P, uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c, const double *Pc,
+                   double *site_l, int32_t *site_k, double *post, double *rho, double *d1, double *d2, size_t block_bytes) {
     if (!w || !post || !cand_v || !cand_a || !cand_c || !rho) error("tree likelihood: null argument");
     treelik_check_rates_host(ncat, w);
     const TreelikChildren ch = treelik_check_host(dim, nleaves, nnodes, parent, ncols, rows, pi, P, 0, site_l, site_k, nullptr, nullptr);
@@ -27,6 +31,7 @@ void tree_nni_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32
     const size_t block_chunks = std::min(nchunks, std::max<size_t>(1, block_bytes / per_chunk));
     const size_t cstride = vstride * block_chunks * kTreelikChunk;
     std::vector<double> U(cstride * ncat), O(cstride * ncat);
+    std::vector<double> c1(Pc ? (size_t)ncand * nchunks : 0), c2(c1.size());   // the chunk sums of g and h, [candidate][chunk]
     for (size_t chunk0 = 0; chunk0 < nchunks; chunk0 += block_chunks) {
         const size_t chunks_here = std::min(block_chunks, nchunks - chunk0), site0 = chunk0 * kTreelikChunk;
 
@@ -64,8 +69,9 @@ void tree_nni_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32
             const size_t chunk = chunk0 + item % chunks_here;
             const uint32_t s0 = (uint32_t)(chunk * kTreelikChunk), s1 = (uint32_t)std::min<size_t>(ncols, (size_t)s0 + kTreelikChunk);
             std::vector<double> S(dim), R(dim), T(dim), Sa(dim), Sc(dim), X(dim), Y(dim);
+            double a1 = 0.0, a2 = 0.0;
             for (uint32_t s = s0; s < s1; ++s) {
-                double mixed = 0.0;
+                double mixed = 0.0, G = 0.0, Q = 0.0;
                 for (uint32_t k = 0; k < ncat; ++k) {
                     const double *Pk = P + pstride * k, *Uk = &U[cstride * k + vstride * (s - site0)], *Ok = &O[cstride * k + vstride * (s - site0)];
                     auto apply = [&](uint32_t x, double *out) {
@@ -96,29 +102,72 @@ void tree_nni_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32
                     }
                     apply(a, Sa.data());
                     apply(c, Sc.data());
-                    double A[2];
+                    double A[2], A12[2] = {0.0, 0.0};   // (A12: the neighbour's sums under P' and P'', with Pc only)
                     int32_t count[2];
                     for (int side = 0; side < 2; ++side) {   // the tree as it is, then the neighbour
                         const double *Sx = side == 0 ? Sa.data() : Sc.data(), *Sy = side == 0 ? Sc.data() : Sa.data();
                         for (uint32_t i = 0; i < dim; ++i) { X[i] = T[i] * Sx[i]; Y[i] = R[i] * Sy[i]; }
                         count[side] = (treelik_rescale(X.data(), dim) ? 1 : 0) + (treelik_rescale(Y.data(), dim) ? 1 : 0);
-                        treelik_apply(Pk + mat * v, dim, X.data(), 0, S.data());   // W
+                        const double *Z = side == 1 && Pc ? Pc + ((size_t)k * ncand + q) * 3 * mat : Pk + mat * v;   // the neighbour's own edge above v
+                        treelik_apply(Z, dim, X.data(), 0, S.data());   // W
                         double acc = 0.0;
                         for (uint32_t i = 0; i < dim; ++i) acc = acc + Y[i] * S[i];
                         A[side] = acc;
+                        for (int x = 1; side == 1 && Pc && x < 3; ++x) {
+                            treelik_apply(Z + mat * x, dim, X.data(), 0, S.data());
+                            acc = 0.0;
+                            for (uint32_t i = 0; i < dim; ++i) acc = acc + Y[i] * S[i];
+                            A12[x - 1] = acc;
+                        }
                     }
-                    double r = 0.0;
+                    double r = 0.0, r1 = 0.0, r2 = 0.0;
                     if (A[0] != 0.0) {
-                        r = A[1] / A[0];
-                        for (int32_t d = count[1] - count[0]; d > 0; --d) r = r * kTreelikTiny;
-                        for (int32_t d = count[0] - count[1]; d > 0; --d) r = r * kTreelikScale;
+                        r = A[1] / A[0]; r1 = A12[0] / A[0]; r2 = A12[1] / A[0];
+                        for (int32_t d = count[1] - count[0]; d > 0; --d) { r = r * kTreelikTiny; r1 = r1 * kTreelikTiny; r2 = r2 * kTreelikTiny; }
+                        for (int32_t d = count[0] - count[1]; d > 0; --d) { r = r * kTreelikScale; r1 = r1 * kTreelikScale; r2 = r2 * kTreelikScale; }
                     }
-                    mixed = mixed + post[(size_t)k * ncols + s] * r;
+                    const double pk = post[(size_t)k * ncols + s];
+                    mixed = mixed + pk * r;
+                    G = G + pk * r1;
+                    Q = Q + pk * r2;
                 }
                 rho[(size_t)q * ncols + s] = mixed;
+                if (Pc) {
+                    double g = 0.0, h = 0.0;
+                    if (mixed != 0.0) { g = G / mixed; h = Q / mixed - g * g; }
+                    a1 = a1 + g;
+                    a2 = a2 + h;
+                }
             }
+            if (Pc) { c1[(size_t)q * nchunks + chunk] = a1; c2[(size_t)q * nchunks + chunk] = a2; }
         });
     }
+    for (uint32_t q = 0; Pc && q < ncand; ++q) {   // the chunk sums ascending
+        double a1 = 0.0, a2 = 0.0;
+        for (size_t chunk = 0; chunk < nchunks; ++chunk) { a1 = a1 + c1[(size_t)q * nchunks + chunk]; a2 = a2 + c2[(size_t)q * nchunks + chunk]; }
+        d1[q] = a1;
+        d2[q] = a2;
+    }
+}
+}  // namespace
+
+void tree_nni_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
+                   const double *w, const double *P, uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c, double *site_l,
+                   int32_t *site_k, double *post, double *rho, size_t block_bytes) {
+    tree_nni_body(dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, ncand, cand_v, cand_a, cand_c, nullptr, site_l, site_k, post, rho, nullptr, nullptr, block_bytes);
+}
+
+void tree_nni_edge_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
+                        const double *w, const double *P, uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c, const double *Pc,
+                        double *site_l, int32_t *site_k, double *post, double *rho, double *d1, double *d2, size_t block_bytes) {
+    if (!Pc || !d1 || !d2) error("tree likelihood: null argument");
+    tree_nni_body(dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, ncand, cand_v, cand_a, cand_c, Pc, site_l, site_k, post, rho, d1, d2, block_bytes);
+}
+
+void Backend::tree_nni_edge(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
+                            const double *w, const double *P, uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c, const double *Pc,
+                            double *site_l, int32_t *site_k, double *post, double *rho, double *d1, double *d2, int) {
+    tree_nni_edge_host(dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, ncand, cand_v, cand_a, cand_c, Pc, site_l, site_k, post, rho, d1, d2);
 }
 
 void Backend::tree_nni(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
@@ -133,6 +182,60 @@ void treelik_nni_gain(uint32_t ncand, uint32_t ncols, const double *rho, double 
         for (uint32_t s = 0; s < ncols; ++s) acc = acc + std::log(rho[(size_t)q * ncols + s]);   // (log 0 is -infinity)
         gain[q] = acc;
     }
+}
+
+MlNniEdgeResult ml_nni_edge_lengths(const ModelFactory &mf, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
+                                    const std::vector<double> &rates, const double *P, const std::vector<double> &lengths, uint32_t ncand, const uint32_t *cand_v,
+                                    const uint32_t *cand_a, const uint32_t *cand_c, uint32_t rounds, Backend *be, size_t pc_bytes) {
+    const uint32_t ncat = rates.empty() ? 1u : (uint32_t)rates.size();
+    const std::vector<double> r = rates.empty() ? std::vector<double>(1, 1.0) : rates;   // (one rate of 1.0: 1.0 * x is exact, the matrices are the plain ones)
+    const std::vector<double> w(ncat, rates.empty() ? 1.0 : 1.0 / (double)ncat);
+    return ml_nni_edge_lengths([&](const std::vector<double> &t, std::vector<double> &Pc) { treelik_matrices(mf, t, true, r, Pc); }, (uint32_t)mf.dim(), nleaves, nnodes, parent,
+                               ncols, rows, mf.freqs().data(), ncat, w.data(), P, lengths, ncand, cand_v, cand_a, cand_c, rounds, be, pc_bytes);
+}
+
+MlNniEdgeResult ml_nni_edge_lengths(const MlNniEdgeMatrices &matrices, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols,
+                                    const int8_t *rows, const double *pi, uint32_t ncat, const double *w, const double *P, const std::vector<double> &lengths, uint32_t ncand,
+                                    const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c, uint32_t rounds, Backend *be, size_t pc_bytes) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!cand_v || ncand == 0) error("tree nni: no candidate");
+    for (uint32_t q = 0; q < ncand; ++q)
+        if (cand_v[q] >= lengths.size()) error("tree nni: candidate %u: v is not an inner node below the root", q);
+    MlNniEdgeResult out;
+    out.t_opt.resize(ncand); out.gain_opt.resize(ncand); out.rho.resize((size_t)ncand * ncols);
+    out.site_l.resize(ncols); out.site_k.resize(ncols); out.post.resize((size_t)ncat * ncols);
+    auto clamp = [](double x) { return x < kMlMinLength ? kMlMinLength : x > kMlMaxLength ? kMlMaxLength : x; };
+    // the candidates in groups whose Pc stays within pc_bytes; every group is a call, which walks the tree again (the entries are stateless)
+    const size_t per_call = std::max<size_t>(1, pc_bytes / (24 * (size_t)ncat * dim * dim));
+    std::vector<double> best_d1(ncand), best_d2(ncand), lambda(ncand, 1.0), trial(ncand), d1(ncand), d2(ncand), gain(ncand), rho((size_t)ncand * ncols), Pc, tg;
+    for (uint32_t round = 0; round <= rounds; ++round) {
+        for (uint32_t q = 0; q < ncand; ++q) {
+            if (round == 0) { trial[q] = lengths[cand_v[q]]; continue; }   // the tree's own length: rho is tree_nni's
+            const double t = out.t_opt[q], target = best_d2[q] < 0 ? t - best_d1[q] / best_d2[q] : best_d1[q] > 0 ? 2 * t : t / 2;
+            trial[q] = clamp(t + lambda[q] * (clamp(target) - t));
+        }
+        for (size_t q0 = 0; q0 < ncand; q0 += per_call) {
+            const uint32_t g = (uint32_t)std::min<size_t>(per_call, ncand - q0);
+            tg.assign(trial.begin() + q0, trial.begin() + q0 + g);
+            matrices(tg, Pc);
+            double *rh = rho.data() + q0 * ncols;
+            if (be) be->tree_nni_edge(dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, g, cand_v + q0, cand_a + q0, cand_c + q0, Pc.data(), out.site_l.data(),
+                                      out.site_k.data(), out.post.data(), rh, d1.data() + q0, d2.data() + q0);
+            else tree_nni_edge_host(dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, g, cand_v + q0, cand_a + q0, cand_c + q0, Pc.data(), out.site_l.data(),
+                                    out.site_k.data(), out.post.data(), rh, d1.data() + q0, d2.data() + q0);
+            ++ml_nni_opt_stats.calls;
+        }
+        // the gains: candidates on the host threads, each sum in site order (treelik_nni_gain of the row)
+        parallel_for(ncand, [&](size_t q) { treelik_nni_gain(1, ncols, rho.data() + q * ncols, &gain[q]); });
+        for (uint32_t q = 0; q < ncand; ++q) {
+            if (round == 0 || gain[q] > out.gain_opt[q]) {
+                out.t_opt[q] = trial[q]; out.gain_opt[q] = gain[q]; best_d1[q] = d1[q]; best_d2[q] = d2[q]; lambda[q] = 1.0;
+                std::copy(rho.begin() + (size_t)q * ncols, rho.begin() + (size_t)(q + 1) * ncols, out.rho.begin() + (size_t)q * ncols);
+            } else lambda[q] = lambda[q] * 0.5;
+        }
+    }
+    ml_nni_opt_stats.seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return out;
 }
 
 namespace {
@@ -162,7 +265,7 @@ PhyTree *ml_search_build(const MlSearchTree &t, uint32_t v) {
 }  // namespace
 
 MlSearchResult ml_topology_search(const Alphabet &a, const std::vector<std::vector<int8_t>> &rows, const ModelFactory &model_factory, const PhyTree &start,
-                                  uint32_t search_rounds, uint32_t rounds, double eps, Backend *be, const MlGamma &gamma) {
+                                  uint32_t search_rounds, uint32_t rounds, double eps, Backend *be, const MlGamma &gamma, uint32_t nni_opt) {
     const auto t0 = std::chrono::steady_clock::now();
     MlSearchResult out;
     out.tree.reset(start.copy());
@@ -190,16 +293,24 @@ MlSearchResult ml_topology_search(const Alphabet &a, const std::vector<std::vect
         const uint32_t ncand = (uint32_t)cv.size();
         const uint32_t ncat = out.res.rates.empty() ? 1u : (uint32_t)out.res.rates.size();
         const std::vector<double> w(ncat, out.res.rates.empty() ? 1.0 : 1.0 / (double)ncat);
-        std::vector<double> P, site_l(ncols), post((size_t)ncat * ncols), rho((size_t)ncand * ncols), gain(ncand);
+        std::vector<double> P, site_l(ncols), post((size_t)ncat * ncols), rho(nni_opt ? 0 : (size_t)ncand * ncols), gain(ncand);
         std::vector<int32_t> site_k(ncols);
         if (out.res.rates.empty()) treelik_matrices(model_factory, out.res.lengths, false, P);
         else treelik_matrices(model_factory, out.res.lengths, false, out.res.rates, P);
-        if (be) be->tree_nni(dim, nleaves, nnodes, topo.parent.data(), ncols, flat.data(), pi, ncat, w.data(), P.data(), ncand, cv.data(), ca.data(), cc.data(), site_l.data(),
-                             site_k.data(), post.data(), rho.data());
-        else tree_nni_host(dim, nleaves, nnodes, topo.parent.data(), ncols, flat.data(), pi, ncat, w.data(), P.data(), ncand, cv.data(), ca.data(), cc.data(), site_l.data(),
-                           site_k.data(), post.data(), rho.data());
+        std::vector<double> t_opt;   // with nni_opt: the central length every candidate is ranked at
+        if (nni_opt) {
+            MlNniEdgeResult opt = ml_nni_edge_lengths(model_factory, nleaves, nnodes, topo.parent.data(), ncols, flat.data(), out.res.rates, P.data(), out.res.lengths, ncand, cv.data(),
+                                                      ca.data(), cc.data(), nni_opt, be);
+            gain.swap(opt.gain_opt);
+            t_opt.swap(opt.t_opt);
+        } else {
+            if (be) be->tree_nni(dim, nleaves, nnodes, topo.parent.data(), ncols, flat.data(), pi, ncat, w.data(), P.data(), ncand, cv.data(), ca.data(), cc.data(), site_l.data(),
+                                 site_k.data(), post.data(), rho.data());
+            else tree_nni_host(dim, nleaves, nnodes, topo.parent.data(), ncols, flat.data(), pi, ncat, w.data(), P.data(), ncand, cv.data(), ca.data(), cc.data(), site_l.data(),
+                               site_k.data(), post.data(), rho.data());
+            treelik_nni_gain(ncand, ncols, rho.data(), gain.data());
+        }
         ++ml_search_stats.calls;
-        treelik_nni_gain(ncand, ncols, rho.data(), gain.data());
         line.best_gain = *std::max_element(gain.begin(), gain.end());
         // the candidates above the threshold by gain descending, then by index; picked greedily while they share no node
         std::vector<uint32_t> order;
@@ -223,6 +334,7 @@ MlSearchResult ml_topology_search(const Alphabet &a, const std::vector<std::vect
                 const uint32_t q = picked[p], v = cv[q], u = topo.parent[v];
                 *std::find(next.kids[v].begin(), next.kids[v].end(), ca[q]) = cc[q];
                 *std::find(next.kids[u].begin(), next.kids[u].end(), cc[q]) = ca[q];
+                if (nni_opt) next.length[v] = t_opt[q];   // the length the move was ranked at
             }
             std::unique_ptr<PhyTree> tree(ml_search_build(next, next.root));
             // one evaluation without derivatives at the carried lengths and the rates in hand (ml_tree_topology numbers the new tree)

@@ -56,7 +56,8 @@ void ml_support_candidates(uint32_t nleaves, uint32_t nnodes, const uint32_t *pa
 }
 
 std::vector<MlSupportNode> ml_branch_support(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
-                                             uint32_t ncat, const double *w, const double *P, uint32_t nrep, const uint32_t *cols, Backend *be, size_t x_bytes) {
+                                             uint32_t ncat, const double *w, const double *P, uint32_t nrep, const uint32_t *cols, Backend *be, size_t x_bytes,
+                                             const MlSupportOpt *opt) {
     const auto t0 = std::chrono::steady_clock::now();
     if (nrep == 0 || !cols) error("ml support: no replicate");
     std::vector<uint32_t> node, cv, ca, cc;
@@ -72,7 +73,11 @@ std::vector<MlSupportNode> ml_branch_support(uint32_t dim, uint32_t nleaves, uin
     std::vector<double> site_l(ncols), post((size_t)ncat * ncols), x((size_t)ncand * ncols), gain(ncand);
     std::vector<int32_t> site_k(ncols);
     const double nni_ms = ml_search_stats.kernel_ms;   // (the search's key counts its own calls alone)
-    if (be) be->tree_nni(dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, ncand, cv.data(), ca.data(), cc.data(), site_l.data(), site_k.data(), post.data(), x.data());
+    if (opt && opt->rounds) {   // every neighbour at its own central length
+        MlNniEdgeResult found = ml_nni_edge_lengths(*opt->mf, nleaves, nnodes, parent, ncols, rows, *opt->rates, P, *opt->lengths, ncand, cv.data(), ca.data(), cc.data(),
+                                                    opt->rounds, be);
+        x.swap(found.rho);
+    } else if (be) be->tree_nni(dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, ncand, cv.data(), ca.data(), cc.data(), site_l.data(), site_k.data(), post.data(), x.data());
     else tree_nni_host(dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, ncand, cv.data(), ca.data(), cc.data(), site_l.data(), site_k.data(), post.data(), x.data());
     ml_support_stats.kernel_ms += ml_search_stats.kernel_ms - nni_ms;
     ml_search_stats.kernel_ms = nni_ms;
