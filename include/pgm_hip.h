@@ -505,7 +505,7 @@ int pgm_tree_likelihood(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t n
                         uint32_t ncols, const int8_t *rows /* nleaves x ncols */, const double *pi /* dim */,
                         const double *P /* (nnodes-1) x {1 or 3} x dim x dim */, int derivs,
                         double *site_l /* ncols */, int32_t *site_k /* ncols */, double *d1, double *d2 /* nnodes-1, derivs only */);
-float pgm_treelik_last_kernel_ms(pgm_ctx *ctx);   /* device time of the kernels of the last pgm_tree_likelihood, pgm_tree_likelihood_rates, pgm_tree_ancestral, pgm_tree_nni or pgm_tree_nni_edge call */
+float pgm_treelik_last_kernel_ms(pgm_ctx *ctx);   /* device time of the kernels of the last pgm_tree_likelihood, pgm_tree_likelihood_rates, pgm_tree_ancestral, pgm_tree_nni, pgm_tree_nni_edge or pgm_tree_spr call */
 
 /* ---- the same likelihood under a mixture of ncat rate categories (pgmsa --ml_tree --ml_gamma).
  * Everything from dim to pi, and derivs, d1, d2, is as in pgm_tree_likelihood, with the same checks.  ncat: 1 .. PGM_TREELIK_MAXCAT;
@@ -620,6 +620,53 @@ int pgm_tree_nni_edge(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nno
                       uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c /* ncand each */,
                       const double *Pc /* ncat x ncand x 3 x dim x dim */, double *site_l /* ncols */, int32_t *site_k /* ncols */,
                       double *post /* ncat x ncols */, double *rho /* ncand x ncols */, double *d1, double *d2 /* ncand each */);
+
+/* ---- subtree pruning and regrafting on the same tree under the same mixture (pgmsa --ml_tree --ml_search --ml_spr).
+ * Everything from dim to P is as in pgm_tree_nni, with the same checks; site_l, site_k and post are pgm_tree_likelihood_rates's values
+ * with derivs == 0, bit for bit.  Ph: the shape of P, per category and edge the matrix of HALF that edge (the caller's choice of
+ * half; the category's rate folded in).  The device sees no lengths or rates and runs no transcendental function.
+ * Candidate q = (v, y) = (cand_v[q], cand_y[q]) prunes the subtree below v, with the edge above v and its matrix P_v, from
+ * p = parent[v], and regrafts it on the edge above y: that edge gets a new node n in its middle, both halves with Ph_y, the children
+ * of n are y and v.  The root stays and every matrix keeps its parent -> child direction (a generator need not be reversible).  Where
+ * p is left with one child s it is kept as a node of one child: P_p P_s is the matrix of the joined edge (Chapman-Kolmogorov).
+ * Valid: v and y are not the root, y is not in the subtree of v (v itself included), p is not a root of exactly two children, and
+ * where p has exactly two children y is neither p nor the sibling of v (both give the tree itself).
+ * The path: a the lowest common ancestor of p and y (a node is its own ancestor); up a_0 = p, a_1 = parent[a_0], .., a_J = a; down
+ * a = c_0, c_1, .., c_M = y (M == 0: y is p or an ancestor of p); J + M <= PGM_TREE_SPR_MAXPATH edges.
+ * Per category k, site s and candidate, with S_x(i) = sum_j P_x(i, j) U_x(j) (the leaf rule for U), the stored scaled U and O of
+ * pgm_tree_nni, and the scaling rule with a count (largest of a vector's dim values below 2^-256 and above 0: the vector times 2^256,
+ * the count plus one).  Two chains, - without v and + with it, each with its own count k- or k+:
+ *   start (only where J >= 1 or M == 0): E-_0(i) = the product of S_c(i) over the children c of p other than v, in child order (it
+ *     starts with its first factor); E+_0(i) = E-_0(i) * S_v(i) (from the unscaled E-_0); the rule on each
+ *   up, j = 1 .. J: Mup(+-)(i) = sum_l P_{a_{j-1}}(i, l) E(+-)_{j-1}(l), l ascending from 0.0; if j < J or M == 0:
+ *     E(+-)_j(i) = Mup(+-)(i) times S_c(i) of the children c of a_j other than a_{j-1}, in child order (it starts with Mup); the rule
+ *   M == 0, the target on the up chain: Z(m) = sum_j Ph_y(m, j) E-_J(j); X(m) = S_v(m) * Z(m), the rule, counted into k-;
+ *     W(h) = sum_m Ph_y(h, m) X(m); N = sum_h O_y(h) * W(h); D = sum_h O_y(h) * (sum_j P_y(h, j) E+_J(j))
+ *   M >= 1, the turn: B_a(i) = pi[i] at the root, else sum_h O_a(h) P_a(h, i), h ascending from 0.0.  J >= 1: G(+-)_1(i) = B_a(i) *
+ *     Mup(+-)(i) (the Mup of j = J), times S_c(i) of the children c of a other than a_{J-1} and c_1, in child order.  J == 0:
+ *     G-_1(i) = B_a(i) times S_c(i) of the children of a other than v and c_1, in child order; G+_1(i) = G-_1(i) * S_v(i), before
+ *     either is scaled.  The rule on each.
+ *   down, m = 1 .. M - 1: Bc(+-)(i) = sum_h G(+-)_m(h) P_{c_m}(h, i), h ascending from 0.0; G(+-)_{m+1}(i) = Bc(+-)(i) times S_c(i) of
+ *     the children of c_m other than c_{m+1}, in child order; the rule
+ *   the target below the turn: Z(m) = sum_j Ph_y(m, j) U_y(j) (the leaf rule); X(m) = S_v(m) * Z(m), the rule into k-;
+ *     W(h) = sum_m Ph_y(h, m) X(m); N = sum_h G-_M(h) * W(h); D = sum_h G+_M(h) * S_y(h)
+ *   rho_k = 0.0 when D == 0.0, else N / D multiplied by 2^-256 exactly (k- - k+) times, or by 2^256 exactly (k+ - k-) times
+ *   rho[q * ncols + s] = sum_k post[k][s] * rho_k, k ascending from 0.0
+ * N and D are multilinear in the same stored pieces, so their unknown scale factors cancel: rho is the regrafted tree's site
+ * likelihood over the tree's own.  Every sum runs ascending from 0.0 with one multiply and one add per term, only + - * / occur and
+ * nothing is contracted: the values do not depend on the launch or on the order of the candidates and equal the host statement's
+ * (tree_spr_host) bit for bit.  site_l, site_k, post and rho are overwritten.
+ * Device memory: that of pgm_tree_nni without its candidates, and 8 * ncat * (nnodes-1) * dim * dim bytes for Ph,
+ * (4 + 4 * (PGM_TREE_SPR_MAXPATH + 4)) * ncand bytes for the candidates and their paths.  Memory that cannot be had is PGM_ERR_NOMEM.
+ * pgm_treelik_last_kernel_ms covers the call.
+ * PGM_ERR_INVALID, before anything is launched or an output is touched: what pgm_tree_nni refuses of the arguments they share, a null
+ * Ph, cand_v, cand_y or rho, ncand == 0, a candidate that is not valid, a path of more than PGM_TREE_SPR_MAXPATH edges. */
+#define PGM_TREE_SPR_MAXPATH 16
+int pgm_tree_spr(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
+                 const double *pi, uint32_t ncat, const double *w /* ncat */, const double *P /* ncat x (nnodes-1) x dim x dim */,
+                 const double *Ph /* as P: the matrix of half of every edge */, uint32_t ncand, const uint32_t *cand_v,
+                 const uint32_t *cand_y /* ncand each */, double *site_l /* ncols */, int32_t *site_k /* ncols */,
+                 double *post /* ncat x ncols */, double *rho /* ncand x ncols */);
 
 /* The sums of every row of a matrix over nrep resamplings of its columns (`pgmsa --ml_tree --ml_support`): with
  * x = log rho of pgm_tree_nni, the resampled log-likelihood gain of every neighbour of the tree in every bootstrap replicate.

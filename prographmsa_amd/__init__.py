@@ -93,7 +93,7 @@ EXPORTS = [
     "pgm_bionj_plan", "pgm_bionj_plan_multi",
     "pgm_msa_agreement", "pgm_agreement_last_kernel_ms",
     "pgm_transfer_min", "pgm_transfer_last_kernel_ms", "pgm_transfer_taxa",
-    "pgm_tree_likelihood", "pgm_treelik_last_kernel_ms", "pgm_tree_likelihood_rates", "pgm_tree_ancestral", "pgm_tree_nni", "pgm_tree_nni_edge",
+    "pgm_tree_likelihood", "pgm_treelik_last_kernel_ms", "pgm_tree_likelihood_rates", "pgm_tree_ancestral", "pgm_tree_nni", "pgm_tree_nni_edge", "pgm_tree_spr",
     "pgm_resampled_sums", "pgm_resample_last_kernel_ms",
 ]
 
@@ -191,6 +191,9 @@ def _load():
         "pgm_tree_nni_edge": (C.c_int, [vp, u32, u32, u32, C.POINTER(u32), u32, C.POINTER(C.c_int8), C.POINTER(C.c_double), u32, C.POINTER(C.c_double),
                                         C.POINTER(C.c_double), u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                         C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "pgm_tree_spr": (C.c_int, [vp, u32, u32, u32, C.POINTER(u32), u32, C.POINTER(C.c_int8), C.POINTER(C.c_double), u32, C.POINTER(C.c_double),
+                                   C.POINTER(C.c_double), C.POINTER(C.c_double), u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(i32),
+                                   C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "pgm_resampled_sums": (C.c_int, [vp, u32, u32, C.POINTER(C.c_double), u32, C.POINTER(u32), C.POINTER(C.c_double)]),
         "pgm_resample_last_kernel_ms": (C.c_float, [vp]),
     }
@@ -418,6 +421,33 @@ class Context:
                                     P_(P, C.c_double), ncand, P_(cv, C.c_uint32), P_(ca, C.c_uint32), P_(cc, C.c_uint32), P_(Pc, C.c_double), P_(out[0], C.c_double),
                                     P_(out[1], C.c_int32), P_(out[2], C.c_double), P_(out[3], C.c_double), P_(out[4], C.c_double), P_(out[5], C.c_double)),
               "pgm_tree_nni_edge")
+        return tuple(out)
+
+    def tree_spr(self, dim, parent, rows, pi, w, P, Ph, cand, out=None):
+        """pgm_tree_spr: inputs as tree_nni; Ph: the shape of P, the matrix of half of every edge; cand: ncand x 2 uint32, a row (v, y)
+        -> (site_l, site_k, post, rho (ncand x ncols float64)).  Given output arrays (a tuple of four, C-contiguous of those kinds) are
+        overwritten."""
+        import numpy as np
+        parent = np.ascontiguousarray(parent, np.uint32)
+        rows = np.ascontiguousarray(rows, np.int8)
+        pi = np.ascontiguousarray(pi, np.float64)
+        w = np.ascontiguousarray(w, np.float64)
+        P = np.ascontiguousarray(P, np.float64)
+        Ph = np.ascontiguousarray(Ph, np.float64)
+        cand = np.asarray(cand, np.uint32)
+        if (parent.ndim != 1 or rows.ndim != 2 or pi.shape != (dim,) or w.ndim != 1 or P.size != len(w) * (len(parent) - 1) * dim * dim or Ph.size != P.size
+                or cand.ndim != 2 or cand.shape[1] != 2):
+            raise ValueError("tree_spr: input array of the wrong shape")
+        nnodes, (nleaves, ncols), ncat, ncand = len(parent), rows.shape, len(w), len(cand)
+        cv, cy = (np.ascontiguousarray(cand[:, k]) for k in range(2))
+        kinds = [((ncols,), np.float64), ((ncols,), np.int32), ((ncat, ncols), np.float64), ((ncand, ncols), np.float64)]
+        if out is None: out = tuple(np.zeros(s, t) for s, t in kinds)
+        if len(out) != 4 or any(a.dtype != t or a.shape != s or not a.flags.c_contiguous for a, (s, t) in zip(out, kinds)):
+            raise ValueError("tree_spr: output array of the wrong kind")
+        P_ = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+        check(lib.pgm_tree_spr(self.handle, dim, nleaves, nnodes, P_(parent, C.c_uint32), ncols, P_(rows, C.c_int8), P_(pi, C.c_double), ncat, P_(w, C.c_double),
+                               P_(P, C.c_double), P_(Ph, C.c_double), ncand, P_(cv, C.c_uint32), P_(cy, C.c_uint32), P_(out[0], C.c_double), P_(out[1], C.c_int32),
+                               P_(out[2], C.c_double), P_(out[3], C.c_double)), "pgm_tree_spr")
         return tuple(out)
 
     def resampled_sums(self, x, cols, out=None):

@@ -1,7 +1,7 @@
 // pgm_treelik_capi.inc — C ABI of the tree likelihood and what is built on it (included by pgm_capi.hip): pgm_tree_likelihood
 // (pgmsa --ml_tree, DESIGN.md 3.17), pgm_tree_likelihood_rates (--ml_gamma, 3.18), pgm_tree_ancestral (--ml_ancestral, 3.19),
-// pgm_tree_nni (--ml_search, 3.20) and pgm_tree_nni_edge (--ml_nni_opt, 3.22).  The arguments are checked on the host and the children lists are built there
-// (pgm_treelik_check.h), then: one upload of the inputs, the launches, one copy back.  The five entries share five scratch slots,
+// pgm_tree_nni (--ml_search, 3.20), pgm_tree_nni_edge (--ml_nni_opt, 3.22) and pgm_tree_spr (--ml_spr, 3.23).  The arguments are checked on the host and the children lists are built there
+// (pgm_treelik_check.h), then: one upload of the inputs, the launches, one copy back.  The six entries share five scratch slots,
 // laid out by pgm_treelik_plan.h.  Stateless: nothing of a call is read by the next.
 extern "C" float pgm_treelik_last_kernel_ms(pgm_ctx *ctx) { return ctx ? ctx->treelik_ms : 0.0f; }
 
@@ -12,6 +12,7 @@ struct TreelikIn {
     uint32_t ncat; const double *w, *P; int derivs;   // (ncat, w: all but the plain entry)
     uint32_t ncand; const uint32_t *cand_v, *cand_a, *cand_c; bool full;
     const double *Pc = nullptr;   // (pgm_tree_nni_edge alone)
+    const double *Ph = nullptr; const uint32_t *cand_y = nullptr;   // (pgm_tree_spr alone)
 };
 static_assert(pgm_ctx::SC_TREELIK_OUT - pgm_ctx::SC_TREELIK_TREE == PGM_TL_SLOT_OUT, "the five slots in the order of pgm_treelik_plan.h");
 struct TreelikCall {
@@ -21,6 +22,7 @@ struct TreelikCall {
     PgmTreelikArgs a;
     PgmTreelikRatesStride st;
     PgmTreelikCombineArgs m;
+    std::vector<uint32_t> path;   // pgm_tree_spr: the candidates' paths (pgm_treelik_check_spr)
     uint32_t blocks, cblocks;     // of the walk (sites / spb) and of the combine kernel (sites / 64)
     template <class T> T *at(int region) const { return pl.r[region].bytes ? (T *)(slot[pl.r[region].slot] + pl.r[region].off) : nullptr; }
 
@@ -29,6 +31,7 @@ struct TreelikCall {
         std::vector<uint32_t> tree;   // child_off, then child
         if (bad.empty()) bad = pgm_treelik_check_tree(in.dim, in.nleaves, in.nnodes, in.parent, in.ncols, in.rows, tree);
         if (bad.empty() && (mode == PGM_TREELIK_CALL_NNI || mode == PGM_TREELIK_CALL_NNI_EDGE)) bad = pgm_treelik_check_candidates(in.nleaves, in.nnodes, in.parent, in.ncand, in.cand_v, in.cand_a, in.cand_c);
+        if (bad.empty() && mode == PGM_TREELIK_CALL_SPR) bad = pgm_treelik_check_spr(in.nnodes, in.parent, tree.data(), in.ncand, in.cand_v, in.cand_y, path);
         if (!bad.empty()) return fail(PGM_ERR_INVALID, bad);
         pl = pgm_treelik_plan(mode, in.dim, in.nleaves, in.nnodes, in.ncols, in.ncat, in.derivs != 0, in.ncand, in.full);
         c.emplace(ctx, what, &ctx->treelik_ms);
@@ -46,6 +49,9 @@ struct TreelikCall {
         c->up(at<void>(PGM_TL_ROWS), in.rows, pl.r[PGM_TL_ROWS].bytes);
         c->up(at<void>(PGM_TL_P), in.P, pl.r[PGM_TL_P].bytes);
         c->up(at<void>(PGM_TL_PC), in.Pc, pl.r[PGM_TL_PC].bytes);
+        c->up(at<void>(PGM_TL_PH), in.Ph, pl.r[PGM_TL_PH].bytes);
+        c->up(at<void>(PGM_TL_SPR_CAND), in.cand_v, pl.r[PGM_TL_SPR_CAND].bytes);   // (cand_y: the last node of a candidate's path)
+        c->up(at<void>(PGM_TL_SPR_PATH), path.data(), pl.r[PGM_TL_SPR_PATH].bytes);
 
         const bool cats = mode != PGM_TREELIK_CALL_PLAIN;   // the walk writes the categories' values; the combine kernel the outputs
         a.dim = in.dim; a.nleaves = in.nleaves; a.nnodes = in.nnodes; a.ncols = in.ncols; a.spb = PGM_TREELIK_THREADS / in.dim; a.derivs = in.derivs ? 1 : 0;
@@ -204,6 +210,35 @@ extern "C" int pgm_tree_nni_edge(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, u
     }
     t.c->end();
     t.down(site_l, site_k, post, d1, d2);
+    t.c->down(rho, x.rho, t.pl.r[PGM_TL_RHO].bytes);
+    return t.c->finish();
+}
+
+// The same walk and combine launches as pgm_tree_nni, then pgm_treelik_spr_kernel over (site block x candidate): a workgroup recomputes
+// the chain of its candidate from the paths pgm_treelik_check_spr wrote, so the order of the candidates changes no value.
+extern "C" int pgm_tree_spr(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
+                            const double *pi, uint32_t ncat, const double *w, const double *P, const double *Ph, uint32_t ncand, const uint32_t *cand_v,
+                            const uint32_t *cand_y, double *site_l, int32_t *site_k, double *post, double *rho) {
+    if (!ctx) return fail(PGM_ERR_INVALID, "null argument");
+    ctx->treelik_ms = 0;
+    if (!parent || !rows || !pi || !w || !P || !Ph || !site_l || !site_k || !post || !cand_v || !cand_y || !rho) return fail(PGM_ERR_INVALID, "null argument");
+    TreelikCall t;
+    TreelikIn in = {dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, 0, ncand, cand_v, nullptr, nullptr, false};
+    in.Ph = Ph; in.cand_y = cand_y;
+    if (const int rc = t.open(ctx, "tree spr", PGM_TREELIK_CALL_SPR, in)) return rc;
+    PgmTreelikSprArgs x;
+    x.t = t.a; x.st = t.st; x.ncat = ncat; x.ncand = ncand; x.stride = PGM_TREELIK_SPR_STRIDE;
+    x.cand_v = t.at<const uint32_t>(PGM_TL_SPR_CAND); x.path = t.at<const uint32_t>(PGM_TL_SPR_PATH);
+    x.Ph = t.at<const double>(PGM_TL_PH); x.post = t.m.post; x.rho = t.at<double>(PGM_TL_RHO);
+    const uint32_t per = t.a.spb * PGM_TREELIK_NNI_WAVES;   // sites per workgroup of the candidates' kernel
+    const uint32_t xblocks = (uint32_t)(((uint64_t)ncols + per - 1) / per);
+    if (t.c->begin()) {
+        hipLaunchKernelGGL(pgm_treelik_cat_kernel<PGM_TREELIK_NNI>, dim3(t.blocks, ncat), dim3(PGM_TREELIK_THREADS), 0, t.c->s, t.a, t.st);
+        hipLaunchKernelGGL(pgm_treelik_combine_kernel, dim3(t.cblocks, 1u), dim3(PGM_TREELIK_THREADS), 0, t.c->s, t.m);
+        hipLaunchKernelGGL(pgm_treelik_spr_kernel, dim3(xblocks, std::min<uint32_t>(ncand, 65535u)), dim3(PGM_TREELIK_NNI_THREADS), 0, t.c->s, x);   // (the kernel strides over the rest)
+    }
+    t.c->end();
+    t.down(site_l, site_k, post, nullptr, nullptr);
     t.c->down(rho, x.rho, t.pl.r[PGM_TL_RHO].bytes);
     return t.c->finish();
 }

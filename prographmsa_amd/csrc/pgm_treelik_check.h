@@ -65,4 +65,40 @@ inline std::string pgm_treelik_check_candidates(uint32_t nleaves, uint32_t nnode
     return std::string();
 }
 
+// The candidates of pgm_tree_spr on a tree that passed pgm_treelik_check_tree (child_off: the start of its children lists).  `path`
+// gets PGM_TREELIK_SPR_STRIDE values per candidate: J, M, then the J + M + 1 nodes a_0 = p .. a_J = a, c_1 .. c_M = y of the
+// interface's path (the rest of the stride is 0).
+#define PGM_TREELIK_SPR_STRIDE (PGM_TREE_SPR_MAXPATH + 4)
+inline std::string pgm_treelik_check_spr(uint32_t nnodes, const uint32_t *parent, const uint32_t *child_off, uint32_t ncand, const uint32_t *cand_v,
+                                         const uint32_t *cand_y, std::vector<uint32_t> &path) {
+    if (ncand == 0) return "tree spr: no candidate";
+    path.assign((size_t)ncand * PGM_TREELIK_SPR_STRIDE, 0);
+    for (uint32_t q = 0; q < ncand; ++q) {
+        const uint32_t v = cand_v[q], y = cand_y[q];
+        const std::string what = "tree spr: candidate " + std::to_string(q) + ": ";
+        if (v >= nnodes || parent[v] == UINT32_MAX) return what + "v is not a node below the root";
+        if (y >= nnodes || parent[y] == UINT32_MAX) return what + "y is not a node below the root";
+        const uint32_t p = parent[v], arity = child_off[p + 1] - child_off[p];
+        if (arity == 2 && parent[p] == UINT32_MAX) return what + "the parent of v is a root of two children";
+        if (arity == 2 && (y == p || parent[y] == p)) return what + "y is the parent or the sibling of v: the tree itself";
+        // both ends climb to the lowest common ancestor, the lower numbered first (a parent's number is above its children's)
+        uint32_t up[PGM_TREE_SPR_MAXPATH + 1], down[PGM_TREE_SPR_MAXPATH + 1], J = 0, M = 0, x = p, z = y;
+        while (x != z) {
+            if (J + M == PGM_TREE_SPR_MAXPATH) return what + "a path of more than " + std::to_string(PGM_TREE_SPR_MAXPATH) + " edges";
+            if (x < z) { up[J++] = x; x = parent[x]; }
+            else {
+                if (z == v) return what + "y is in the subtree of v";
+                down[M++] = z;
+                z = parent[z];
+            }
+        }
+        uint32_t *out = &path[(size_t)q * PGM_TREELIK_SPR_STRIDE];
+        out[0] = J; out[1] = M;
+        for (uint32_t j = 0; j < J; ++j) out[2 + j] = up[j];
+        out[2 + J] = x;
+        for (uint32_t m = 0; m < M; ++m) out[2 + J + 1 + m] = down[M - 1 - m];
+    }
+    return std::string();
+}
+
 #endif

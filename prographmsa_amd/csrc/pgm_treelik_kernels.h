@@ -14,6 +14,8 @@
 // pgm_tree_nni is a fourth mode (PGM_TREELIK_NNI): that down pass without the posteriors, so the outside
 // vectors stay; pgm_treelik_nni_kernel then scores every nearest-neighbour interchange from four stored pieces around its edge.
 // pgm_tree_nni_edge is that kernel's second instantiation: the neighbour's edge with three matrices of its own.
+// pgm_tree_spr runs the walk in the same mode; pgm_treelik_spr_kernel then scores every pruning and regrafting from
+// the stored pieces along the candidate's path.
 //
 // Every sum over states runs ascending from 0.0 with one multiply and one add per term (-ffp-contract=off): the bits are those of
 // tree_likelihood_host.  The walk is a chain of dependent steps on one wavefront, so what a step costs is the latency of its loads:
@@ -564,6 +566,228 @@ __global__ __launch_bounds__(PGM_TREELIK_NNI_THREADS) void pgm_treelik_nni_kerne
                 n.h[(size_t)q * ncols + s] = h;
             }
         }
+    }
+}
+
+// Subtree pruning and regrafting scored from the stored pieces (pgm_tree_spr).  Candidate q = (v, y) with the path
+// its C ABI side wrote (n.path: J, M, then a_0 = p .. a_J = a, c_1 .. c_M = y).  The layout is the NNI kernel's: a workgroup of
+// PGM_TREELIK_NNI_WAVES wavefronts owns that many times 64 / dim consecutive sites, a thread per (site, state), and takes the
+// candidates blockIdx.y, blockIdx.y + gridDim.y, ..; the categories run inside, ascending, the mixture in a register of the thread of
+// state 0.  A workgroup recomputes the chain of its candidate: the two chain vectors (- without v, + with it) of a site live in shared
+// memory, a thread holding its own state's values in registers; a step forms the next values from the scaled vectors (rows 2, 3),
+// publishes them unscaled (rows 0, 1), and after a barrier every thread of the site finds the same maxima, scales its own values and
+// publishes them (rows 2, 3) ahead of a second barrier.  Rows 4, 5 carry the terms of N and D to the thread of state 0.  The sums are
+// the walk's: eight operands ahead of eight ordered adds.  No workgroup waits for another, there are no atomics, nothing is zeroed and
+// every rho entry has one writer.  Every thread of the workgroup reaches every barrier: the loops over candidates, categories and path
+// steps, and the branches on J and M, are uniform over the workgroup.
+struct PgmTreelikSprArgs {
+    PgmTreelikArgs t;                      // the tree, rows, pi, and category 0's P, U, O (site_l, site_k, g, h unused)
+    PgmTreelikRatesStride st;              // doubles between two categories' matrices (P, Ph) and partials (U)
+    uint32_t ncat, ncand, stride;          // stride: values per candidate in `path`
+    const uint32_t *cand_v, *path;
+    const double *Ph;                      // ncat x (nnodes - 1) x dim x dim
+    const double *post;                    // ncat x ncols
+    double *rho;                           // ncand x ncols
+};
+
+// am = sum over l ascending of X[step * l] * xm[l], ap the same with xp: X + i and step == dim for sum_l X(i, l) x(l), X + dim * i and
+// step == 1 for sum_h x(h) X(h, i).  xm, xp: the site's vectors in shared memory.
+__device__ __forceinline__ void pgm_treelik_spr_sum2(const double *X, size_t step, uint32_t dim, const double *xm, const double *xp, double &am, double &ap) {
+    am = 0.0; ap = 0.0;
+    uint32_t l = 0;
+    for (; l + 8 <= dim; l += 8) {
+        double pv[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) pv[e] = X[step * (l + e)];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { am = am + pv[e] * xm[l + e]; ap = ap + pv[e] * xp[l + e]; }
+    }
+    for (; l < dim; ++l) { const double pl = X[step * l]; am = am + pl * xm[l]; ap = ap + pl * xp[l]; }
+}
+__device__ __forceinline__ double pgm_treelik_spr_sum1(const double *X, size_t step, uint32_t dim, const double *x) {
+    double acc = 0.0;
+    uint32_t l = 0;
+    for (; l + 8 <= dim; l += 8) {
+        double pv[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) pv[e] = X[step * (l + e)];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc = acc + pv[e] * x[l + e];
+    }
+    for (; l < dim; ++l) acc = acc + X[step * l] * x[l];
+    return acc;
+}
+// the scaling rule on NV vectors of a site at once, a value of each per thread: unscaled through rows 0 .., scaled into rows 2 ..
+// (what the next step reads).  Every thread of the workgroup calls it (two barriers).
+template <int NV>
+__device__ __forceinline__ void pgm_treelik_spr_rule(double (*sh)[PGM_TREELIK_NNI_THREADS], uint32_t dim, uint32_t first, bool active, double (&val)[NV], int32_t (&count)[NV]) {
+    if (active) {
+#pragma unroll
+        for (int x = 0; x < NV; ++x) sh[x][threadIdx.x] = val[x];
+    }
+    __syncthreads();
+    if (active) {
+        double m[NV];
+#pragma unroll
+        for (int x = 0; x < NV; ++x) m[x] = sh[x][first];
+#pragma unroll 8
+        for (uint32_t j = 1; j < dim; ++j) {
+#pragma unroll
+            for (int x = 0; x < NV; ++x) { const double e = sh[x][first + j]; m[x] = e > m[x] ? e : m[x]; }
+        }
+#pragma unroll
+        for (int x = 0; x < NV; ++x) {
+            if (m[x] < 0x1p-256 && m[x] > 0.0) { val[x] = val[x] * 0x1p256; ++count[x]; }
+            sh[2 + x][threadIdx.x] = val[x];
+        }
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(PGM_TREELIK_NNI_THREADS) void pgm_treelik_spr_kernel(PgmTreelikSprArgs n) {
+    __shared__ double sh[6][PGM_TREELIK_NNI_THREADS];
+    const uint32_t dim = n.t.dim, nleaves = n.t.nleaves, root = n.t.nnodes - 1, spb = n.t.spb, ncols = n.t.ncols;
+    const uint32_t wave = threadIdx.x / PGM_TREELIK_THREADS, lane = threadIdx.x - wave * PGM_TREELIK_THREADS;
+    const uint32_t local = lane / dim, i = lane - local * dim;
+    const uint64_t s64 = ((uint64_t)blockIdx.x * PGM_TREELIK_NNI_WAVES + wave) * spb + local;
+    const bool active = local < spb && s64 < ncols;
+    const uint32_t s = (uint32_t)s64, first = threadIdx.x - i;   // first: the slot of this site's state 0
+    const size_t mat = (size_t)dim * dim;
+
+    for (uint32_t q = blockIdx.y; q < n.ncand; q += gridDim.y) {   // (uniform over the workgroup)
+        const uint32_t *path = n.path + (size_t)q * n.stride, *node = path + 2;
+        const uint32_t J = path[0], M = path[1], v = n.cand_v[q], p = node[0], y = node[J + M];
+        double rho = 0.0;
+        for (uint32_t k = 0; k < n.ncat; ++k) {
+            PgmTreelikArgs a = n.t;
+            a.P += n.st.P * k;
+            a.U += n.st.U * k;
+            a.O += n.st.U * k;
+            const double *Phy = n.Ph + n.st.P * k + mat * y;
+            double e[2] = {0.0, 0.0}, Sv = 0.0, S[1];   // e: this thread's values of the - and the + chain vector
+            int32_t cnt[2] = {0, 0};
+            if (active) { pgm_treelik_apply<1>(a, a.P + mat * v, mat, v, s, i, S); Sv = S[0]; }
+            if (J >= 1 || M == 0) {   // the chain start
+                if (active) {
+                    bool have = false;
+                    for (uint32_t r = a.child_off[p]; r < a.child_off[p + 1]; ++r) {
+                        const uint32_t c = a.child[r];
+                        if (c == v) continue;
+                        pgm_treelik_apply<1>(a, a.P + mat * c, mat, c, s, i, S);
+                        e[0] = have ? e[0] * S[0] : S[0];
+                        have = true;
+                    }
+                    e[1] = e[0] * Sv;
+                }
+                pgm_treelik_spr_rule<2>(sh, dim, first, active, e, cnt);
+            }
+            double mup[2] = {0.0, 0.0};
+            for (uint32_t j = 1; j <= J; ++j) {   // up
+                const uint32_t below = node[j - 1], at = node[j];
+                if (active) pgm_treelik_spr_sum2(a.P + mat * below + i, dim, dim, &sh[2][first], &sh[3][first], mup[0], mup[1]);
+                if (j < J || M == 0) {
+                    if (active) {
+                        e[0] = mup[0]; e[1] = mup[1];
+                        for (uint32_t r = a.child_off[at]; r < a.child_off[at + 1]; ++r) {
+                            const uint32_t c = a.child[r];
+                            if (c == below) continue;
+                            pgm_treelik_apply<1>(a, a.P + mat * c, mat, c, s, i, S);
+                            e[0] = e[0] * S[0]; e[1] = e[1] * S[0];
+                        }
+                    }
+                    pgm_treelik_spr_rule<2>(sh, dim, first, active, e, cnt);
+                }
+            }
+            double tn = 0.0, td = 0.0;   // this state's terms of N and D
+            if (M == 0) {   // the target on the up chain: y = a_J, an inner node below the root
+                double X[1] = {0.0}, T = 0.0;
+                if (active) {
+                    X[0] = Sv * pgm_treelik_spr_sum1(Phy + i, dim, dim, &sh[2][first]);
+                    T = pgm_treelik_spr_sum1(a.P + mat * y + i, dim, dim, &sh[3][first]);
+                }
+                int32_t c1[1] = {0};
+                pgm_treelik_spr_rule<1>(sh, dim, first, active, X, c1);   // (scaled X into row 2: the sums above are done at its first barrier)
+                cnt[0] += c1[0];
+                if (active) {
+                    const double W = pgm_treelik_spr_sum1(Phy + i, dim, dim, &sh[2][first]);
+                    const double Oy = a.O[((size_t)(y - nleaves) * ncols + s) * dim + i];
+                    tn = Oy * W; td = Oy * T;
+                }
+            } else {
+                const uint32_t top = node[J], c_1 = node[J + 1];
+                if (active) {   // the turn
+                    double B = 0.0;
+                    if (top == root) B = a.pi[i];
+                    else {
+                        const double *o = a.O + ((size_t)(top - nleaves) * ncols + s) * dim, *Pa = a.P + mat * top + (size_t)dim * i;
+                        uint32_t h = 0;
+                        for (; h + 8 <= dim; h += 8) {
+                            double ov[8], pv[8];
+#pragma unroll
+                            for (int x = 0; x < 8; ++x) { ov[x] = o[h + x]; pv[x] = Pa[h + x]; }
+#pragma unroll
+                            for (int x = 0; x < 8; ++x) B = B + ov[x] * pv[x];
+                        }
+                        for (; h < dim; ++h) B = B + o[h] * Pa[h];
+                    }
+                    const uint32_t skip = J >= 1 ? node[J - 1] : v;
+                    if (J >= 1) { e[0] = B * mup[0]; e[1] = B * mup[1]; }
+                    else e[0] = B;
+                    for (uint32_t r = a.child_off[top]; r < a.child_off[top + 1]; ++r) {
+                        const uint32_t c = a.child[r];
+                        if (c == skip || c == c_1) continue;
+                        pgm_treelik_apply<1>(a, a.P + mat * c, mat, c, s, i, S);
+                        e[0] = e[0] * S[0];
+                        if (J >= 1) e[1] = e[1] * S[0];
+                    }
+                    if (J == 0) e[1] = e[0] * Sv;
+                }
+                pgm_treelik_spr_rule<2>(sh, dim, first, active, e, cnt);
+                for (uint32_t m = 1; m < M; ++m) {   // down
+                    const uint32_t at = node[J + m], next = node[J + m + 1];
+                    if (active) {
+                        pgm_treelik_spr_sum2(a.P + mat * at + (size_t)dim * i, 1, dim, &sh[2][first], &sh[3][first], e[0], e[1]);
+                        for (uint32_t r = a.child_off[at]; r < a.child_off[at + 1]; ++r) {
+                            const uint32_t c = a.child[r];
+                            if (c == next) continue;
+                            pgm_treelik_apply<1>(a, a.P + mat * c, mat, c, s, i, S);
+                            e[0] = e[0] * S[0]; e[1] = e[1] * S[0];
+                        }
+                    }
+                    pgm_treelik_spr_rule<2>(sh, dim, first, active, e, cnt);
+                }
+                double X[1] = {0.0}, Sy = 0.0;   // the target below the turn
+                if (active) {
+                    pgm_treelik_apply<1>(a, Phy, mat, y, s, i, S);
+                    X[0] = Sv * S[0];
+                    pgm_treelik_apply<1>(a, a.P + mat * y, mat, y, s, i, S);
+                    Sy = S[0];
+                }
+                int32_t c1[1] = {0};
+                pgm_treelik_spr_rule<1>(sh, dim, first, active, X, c1);
+                cnt[0] += c1[0];
+                if (active) {
+                    const double W = pgm_treelik_spr_sum1(Phy + i, dim, dim, &sh[2][first]);
+                    tn = e[0] * W; td = e[1] * Sy;
+                }
+            }
+            if (active) { sh[4][threadIdx.x] = tn; sh[5][threadIdx.x] = td; }
+            __syncthreads();
+            if (active && i == 0) {
+                double N = 0.0, D = 0.0;
+#pragma unroll 8
+                for (uint32_t j = 0; j < dim; ++j) { N = N + sh[4][threadIdx.x + j]; D = D + sh[5][threadIdx.x + j]; }
+                double r = 0.0;
+                if (D != 0.0) {
+                    r = N / D;
+                    for (int32_t d = cnt[0] - cnt[1]; d > 0; --d) r = r * 0x1p-256;
+                    for (int32_t d = cnt[1] - cnt[0]; d > 0; --d) r = r * 0x1p256;
+                }
+                rho = rho + n.post[(size_t)k * ncols + s] * r;
+            }
+            // (rows 4, 5 are written again only after the barriers of the next round's target)
+        }
+        if (active && i == 0) n.rho[(size_t)q * ncols + s] = rho;
     }
 }
 

@@ -1,19 +1,23 @@
-// pgm_treelik_plan.h — where everything of a tree-likelihood call lies in the five scratch slots the five entries share
-// (pgm_tree_likelihood, pgm_tree_likelihood_rates, pgm_tree_ancestral, pgm_tree_nni, pgm_tree_nni_edge; pgm_treelik_capi.inc fills the
+// pgm_treelik_plan.h — where everything of a tree-likelihood call lies in the five scratch slots the six entries share
+// (pgm_tree_likelihood, pgm_tree_likelihood_rates, pgm_tree_ancestral, pgm_tree_nni, pgm_tree_nni_edge, pgm_tree_spr; pgm_treelik_capi.inc fills the
 // kernels' arguments from it).  Plain C++17 without HIP types: the host compiler takes it alone (tests/test_cpu_treelik_plan.py).
 //
 // A region is absent (0 bytes) where the call has no use for it.  The regions of a slot follow each other in the order of the list
 // below, each at the next multiple of its alignment; a slot ends where its last region ends.  C = ncat (1 in the plain entry),
 // X = 3 with derivs, else 1.  "nni" is both pgm_tree_nni and pgm_tree_nni_edge; "edge" the latter alone, whose per-site ratios,
 // chunk sums and sums are those of its candidates, so they take the regions of the edges' (G, H, PART, D1, D2: never both in a call).
+// "spr" is pgm_tree_spr: the walk's regions of nni (U, O, CL, CK, the outputs, RHO) and three of its own behind the others of their slot.
 //   TREE  CHILD   uint32  (nnodes + 1) + nedges      child_off, then child: the children of every node, ascending
 //         PI      double  dim
 //         W       double  ncat                       all but plain
 //         PARENT  uint32  nnodes                     nni
 //         CAND    uint32  3 x ncand                  nni: cand_v, cand_a, cand_c
 //         ROWS    int8    nleaves x ncols
+//         SPR_CAND uint32 ncand                      spr: cand_v (y is the last node of the candidate's path)
+//         SPR_PATH uint32 PGM_TREELIK_SPR_STRIDE x ncand   spr: per candidate J, M and the nodes of its path (pgm_treelik_check.h)
 //   P     P       double  C x nedges x X x dim x dim
 //         PC      double  ncat x ncand x 3 x dim x dim   edge: the candidates' own matrices
+//         PH      double  ncat x nedges x dim x dim  spr: the matrix of half of every edge
 //   U     U       double  C x ninner x ncols x dim   the partials
 //         O       double  as U                       derivs, ancestral (the posteriors take their place), nni: the outside vectors
 //   G     CL      double  ncat x ncols               all but plain: L_c of every category
@@ -28,7 +32,7 @@
 //         ANC_PROB double ninner x ncols             ancestral
 //         ANC_STATE int8  ninner x ncols             ancestral
 //         ANC_POST double ninner x ncols x dim       ancestral, when asked for
-//         RHO     double  ncand x ncols              nni
+//         RHO     double  ncand x ncols              nni, spr
 #ifndef PGM_TREELIK_PLAN_H_
 #define PGM_TREELIK_PLAN_H_
 
@@ -36,8 +40,9 @@
 #include <cstdint>
 
 #include "../../include/pgm_hip.h"
+#include "pgm_treelik_check.h"
 
-enum { PGM_TREELIK_CALL_PLAIN = 0, PGM_TREELIK_CALL_RATES, PGM_TREELIK_CALL_ANC, PGM_TREELIK_CALL_NNI, PGM_TREELIK_CALL_NNI_EDGE };
+enum { PGM_TREELIK_CALL_PLAIN = 0, PGM_TREELIK_CALL_RATES, PGM_TREELIK_CALL_ANC, PGM_TREELIK_CALL_NNI, PGM_TREELIK_CALL_NNI_EDGE, PGM_TREELIK_CALL_SPR };
 enum { PGM_TL_SLOT_TREE = 0, PGM_TL_SLOT_P, PGM_TL_SLOT_U, PGM_TL_SLOT_G, PGM_TL_SLOT_OUT, PGM_TL_NSLOTS };   // the order of pgm_ctx's SC_TREELIK_*
 enum {
     PGM_TL_CHILD = 0, PGM_TL_PI, PGM_TL_W, PGM_TL_PARENT, PGM_TL_CAND, PGM_TL_ROWS,
@@ -47,6 +52,7 @@ enum {
     PGM_TL_SITE_L, PGM_TL_SITE_K, PGM_TL_POST, PGM_TL_D1, PGM_TL_D2, PGM_TL_ANC_PROB, PGM_TL_ANC_STATE, PGM_TL_ANC_POST, PGM_TL_RHO,
     PGM_TL_NREGIONS,                      // the regions the four first modes have between them
     PGM_TL_PC = PGM_TL_NREGIONS,          // pgm_tree_nni_edge's own, numbered behind them
+    PGM_TL_PH, PGM_TL_SPR_CAND, PGM_TL_SPR_PATH,   // pgm_tree_spr's own
     PGM_TL_NREGIONS_ALL
 };
 
@@ -59,11 +65,12 @@ struct PgmTreelikPlan {
     PgmTreelikRegion r[PGM_TL_NREGIONS_ALL];
 };
 
-// ncat: 0 for the plain entry; derivs: plain and rates alone; ncand: nni and nni edge alone; full: ancestral alone, anc_post asked for
+// ncat: 0 for the plain entry; derivs: plain and rates alone; ncand: nni, nni edge and spr alone; full: ancestral alone, anc_post asked for
 inline PgmTreelikPlan pgm_treelik_plan(int mode, uint32_t dim, uint32_t nleaves, uint32_t nnodes, uint32_t ncols, uint32_t ncat, bool derivs, uint32_t ncand, bool full) {
     PgmTreelikPlan p = {};
     const bool edge = mode == PGM_TREELIK_CALL_NNI_EDGE, nni = mode == PGM_TREELIK_CALL_NNI || edge;
-    const bool cats = mode != PGM_TREELIK_CALL_PLAIN, outside = derivs || mode == PGM_TREELIK_CALL_ANC || nni;
+    const bool spr = mode == PGM_TREELIK_CALL_SPR;
+    const bool cats = mode != PGM_TREELIK_CALL_PLAIN, outside = derivs || mode == PGM_TREELIK_CALL_ANC || nni || spr;
     p.nedges = nnodes - 1; p.ninner = nnodes - nleaves; p.cats = cats ? ncat : 1;
     p.mat = (size_t)dim * dim; p.nrow = (size_t)nleaves * ncols; p.nchunks = ((size_t)ncols + PGM_TREELIK_CHUNK - 1) / PGM_TREELIK_CHUNK;
     p.npairs = (size_t)p.ninner * ncols;
@@ -81,8 +88,11 @@ inline PgmTreelikPlan pgm_treelik_plan(int mode, uint32_t dim, uint32_t nleaves,
     put(PGM_TL_PARENT, PGM_TL_SLOT_TREE, 4, nni ? 4 * (size_t)nnodes : 0);
     put(PGM_TL_CAND, PGM_TL_SLOT_TREE, 4, nni ? 12 * (size_t)ncand : 0);
     put(PGM_TL_ROWS, PGM_TL_SLOT_TREE, 1, p.nrow);
+    put(PGM_TL_SPR_CAND, PGM_TL_SLOT_TREE, 4, spr ? 4 * (size_t)ncand : 0);
+    put(PGM_TL_SPR_PATH, PGM_TL_SLOT_TREE, 4, spr ? 4 * (size_t)PGM_TREELIK_SPR_STRIDE * ncand : 0);
     put(PGM_TL_P, PGM_TL_SLOT_P, 8, 8 * p.p_count * p.cats);
     put(PGM_TL_PC, PGM_TL_SLOT_P, 8, edge ? 8 * 3 * p.mat * ncand * ncat : 0);
+    put(PGM_TL_PH, PGM_TL_SLOT_P, 8, spr ? 8 * p.p_count * p.cats : 0);
     put(PGM_TL_U, PGM_TL_SLOT_U, 8, 8 * p.u_count * p.cats);
     put(PGM_TL_O, PGM_TL_SLOT_U, 8, outside ? 8 * p.u_count * p.cats : 0);
     put(PGM_TL_CL, PGM_TL_SLOT_G, 8, 8 * p.cl_count);
@@ -100,7 +110,7 @@ inline PgmTreelikPlan pgm_treelik_plan(int mode, uint32_t dim, uint32_t nleaves,
     put(PGM_TL_ANC_PROB, PGM_TL_SLOT_OUT, 8, mode == PGM_TREELIK_CALL_ANC ? 8 * p.npairs : 0);
     put(PGM_TL_ANC_STATE, PGM_TL_SLOT_OUT, 1, mode == PGM_TREELIK_CALL_ANC ? p.npairs : 0);
     put(PGM_TL_ANC_POST, PGM_TL_SLOT_OUT, 8, mode == PGM_TREELIK_CALL_ANC && full ? 8 * p.u_count : 0);
-    put(PGM_TL_RHO, PGM_TL_SLOT_OUT, 8, nni ? 8 * (size_t)ncand * ncols : 0);
+    put(PGM_TL_RHO, PGM_TL_SLOT_OUT, 8, nni || spr ? 8 * (size_t)ncand * ncols : 0);
     return p;
 }
 

@@ -184,6 +184,14 @@ struct HipBackend : Backend {
         if (rc != PGM_OK) error("pgm_tree_nni_edge failed (%d): %s", rc, pgm_last_error());
         ml_nni_opt_stats.kernel_ms += pgm_treelik_last_kernel_ms(c);
     }
+    void tree_spr(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
+                  const double *w, const double *P, const double *Ph, uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_y, double *site_l, int32_t *site_k,
+                  double *post, double *rho, int worker) override {
+        pgm_ctx *c = ctx_of(worker);
+        int rc = pgm_tree_spr(c, dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, Ph, ncand, cand_v, cand_y, site_l, site_k, post, rho);
+        if (rc != PGM_OK) error("pgm_tree_spr failed (%d): %s", rc, pgm_last_error());
+        ml_spr_stats.kernel_ms += pgm_treelik_last_kernel_ms(c);
+    }
     void resampled_sums(uint32_t nrow, uint32_t ncols, const double *x, uint32_t nrep, const uint32_t *cols, double *out, int worker) override {
         pgm_ctx *c = ctx_of(worker);
         int rc = pgm_resampled_sums(c, nrow, ncols, x, nrep, cols, out);

@@ -75,7 +75,9 @@ void doBootstrap(const Alphabet &a, const DriverOptions &o, const Family &fam, c
 // per node and column.  --ml_search N: up to N rounds of nearest-neighbour interchanges from the start tree, every
 // candidate of a round scored by one Backend::tree_nni call (the same route); --ml_start FILE: a newick in place of the BioNJ tree;
 // --ml_search_log FILE: a line per round; --ml_nni_opt N: the candidates of the search and of --ml_support each at a
-// central length of their own, N Newton rounds by Backend::tree_nni_edge calls (the same route)
+// central length of their own, N Newton rounds by Backend::tree_nni_edge calls (the same route); --ml_spr R: where the
+// interchanges of a round apply no move, every pruning and regrafting within R edges scored by Backend::tree_spr calls (the same
+// route), and a ninth column, nni or spr, in every line of the log
 // the names of the inner nodes of a numbered tree, N1 .. in node order; a leaf that has one of them is an error()
 static std::vector<std::string> ml_ancestral_names(const MlTreeTopology &topo) {
     std::vector<std::string> node_name(topo.nnodes - topo.nleaves);
@@ -211,8 +213,10 @@ void doMlTree(const Alphabet &a, const DriverOptions &o, const Family &fam, cons
     if (mo.anc_given) (void)ml_ancestral_names(ml_tree_topology(*tree));   // (refused before the optimiser runs and before any file is written)
     MlTreeResult res;
     if (mo.search_given) {   // --ml_search: every file below describes the searched tree
+        MlSprHook spr;
+        spr.radius = (uint32_t)mo.spr; spr.scan = ml_spr_scan; spr.apply = ml_spr_apply;
         MlSearchResult found = ml_topology_search(a, values, *fam.model_factory, *tree, (uint32_t)mo.search, (uint32_t)mo.rounds, mo.eps, be, gamma,
-                                                  mo.nni_opt_given ? (uint32_t)mo.nni_opt : 0u);
+                                                  mo.nni_opt_given ? (uint32_t)mo.nni_opt : 0u, mo.spr_given ? &spr : nullptr);
         tree = std::move(found.tree);
         res = std::move(found.res);
         if (mo.anc_given) (void)ml_ancestral_names(ml_tree_topology(*tree));
@@ -220,8 +224,8 @@ void doMlTree(const Alphabet &a, const DriverOptions &o, const Family &fam, cons
             std::ofstream log = open_output(mo.search_log, "ml search output");
             char buf[256];
             for (const MlSearchRound &r : found.log) {
-                snprintf(buf, sizeof buf, "%u\t%u\t%u\t%u\t%.17g\t%.17g\t%.17g\t%.17g\n", r.round, r.candidates, r.positive, r.applied, r.best_gain, r.lnl_before,
-                         r.lnl_applied, r.lnl_after);
+                snprintf(buf, sizeof buf, "%u\t%u\t%u\t%u\t%.17g\t%.17g\t%.17g\t%.17g%s\n", r.round, r.candidates, r.positive, r.applied, r.best_gain, r.lnl_before,
+                         r.lnl_applied, r.lnl_after, !mo.spr_given ? "" : r.spr ? "\tspr" : "\tnni");
                 log << buf;
             }
         }

@@ -103,7 +103,7 @@ static bool real_number(const std::string &text, double &v) {
 
 int parse_driver_options(int argc, char **argv, DriverOptions &o) {
     bool missing = false;   // a flag without its value
-    bool cutoff_ok = true, rounds_ok = true, eps_ok = true, gamma_ok = true, alpha_ok = true, search_ok = true, reps_ok = true, nni_opt_ok = true;
+    bool cutoff_ok = true, rounds_ok = true, eps_ok = true, gamma_ok = true, alpha_ok = true, search_ok = true, reps_ok = true, nni_opt_ok = true, spr_ok = true;
     for (int i = 1; i < argc && !missing; ++i) {
         std::string s = argv[i];
         auto val = [&]() -> std::string { if (i + 1 >= argc) { missing = true; return ""; } return argv[++i]; };
@@ -172,6 +172,7 @@ int parse_driver_options(int argc, char **argv, DriverOptions &o) {
         else if (s == "--ml_start") { o.mltree.start_given = true; o.mltree.start = val(); }
         else if (s == "--ml_search_log") { o.mltree.search_log_given = true; o.mltree.search_log = val(); }
         else if (s == "--ml_nni_opt") { o.mltree.nni_opt_given = true; nni_opt_ok = whole_number(val(), o.mltree.nni_opt); }
+        else if (s == "--ml_spr") { o.mltree.spr_given = true; spr_ok = whole_number(val(), o.mltree.spr); }
         else if (s == "--ml_support") { o.mltree.support_given = true; o.mltree.support = val(); }
         else if (s == "--ml_support_table") { o.mltree.support_table_given = true; o.mltree.support_table = val(); }
         else if (s == "--ml_support_reps") { o.mltree.support_reps_given = true; reps_ok = whole_number(val(), o.mltree.support_reps); }
@@ -234,12 +235,14 @@ int parse_driver_options(int argc, char **argv, DriverOptions &o) {
         search_ok = !o.mltree.search_given || (search_ok && o.mltree.search >= 1 && o.mltree.search <= 1000);
         reps_ok = reps_ok && o.mltree.support_reps >= 1 && o.mltree.support_reps <= 10000;
         nni_opt_ok = !o.mltree.nni_opt_given || (nni_opt_ok && o.mltree.nni_opt >= 1 && o.mltree.nni_opt <= 20);
+        spr_ok = !o.mltree.spr_given || (spr_ok && o.mltree.spr >= 1 && o.mltree.spr <= 10);
         const bool plain = o.mltree.sites_given || o.mltree.rounds_given || o.mltree.eps_given;   // (the flags from before --ml_gamma keep their message)
         const bool rates = o.mltree.gamma_given || o.mltree.alpha_given || o.mltree.rates_given;   // (... and so do those from before --ml_ancestral)
         const char *why = !o.mltree.tree_given ? (plain ? "--ml_sites, --ml_rounds and --ml_epsilon need --ml_tree"
                                                   : rates ? "--ml_gamma, --ml_alpha and --ml_rates need --ml_tree"
                                                   : o.mltree.any_anc() ? "--ml_ancestral needs --ml_tree"
                                                   : o.mltree.nni_opt_given ? "--ml_nni_opt needs --ml_tree"
+                                                  : o.mltree.spr_given ? "--ml_spr needs --ml_tree"
                                                   : o.mltree.any_search() ? "--ml_search, --ml_start and --ml_search_log need --ml_tree"
                                                                           : "--ml_support, --ml_support_table, --ml_support_reps and --ml_support_seed need --ml_tree")
                           : (!o.mltree.gamma_given && (o.mltree.alpha_given || o.mltree.rates_given)) ? "--ml_alpha and --ml_rates need --ml_gamma"
@@ -248,6 +251,8 @@ int parse_driver_options(int argc, char **argv, DriverOptions &o) {
                           : (!o.mltree.support_given && o.mltree.any_support()) ? "--ml_support_table, --ml_support_reps and --ml_support_seed need --ml_support"
                           : (o.mltree.nni_opt_given && !o.mltree.search_given && !o.mltree.support_given) ? "--ml_nni_opt needs --ml_search or --ml_support"
                           : !nni_opt_ok ? "--ml_nni_opt takes a number of rounds from 1 to 20"
+                          : (o.mltree.spr_given && !o.mltree.search_given) ? "--ml_spr needs --ml_search"
+                          : !spr_ok ? "--ml_spr takes a radius from 1 to 10"
                           : !reps_ok ? "--ml_support_reps takes a number of replicates from 1 to 10000"
                           : !search_ok ? "--ml_search takes a number of rounds from 1 to 1000"
                           : !gamma_ok ? "--ml_gamma takes a number of categories from 2 to 16"

@@ -27,7 +27,7 @@ struct GuidanceOpts {   // --guidance N --guidance_out FILE --guidance_seed S --
 
 struct MlTreeOpts {   // --ml_tree FILE --ml_sites FILE --ml_rounds N --ml_epsilon X --ml_gamma K --ml_alpha X --ml_rates FILE
                       // --ml_ancestral FILE --ml_ancestral_tree FILE --ml_ancestral_probs FILE --ml_search N --ml_start FILE --ml_search_log FILE
-                      // --ml_support FILE --ml_support_table FILE --ml_support_reps N --ml_support_seed S --ml_nni_opt N
+                      // --ml_support FILE --ml_support_table FILE --ml_support_reps N --ml_support_seed S --ml_nni_opt N --ml_spr R
     std::string tree, sites, rates, anc, anc_tree, anc_probs;
     bool anc_given = false, anc_tree_given = false, anc_probs_given = false;
     bool any_anc() const { return anc_given || anc_tree_given || anc_probs_given; }
@@ -40,6 +40,8 @@ struct MlTreeOpts {   // --ml_tree FILE --ml_sites FILE --ml_rounds N --ml_epsil
     std::shared_ptr<PhyTree> start_tree;   // --ml_start as read and checked against the family's names, before any work (main.cpp)
     bool nni_opt_given = false;   // --ml_nni_opt N: the Newton rounds on the central branch of every interchange
     long nni_opt = 0;
+    bool spr_given = false;   // --ml_spr R: an SPR scan of radius R where the interchanges of the search stall
+    long spr = 0;
     bool any_search() const { return search_given || start_given || search_log_given; }
     bool support_given = false, support_table_given = false, support_reps_given = false, support_seed_given = false;
     std::string support, support_table;
@@ -47,7 +49,7 @@ struct MlTreeOpts {   // --ml_tree FILE --ml_sites FILE --ml_rounds N --ml_epsil
     uint64_t support_seed = 1;
     bool any_support() const { return support_given || support_table_given || support_reps_given || support_seed_given; }
     bool any() const {
-        return tree_given || sites_given || rounds_given || eps_given || gamma_given || alpha_given || rates_given || any_anc() || any_search() || any_support() || nni_opt_given;
+        return tree_given || sites_given || rounds_given || eps_given || gamma_given || alpha_given || rates_given || any_anc() || any_search() || any_support() || nni_opt_given || spr_given;
     }
 };
 

@@ -60,6 +60,10 @@ void print_stats(const DriverOptions &o, double t_init, double t_tree, double t_
     if (o.mltree.nni_opt_given)   // (keys of --ml_nni_opt only)
         fprintf(stderr, ", \"ml_nni_opt_s\": %.6f, \"ml_nni_opt_calls\": %llu, \"ml_nni_opt_kernel_ms\": %.3f", ml_nni_opt_stats.seconds,
                 (unsigned long long)ml_nni_opt_stats.calls, ml_nni_opt_stats.kernel_ms);
+    if (o.mltree.spr_given)   // (keys of --ml_spr only)
+        fprintf(stderr, ", \"ml_spr_s\": %.6f, \"ml_spr_calls\": %llu, \"ml_spr_candidates\": %llu, \"ml_spr_applied\": %llu, \"ml_spr_kernel_ms\": %.3f",
+                ml_spr_stats.seconds, (unsigned long long)ml_spr_stats.calls, (unsigned long long)ml_spr_stats.candidates, (unsigned long long)ml_spr_stats.applied,
+                ml_spr_stats.kernel_ms);
     if (batch)   // (keys of --batch only)
         fprintf(stderr, ", \"batch_families\": %d, \"batch_failed\": %d, \"batch_chunks\": %d, \"batch_passes\": %llu, \"batch_levels\": %llu, "
                         "\"batch_align_calls\": %llu, \"batch_dist_calls\": %llu",

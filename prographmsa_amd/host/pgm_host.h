@@ -361,6 +361,11 @@ struct Backend {
     virtual void tree_nni_edge(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
                                const double *w, const double *P, uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c, const double *Pc,
                                double *site_l, int32_t *site_k, double *post, double *rho, double *d1, double *d2, int worker = 0);
+    // The likelihood ratio of every subtree pruning and regrafting at every column (--ml_spr; include/pgm_hip.h: pgm_tree_spr).  The
+    // default is the host statement, tree_spr_host: the same bits.
+    virtual void tree_spr(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
+                          const double *w, const double *P, const double *Ph, uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_y, double *site_l,
+                          int32_t *site_k, double *post, double *rho, int worker = 0);
     // The sums of every row of x over nrep resamplings of its columns (--ml_support; include/pgm_hip.h: pgm_resampled_sums).  The
     // default is the host statement, resampled_sums_host: the same bits.
     virtual void resampled_sums(uint32_t nrow, uint32_t ncols, const double *x, uint32_t nrep, const uint32_t *cols, double *out, int worker = 0);

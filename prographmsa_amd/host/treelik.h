@@ -35,7 +35,10 @@ namespace pgm {
 //   greedily while no two share a node of {u, v, a, c}; the first m picked applied (m from all of them, halved while the evaluation at
 //   the carried lengths is not above lnL; none left: the search ends), then ml_branch_lengths again from the carried lengths and
 //   the shape in hand.  lnL never decreases.  With nni_opt the candidates are ranked by ml_nni_edge_lengths's gain_opt and an applied
-//   move gives the edge above v its t_opt.
+//   move gives the edge above v its t_opt.  With `spr` (--ml_spr) a round whose interchange step applies no move, where
+//   the search would end, logs that step and runs an SPR scan (ml_spr_scan): its picks go through the same acceptance (the first m
+//   applied, one evaluation, halved while lnL does not rise), an accepted scan is a round and the search goes on; the search ends
+//   where the scan applies no move either.
 const double kMlMinLength = 1e-6, kMlMaxLength = 10.0;   // the interval every branch length stays in
 const double kMlMinAlpha = 0.05, kMlMaxAlpha = 100.0;     // ... and the shape of the gamma
 const uint32_t kMlAlphaEvaluations = 12, kMlMaxPairs = 20;   // one search on ln alpha; branch-length loop + search pairs at the most
@@ -134,7 +137,9 @@ extern MlSearchStats ml_search_stats;
 struct MlSearchRound {   // a line of --ml_search_log
     uint32_t round = 0, candidates = 0, positive = 0, applied = 0;
     double best_gain = 0, lnl_before = 0, lnl_applied = 0, lnl_after = 0;
+    bool spr = false;   // --ml_spr: the line of an SPR scan (the ninth column)
 };
+struct MlSprHook;   // (--ml_spr, below)
 struct MlSearchResult {
     std::unique_ptr<PhyTree> tree;   // the searched tree; `res` is ml_branch_lengths's result on it (lnl_start: the start tree's)
     MlTreeResult res;
@@ -142,7 +147,46 @@ struct MlSearchResult {
 };
 MlSearchResult ml_topology_search(const Alphabet &a, const std::vector<std::vector<int8_t>> &rows, const ModelFactory &model_factory, const PhyTree &start,
                                   uint32_t search_rounds, uint32_t rounds, double eps, Backend *be = nullptr, const MlGamma &gamma = MlGamma(),
-                                  uint32_t nni_opt = 0 /* --ml_nni_opt: the Newton rounds of ml_nni_edge_lengths, 0: rank at the lengths in hand */);
+                                  uint32_t nni_opt = 0 /* --ml_nni_opt: the Newton rounds of ml_nni_edge_lengths, 0: rank at the lengths in hand */,
+                                  const MlSprHook *spr = nullptr /* --ml_spr: a round whose interchanges apply no move runs an SPR scan */);
+// --ml_spr (host/treelik_spr.cpp):
+// tree_spr_host: pgm_tree_spr blocked as tree_nni_host, the same contract and bits, the candidates as a parallel_for over prune nodes x
+//   column chunks; Backend::tree_spr's default.
+// ml_spr_candidates: every valid candidate (v, y) of pgm_tree_spr whose path has at most `radius` edges, v ascending, then y ascending.
+// ml_spr_touched: the nodes a move reads or changes: v, p, parent[p], the children of p, every node of the path, y and parent[y].
+const size_t kSprRhoBytes = (size_t)256 << 20;   // rho of one tree_spr call
+void tree_spr_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
+                   const double *w, const double *P, const double *Ph /* as P: half of every edge */, uint32_t ncand, const uint32_t *cand_v,
+                   const uint32_t *cand_y /* ncand each */, double *site_l, int32_t *site_k, double *post, double *rho /* ncand x ncols */,
+                   size_t block_bytes = kTreelikNniBlockBytes);
+void ml_spr_candidates(uint32_t nnodes, const uint32_t *parent, uint32_t radius, std::vector<uint32_t> &cand_v, std::vector<uint32_t> &cand_y);
+std::vector<uint32_t> ml_spr_touched(uint32_t nnodes, const uint32_t *parent, uint32_t v, uint32_t y);
+// ml_spr_apply: the tree after the first m of the given moves, whose touched sets are disjoint (lengths: per edge of topo): v keeps
+//   t_v, y and the new node both get max(t_y / 2, kMlMinLength), a dissolved p gives its sibling min(t_p + t_s, kMlMaxLength).
+// ml_spr_scan: every candidate within the radius scored at the lengths and rates of `res` (P and Ph from treelik_matrices, the half
+//   lengths max(t_y / 2, kMlMinLength)), in groups of whole prune nodes whose rho stays within rho_bytes, one tree_spr call per group
+//   (be: the backend, nullptr for the host loop); the gain of a candidate is treelik_nni_gain of its rho row; the candidates of
+//   gain > eps by gain descending, then by index, picked greedily while their touched sets are disjoint.
+struct MlSprScan {
+    uint32_t candidates = 0, positive = 0;
+    double best_gain = 0;
+    std::vector<uint32_t> pick_v, pick_y;   // the picked moves in the order they were picked
+};
+PhyTree *ml_spr_apply(const MlTreeTopology &topo, const std::vector<double> &lengths, uint32_t m, const uint32_t *move_v, const uint32_t *move_y);
+MlSprScan ml_spr_scan(const ModelFactory &mf, const MlTreeTopology &topo, const MlTreeResult &res, uint32_t ncols, const int8_t *rows, uint32_t radius, double eps,
+                      Backend *be = nullptr, size_t rho_bytes = kSprRhoBytes);
+// what ml_topology_search needs of the above (the driver fills it with ml_spr_scan and ml_spr_apply, so that the search itself and
+// the stand-alone programs over it link without host/treelik_spr.cpp)
+struct MlSprHook {
+    uint32_t radius = 0;
+    MlSprScan (*scan)(const ModelFactory &, const MlTreeTopology &, const MlTreeResult &, uint32_t, const int8_t *, uint32_t, double, Backend *, size_t) = nullptr;
+    PhyTree *(*apply)(const MlTreeTopology &, const std::vector<double> &, uint32_t, const uint32_t *, const uint32_t *) = nullptr;
+};
+struct MlSprStats {   // `--ml_spr --stats`
+    double seconds = 0, kernel_ms = 0;
+    uint64_t calls = 0, candidates = 0, applied = 0;   // tree_spr calls, candidates scored, moves applied in accepted rounds
+};
+extern MlSprStats ml_spr_stats;
 // --ml_support (host/treelik_support.cpp):
 // resampled_sums_host: pgm_resampled_sums by a loop over rows x chunks of replicates on the host threads, the same contract and the
 //   same bits; what it rejects is an error().  Backend::resampled_sums's default.

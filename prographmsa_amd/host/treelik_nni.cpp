@@ -11,6 +11,7 @@ namespace pgm {
 
 MlSearchStats ml_search_stats;
 MlNniOptStats ml_nni_opt_stats;
+MlSprStats ml_spr_stats;   // (here, beside the search that counts its applied moves: host/treelik_spr.cpp is not linked by every program over the search)
 
 namespace {
 // tree_nni_host (Pc, d1, d2 null) and tree_nni_edge_host: one body, so the pieces both share are formed by the same lines
@@ -265,7 +266,7 @@ PhyTree *ml_search_build(const MlSearchTree &t, uint32_t v) {
 }  // namespace
 
 MlSearchResult ml_topology_search(const Alphabet &a, const std::vector<std::vector<int8_t>> &rows, const ModelFactory &model_factory, const PhyTree &start,
-                                  uint32_t search_rounds, uint32_t rounds, double eps, Backend *be, const MlGamma &gamma, uint32_t nni_opt) {
+                                  uint32_t search_rounds, uint32_t rounds, double eps, Backend *be, const MlGamma &gamma, uint32_t nni_opt, const MlSprHook *spr) {
     const auto t0 = std::chrono::steady_clock::now();
     MlSearchResult out;
     out.tree.reset(start.copy());
@@ -276,7 +277,63 @@ MlSearchResult ml_topology_search(const Alphabet &a, const std::vector<std::vect
     for (const auto &r : rows) flat.insert(flat.end(), r.begin(), r.end());
     const double *pi = model_factory.freqs().data();
 
-    for (uint32_t round = 1; round <= search_rounds; ++round) {
+    // one evaluation of `tree` without derivatives at the lengths it carries and the rates in hand (ml_tree_topology numbers it)
+    auto lnl_of_tree = [&](const PhyTree &tree) -> double {
+        const MlTreeTopology nt = ml_tree_topology(tree);
+        const uint32_t ncat = out.res.rates.empty() ? 1u : (uint32_t)out.res.rates.size();
+        const std::vector<double> w(ncat, out.res.rates.empty() ? 1.0 : 1.0 / (double)ncat);
+        std::vector<double> P, site_l(ncols), post((size_t)ncat * ncols), t(nt.nnodes - 1);
+        std::vector<int32_t> site_k(ncols);
+        for (uint32_t e = 0; e + 1 < nt.nnodes; ++e) t[e] = nt.node[e]->getBranchLength();
+        if (out.res.rates.empty()) {
+            treelik_matrices(model_factory, t, false, P);
+            if (be) be->tree_likelihood(dim, nt.nleaves, nt.nnodes, nt.parent.data(), ncols, flat.data(), pi, P.data(), 0, site_l.data(), site_k.data(), nullptr, nullptr);
+            else tree_likelihood_host(dim, nt.nleaves, nt.nnodes, nt.parent.data(), ncols, flat.data(), pi, P.data(), 0, site_l.data(), site_k.data(), nullptr, nullptr);
+        } else {
+            treelik_matrices(model_factory, t, false, out.res.rates, P);
+            if (be) be->tree_likelihood_rates(dim, nt.nleaves, nt.nnodes, nt.parent.data(), ncols, flat.data(), pi, ncat, w.data(), P.data(), 0, site_l.data(), site_k.data(),
+                                              post.data(), nullptr, nullptr);
+            else tree_likelihood_rates_host(dim, nt.nleaves, nt.nnodes, nt.parent.data(), ncols, flat.data(), pi, ncat, w.data(), P.data(), 0, site_l.data(), site_k.data(),
+                                            post.data(), nullptr, nullptr);
+        }
+        ++ml_tree_stats.evaluations;
+        return treelik_lnl(ncols, site_l.data(), site_k.data(), nullptr);
+    };
+    // a moved tree that raised lnL becomes the search's: ml_branch_lengths from the carried lengths and the shape in hand
+    auto accept = [&](std::unique_ptr<PhyTree> tree) {
+        MlGamma from = gamma;
+        if (gamma.ncat >= 2 && gamma.estimate) from.start = out.res.alpha;
+        out.tree = std::move(tree);
+        out.res = ml_branch_lengths(a, rows, model_factory, *out.tree, rounds, eps, be, from);
+    };
+    // --ml_spr: the scan of a round whose interchanges applied no move; true: a move was applied
+    auto spr_step = [&](uint32_t round) -> bool {
+        const MlTreeTopology topo = ml_tree_topology(*out.tree);
+        const MlSprScan scan = spr->scan(model_factory, topo, out.res, ncols, flat.data(), spr->radius, eps, be, kSprRhoBytes);
+        MlSearchRound line;
+        line.round = round; line.spr = true; line.candidates = scan.candidates; line.positive = scan.positive; line.best_gain = scan.best_gain;
+        line.lnl_before = line.lnl_applied = line.lnl_after = out.res.lnl;
+        bool accepted = false;
+        for (size_t m = scan.pick_v.size(); m >= 1 && !accepted; m = m / 2) {
+            std::unique_ptr<PhyTree> tree(spr->apply(topo, out.res.lengths, (uint32_t)m, scan.pick_v.data(), scan.pick_y.data()));
+            const double there = lnl_of_tree(*tree);
+            if (there > line.lnl_before) {
+                accepted = true;
+                line.applied = (uint32_t)m;
+                line.lnl_applied = there;
+                accept(std::move(tree));
+                line.lnl_after = out.res.lnl;
+            }
+        }
+        out.log.push_back(line);
+        if (!accepted) return false;
+        ++ml_search_stats.rounds;
+        ml_spr_stats.applied += line.applied;
+        return true;
+    };
+
+    // the interchange step of a round; true: a move was applied
+    auto nni_step = [&](uint32_t round) -> bool {
         const MlTreeTopology topo = ml_tree_topology(*out.tree);
         const uint32_t nleaves = topo.nleaves, nnodes = topo.nnodes;
         const MlSearchTree cur = ml_search_tree(topo, out.res.lengths);
@@ -289,7 +346,7 @@ MlSearchResult ml_topology_search(const Alphabet &a, const std::vector<std::vect
         MlSearchRound line;
         line.round = round; line.candidates = (uint32_t)cv.size();
         line.lnl_before = line.lnl_applied = line.lnl_after = out.res.lnl;
-        if (cv.empty()) { out.log.push_back(line); break; }   // (a tree whose root alone is an inner node)
+        if (cv.empty()) { out.log.push_back(line); return false; }   // (a tree whose root alone is an inner node)
         const uint32_t ncand = (uint32_t)cv.size();
         const uint32_t ncat = out.res.rates.empty() ? 1u : (uint32_t)out.res.rates.size();
         const std::vector<double> w(ncat, out.res.rates.empty() ? 1.0 : 1.0 / (double)ncat);
@@ -326,7 +383,7 @@ MlSearchResult ml_topology_search(const Alphabet &a, const std::vector<std::vect
             for (uint32_t x : four) used[x] = 1;
             picked.push_back(q);
         }
-        if (picked.empty()) { out.log.push_back(line); break; }
+        if (picked.empty()) { out.log.push_back(line); return false; }
         bool accepted = false;
         for (size_t m = picked.size(); m >= 1 && !accepted; m = m / 2) {
             MlSearchTree next = cur;
@@ -337,38 +394,25 @@ MlSearchResult ml_topology_search(const Alphabet &a, const std::vector<std::vect
                 if (nni_opt) next.length[v] = t_opt[q];   // the length the move was ranked at
             }
             std::unique_ptr<PhyTree> tree(ml_search_build(next, next.root));
-            // one evaluation without derivatives at the carried lengths and the rates in hand (ml_tree_topology numbers the new tree)
-            const MlTreeTopology nt = ml_tree_topology(*tree);
-            std::vector<double> t(nt.nnodes - 1);
-            for (uint32_t e = 0; e + 1 < nt.nnodes; ++e) t[e] = nt.node[e]->getBranchLength();
-            if (out.res.rates.empty()) {
-                treelik_matrices(model_factory, t, false, P);
-                if (be) be->tree_likelihood(dim, nleaves, nnodes, nt.parent.data(), ncols, flat.data(), pi, P.data(), 0, site_l.data(), site_k.data(), nullptr, nullptr);
-                else tree_likelihood_host(dim, nleaves, nnodes, nt.parent.data(), ncols, flat.data(), pi, P.data(), 0, site_l.data(), site_k.data(), nullptr, nullptr);
-            } else {
-                treelik_matrices(model_factory, t, false, out.res.rates, P);
-                if (be) be->tree_likelihood_rates(dim, nleaves, nnodes, nt.parent.data(), ncols, flat.data(), pi, ncat, w.data(), P.data(), 0, site_l.data(), site_k.data(),
-                                                  post.data(), nullptr, nullptr);
-                else tree_likelihood_rates_host(dim, nleaves, nnodes, nt.parent.data(), ncols, flat.data(), pi, ncat, w.data(), P.data(), 0, site_l.data(), site_k.data(),
-                                                post.data(), nullptr, nullptr);
-            }
-            ++ml_tree_stats.evaluations;
-            const double there = treelik_lnl(ncols, site_l.data(), site_k.data(), nullptr);
+            const double there = lnl_of_tree(*tree);
             if (there > line.lnl_before) {
                 accepted = true;
                 line.applied = (uint32_t)m;
                 line.lnl_applied = there;
-                MlGamma from = gamma;
-                if (gamma.ncat >= 2 && gamma.estimate) from.start = out.res.alpha;
-                out.tree = std::move(tree);
-                out.res = ml_branch_lengths(a, rows, model_factory, *out.tree, rounds, eps, be, from);
+                accept(std::move(tree));
                 line.lnl_after = out.res.lnl;
             }
         }
         out.log.push_back(line);
-        if (!accepted) break;
+        if (!accepted) return false;
         ++ml_search_stats.rounds;
         ml_search_stats.applied += line.applied;
+        return true;
+    };
+
+    for (uint32_t round = 1; round <= search_rounds; ++round) {
+        if (nni_step(round)) continue;
+        if (!spr || !spr_step(round)) break;   // (the search ends where no step applies a move)
     }
     out.res.lnl_start = lnl_start;
     ml_tree_stats.lnl_start = lnl_start;
