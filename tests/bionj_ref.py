@@ -51,7 +51,8 @@ def column_sums(R):
 
 def bionj_joins(D, V):
     """(joins, final_d, info) of the n x n matrices D, V (n >= 4; entry (i, j) at [i, j]); the inputs are not modified.
-    joins: array of JOIN_DTYPE, n - 3 records; final_d: 3 x 3; info: how many joins clamped lambda to 0 and to 1."""
+    joins: array of JOIN_DTYPE, n - 3 records; final_d: 3 x 3; info: how many joins clamped lambda to 0 and to 1, and under
+    "lambda" the unclamped lambda of every join (NaN where the host takes 0.5)."""
     D = np.array(D, dtype=np.float64)
     V = np.array(V, dtype=np.float64)
     n = D.shape[0]
@@ -62,7 +63,7 @@ def bionj_joins(D, V):
     np.fill_diagonal(V, 0.0)
     act = np.arange(n)
     joins = np.zeros(n - 3, dtype=JOIN_DTYPE)
-    info = dict(lambda_at_0=0, lambda_at_1=0)
+    info = dict(lambda_at_0=0, lambda_at_1=0, **{"lambda": np.full(n - 3, np.nan)})
     fresh = -1
     with np.errstate(all="ignore"):
         for step, dim in enumerate(range(n, 3, -1)):
@@ -99,6 +100,7 @@ def bionj_joins(D, V):
             vsum = np.add.accumulate(np.concatenate([[0.0], diffs]))[-1]
             v12 = V[a1, a2]
             lam = np.float64(0.5) + vsum / (np.float64(2 * (dim - 2)) * v12)
+            info["lambda"][step] = lam
             if np.isnan(lam):
                 lam = np.float64(0.5)
             else:   # std::min(std::max(0.0, lambda), 1.0)
