@@ -505,7 +505,7 @@ int pgm_tree_likelihood(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t n
                         uint32_t ncols, const int8_t *rows /* nleaves x ncols */, const double *pi /* dim */,
                         const double *P /* (nnodes-1) x {1 or 3} x dim x dim */, int derivs,
                         double *site_l /* ncols */, int32_t *site_k /* ncols */, double *d1, double *d2 /* nnodes-1, derivs only */);
-float pgm_treelik_last_kernel_ms(pgm_ctx *ctx);   /* device time of the kernels of the last pgm_tree_likelihood, pgm_tree_likelihood_rates, pgm_tree_ancestral, pgm_tree_nni, pgm_tree_nni_edge or pgm_tree_spr call */
+float pgm_treelik_last_kernel_ms(pgm_ctx *ctx);   /* device time of the kernels of the last pgm_tree_likelihood, pgm_tree_likelihood_rates, pgm_tree_ancestral, pgm_tree_nni, pgm_tree_nni_edge, pgm_tree_spr, pgm_tree_ancestral_joint or pgm_tree_ancestral_sample call */
 
 /* ---- the same likelihood under a mixture of ncat rate categories (pgmsa --ml_tree --ml_gamma).
  * Everything from dim to pi, and derivs, d1, d2, is as in pgm_tree_likelihood, with the same checks.  ncat: 1 .. PGM_TREELIK_MAXCAT;
@@ -667,6 +667,71 @@ int pgm_tree_spr(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, 
                  const double *Ph /* as P: the matrix of half of every edge */, uint32_t ncand, const uint32_t *cand_v,
                  const uint32_t *cand_y /* ncand each */, double *site_l /* ncols */, int32_t *site_k /* ncols */,
                  double *post /* ncat x ncols */, double *rho /* ncand x ncols */);
+
+/* ---- the jointly most probable ancestral states on the same tree under the same mixture (pgmsa --ml_tree --ml_ancestral_joint;
+ * Pupko et al. 2000).
+ * Everything from dim to P is as in pgm_tree_ancestral, with the same checks; site_l, site_k and post are pgm_tree_likelihood_rates's
+ * values with derivs == 0, bit for bit: the same up pass and the same combine.  ninner = nnodes - nleaves; inner node v has row
+ * v - nleaves.  Per site s:
+ *   cat[s] = the smallest k whose post[k][s] is the largest (k ascending from 0; a later k takes over only when strictly greater).  The
+ *          joint assignment is taken under that category: the arg-max over the assignments of the whole mixture does not decompose
+ *          over the tree and is not computed.
+ *   With the matrices of category cat[s], a max-product up pass over the inner nodes ascending:
+ *   leaf   m_c(i) = S_c(i) of pgm_tree_likelihood: 0.0 + P_c(i, r) for a leaf of state r, the sum of P_c(i, j) over j ascending from 0.0
+ *          for missing data
+ *   F_v(j) = the product of m_c(j) over the children c of v in child order (it starts with its first factor); then the scaling rule
+ *          on its dim values (largest below 2^-256 and above 0: every value * 2^256, joint_k += 1)
+ *   v not the root:  m_v(i) = max_j P_v(i, j) * F_v(j): one multiply per term, j ascending, the maximum starts as the term of j = 0 and
+ *          a later term replaces it only when strictly greater;  ptr_v(i) = the j that holds it (the smallest such j)
+ *   root   r(j) = pi[j] * F_root(j);  joint_l[s] = the maximum of r by the same rule, the root's state the j that holds it
+ *   back   the inner nodes below the root descending (parents first): state(v) = ptr_v(state(parent[v]))
+ *   joint_state[(v - nleaves) * ncols + s] = state(v);  every state of the site is -1 when joint_l[s] == 0.0
+ * joint_l * 2^(-256 joint_k) is the probability of the column together with that assignment under category cat[s].  Only * and
+ * comparisons occur past the leaves' sums and nothing is contracted: the values do not depend on the launch and equal the host
+ * statement's (tree_ancestral_joint_host) bit for bit.  Every output is overwritten.
+ * Device memory: that of pgm_tree_likelihood_rates with derivs == 0 (ncat * 8 * ninner * ncols * dim bytes of partials, the inputs,
+ * 12 * ncat * ncols for (L_c, k_c), (12 + 8 * ncat) * ncols of outputs), and 8 * ninner * ncols * dim bytes for F, ninner * ncols * dim
+ * for the back-pointers, (13 + ninner) * ncols for cat, joint_l, joint_k and joint_state.  Memory that cannot be had is PGM_ERR_NOMEM.
+ * pgm_treelik_last_kernel_ms covers the call.
+ * PGM_ERR_INVALID, before anything is launched or an output is touched: what pgm_tree_ancestral refuses (its own outputs aside), a null
+ * cat, joint_state, joint_l or joint_k. */
+int pgm_tree_ancestral_joint(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
+                             const double *pi, uint32_t ncat, const double *w /* ncat */, const double *P /* ncat x (nnodes-1) x dim x dim */,
+                             double *site_l /* ncols */, int32_t *site_k /* ncols */, double *post /* ncat x ncols */, uint8_t *cat /* ncols */,
+                             int8_t *joint_state /* ninner x ncols */, double *joint_l /* ncols */, int32_t *joint_k /* ncols */);
+
+/* ---- ancestral states drawn from their joint posterior on the same tree under the same mixture (pgmsa --ml_tree
+ * --ml_ancestral_samples; the stochastic traceback through the partials).
+ * Everything from dim to P, and site_l, site_k, post, is as in pgm_tree_ancestral_joint, with the same checks.  The call writes the
+ * samples N = first_sample + n, n = 0 .. nsamp - 1; what a sample holds depends on N, the site and seed alone, so a caller may cut its
+ * samples into calls of bounded output.
+ * Draw x of sample N at site s (x = 0: the category; x = 1 + (v - nleaves): inner node v), all integer arithmetic mod 2^64:
+ *   z = splitmix64 of the state seed + 0x9E3779B97F4A7C15 * (((N * ncols) + s) * (ninner + 1) + x), that is
+ *       z = state + 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z = z ^ (z >> 31)
+ *   u = (z >> 11) * 2^-53   (exact: 0 <= u < 1)
+ * The pick of a draw on the weights q_0 .. q_{m-1}:
+ *   T = the sum of the weights, ascending from 0.0;  T == 0.0: the pick is -1
+ *   target = u * T;  c = 0.0, then c = c + q_j for j ascending: the pick is the first j with c > target;  when there is none (a NaN
+ *   among the weights; with finite weights u * T is below T, where c ends) the largest j with q_j > 0, and -1 when there is none either
+ * The weights:
+ *   category   post[k][s], k = 0 .. ncat - 1
+ *   root, in the picked category k:   pi[i] * U_root(i), U the stored scaled partials of category k at the site
+ *   node v below the root, descending (parents first), its parent in state i:   P_v(i, j) * U_v(j), the matrix and partial of category k
+ *   a category of -1 or a parent of -1 gives -1
+ * The scale factors of the partials cancel in target / T: every draw is from the exact conditional distribution, so a sample is an
+ * independent draw from the posterior of (category, every inner state) given the column.
+ *   samp_cat[s * nsamp + n] = the category (255 for -1);   samp_state[((v - nleaves) * ncols + s) * nsamp + n] = the state of v
+ * A weight is formed by one multiply wherever it is needed, every sum runs ascending from 0.0 with one add per term and nothing is
+ * contracted: the values do not depend on the launch and equal the host statement's (tree_ancestral_sample_host) byte for byte.  Every
+ * output is overwritten.
+ * Device memory: that of pgm_tree_likelihood_rates with derivs == 0, and (1 + ninner) * ncols * nsamp bytes for the samples.  Memory
+ * that cannot be had is PGM_ERR_NOMEM.  pgm_treelik_last_kernel_ms covers the call.
+ * PGM_ERR_INVALID, before anything is launched or an output is touched: what pgm_tree_ancestral refuses (its own outputs aside),
+ * nsamp == 0, a null samp_cat or samp_state. */
+int pgm_tree_ancestral_sample(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
+                              const double *pi, uint32_t ncat, const double *w /* ncat */, const double *P /* ncat x (nnodes-1) x dim x dim */,
+                              uint32_t nsamp, uint64_t first_sample, uint64_t seed, double *site_l /* ncols */, int32_t *site_k /* ncols */,
+                              double *post /* ncat x ncols */, uint8_t *samp_cat /* ncols x nsamp */, int8_t *samp_state /* ninner x ncols x nsamp */);
 
 /* The sums of every row of a matrix over nrep resamplings of its columns (`pgmsa --ml_tree --ml_support`): with
  * x = log rho of pgm_tree_nni, the resampled log-likelihood gain of every neighbour of the tree in every bootstrap replicate.

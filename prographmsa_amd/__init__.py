@@ -94,6 +94,7 @@ EXPORTS = [
     "pgm_msa_agreement", "pgm_agreement_last_kernel_ms",
     "pgm_transfer_min", "pgm_transfer_last_kernel_ms", "pgm_transfer_taxa",
     "pgm_tree_likelihood", "pgm_treelik_last_kernel_ms", "pgm_tree_likelihood_rates", "pgm_tree_ancestral", "pgm_tree_nni", "pgm_tree_nni_edge", "pgm_tree_spr",
+    "pgm_tree_ancestral_joint", "pgm_tree_ancestral_sample",
     "pgm_resampled_sums", "pgm_resample_last_kernel_ms",
 ]
 
@@ -194,6 +195,12 @@ def _load():
         "pgm_tree_spr": (C.c_int, [vp, u32, u32, u32, C.POINTER(u32), u32, C.POINTER(C.c_int8), C.POINTER(C.c_double), u32, C.POINTER(C.c_double),
                                    C.POINTER(C.c_double), C.POINTER(C.c_double), u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(C.c_double), C.POINTER(i32),
                                    C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "pgm_tree_ancestral_joint": (C.c_int, [vp, u32, u32, u32, C.POINTER(u32), u32, C.POINTER(C.c_int8), C.POINTER(C.c_double), u32, C.POINTER(C.c_double),
+                                               C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(C.c_double), C.POINTER(C.c_uint8),
+                                               C.POINTER(C.c_int8), C.POINTER(C.c_double), C.POINTER(i32)]),
+        "pgm_tree_ancestral_sample": (C.c_int, [vp, u32, u32, u32, C.POINTER(u32), u32, C.POINTER(C.c_int8), C.POINTER(C.c_double), u32, C.POINTER(C.c_double),
+                                                C.POINTER(C.c_double), u32, C.c_uint64, C.c_uint64, C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(C.c_double),
+                                                C.POINTER(C.c_uint8), C.POINTER(C.c_int8)]),
         "pgm_resampled_sums": (C.c_int, [vp, u32, u32, C.POINTER(C.c_double), u32, C.POINTER(u32), C.POINTER(C.c_double)]),
         "pgm_resample_last_kernel_ms": (C.c_float, [vp]),
     }
@@ -369,6 +376,57 @@ class Context:
         check(lib.pgm_tree_ancestral(self.handle, dim, nleaves, nnodes, P_(parent, C.c_uint32), ncols, P_(rows, C.c_int8), P_(pi, C.c_double), ncat,
                                      P_(w, C.c_double), P_(P, C.c_double), P_(out[0], C.c_double), P_(out[1], C.c_int32), P_(out[2], C.c_double),
                                      P_(out[3], C.c_int8), P_(out[4], C.c_double), P_(out[5], C.c_double) if full else None), "pgm_tree_ancestral")
+        return tuple(out)
+
+    def _tree_ancestral_inputs(self, what, dim, parent, rows, pi, w, P):
+        import numpy as np
+        parent = np.ascontiguousarray(parent, np.uint32)
+        rows = np.ascontiguousarray(rows, np.int8)
+        pi = np.ascontiguousarray(pi, np.float64)
+        w = np.ascontiguousarray(w, np.float64)
+        P = np.ascontiguousarray(P, np.float64)
+        if parent.ndim != 1 or rows.ndim != 2 or pi.shape != (dim,) or w.ndim != 1 or P.size != len(w) * (len(parent) - 1) * dim * dim or len(parent) <= rows.shape[0]:
+            raise ValueError("%s: input array of the wrong shape" % what)
+        return parent, rows, pi, w, P
+
+    def tree_ancestral_joint(self, dim, parent, rows, pi, w, P, out=None):
+        """pgm_tree_ancestral_joint: inputs as tree_ancestral -> (site_l, site_k, post, cat (ncols uint8), joint_state (ninner x ncols
+        int8), joint_l (ncols float64), joint_k (ncols int32)).  Given output arrays (a tuple of seven, C-contiguous of those kinds)
+        are overwritten."""
+        import numpy as np
+        parent, rows, pi, w, P = self._tree_ancestral_inputs("tree_ancestral_joint", dim, parent, rows, pi, w, P)
+        nnodes, (nleaves, ncols), ncat = len(parent), rows.shape, len(w)
+        ninner = nnodes - nleaves
+        kinds = [((ncols,), np.float64), ((ncols,), np.int32), ((ncat, ncols), np.float64), ((ncols,), np.uint8), ((ninner, ncols), np.int8), ((ncols,), np.float64),
+                 ((ncols,), np.int32)]
+        if out is None: out = tuple(np.zeros(s, t) for s, t in kinds)
+        if len(out) != 7 or any(not isinstance(a, np.ndarray) or a.dtype != t or a.shape != s or not a.flags.c_contiguous for a, (s, t) in zip(out, kinds)):
+            raise ValueError("tree_ancestral_joint: output array of the wrong kind")
+        P_ = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+        check(lib.pgm_tree_ancestral_joint(self.handle, dim, nleaves, nnodes, P_(parent, C.c_uint32), ncols, P_(rows, C.c_int8), P_(pi, C.c_double), ncat,
+                                           P_(w, C.c_double), P_(P, C.c_double), P_(out[0], C.c_double), P_(out[1], C.c_int32), P_(out[2], C.c_double),
+                                           P_(out[3], C.c_uint8), P_(out[4], C.c_int8), P_(out[5], C.c_double), P_(out[6], C.c_int32)), "pgm_tree_ancestral_joint")
+        return tuple(out)
+
+    def tree_ancestral_sample(self, dim, parent, rows, pi, w, P, nsamp, seed, first_sample=0, out=None):
+        """pgm_tree_ancestral_sample: inputs as tree_ancestral; the samples first_sample .. first_sample + nsamp - 1 of the stream of
+        `seed` -> (site_l, site_k, post, samp_cat (ncols x nsamp uint8), samp_state (ninner x ncols x nsamp int8)).  Given output arrays
+        (a tuple of five, C-contiguous of those kinds) are overwritten."""
+        import numpy as np
+        parent, rows, pi, w, P = self._tree_ancestral_inputs("tree_ancestral_sample", dim, parent, rows, pi, w, P)
+        nsamp, seed, first_sample = int(nsamp), int(seed), int(first_sample)
+        if not (0 < nsamp < 2 ** 32 and 0 <= seed < 2 ** 64 and 0 <= first_sample < 2 ** 64):
+            raise ValueError("tree_ancestral_sample: nsamp, seed or first_sample out of range")
+        nnodes, (nleaves, ncols), ncat = len(parent), rows.shape, len(w)
+        ninner = nnodes - nleaves
+        kinds = [((ncols,), np.float64), ((ncols,), np.int32), ((ncat, ncols), np.float64), ((ncols, nsamp), np.uint8), ((ninner, ncols, nsamp), np.int8)]
+        if out is None: out = tuple(np.zeros(s, t) for s, t in kinds)
+        if len(out) != 5 or any(not isinstance(a, np.ndarray) or a.dtype != t or a.shape != s or not a.flags.c_contiguous for a, (s, t) in zip(out, kinds)):
+            raise ValueError("tree_ancestral_sample: output array of the wrong kind")
+        P_ = lambda a, t: a.ctypes.data_as(C.POINTER(t))
+        check(lib.pgm_tree_ancestral_sample(self.handle, dim, nleaves, nnodes, P_(parent, C.c_uint32), ncols, P_(rows, C.c_int8), P_(pi, C.c_double), ncat,
+                                            P_(w, C.c_double), P_(P, C.c_double), nsamp, first_sample, seed, P_(out[0], C.c_double), P_(out[1], C.c_int32),
+                                            P_(out[2], C.c_double), P_(out[3], C.c_uint8), P_(out[4], C.c_int8)), "pgm_tree_ancestral_sample")
         return tuple(out)
 
     def tree_nni(self, dim, parent, rows, pi, w, P, cand, out=None):

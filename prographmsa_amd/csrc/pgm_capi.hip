@@ -100,7 +100,7 @@ struct pgm_ctx {
         SC_TRANSFER_REF,                    // pgm_transfer_min and pgm_transfer_taxa (shared): reference sets, rep_off, thresholds
         SC_TRANSFER_REP,                    //   replicate sets
         SC_TRANSFER_OUT,                    //   phi (taxa: phi, arg, flip, moved, counted)
-        SC_TREELIK_TREE,                    // tree likelihood, ancestral states, NNI and SPR scores, all six entries (shared; pgm_treelik_plan.h has the layouts): children lists, pi, weights, rows
+        SC_TREELIK_TREE,                    // tree likelihood, ancestral states, NNI and SPR scores, joint states and samples, all eight entries (shared; pgm_treelik_plan.h has the layouts): children lists, pi, weights, rows
         SC_TREELIK_P,                       //   the matrices
         SC_TREELIK_U,                       //   partials and outside vectors (ancestral: the categories' posteriors in their place)
         SC_TREELIK_G,                       //   per-site ratios and chunk sums (rates: the categories' site values and ratios first)

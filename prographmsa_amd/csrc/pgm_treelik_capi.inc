@@ -1,8 +1,9 @@
 // pgm_treelik_capi.inc — C ABI of the tree likelihood and what is built on it (included by pgm_capi.hip): pgm_tree_likelihood
 // (pgmsa --ml_tree, DESIGN.md 3.17), pgm_tree_likelihood_rates (--ml_gamma, 3.18), pgm_tree_ancestral (--ml_ancestral, 3.19),
 // pgm_tree_nni (--ml_search, 3.20), pgm_tree_nni_edge (--ml_nni_opt, 3.22) and pgm_tree_spr (--ml_spr, 3.23).  The arguments are checked on the host and the children lists are built there
-// (pgm_treelik_check.h), then: one upload of the inputs, the launches, one copy back.  The six entries share five scratch slots,
-// laid out by pgm_treelik_plan.h.  Stateless: nothing of a call is read by the next.
+// (pgm_treelik_check.h), then: one upload of the inputs, the launches, one copy back.  pgm_tree_ancestral_joint and
+// pgm_tree_ancestral_sample (--ml_ancestral_joint, --ml_ancestral_samples, 3.24) are the last two.  The eight entries share five scratch
+// slots, laid out by pgm_treelik_plan.h.  Stateless: nothing of a call is read by the next.
 extern "C" float pgm_treelik_last_kernel_ms(pgm_ctx *ctx) { return ctx ? ctx->treelik_ms : 0.0f; }
 
 // What every entry does past its own null checks: the shared refusals (ncat and the weights, the tree, the candidates), the slots,
@@ -13,6 +14,7 @@ struct TreelikIn {
     uint32_t ncand; const uint32_t *cand_v, *cand_a, *cand_c; bool full;
     const double *Pc = nullptr;   // (pgm_tree_nni_edge alone)
     const double *Ph = nullptr; const uint32_t *cand_y = nullptr;   // (pgm_tree_spr alone)
+    uint32_t nsamp = 0;           // (pgm_tree_ancestral_sample alone)
 };
 static_assert(pgm_ctx::SC_TREELIK_OUT - pgm_ctx::SC_TREELIK_TREE == PGM_TL_SLOT_OUT, "the five slots in the order of pgm_treelik_plan.h");
 struct TreelikCall {
@@ -33,7 +35,7 @@ struct TreelikCall {
         if (bad.empty() && (mode == PGM_TREELIK_CALL_NNI || mode == PGM_TREELIK_CALL_NNI_EDGE)) bad = pgm_treelik_check_candidates(in.nleaves, in.nnodes, in.parent, in.ncand, in.cand_v, in.cand_a, in.cand_c);
         if (bad.empty() && mode == PGM_TREELIK_CALL_SPR) bad = pgm_treelik_check_spr(in.nnodes, in.parent, tree.data(), in.ncand, in.cand_v, in.cand_y, path);
         if (!bad.empty()) return fail(PGM_ERR_INVALID, bad);
-        pl = pgm_treelik_plan(mode, in.dim, in.nleaves, in.nnodes, in.ncols, in.ncat, in.derivs != 0, in.ncand, in.full);
+        pl = pgm_treelik_plan(mode, in.dim, in.nleaves, in.nnodes, in.ncols, in.ncat, in.derivs != 0, in.ncand, in.full, in.nsamp);
         c.emplace(ctx, what, &ctx->treelik_ms);
         for (int k = 0; k < PGM_TL_NSLOTS; ++k)
             if (pl.slot_bytes[k]) c->buf(pgm_ctx::SC_TREELIK_TREE + k, pl.slot_bytes[k], &slot[k]);
@@ -240,5 +242,65 @@ extern "C" int pgm_tree_spr(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32
     t.c->end();
     t.down(site_l, site_k, post, nullptr, nullptr);
     t.c->down(rho, x.rho, t.pl.r[PGM_TL_RHO].bytes);
+    return t.c->finish();
+}
+
+// The walk and the combine launches of pgm_tree_likelihood_rates without derivs, then pgm_treelik_joint_kernel (the max pass, a
+// workgroup per block of sites as in the walk) and pgm_treelik_joint_trace_kernel (a thread per site).
+extern "C" int pgm_tree_ancestral_joint(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
+                                        const double *pi, uint32_t ncat, const double *w, const double *P, double *site_l, int32_t *site_k, double *post, uint8_t *cat,
+                                        int8_t *joint_state, double *joint_l, int32_t *joint_k) {
+    if (!ctx) return fail(PGM_ERR_INVALID, "null argument");
+    ctx->treelik_ms = 0;
+    if (!parent || !rows || !pi || !w || !P || !site_l || !site_k || !post || !cat || !joint_state || !joint_l || !joint_k) return fail(PGM_ERR_INVALID, "null argument");
+    TreelikCall t;
+    if (const int rc = t.open(ctx, "tree ancestral joint", PGM_TREELIK_CALL_JOINT, {dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, 0, 0, nullptr, nullptr, nullptr, false}))
+        return rc;
+    PgmTreelikJointArgs x;
+    x.t = t.a; x.pstride = t.pl.p_count; x.ncat = ncat;
+    x.parent = t.at<const uint32_t>(PGM_TL_PARENT); x.post = t.m.post;
+    x.F = t.at<double>(PGM_TL_JF); x.ptr = t.at<uint8_t>(PGM_TL_JPTR);
+    x.cat = t.at<uint8_t>(PGM_TL_JCAT); x.state = t.at<int8_t>(PGM_TL_JSTATE); x.joint_l = t.at<double>(PGM_TL_JL); x.joint_k = t.at<int32_t>(PGM_TL_JK);
+    if (t.c->begin()) {
+        hipLaunchKernelGGL(pgm_treelik_cat_kernel<PGM_TREELIK_RAW>, dim3(t.blocks, ncat), dim3(PGM_TREELIK_THREADS), 0, t.c->s, t.a, t.st);
+        hipLaunchKernelGGL(pgm_treelik_combine_kernel, dim3(t.cblocks, 1u), dim3(PGM_TREELIK_THREADS), 0, t.c->s, t.m);
+        hipLaunchKernelGGL(pgm_treelik_joint_kernel, dim3(t.blocks), dim3(PGM_TREELIK_THREADS), 0, t.c->s, x);
+        hipLaunchKernelGGL(pgm_treelik_joint_trace_kernel, dim3(t.cblocks), dim3(PGM_TREELIK_THREADS), 0, t.c->s, x);
+    }
+    t.c->end();
+    t.down(site_l, site_k, post, nullptr, nullptr);
+    t.c->down(cat, x.cat, t.pl.r[PGM_TL_JCAT].bytes);
+    t.c->down(joint_state, x.state, t.pl.r[PGM_TL_JSTATE].bytes);
+    t.c->down(joint_l, x.joint_l, t.pl.r[PGM_TL_JL].bytes);
+    t.c->down(joint_k, x.joint_k, t.pl.r[PGM_TL_JK].bytes);
+    return t.c->finish();
+}
+
+// The same walk and combine launches, then pgm_treelik_sample_kernel over (block of 64 samples x site): a lane is a sample.
+extern "C" int pgm_tree_ancestral_sample(pgm_ctx *ctx, uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows,
+                                         const double *pi, uint32_t ncat, const double *w, const double *P, uint32_t nsamp, uint64_t first_sample, uint64_t seed,
+                                         double *site_l, int32_t *site_k, double *post, uint8_t *samp_cat, int8_t *samp_state) {
+    if (!ctx) return fail(PGM_ERR_INVALID, "null argument");
+    ctx->treelik_ms = 0;
+    if (!parent || !rows || !pi || !w || !P || !site_l || !site_k || !post || !samp_cat || !samp_state) return fail(PGM_ERR_INVALID, "null argument");
+    if (nsamp == 0) return fail(PGM_ERR_INVALID, "tree ancestral sample: no sample");
+    TreelikCall t;
+    TreelikIn in = {dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, 0, 0, nullptr, nullptr, nullptr, false};
+    in.nsamp = nsamp;
+    if (const int rc = t.open(ctx, "tree ancestral sample", PGM_TREELIK_CALL_SAMPLE, in)) return rc;
+    PgmTreelikSampleArgs x;
+    x.t = t.a; x.st = t.st; x.ncat = ncat; x.nsamp = nsamp; x.first = first_sample; x.seed = seed;
+    x.parent = t.at<const uint32_t>(PGM_TL_PARENT); x.post = t.m.post;
+    x.cat = t.at<uint8_t>(PGM_TL_SCAT); x.state = t.at<int8_t>(PGM_TL_SSTATE);
+    const uint32_t sblocks = (nsamp - 1) / PGM_TREELIK_THREADS + 1;
+    if (t.c->begin()) {
+        hipLaunchKernelGGL(pgm_treelik_cat_kernel<PGM_TREELIK_RAW>, dim3(t.blocks, ncat), dim3(PGM_TREELIK_THREADS), 0, t.c->s, t.a, t.st);
+        hipLaunchKernelGGL(pgm_treelik_combine_kernel, dim3(t.cblocks, 1u), dim3(PGM_TREELIK_THREADS), 0, t.c->s, t.m);
+        hipLaunchKernelGGL(pgm_treelik_sample_kernel, dim3(sblocks, std::min<uint32_t>(ncols, 65535u)), dim3(PGM_TREELIK_THREADS), 0, t.c->s, x);   // (the kernel strides over the rest)
+    }
+    t.c->end();
+    t.down(site_l, site_k, post, nullptr, nullptr);
+    t.c->down(samp_cat, x.cat, t.pl.r[PGM_TL_SCAT].bytes);
+    t.c->down(samp_state, x.state, t.pl.r[PGM_TL_SSTATE].bytes);
     return t.c->finish();
 }

@@ -16,6 +16,9 @@
 // pgm_tree_nni_edge is that kernel's second instantiation: the neighbour's edge with three matrices of its own.
 // pgm_tree_spr runs the walk in the same mode; pgm_treelik_spr_kernel then scores every pruning and regrafting from
 // the stored pieces along the candidate's path.
+// pgm_tree_ancestral_joint and pgm_tree_ancestral_sample run the walk as pgm_tree_likelihood_rates does without
+// derivs and then kernels of their own, at the end of this file: a max-product pass with back-pointers and its traceback, and a
+// stochastic traceback through the stored partials.
 //
 // Every sum over states runs ascending from 0.0 with one multiply and one add per term (-ffp-contract=off): the bits are those of
 // tree_likelihood_host.  The walk is a chain of dependent steps on one wavefront, so what a step costs is the latency of its loads:
@@ -813,6 +816,198 @@ __global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_sums_kernel(c
 #pragma unroll 8
         for (uint32_t chunk = 0; chunk < nchunks; ++chunk) acc = acc + p[chunk];
         (threadIdx.x == 0 ? d1 : d2)[e] = acc;
+    }
+}
+
+// The jointly most probable ancestral states (pgm_tree_ancestral_joint), after the walk (PGM_TREELIK_RAW without
+// derivs) and the combine kernel gave post.  pgm_treelik_joint_kernel is the max-product up pass in the shape of the walk: a workgroup
+// of one wavefront owns 64 / dim consecutive sites, a thread per (site, state), and goes over the inner nodes ascending.  The threads of
+// a site find the site's category (the first of the largest post) themselves and read that category's matrices, so the sites of a
+// workgroup may each read another category's; every loop and every barrier is uniform all the same.  At node v the thread of state i
+// forms, per child c, m_c(i): the leaf rule of the walk, or max_j P_c(i, j) F_c(j) from the F the workgroup stored at c (eight
+// operands fetched ahead of eight ordered compares), and writes the j that holds it as the back-pointer of (c, i): every node but the
+// root has one parent, so a back-pointer has one writer.  The product of the m_c meets the scaling rule and goes to F.  The thread of
+// state 0 then scans pi F_root.  The back-pointers lie [node][state][site], the sites fastest: pgm_treelik_joint_trace_kernel has a thread
+// per site, 64 dependent chains in flight per wavefront, and its loads of one node run along the sites (different lanes read different
+// state rows, each a run of the same 64 sites).  It goes over the nodes descending and finds the state of a node's parent in its own
+// earlier write of joint_state.  No workgroup waits for another, nothing spins, there are no atomics and every entry has one writer.
+struct PgmTreelikJointArgs {
+    PgmTreelikArgs t;                      // the tree, rows, pi and category 0's P (U, O, g, h, site_l, site_k unused)
+    size_t pstride;                        // doubles between two categories' matrices
+    uint32_t ncat;
+    const uint32_t *parent;                // nnodes
+    const double *post;                    // ncat x ncols
+    double *F;                             // ninner x ncols x dim
+    uint8_t *ptr;                          // ninner x dim x ncols
+    uint8_t *cat;                          // ncols
+    int8_t *state;                         // ninner x ncols
+    double *joint_l;                       // ncols
+    int32_t *joint_k;                      // ncols
+};
+__global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_joint_kernel(PgmTreelikJointArgs n) {
+    __shared__ double sh[PGM_TREELIK_THREADS];
+    const PgmTreelikArgs &a = n.t;
+    const uint32_t dim = a.dim, nleaves = a.nleaves, root = a.nnodes - 1, ncols = a.ncols;
+    const uint32_t local = threadIdx.x / dim, i = threadIdx.x - local * dim;
+    const uint64_t s64 = (uint64_t)blockIdx.x * a.spb + local;
+    const bool active = local < a.spb && s64 < ncols;
+    const uint32_t s = (uint32_t)s64;
+    const size_t mat = (size_t)dim * dim;
+    double *shs = &sh[local * dim];
+
+    uint32_t k = 0;   // the site's category
+    if (active) {
+        double top = n.post[s];
+        for (uint32_t c = 1; c < n.ncat; ++c) { const double x = n.post[(size_t)c * ncols + s]; if (x > top) { top = x; k = c; } }
+    }
+    const double *Pk = a.P + n.pstride * k;
+    int32_t count = 0;
+    for (uint32_t v = nleaves; v <= root; ++v) {
+        double prod = 0.0;
+        if (active) {
+            const uint32_t q0 = a.child_off[v], q1 = a.child_off[v + 1];
+            for (uint32_t q = q0; q < q1; ++q) {
+                const uint32_t c = a.child[q];
+                double m;
+                if (c < nleaves) {
+                    double S[1];
+                    pgm_treelik_apply<1>(a, Pk + mat * c, mat, c, s, i, S);
+                    m = S[0];
+                } else {
+                    const double *col = Pk + mat * c + i, *f = n.F + ((size_t)(c - nleaves) * ncols + s) * dim;
+                    uint32_t arg = 0, j = 1;
+                    m = col[0] * f[0];
+                    for (; j + 8 <= dim; j += 8) {
+                        double pv[8], fv[8];
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) { pv[e] = col[(size_t)dim * (j + e)]; fv[e] = f[j + e]; }
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) { const double x = pv[e] * fv[e]; if (x > m) { m = x; arg = j + e; } }
+                    }
+                    for (; j < dim; ++j) { const double x = col[(size_t)dim * j] * f[j]; if (x > m) { m = x; arg = j; } }
+                    n.ptr[((size_t)(c - nleaves) * dim + i) * ncols + s] = (uint8_t)arg;
+                }
+                prod = q == q0 ? m : prod * m;
+            }
+        }
+        if (pgm_treelik_rescale(prod, shs, dim, i, active)) ++count;
+        if (active) n.F[((size_t)(v - nleaves) * ncols + s) * dim + i] = prod;
+        __syncthreads();   // the node's F is in memory before its parent reads it
+    }
+    if (active && i == 0) {
+        const double *f = n.F + ((size_t)(root - nleaves) * ncols + s) * dim;
+        double best = a.pi[0] * f[0];
+        uint32_t arg = 0;
+#pragma unroll 8
+        for (uint32_t j = 1; j < dim; ++j) { const double x = a.pi[j] * f[j]; if (x > best) { best = x; arg = j; } }
+        n.joint_l[s] = best;
+        n.joint_k[s] = count;
+        n.cat[s] = (uint8_t)k;
+        n.state[(size_t)(root - nleaves) * ncols + s] = best == 0.0 ? (int8_t)-1 : (int8_t)arg;
+    }
+}
+__global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_joint_trace_kernel(PgmTreelikJointArgs n) {
+    const uint32_t dim = n.t.dim, nleaves = n.t.nleaves, root = n.t.nnodes - 1, ncols = n.t.ncols;
+    const uint64_t s64 = (uint64_t)blockIdx.x * PGM_TREELIK_THREADS + threadIdx.x;
+    if (s64 >= ncols) return;
+    const size_t s = (size_t)s64;
+    for (uint32_t v = root; v-- > nleaves;) {   // root - 1 down to nleaves: a parent's state is written before its children ask for it
+        const int up = n.state[(size_t)(n.parent[v] - nleaves) * ncols + s];
+        n.state[(size_t)(v - nleaves) * ncols + s] = up < 0 ? (int8_t)-1 : (int8_t)n.ptr[((size_t)(v - nleaves) * dim + (uint32_t)up) * ncols + s];
+    }
+}
+
+// Ancestral states drawn from their joint posterior (pgm_tree_ancestral_sample), after the same walk and combine: the
+// stochastic traceback through the stored partials.  A lane is a sample and a wavefront owns 64 consecutive samples of one site
+// (blockIdx.x: the block of samples; the sites blockIdx.y, blockIdx.y + gridDim.y, ..), so the partial U_v(s, .) a node's draw reads is
+// the same for the lanes of a category and the 64 bytes a node's draw writes are consecutive.  A lane draws its category, then the
+// root, then the nodes descending, and finds the state of a node's parent in its own earlier write of samp_state.  Every draw has its
+// own counter, so what a lane draws depends on (sample, site, node, seed) alone.  A weight is one multiply wherever it is read: the sum
+// T and the running sum c form the same weights twice, eight fetched ahead of eight ordered adds.  No barriers, no atomics, one writer
+// per entry.
+struct PgmTreelikSampleArgs {
+    PgmTreelikArgs t;                      // the tree, pi and category 0's P and U (the rest unused)
+    PgmTreelikRatesStride st;              // doubles between two categories' matrices (P) and partials (U)
+    uint32_t ncat, nsamp;
+    uint64_t first, seed;
+    const uint32_t *parent;                // nnodes
+    const double *post;                    // ncat x ncols
+    uint8_t *cat;                          // ncols x nsamp
+    int8_t *state;                         // ninner x ncols x nsamp
+};
+// u of the draw numbered `counter`: splitmix64 (host/pgm_host.h) of the state seed + golden * counter, its top 53 bits times 2^-53
+__device__ __forceinline__ double pgm_treelik_uniform(uint64_t seed, uint64_t counter) {
+    uint64_t z = seed + 0x9E3779B97F4A7C15ull * counter;
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z = z ^ (z >> 31);
+    return (double)(z >> 11) * 0x1p-53;
+}
+// the pick rule of the interface on the weights weight(0) .. weight(m - 1)
+template <class W>
+__device__ __forceinline__ int pgm_treelik_pick(uint32_t m, double u, W weight) {
+    double T = 0.0;
+    uint32_t j = 0;
+    for (; j + 8 <= m; j += 8) {
+        double qv[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) qv[e] = weight(j + e);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) T = T + qv[e];
+    }
+    for (; j < m; ++j) T = T + weight(j);
+    if (T == 0.0) return -1;
+    const double target = u * T;
+    double c = 0.0;
+    int last = -1;
+    for (j = 0; j + 8 <= m; j += 8) {
+        double qv[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) qv[e] = weight(j + e);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            c = c + qv[e];
+            if (c > target) return (int)(j + e);
+            if (qv[e] > 0.0) last = (int)(j + e);
+        }
+    }
+    for (; j < m; ++j) {
+        const double q = weight(j);
+        c = c + q;
+        if (c > target) return (int)j;
+        if (q > 0.0) last = (int)j;
+    }
+    return last;
+}
+__global__ __launch_bounds__(PGM_TREELIK_THREADS) void pgm_treelik_sample_kernel(PgmTreelikSampleArgs n) {
+    const uint32_t dim = n.t.dim, nleaves = n.t.nleaves, root = n.t.nnodes - 1, ncols = n.t.ncols, ninner = n.t.nnodes - nleaves;
+    const uint64_t n64 = (uint64_t)blockIdx.x * PGM_TREELIK_THREADS + threadIdx.x;
+    if (n64 >= n.nsamp) return;   // (no barrier below)
+    const uint64_t N = n.first + n64;
+    const size_t mat = (size_t)dim * dim, nsamp = n.nsamp, lane = (size_t)n64;
+    const double *pi = n.t.pi;
+    for (uint32_t s = blockIdx.y; s < ncols; s += gridDim.y) {
+        const uint64_t base = (N * ncols + s) * ((uint64_t)ninner + 1);
+        const double *post = n.post + s;
+        const int k = pgm_treelik_pick(n.ncat, pgm_treelik_uniform(n.seed, base), [&](uint32_t c) { return post[(size_t)c * ncols]; });
+        n.cat[(size_t)s * nsamp + lane] = (uint8_t)k;   // (-1: 255)
+        const double *Pk = n.t.P + n.st.P * (size_t)(k < 0 ? 0 : k), *Uk = n.t.U + n.st.U * (size_t)(k < 0 ? 0 : k);
+        int x = -1;
+        if (k >= 0) {
+            const double *u = Uk + ((size_t)(root - nleaves) * ncols + s) * dim;
+            x = pgm_treelik_pick(dim, pgm_treelik_uniform(n.seed, base + 1 + (root - nleaves)), [&](uint32_t j) { return pi[j] * u[j]; });
+        }
+        n.state[((size_t)(root - nleaves) * ncols + s) * nsamp + lane] = (int8_t)x;
+        for (uint32_t v = root; v-- > nleaves;) {   // root - 1 down to nleaves, parents first
+            const int up = n.state[((size_t)(n.parent[v] - nleaves) * ncols + s) * nsamp + lane];
+            x = -1;
+            if (up >= 0) {   // (then k >= 0)
+                const double *row = Pk + mat * v + (uint32_t)up, *u = Uk + ((size_t)(v - nleaves) * ncols + s) * dim;
+                x = pgm_treelik_pick(dim, pgm_treelik_uniform(n.seed, base + 1 + (v - nleaves)), [&](uint32_t j) { return row[(size_t)dim * j] * u[j]; });
+            }
+            n.state[((size_t)(v - nleaves) * ncols + s) * nsamp + lane] = (int8_t)x;
+        }
     }
 }
 

@@ -168,6 +168,22 @@ struct HipBackend : Backend {
         if (rc != PGM_OK) error("pgm_tree_ancestral failed (%d): %s", rc, pgm_last_error());
         ml_tree_stats.kernel_ms += pgm_treelik_last_kernel_ms(c);
     }
+    void tree_ancestral_joint(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
+                              const double *w, const double *P, double *site_l, int32_t *site_k, double *post, uint8_t *cat, int8_t *joint_state, double *joint_l,
+                              int32_t *joint_k, int worker) override {
+        pgm_ctx *c = ctx_of(worker);
+        int rc = pgm_tree_ancestral_joint(c, dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, site_l, site_k, post, cat, joint_state, joint_l, joint_k);
+        if (rc != PGM_OK) error("pgm_tree_ancestral_joint failed (%d): %s", rc, pgm_last_error());
+        ml_tree_stats.kernel_ms += pgm_treelik_last_kernel_ms(c);
+    }
+    void tree_ancestral_sample(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
+                               const double *w, const double *P, uint32_t nsamp, uint64_t first_sample, uint64_t seed, double *site_l, int32_t *site_k, double *post,
+                               uint8_t *samp_cat, int8_t *samp_state, int worker) override {
+        pgm_ctx *c = ctx_of(worker);
+        int rc = pgm_tree_ancestral_sample(c, dim, nleaves, nnodes, parent, ncols, rows, pi, ncat, w, P, nsamp, first_sample, seed, site_l, site_k, post, samp_cat, samp_state);
+        if (rc != PGM_OK) error("pgm_tree_ancestral_sample failed (%d): %s", rc, pgm_last_error());
+        ml_tree_stats.kernel_ms += pgm_treelik_last_kernel_ms(c);
+    }
     void tree_nni(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
                   const double *w, const double *P, uint32_t ncand, const uint32_t *cand_v, const uint32_t *cand_a, const uint32_t *cand_c, double *site_l, int32_t *site_k,
                   double *post, double *rho, int worker) override {

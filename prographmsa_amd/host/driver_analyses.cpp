@@ -72,71 +72,80 @@ void doBootstrap(const Alphabet &a, const DriverOptions &o, const Family &fam, c
 // shape, the categories' rates, and per column the posterior mean rate and the category of the largest posterior.
 // --ml_ancestral: one Backend::tree_ancestral call at the estimated lengths (and rates) by the same route, and the
 // FASTA of the inner nodes' most probable states; --ml_ancestral_tree: the tree with the nodes' names; --ml_ancestral_probs: a line
-// per node and column.  --ml_search N: up to N rounds of nearest-neighbour interchanges from the start tree, every
+// per node and column; --ml_ancestral_joint and --ml_ancestral_samples: the jointly most probable states and draws
+// from the posterior, by the same route.  --ml_search N: up to N rounds of nearest-neighbour interchanges from the start tree, every
 // candidate of a round scored by one Backend::tree_nni call (the same route); --ml_start FILE: a newick in place of the BioNJ tree;
 // --ml_search_log FILE: a line per round; --ml_nni_opt N: the candidates of the search and of --ml_support each at a
 // central length of their own, N Newton rounds by Backend::tree_nni_edge calls (the same route); --ml_spr R: where the
 // interchanges of a round apply no move, every pruning and regrafting within R edges scored by Backend::tree_spr calls (the same
 // route), and a ninth column, nni or spr, in every line of the log
 // the names of the inner nodes of a numbered tree, N1 .. in node order; a leaf that has one of them is an error()
-static std::vector<std::string> ml_ancestral_names(const MlTreeTopology &topo) {
+static std::vector<std::string> ml_ancestral_names(const MlTreeTopology &topo, const char *flag = "--ml_ancestral") {
     std::vector<std::string> node_name(topo.nnodes - topo.nleaves);
     for (size_t k = 0; k < node_name.size(); ++k) node_name[k] = "N" + std::to_string(k + 1);
     const std::set<std::string> taken(node_name.begin(), node_name.end());
     for (const std::string &leaf : topo.names)
-        if (taken.count(leaf)) error("--ml_ancestral: the sequence name %s is the name of an inner node", leaf.c_str());
+        if (taken.count(leaf)) error("%s: the sequence name %s is the name of an inner node", flag, leaf.c_str());
     return node_name;
 }
+// What the files of the inner nodes' states share (--ml_ancestral, --ml_ancestral_joint, --ml_ancestral_samples): the numbered tree,
+// the rows, the categories' weights and matrices at the estimated lengths (and rates), and the text of a state under the gap rule.
+struct MlNodeStates {
+    MlTreeTopology topo;
+    uint32_t dim, nleaves, nnodes, ninner, ncols, ncat;
+    std::vector<std::string> node_name;
+    std::vector<int8_t> flat;
+    std::vector<double> w, P;
+    const double *pi;
+    std::vector<uint8_t> present;      // tree_ancestral_presence
+    std::vector<std::string> symbol;   // the character(s) of a state: the alphabet's own symbol (the first letter that has the value; a codon's three)
+    std::string gap;
+    MlNodeStates(const Alphabet &a, const Family &fam, const PhyTree &ml, const std::vector<std::vector<int8_t>> &values, const MlTreeResult &res, const char *flag)
+        : topo(ml_tree_topology(ml)), dim((uint32_t)a.DIM), nleaves(topo.nleaves), nnodes(topo.nnodes), ninner(nnodes - nleaves), ncols((uint32_t)values[0].size()),
+          ncat(res.rates.empty() ? 1u : (uint32_t)res.rates.size()), node_name(ml_ancestral_names(topo, flag)), flat((size_t)nleaves * ncols),
+          w(ncat, res.rates.empty() ? 1.0 : 1.0 / (double)ncat), pi(fam.model_factory->freqs().data()), present((size_t)ninner * ncols, 0), symbol(dim),
+          gap(a.rawChars() ? a.asString(a.gap()) : "---") {
+        for (uint32_t r = 0; r < nleaves; ++r) std::copy(values[r].begin(), values[r].end(), flat.begin() + (size_t)r * ncols);
+        tree_ancestral_presence(nleaves, nnodes, topo.parent.data(), ncols, flat.data(), present.data());
+        for (uint32_t x = 0; x < dim; ++x) {
+            if (!a.rawChars()) { symbol[x] = a.asString((int8_t)x); continue; }
+            for (char ch = 'A'; ch <= 'Z' && symbol[x].empty(); ++ch)
+                if (a.value((int8_t)ch) == (int)x) symbol[x] = std::string(1, ch);
+        }
+    }
+    // the categories' rates at the estimated shape and equal weights, or one category of weight 1.0 and the plain matrices
+    void matrices(const Family &fam, const MlTreeResult &res) {
+        if (res.rates.empty()) treelik_matrices(*fam.model_factory, res.lengths, false, P);
+        else treelik_matrices(*fam.model_factory, res.lengths, false, res.rates, P);
+    }
+    const std::string &text_of(int8_t x, bool held) const { return held && x >= 0 ? symbol[(size_t)x] : gap; }
+    bool held(uint32_t k, uint32_t s) const { return present[(size_t)k * ncols + s] != 0; }
+};
 static void write_ml_ancestral(const Alphabet &a, const MlTreeOpts &mo, const Family &fam, const PhyTree &ml, const std::vector<std::vector<int8_t>> &values,
                                const MlTreeResult &res, Backend *be) {
-    const MlTreeTopology topo = ml_tree_topology(ml);
-    const uint32_t dim = (uint32_t)a.DIM, nleaves = topo.nleaves, nnodes = topo.nnodes, ninner = nnodes - nleaves;
-    const uint32_t ncols = (uint32_t)values[0].size();
-    const std::vector<std::string> node_name = ml_ancestral_names(topo);
-    std::vector<int8_t> flat((size_t)nleaves * ncols);
-    for (uint32_t r = 0; r < nleaves; ++r) std::copy(values[r].begin(), values[r].end(), flat.begin() + (size_t)r * ncols);
-
+    MlNodeStates n(a, fam, ml, values, res, "--ml_ancestral");
+    const uint32_t ninner = n.ninner, ncols = n.ncols;
     const auto t0 = std::chrono::steady_clock::now();   // (ml_ancestral_s: the matrices and the call)
-    // the categories' rates at the estimated shape and equal weights, or one category of weight 1.0 and the plain matrices
-    const uint32_t ncat = res.rates.empty() ? 1u : (uint32_t)res.rates.size();
-    const std::vector<double> w(ncat, res.rates.empty() ? 1.0 : 1.0 / (double)ncat);
-    std::vector<double> P;
-    if (res.rates.empty()) treelik_matrices(*fam.model_factory, res.lengths, false, P);
-    else treelik_matrices(*fam.model_factory, res.lengths, false, res.rates, P);
-    std::vector<double> site_l(ncols), post((size_t)ncat * ncols), prob((size_t)ninner * ncols);
+    n.matrices(fam, res);
+    std::vector<double> site_l(ncols), post((size_t)n.ncat * ncols), prob((size_t)ninner * ncols);
     std::vector<int32_t> site_k(ncols);
     std::vector<int8_t> state((size_t)ninner * ncols);
-    const double *pi = fam.model_factory->freqs().data();
-    if (be) be->tree_ancestral(dim, nleaves, nnodes, topo.parent.data(), ncols, flat.data(), pi, ncat, w.data(), P.data(), site_l.data(), site_k.data(), post.data(),
-                               state.data(), prob.data(), nullptr);
-    else tree_ancestral_host(dim, nleaves, nnodes, topo.parent.data(), ncols, flat.data(), pi, ncat, w.data(), P.data(), site_l.data(), site_k.data(), post.data(),
-                             state.data(), prob.data(), nullptr);
+    if (be) be->tree_ancestral(n.dim, n.nleaves, n.nnodes, n.topo.parent.data(), ncols, n.flat.data(), n.pi, n.ncat, n.w.data(), n.P.data(), site_l.data(), site_k.data(),
+                               post.data(), state.data(), prob.data(), nullptr);
+    else tree_ancestral_host(n.dim, n.nleaves, n.nnodes, n.topo.parent.data(), ncols, n.flat.data(), n.pi, n.ncat, n.w.data(), n.P.data(), site_l.data(), site_k.data(),
+                             post.data(), state.data(), prob.data(), nullptr);
     ml_tree_stats.ancestral_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 
-    std::vector<uint8_t> present((size_t)ninner * ncols, 0);
-    tree_ancestral_presence(nleaves, nnodes, topo.parent.data(), ncols, flat.data(), present.data());
-    // the character(s) of a state: the alphabet's own symbol (the first letter that has the value; a codon's three)
-    std::vector<std::string> symbol(dim);
-    for (uint32_t x = 0; x < dim; ++x) {
-        if (!a.rawChars()) { symbol[x] = a.asString((int8_t)x); continue; }
-        for (char ch = 'A'; ch <= 'Z' && symbol[x].empty(); ++ch)
-            if (a.value((int8_t)ch) == (int)x) symbol[x] = std::string(1, ch);
-    }
-    const std::string gap = a.rawChars() ? a.asString(a.gap()) : "---";
-    auto text_of = [&](uint32_t k, uint32_t s, bool held) -> const std::string & {
-        const int8_t x = state[(size_t)k * ncols + s];
-        return held && x >= 0 ? symbol[(size_t)x] : gap;
-    };
     std::map<std::string, std::string> records;
     for (uint32_t k = 0; k < ninner; ++k) {
-        std::string &seq = records[node_name[k]];
-        for (uint32_t s = 0; s < ncols; ++s) seq += text_of(k, s, present[(size_t)k * ncols + s] != 0);
+        std::string &seq = records[n.node_name[k]];
+        for (uint32_t s = 0; s < ncols; ++s) seq += n.text_of(state[(size_t)k * ncols + s], n.held(k, s));
     }
     std::ofstream out = open_output(mo.anc, "ml ancestral output");
-    write_fasta(records, node_name, out);
+    write_fasta(records, n.node_name, out);
     if (mo.anc_tree_given) {
         std::map<const PhyTree *, std::string> labels;
-        for (uint32_t k = 0; k < ninner; ++k) labels[topo.node[nleaves + k]] = node_name[k];
+        for (uint32_t k = 0; k < ninner; ++k) labels[n.topo.node[n.nleaves + k]] = n.node_name[k];
         open_output(mo.anc_tree, "ml ancestral output") << ml.formatNewick(labels) << std::endl;
     }
     if (mo.anc_probs_given) {
@@ -144,11 +153,86 @@ static void write_ml_ancestral(const Alphabet &a, const MlTreeOpts &mo, const Fa
         char buf[64];
         for (uint32_t k = 0; k < ninner; ++k)
             for (uint32_t s = 0; s < ncols; ++s) {
-                const bool held = present[(size_t)k * ncols + s] != 0;
-                snprintf(buf, sizeof buf, "\t%u\t%s\t%.17g\t%d\n", s + 1, text_of(k, s, true).c_str(), prob[(size_t)k * ncols + s], held ? 1 : 0);
-                probs << node_name[k] << buf;
+                snprintf(buf, sizeof buf, "\t%u\t%s\t%.17g\t%d\n", s + 1, n.text_of(state[(size_t)k * ncols + s], true).c_str(), prob[(size_t)k * ncols + s], n.held(k, s) ? 1 : 0);
+                probs << n.node_name[k] << buf;
             }
     }
+}
+
+// --ml_ancestral_joint: one Backend::tree_ancestral_joint call by the same route, the FASTA of the inner nodes' jointly
+// most probable states under the gap rule of --ml_ancestral, and --ml_ancestral_joint_sites: `lnJ <sum>`, then per column
+// column<TAB>category (from 1)<TAB>log(joint_l) - 256 ln 2 joint_k
+static void write_ml_joint(const Alphabet &a, const MlTreeOpts &mo, const Family &fam, const PhyTree &ml, const std::vector<std::vector<int8_t>> &values,
+                           const MlTreeResult &res, Backend *be) {
+    MlNodeStates n(a, fam, ml, values, res, "--ml_ancestral_joint");
+    const uint32_t ninner = n.ninner, ncols = n.ncols;
+    const auto t0 = std::chrono::steady_clock::now();   // (ml_ancestral_joint_s: the matrices and the call)
+    n.matrices(fam, res);
+    std::vector<double> site_l(ncols), post((size_t)n.ncat * ncols), joint_l(ncols);
+    std::vector<int32_t> site_k(ncols), joint_k(ncols);
+    std::vector<uint8_t> cat(ncols);
+    std::vector<int8_t> state((size_t)ninner * ncols);
+    if (be) be->tree_ancestral_joint(n.dim, n.nleaves, n.nnodes, n.topo.parent.data(), ncols, n.flat.data(), n.pi, n.ncat, n.w.data(), n.P.data(), site_l.data(), site_k.data(),
+                                     post.data(), cat.data(), state.data(), joint_l.data(), joint_k.data());
+    else tree_ancestral_joint_host(n.dim, n.nleaves, n.nnodes, n.topo.parent.data(), ncols, n.flat.data(), n.pi, n.ncat, n.w.data(), n.P.data(), site_l.data(), site_k.data(),
+                                   post.data(), cat.data(), state.data(), joint_l.data(), joint_k.data());
+    ml_tree_stats.ancestral_joint_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+
+    std::map<std::string, std::string> records;
+    for (uint32_t k = 0; k < ninner; ++k) {
+        std::string &seq = records[n.node_name[k]];
+        for (uint32_t s = 0; s < ncols; ++s) seq += n.text_of(state[(size_t)k * ncols + s], n.held(k, s));
+    }
+    std::ofstream out = open_output(mo.joint, "ml ancestral output");
+    write_fasta(records, n.node_name, out);
+    if (mo.joint_sites_given) {
+        std::vector<double> site_lnj(ncols);
+        const double lnj = treelik_lnl(ncols, joint_l.data(), joint_k.data(), site_lnj.data());
+        std::ofstream sites = open_output(mo.joint_sites, "ml ancestral output");
+        char buf[96];
+        snprintf(buf, sizeof buf, "lnJ %.17g\n", lnj);
+        sites << buf;
+        for (uint32_t s = 0; s < ncols; ++s) {
+            snprintf(buf, sizeof buf, "%u\t%u\t%.17g\n", s + 1, (unsigned)cat[s] + 1, site_lnj[s]);
+            sites << buf;
+        }
+    }
+}
+
+// --ml_ancestral_samples N: N draws of every inner node's states from their joint posterior by
+// Backend::tree_ancestral_sample calls (the same route), the samples cut into calls whose states stay within kSampleStateBytes; the
+// records N<k>/<sample> of --ml_ancestral_samples_out, samples ascending and the nodes of a sample in node order, under the same gap rule
+static void write_ml_samples(const Alphabet &a, const MlTreeOpts &mo, const Family &fam, const PhyTree &ml, const std::vector<std::vector<int8_t>> &values,
+                             const MlTreeResult &res, Backend *be) {
+    MlNodeStates n(a, fam, ml, values, res, "--ml_ancestral_samples");
+    const uint32_t ninner = n.ninner, ncols = n.ncols, total = (uint32_t)mo.samples;
+    const auto t0 = std::chrono::steady_clock::now();   // (ml_ancestral_samples_s: the matrices, the calls and the records)
+    n.matrices(fam, res);
+    const uint32_t per_call = (uint32_t)std::min<size_t>(total, std::max<size_t>(1, kSampleStateBytes / ((size_t)ninner * ncols)));
+    std::vector<double> site_l(ncols), post((size_t)n.ncat * ncols);
+    std::vector<int32_t> site_k(ncols);
+    std::vector<uint8_t> cat((size_t)ncols * per_call);
+    std::vector<int8_t> state((size_t)ninner * ncols * per_call);
+    std::ofstream out = open_output(mo.samples_out, "ml ancestral output");
+    std::string text;
+    for (uint32_t first = 0; first < total; first += per_call) {
+        const uint32_t m = std::min(per_call, total - first);
+        if (be) be->tree_ancestral_sample(n.dim, n.nleaves, n.nnodes, n.topo.parent.data(), ncols, n.flat.data(), n.pi, n.ncat, n.w.data(), n.P.data(), m, first, mo.samples_seed,
+                                          site_l.data(), site_k.data(), post.data(), cat.data(), state.data());
+        else tree_ancestral_sample_host(n.dim, n.nleaves, n.nnodes, n.topo.parent.data(), ncols, n.flat.data(), n.pi, n.ncat, n.w.data(), n.P.data(), m, first, mo.samples_seed,
+                                        site_l.data(), site_k.data(), post.data(), cat.data(), state.data());
+        for (uint32_t j = 0; j < m; ++j) {
+            text.clear();
+            for (uint32_t k = 0; k < ninner; ++k) {
+                text += ">" + n.node_name[k] + "/" + std::to_string(first + j + 1) + "\n";
+                for (uint32_t s = 0; s < ncols; ++s) text += n.text_of(state[((size_t)k * ncols + s) * m + j], n.held(k, s));
+                text += "\n";
+            }
+            out << text;
+        }
+    }
+    out << std::flush;
+    ml_tree_stats.ancestral_samples_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
 // --ml_support: ml_branch_support on the tree the run ends with, at the estimated lengths (and rates), by the same
@@ -210,7 +294,13 @@ void doMlTree(const Alphabet &a, const DriverOptions &o, const Family &fam, cons
     MlGamma gamma;
     if (mo.gamma_given) { gamma.ncat = (uint32_t)mo.gamma; gamma.estimate = !mo.alpha_given; gamma.alpha = mo.alpha; }
     Backend *be = device ? &default_backend() : nullptr;
-    if (mo.anc_given) (void)ml_ancestral_names(ml_tree_topology(*tree));   // (refused before the optimiser runs and before any file is written)
+    // (a leaf with the name of an inner node is refused before the optimiser runs and before any file is written)
+    auto check_node_names = [&]() {
+        if (mo.anc_given) (void)ml_ancestral_names(ml_tree_topology(*tree));
+        if (mo.joint_given) (void)ml_ancestral_names(ml_tree_topology(*tree), "--ml_ancestral_joint");
+        if (mo.samples_given) (void)ml_ancestral_names(ml_tree_topology(*tree), "--ml_ancestral_samples");
+    };
+    check_node_names();
     MlTreeResult res;
     if (mo.search_given) {   // --ml_search: every file below describes the searched tree
         MlSprHook spr;
@@ -219,7 +309,7 @@ void doMlTree(const Alphabet &a, const DriverOptions &o, const Family &fam, cons
                                                   mo.nni_opt_given ? (uint32_t)mo.nni_opt : 0u, mo.spr_given ? &spr : nullptr);
         tree = std::move(found.tree);
         res = std::move(found.res);
-        if (mo.anc_given) (void)ml_ancestral_names(ml_tree_topology(*tree));
+        check_node_names();
         if (mo.search_log_given) {
             std::ofstream log = open_output(mo.search_log, "ml search output");
             char buf[256];
@@ -264,6 +354,8 @@ void doMlTree(const Alphabet &a, const DriverOptions &o, const Family &fam, cons
         }
     }
     if (mo.anc_given) write_ml_ancestral(a, mo, fam, *ml, values, res, be);
+    if (mo.joint_given) write_ml_joint(a, mo, fam, *ml, values, res, be);
+    if (mo.samples_given) write_ml_samples(a, mo, fam, *ml, values, res, be);
     if (mo.support_given) write_ml_support(a, mo, fam, *ml, values, res, be);
 }
 // --guidance (Penn et al. 2010, GUIDANCE: the guide tree as the source of alignment uncertainty): the final alignment's columns are

@@ -2,6 +2,7 @@
 // the reference's spellings) and what is refused before anything is read.
 #include "driver_options.h"
 
+#include <cerrno>
 #include <cmath>
 #include <cstdlib>
 #include <iostream>
@@ -89,11 +90,20 @@ void usage() {
                  "                interchanges of quartets); given twice (-WW), quintet moves as well\n";
 }
 
+// (--ml_ancestral_joint, --ml_ancestral_joint_sites, --ml_ancestral_samples, --ml_ancestral_samples_out and
+// --ml_ancestral_samples_seed came later still: README.md and DESIGN.md 3.24)
 // "the whole text is a number": not empty and nothing after the number.  The ranges differ and stay with the callers.
 static bool whole_number(const std::string &text, long &v) {
     char *end = nullptr;
     v = strtol(text.c_str(), &end, 10);
     return !text.empty() && *end == '\0';
+}
+// a seed: decimal digits alone, within 64 bits
+static bool whole_seed(const std::string &text, uint64_t &v) {
+    if (text.empty() || text.find_first_not_of("0123456789") != std::string::npos) return false;
+    errno = 0;
+    v = strtoull(text.c_str(), nullptr, 10);
+    return errno == 0;
 }
 static bool real_number(const std::string &text, double &v) {
     char *end = nullptr;
@@ -103,7 +113,7 @@ static bool real_number(const std::string &text, double &v) {
 
 int parse_driver_options(int argc, char **argv, DriverOptions &o) {
     bool missing = false;   // a flag without its value
-    bool cutoff_ok = true, rounds_ok = true, eps_ok = true, gamma_ok = true, alpha_ok = true, search_ok = true, reps_ok = true, nni_opt_ok = true, spr_ok = true;
+    bool cutoff_ok = true, rounds_ok = true, eps_ok = true, gamma_ok = true, alpha_ok = true, search_ok = true, reps_ok = true, nni_opt_ok = true, spr_ok = true, samples_ok = true, samples_seed_ok = true;
     for (int i = 1; i < argc && !missing; ++i) {
         std::string s = argv[i];
         auto val = [&]() -> std::string { if (i + 1 >= argc) { missing = true; return ""; } return argv[++i]; };
@@ -168,6 +178,11 @@ int parse_driver_options(int argc, char **argv, DriverOptions &o) {
         else if (s == "--ml_ancestral") { o.mltree.anc_given = true; o.mltree.anc = val(); }
         else if (s == "--ml_ancestral_tree") { o.mltree.anc_tree_given = true; o.mltree.anc_tree = val(); }
         else if (s == "--ml_ancestral_probs") { o.mltree.anc_probs_given = true; o.mltree.anc_probs = val(); }
+        else if (s == "--ml_ancestral_joint") { o.mltree.joint_given = true; o.mltree.joint = val(); }
+        else if (s == "--ml_ancestral_joint_sites") { o.mltree.joint_sites_given = true; o.mltree.joint_sites = val(); }
+        else if (s == "--ml_ancestral_samples") { o.mltree.samples_given = true; samples_ok = whole_number(val(), o.mltree.samples); }
+        else if (s == "--ml_ancestral_samples_out") { o.mltree.samples_out_given = true; o.mltree.samples_out = val(); }
+        else if (s == "--ml_ancestral_samples_seed") { o.mltree.samples_seed_given = true; samples_seed_ok = whole_seed(val(), o.mltree.samples_seed); }
         else if (s == "--ml_search") { o.mltree.search_given = true; search_ok = whole_number(val(), o.mltree.search); }
         else if (s == "--ml_start") { o.mltree.start_given = true; o.mltree.start = val(); }
         else if (s == "--ml_search_log") { o.mltree.search_log_given = true; o.mltree.search_log = val(); }
@@ -236,17 +251,24 @@ int parse_driver_options(int argc, char **argv, DriverOptions &o) {
         reps_ok = reps_ok && o.mltree.support_reps >= 1 && o.mltree.support_reps <= 10000;
         nni_opt_ok = !o.mltree.nni_opt_given || (nni_opt_ok && o.mltree.nni_opt >= 1 && o.mltree.nni_opt <= 20);
         spr_ok = !o.mltree.spr_given || (spr_ok && o.mltree.spr >= 1 && o.mltree.spr <= 10);
+        samples_ok = !o.mltree.samples_given || (samples_ok && o.mltree.samples >= 1 && o.mltree.samples <= 1000);
         const bool plain = o.mltree.sites_given || o.mltree.rounds_given || o.mltree.eps_given;   // (the flags from before --ml_gamma keep their message)
         const bool rates = o.mltree.gamma_given || o.mltree.alpha_given || o.mltree.rates_given;   // (... and so do those from before --ml_ancestral)
         const char *why = !o.mltree.tree_given ? (plain ? "--ml_sites, --ml_rounds and --ml_epsilon need --ml_tree"
                                                   : rates ? "--ml_gamma, --ml_alpha and --ml_rates need --ml_tree"
                                                   : o.mltree.any_anc() ? "--ml_ancestral needs --ml_tree"
+                                                  : o.mltree.any_joint() ? "--ml_ancestral_joint and --ml_ancestral_samples need --ml_tree"
                                                   : o.mltree.nni_opt_given ? "--ml_nni_opt needs --ml_tree"
                                                   : o.mltree.spr_given ? "--ml_spr needs --ml_tree"
                                                   : o.mltree.any_search() ? "--ml_search, --ml_start and --ml_search_log need --ml_tree"
                                                                           : "--ml_support, --ml_support_table, --ml_support_reps and --ml_support_seed need --ml_tree")
                           : (!o.mltree.gamma_given && (o.mltree.alpha_given || o.mltree.rates_given)) ? "--ml_alpha and --ml_rates need --ml_gamma"
                           : (!o.mltree.anc_given && o.mltree.any_anc()) ? "--ml_ancestral_tree and --ml_ancestral_probs need --ml_ancestral"
+                          : (!o.mltree.joint_given && o.mltree.joint_sites_given) ? "--ml_ancestral_joint_sites needs --ml_ancestral_joint"
+                          : o.mltree.samples_given != o.mltree.samples_out_given ? "--ml_ancestral_samples and --ml_ancestral_samples_out need each other"
+                          : (!o.mltree.samples_given && o.mltree.samples_seed_given) ? "--ml_ancestral_samples_seed needs --ml_ancestral_samples"
+                          : !samples_ok ? "--ml_ancestral_samples takes a number of samples from 1 to 1000"
+                          : !samples_seed_ok ? "--ml_ancestral_samples_seed takes a whole number from 0 to 18446744073709551615"
                           : (!o.mltree.search_given && o.mltree.search_log_given) ? "--ml_search_log needs --ml_search"
                           : (!o.mltree.support_given && o.mltree.any_support()) ? "--ml_support_table, --ml_support_reps and --ml_support_seed need --ml_support"
                           : (o.mltree.nni_opt_given && !o.mltree.search_given && !o.mltree.support_given) ? "--ml_nni_opt needs --ml_search or --ml_support"

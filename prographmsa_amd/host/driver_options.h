@@ -28,9 +28,17 @@ struct GuidanceOpts {   // --guidance N --guidance_out FILE --guidance_seed S --
 struct MlTreeOpts {   // --ml_tree FILE --ml_sites FILE --ml_rounds N --ml_epsilon X --ml_gamma K --ml_alpha X --ml_rates FILE
                       // --ml_ancestral FILE --ml_ancestral_tree FILE --ml_ancestral_probs FILE --ml_search N --ml_start FILE --ml_search_log FILE
                       // --ml_support FILE --ml_support_table FILE --ml_support_reps N --ml_support_seed S --ml_nni_opt N --ml_spr R
+                      // --ml_ancestral_joint FILE --ml_ancestral_joint_sites FILE --ml_ancestral_samples N --ml_ancestral_samples_out FILE
+                      // --ml_ancestral_samples_seed S
     std::string tree, sites, rates, anc, anc_tree, anc_probs;
     bool anc_given = false, anc_tree_given = false, anc_probs_given = false;
     bool any_anc() const { return anc_given || anc_tree_given || anc_probs_given; }
+    // --ml_ancestral_joint, --ml_ancestral_samples: the jointly most probable states; N draws from the posterior
+    std::string joint, joint_sites, samples_out;
+    bool joint_given = false, joint_sites_given = false, samples_given = false, samples_out_given = false, samples_seed_given = false;
+    long samples = 0;
+    uint64_t samples_seed = 1;
+    bool any_joint() const { return joint_given || joint_sites_given || samples_given || samples_out_given || samples_seed_given; }
     bool tree_given = false, sites_given = false, rounds_given = false, eps_given = false, gamma_given = false, alpha_given = false, rates_given = false;
     long rounds = 100, gamma = 0;
     double eps = 1e-4, alpha = 1.0;
@@ -49,7 +57,7 @@ struct MlTreeOpts {   // --ml_tree FILE --ml_sites FILE --ml_rounds N --ml_epsil
     uint64_t support_seed = 1;
     bool any_support() const { return support_given || support_table_given || support_reps_given || support_seed_given; }
     bool any() const {
-        return tree_given || sites_given || rounds_given || eps_given || gamma_given || alpha_given || rates_given || any_anc() || any_search() || any_support() || nni_opt_given || spr_given;
+        return tree_given || sites_given || rounds_given || eps_given || gamma_given || alpha_given || rates_given || any_anc() || any_search() || any_support() || nni_opt_given || spr_given || any_joint();
     }
 };
 

@@ -50,6 +50,10 @@ void print_stats(const DriverOptions &o, double t_init, double t_tree, double t_
         fprintf(stderr, ", \"ml_categories\": %u, \"ml_alpha\": %.17g", ml_tree_stats.categories, ml_tree_stats.alpha);
     if (o.mltree.anc_given)   // (key of --ml_ancestral only)
         fprintf(stderr, ", \"ml_ancestral_s\": %.6f", ml_tree_stats.ancestral_s);
+    if (o.mltree.joint_given)   // (key of --ml_ancestral_joint only)
+        fprintf(stderr, ", \"ml_ancestral_joint_s\": %.6f", ml_tree_stats.ancestral_joint_s);
+    if (o.mltree.samples_given)   // (key of --ml_ancestral_samples only)
+        fprintf(stderr, ", \"ml_ancestral_samples_s\": %.6f", ml_tree_stats.ancestral_samples_s);
     if (o.mltree.search_given)   // (keys of --ml_search only)
         fprintf(stderr, ", \"ml_search_s\": %.6f, \"ml_search_rounds\": %llu, \"ml_nni_applied\": %llu, \"ml_nni_calls\": %llu, \"ml_nni_kernel_ms\": %.3f",
                 ml_search_stats.seconds, (unsigned long long)ml_search_stats.rounds, (unsigned long long)ml_search_stats.applied,

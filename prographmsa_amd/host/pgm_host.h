@@ -351,6 +351,16 @@ struct Backend {
     virtual void tree_ancestral(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
                                 uint32_t ncat, const double *w, const double *P, double *site_l, int32_t *site_k, double *post, int8_t *anc_state, double *anc_prob,
                                 double *anc_post, int worker = 0);
+    // The jointly most probable states of the inner nodes under the column's most probable category (--ml_ancestral_joint;
+    // include/pgm_hip.h: pgm_tree_ancestral_joint).  The default is the host statement, tree_ancestral_joint_host: the same bits.
+    virtual void tree_ancestral_joint(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
+                                      uint32_t ncat, const double *w, const double *P, double *site_l, int32_t *site_k, double *post, uint8_t *cat, int8_t *joint_state,
+                                      double *joint_l, int32_t *joint_k, int worker = 0);
+    // nsamp draws of (category, every inner state) from their posterior at every column (--ml_ancestral_samples; include/pgm_hip.h:
+    // pgm_tree_ancestral_sample).  The default is the host statement, tree_ancestral_sample_host: the same bytes.
+    virtual void tree_ancestral_sample(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi,
+                                       uint32_t ncat, const double *w, const double *P, uint32_t nsamp, uint64_t first_sample, uint64_t seed, double *site_l,
+                                       int32_t *site_k, double *post, uint8_t *samp_cat, int8_t *samp_state, int worker = 0);
     // The likelihood ratio of every nearest-neighbour interchange at every column (--ml_search; include/pgm_hip.h: pgm_tree_nni).  The
     // default is the host statement, tree_nni_host: the same bits.
     virtual void tree_nni(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,

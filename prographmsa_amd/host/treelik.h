@@ -48,6 +48,7 @@ const uint32_t kTreelikDeviceMin = 24;
 struct MlTreeStats {   // `pgmsa --ml_tree --stats`
     double seconds = 0, kernel_ms = 0, lnl_start = 0, lnl = 0;
     double ancestral_s = 0;    // --ml_ancestral only: the tree_ancestral call, its matrices included
+    double ancestral_joint_s = 0, ancestral_samples_s = 0;   // --ml_ancestral_joint, --ml_ancestral_samples only: the same of their calls
     uint64_t rounds = 0, evaluations = 0;
     uint32_t categories = 0;   // --ml_gamma only
     double alpha = 0;
@@ -70,6 +71,17 @@ void tree_ancestral_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const 
                          const double *w, const double *P, double *site_l, int32_t *site_k, double *post, int8_t *anc_state /* ninner x ncols */,
                          double *anc_prob /* ninner x ncols */, double *anc_post /* ninner x ncols x dim, or null */);
 void tree_ancestral_presence(uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, uint8_t *present /* ninner x ncols */);
+// --ml_ancestral_joint, --ml_ancestral_samples (host/treelik_joint.cpp):
+// tree_ancestral_joint_host: pgm_tree_ancestral_joint by the same loop over the sites, Backend::tree_ancestral_joint's default.
+// tree_ancestral_sample_host: pgm_tree_ancestral_sample by the same loop, the samples of a site inside; Backend::tree_ancestral_sample's
+//   default.  A caller cuts its samples into calls whose samp_state stays within kSampleStateBytes (first_sample: the draws do not
+//   depend on the cut).
+void tree_ancestral_joint_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
+                               const double *w, const double *P, double *site_l, int32_t *site_k, double *post, uint8_t *cat /* ncols */,
+                               int8_t *joint_state /* ninner x ncols */, double *joint_l /* ncols */, int32_t *joint_k /* ncols */);
+void tree_ancestral_sample_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
+                                const double *w, const double *P, uint32_t nsamp, uint64_t first_sample, uint64_t seed, double *site_l, int32_t *site_k, double *post,
+                                uint8_t *samp_cat /* ncols x nsamp */, int8_t *samp_state /* ninner x ncols x nsamp */);
 std::vector<double> gamma_rates(double alpha, uint32_t K);
 void treelik_matrices(const ModelFactory &mf, const std::vector<double> &t, bool derivs, const std::vector<double> &rates, std::vector<double> &P);
 struct MlGamma {
@@ -155,6 +167,7 @@ MlSearchResult ml_topology_search(const Alphabet &a, const std::vector<std::vect
 // ml_spr_candidates: every valid candidate (v, y) of pgm_tree_spr whose path has at most `radius` edges, v ascending, then y ascending.
 // ml_spr_touched: the nodes a move reads or changes: v, p, parent[p], the children of p, every node of the path, y and parent[y].
 const size_t kSprRhoBytes = (size_t)256 << 20;   // rho of one tree_spr call
+const size_t kSampleStateBytes = (size_t)256 << 20;   // samp_state of one tree_ancestral_sample call
 void tree_spr_host(uint32_t dim, uint32_t nleaves, uint32_t nnodes, const uint32_t *parent, uint32_t ncols, const int8_t *rows, const double *pi, uint32_t ncat,
                    const double *w, const double *P, const double *Ph /* as P: half of every edge */, uint32_t ncand, const uint32_t *cand_v,
                    const uint32_t *cand_y /* ncand each */, double *site_l, int32_t *site_k, double *post, double *rho /* ncand x ncols */,
